@@ -14,7 +14,9 @@ environment this process IS one rank (torchrun).  Without it and with --gpus N >
 ranks BEFORE touching a GPU (fresh python processes, rank r bound to GPU r, backend nccl = RCCL), waits for
 them and exits non-zero if any rank fails or fewer than N devices are visible: it never falls back to one rank.
 
-Rank 0 prints ONE JSON line.  Extra objects on it:
+A plain run sets up, primes the clock, runs the W warm-up steps, times exactly K steps, writes the last step's outputs
+(--dump-outputs DIR) and prints the result line.  Rank 0 prints ONE JSON line.  With --full the timed region is run
+--regions times (default 7; ms_per_step is then the median region) and these extra objects join it:
   roofline      dominant kernel AMONG THE LAUNCHES OF THE STEP (fp32 MFMA bound), algorithmic flops / its HIP-event time
                 measured inside the running step (an event between the step's launch groups, a second pass right after
                 the timed region); profiles/rNN_cfg2_kernel_stats.csv holds rocprofv3's average for the same kernel
@@ -58,9 +60,17 @@ def parse_args(argv=None):
                          "step, which then sits in the 256 MB Infinity Cache from one step to the next - no loader does that)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--regions", type=int, default=7,
+    ap.add_argument("--regions", type=int, default=None,
                     help="the timed region (exactly --steps steps between two barrier + synchronize pairs) is run this many times "
-                         "back to back; ms_per_step is the MEDIAN region, every region is listed in ms_per_step_runs")
+                         "back to back; ms_per_step is the MEDIAN region, every region is listed in ms_per_step_runs "
+                         "(default: 1, with --full 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: 7 timed regions, in-step kernel breakdown and roofline "
+                         "objects, rccl_floor, configs 3 / 5 and the ragged regimes, the CPU baseline (the --no-* flags below "
+                         "drop single objects of this run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (loss, prob, logits, updated parameters, gradient) "
+                         "as DIR/<name>.npy, float32")
     ap.add_argument("--bags-per-gpu", type=int, default=32)
     ap.add_argument("--global-bags", type=int, default=0,
                     help="strong scaling (SURVEY 8d, config 4 for W < 8): G bags in total, G / W per GPU (G % W == 0); "
@@ -87,7 +97,10 @@ def parse_args(argv=None):
                     "the step is GPU-bound either way)")
     ap.add_argument("--dump", default="", help="(tests) rank 0 saves loss + flat gradient of the first step here")
     ap.add_argument("--launch-timeout", type=float, default=1500.0)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.regions is None:
+        args.regions = 7 if args.full else 1
+    return args
 
 
 # ----------------------------------------------------------------------------------------------- launcher
@@ -158,6 +171,22 @@ def timed(fn, iters, warm=2):
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1) / iters
+
+
+DUMP_MAX_ELEMS = 4 << 20          # per array (16 MiB of float32); a larger output is written as a fixed, seeded sample
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor as out_dir/<name>.npy in float32 (two builds compare output for output).  An array
+    above DUMP_MAX_ELEMS keeps only the elements at a fixed, seeded set of flat indices (sorted), so the files stay
+    below 64 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(1234).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _pmc_traffic(name):
@@ -872,13 +901,22 @@ def run_rank(args):
     # the driver's flags one region is 20 steps = 5 ms, where a single 0.3 ms host hiccup moves the figure by 6 % (round 3's
     # driver run read 8 % below every other run of the same command); the median region is what the line reports
     regions = []
+    out = None
     for _ in range(max(1, args.regions)):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            out = step()
         barrier()
         regions.append(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0 and out is not None:
+        # what the caller of the timed step receives from its last call (loss, prob) and what it leaves behind: the logits
+        # of that forward, the parameters after its update and its (all-reduced) gradient, concatenated in PARAM_ORDER
+        order = tr.fp.order
+        dump_outputs(args.dump_outputs, {
+            "loss": out[0].reshape(-1), "prob": out[1], "logits": tr.last["logits"],
+            "params": torch.cat([tr.fp.p(k).reshape(-1) for k in order]),
+            "grad": torch.cat([tr.fp.g(k).reshape(-1) for k in order])})
     if use_dist:
         t = torch.tensor(regions, device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)            # per region: the slowest rank
@@ -917,8 +955,8 @@ def run_rank(args):
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
             "ms_per_step_runs": [round(r / args.steps * 1e3, 4) for r in regions],
             "ms_per_step_min": round(min(regions) / args.steps * 1e3, 4), "ms_per_step_max": round(max(regions) / args.steps * 1e3, 4),
-            "timing": f"median of {len(regions)} timed regions of exactly {args.steps} steps each (barrier + synchronize on both "
-                      "sides, max over ranks per region)",
+            "timing": (f"median of {len(regions)} timed regions" if len(regions) > 1 else "one timed region")
+                      + f" of exactly {args.steps} steps (barrier + synchronize on both sides, max over ranks per region)",
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": args.dtype,
             "data": "synthetic",
             "config": {"workload": f"{B} bags/GPU x {N} patches x {L} dims, image-only gated-attention MIL "
@@ -938,7 +976,7 @@ def run_rank(args):
                                  "unit": "TFLOP/s", "frac": round(2 * gate_flops / (ms_step * 1e-3) / 1e12 / peak, 4),
                                  "flops_per_step": 2 * gate_flops,
                                  "note": "gate GEMMs forward + weight gradient (2 x 4 R L D) over the driver-timed ms_per_step"}
-        if not args.no_breakdown:
+        if args.full and not args.no_breakdown:
             # each launch group of the step, timed INSIDE the running step (HIP events between the groups, on the stream the
             # kernels are launched on; mil_image_only_step_profile) - the figure rocprofv3's kernel trace of the step reports
             rot = list(zip(xs, ys)) if nb > 1 else None       # the same rotation as the timed loop
@@ -998,9 +1036,9 @@ def run_rank(args):
                 del tr_e
             if world == 1 and args.dtype == "f32":
                 line["roofline_pool"] = pool_roofline(dev)
-        if world == 1 and not use_dist and not args.no_breakdown and not args.no_rccl_floor and args.dtype == "f32":
+        if args.full and world == 1 and not use_dist and not args.no_breakdown and not args.no_rccl_floor and args.dtype == "f32":
             line["rccl_floor"] = rccl_floor(args)
-        if world == 1 and not args.no_configs and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_configs and args.dtype == "f32":
             cfgs = {}
             jobs = [("cfg3", config3_fusion), ("cfg5", config5_bf16)]
             if not args.no_ragged:
@@ -1013,7 +1051,7 @@ def run_rank(args):
                     cfgs[name] = {"error": f"{type(e).__name__}: {e}"}
                 torch.cuda.empty_cache()
             line["configs"] = cfgs
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(N, L)
         print(json.dumps(line), flush=True)
         if os.environ.get("MIL_BENCH_STRICT") == "1" and not line.get("consistency", {}).get("ok", True):

@@ -13,6 +13,7 @@ tests/golden/.  Fixtures hold data only - no reference source travels.
 """
 from __future__ import annotations
 
+import glob
 import importlib.util
 import os
 import sys
@@ -55,6 +56,9 @@ def sub(p, prefix):
     return {k[len(prefix):]: v for k, v in p.items() if k.startswith(prefix)}
 
 
+MAX_FILE_BYTES = 960 * 1024      # every committed file stays below 1 MiB: a larger fixture goes into <name>.partN.npz too
+
+
 def npz(name, **arrs):
     os.makedirs(OUT, exist_ok=True)
     out = {}
@@ -62,9 +66,19 @@ def npz(name, **arrs):
         if isinstance(v, torch.Tensor):
             v = v.detach().cpu().numpy()
         out[k] = np.asarray(v)
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **out)
-    print(f"{name}: {os.path.getsize(path) / 1024:.1f} KiB")
+    groups, size = [{}], 0
+    for k, v in out.items():
+        if groups[-1] and size + v.nbytes > MAX_FILE_BYTES:
+            groups.append({})
+            size = 0
+        groups[-1][k] = v
+        size += v.nbytes
+    for old in glob.glob(os.path.join(OUT, glob.escape(name) + ".part*.npz")):
+        os.remove(old)
+    for i, g in enumerate(groups):
+        path = os.path.join(OUT, name + (".npz" if i == 0 else f".part{i}.npz"))
+        np.savez_compressed(path, **g)
+        print(f"{os.path.basename(path)}: {os.path.getsize(path) / 1024:.1f} KiB")
 
 
 SAMPLE_STRIDE = 97

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -20,8 +21,16 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
-    return {k: torch.from_numpy(np.asarray(z[k])) for k in z.files}
+    """<name>.npz merged with its <name>.partN.npz files: oracle/gen_golden.py splits a fixture so that every committed
+    file stays below 1 MiB."""
+    out = {}
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz")))
+    for path in [os.path.join(GOLDEN, name + ".npz")] + parts:
+        z = np.load(path)
+        for k in z.files:
+            assert k not in out, (path, k)
+            out[k] = torch.from_numpy(np.asarray(z[k]))
+    return out
 
 
 @pytest.fixture(scope="session")

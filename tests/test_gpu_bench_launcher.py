@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -84,6 +85,26 @@ def test_strong_scaling_rehearsal_keeps_the_global_batch(tmp_path):
     assert rel_err(got["grad"], tr.fp.grad.cpu()) <= 1e-5
     r = bench("--gpus", "2", *small, "--global-bags", "7", env={"MIL_BENCH_REHEARSAL": "1"}, expect_ok=False)
     assert r.returncode != 0 and "multiple" in (r.stderr + r.stdout)
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one region, carries none of the --full objects, and
+    --dump-outputs writes the last timed step's outputs - the same arrays from two runs with the same arguments."""
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--prime", "2", "--bags-per-gpu", "4", "--patches", "128"]
+    a = bench(*argv, "--dump-outputs", str(tmp_path / "a"))
+    bench(*argv, "--dump-outputs", str(tmp_path / "b"))
+    assert a["steps"] == 3 and len(a["ms_per_step_runs"]) == 1 and a["ms_per_step"] > 0
+    assert not {"roofline", "kernels_ms", "roofline_pool", "rccl_floor", "configs", "cpu_baseline"} & set(a)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["grad.npy", "logits.npy", "loss.npy", "params.npy", "prob.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all(), n
+        np.testing.assert_allclose(x, y, rtol=1e-5, atol=1e-7, err_msg=n)
+    assert np.load(tmp_path / "a" / "prob.npy").shape == (4, 2)
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - a["config"]["loss"]) <= 1e-5
+    p0 = syn.image_only_params(1234, L=512)
+    assert np.load(tmp_path / "a" / "params.npy").size == sum(v.numel() for v in p0.values())
 
 
 def test_more_ranks_than_gpus_is_refused_not_downgraded():

@@ -30,7 +30,7 @@ MFMA="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLI
 # QUICK=1: the cfg2 kernel trace + one un-profiled bench line only (the HIP-event vs rocprofv3 cross-check)
 if [ "${QUICK:-0}" = "1" ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_cfg2 -- ${CMD[cfg2]} > $OUT/stats_cfg2.log 2>&1
-  python3 $ROOT/bench.py --steps 200 --warmup 20 --no-configs --no-cpu-baseline > $OUT/bench_line.json 2> $OUT/bench_line.err
+  python3 $ROOT/bench.py --full --steps 200 --warmup 20 --no-configs --no-cpu-baseline > $OUT/bench_line.json 2> $OUT/bench_line.err
   find $OUT -name "*agent_info*" -delete
   echo quick done
   exit 0
@@ -55,11 +55,11 @@ done
 find $OUT -name "*agent_info*" -delete
 fi
 if [[ "$PART" == *B* ]]; then
-python3 $ROOT/bench.py --steps 200 --warmup 20 > $OUT/bench_line.json 2> $OUT/bench_line.err
+python3 $ROOT/bench.py --full --steps 200 --warmup 20 > $OUT/bench_line.json 2> $OUT/bench_line.err
 echo "bench done"
 python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/bench_driver_line.json 2>/dev/null      # the driver's flags
-python3 $ROOT/bench.py --steps 200 --warmup 20 --train-mode 0 --no-configs --no-cpu-baseline --no-rccl-floor > $OUT/bench_eval_line.json 2>/dev/null
-MIL_FORCE_COLLECTIVES=1 python3 $ROOT/bench.py --gpus 1 --no-configs --no-cpu-baseline --no-rccl-floor > $OUT/bench_rccl1_line.json 2>/dev/null
+python3 $ROOT/bench.py --full --steps 200 --warmup 20 --train-mode 0 --no-configs --no-cpu-baseline --no-rccl-floor > $OUT/bench_eval_line.json 2>/dev/null
+MIL_FORCE_COLLECTIVES=1 python3 $ROOT/bench.py --full --gpus 1 --no-configs --no-cpu-baseline --no-rccl-floor > $OUT/bench_rccl1_line.json 2>/dev/null
 echo "part B done"
 fi
 if [[ "$PART" != *C* ]]; then exit 0; fi
