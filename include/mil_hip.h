@@ -36,6 +36,8 @@
  *    `_pad`       operands / outputs in the grouped products' padded layout
  *    `_counted`, `_dev`, `_segs`   Adam with the step number / learning rate in device memory (hipGraph replay), several ranges
  *    `_time`, `_profile[_rot]`     measurement helpers of the one-call step
+ *  The image-only TransMIL extractor (`--model_pathology TransMIL`) has a family of its own, `mil_tm_*` (csrc/transmil.hip):
+ *    one batched product (`mil_tm_bgemm`) and the row-wise / conv stages around it, forward and backward each.
  */
 #ifndef MIL_HIP_H
 #define MIL_HIP_H
@@ -905,6 +907,51 @@ int mil_image_only_step_profile(const mil_image_only_step* a, const uint32_t* gr
  * batches (bench.py --batches); one batch alone stays in the Infinity Cache from step to step.  nrot == 0: as above. */
 int mil_image_only_step_profile_rot(const mil_image_only_step* a, const void* const* xs, const float* const* ys, int nrot,
                                     const uint32_t* groups, int ngroups, int warm, int iters, float* ms_out, void* stream);
+
+/* ---- TransMIL (csrc/transmil.hip) ----------------------------------------------------------------
+ * Reference: model/dim1/TransMIL.py (_fc1, square padding, cls token, PPEG, two TransLayers, norm) and the
+ * nystrom_attention package its TransLayer builds (dim 512, 8 heads x 64, 256 landmarks, 6 pseudo-inverse iterations,
+ * 33-tap residual conv on v).  The dense layers and LayerNorms go through mil_gemm / mil_linear_bwd_params / mil_layernorm_*;
+ * these entries are the rest.  One bag per call; qkv is the [n_pad, 1536] output of to_qkv on the front-zero-padded rows,
+ * n_pad % 256 == 0.
+ *
+ * mil_tm_bgemm: C[b] = alpha A[b] B[b] + beta D[b] + diag I for b < batch (D laid out like C; null: D = C), element (i, k) of A[b] at
+ * A + b sAb + i sAi + k sAk, (k, j) of B[b] at B + b sBb + k sBk + j sBj, (i, j) of C[b] at C + b sCb + i sCi + j sCj
+ * (strides in floats).  fp32 MFMA.  splits > 1 splits K and adds the partial products atomically into C (beta 1, D null). */
+int mil_tm_bgemm(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C, long sCb,
+                 long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta, float diag, int splits,
+                 void* stream);
+/* In place over contiguous rows: x = softmax(x) per row; backward dp = p (dp - <p, dp>). */
+int mil_tm_softmax_rows(float* x, long rows, int cols, void* stream);
+int mil_tm_softmax_rows_bwd(const float* p, float* dp, long rows, int cols, void* stream);
+/* Sequence assembly: dst[r] = src[idx[r]] (idx >= 0), the row `extra` (idx == -2) or zeros (idx == -1); rows of E floats.
+ * Backward: dsrc[idx[r]] += ddst[r] (atomic, repeated indices add), dextra likewise; both caller-initialised. */
+int mil_tm_row_gather(const float* src, const float* extra, const int32_t* idx, int rows, int E, float* dst, void* stream);
+int mil_tm_row_gather_bwd(const float* ddst, const int32_t* idx, int rows, int E, float* dsrc, float* dextra, void* stream);
+/* Landmarks: qL, kL [8, 256, 64] = means of l = n_pad / 256 consecutive rows of q (times qscale) and k, zero pad rows
+ * counted.  Backward: dqkv's q and k columns += the spread-out landmark gradients. */
+int mil_tm_landmarks(const float* qkv, int n_pad, float qscale, float* qL, float* kL, void* stream);
+int mil_tm_landmarks_bwd(const float* dqL, const float* dkL, int n_pad, float qscale, float* dqkv, void* stream);
+/* Pseudo-inverse start: scale[0..2] = (max row abs-sum x max column abs-sum, max row abs-sum, max column abs-sum) of
+ * A2 [8, 256, 256] taken over all 8 heads of the bag, arg[0] = head * 256 + column of the largest column sum;
+ * Z0 = A2^T / scale[0].  scale holds 3 + 16 floats and arg 1 + 8 ints (the per-head maxima behind them).
+ * Backward: dA2 += dZ0^T / s plus the scale's gradient on the arg-max column (the row-sum factor has zero derivative
+ * through the softmax in front); ws: one caller-zeroed float. */
+int mil_tm_pinv_init(const float* A2, float* scale, int32_t* arg, float* Z0, void* stream);
+int mil_tm_pinv_init_bwd(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
+                         void* stream);
+/* Residual depthwise conv on v (33 x 1 per head along the sequence, zero padding 16, no bias): out [n_pad, 512] (merged
+ * heads) += conv(v).  Backward: the v columns of dqkv += conv^T(dout); dw [8, 33] += (atomic, caller-initialised). */
+int mil_tm_resconv(const float* qkv, const float* w, int n_pad, float* out, void* stream);
+int mil_tm_resconv_bwd(const float* dout, const float* qkv, const float* w, int n_pad, float* dqkv, float* dw, void* stream);
+/* PPEG on x [1 + s^2, 512] (row 0 = cls, passed through; token i s + j at grid (i, j)): y = conv7(x) + x + conv5(x) +
+ * conv3(x) as ONE depthwise 7 x 7 with the folded weights W7 + pad(W5) + pad(W3) + delta and bias b7 + b5 + b3.
+ * Backward: dx (cls row passed through), dWf [512, 49] and db [512] += (atomic, caller-initialised); dW7 = dWf, dW5 / dW3 are
+ * its central 5 x 5 / 3 x 3, the three bias gradients are db. */
+int mil_tm_ppeg_fwd(const float* x, int s, const float* W7, const float* b7, const float* W5, const float* b5, const float* W3,
+                    const float* b3, float* y, void* stream);
+int mil_tm_ppeg_bwd(const float* dy, const float* x, int s, const float* W7, const float* W5, const float* W3, float* dx,
+                    float* dWf, float* db, void* stream);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,20 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
                                       c_size_t, _P]),
     "mil_linear_bwd_params_rows": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P,
                                       c_size_t, _P, _P]),
+    "mil_tm_bgemm": (c_int, [_P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P]
+                     + [c_int] * 4 + [c_float] * 3 + [c_int, _P]),
+    "mil_tm_softmax_rows": (c_int, [_P, c_long, c_int, _P]),
+    "mil_tm_softmax_rows_bwd": (c_int, [_P, _P, c_long, c_int, _P]),
+    "mil_tm_row_gather": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
+    "mil_tm_row_gather_bwd": (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
+    "mil_tm_landmarks": (c_int, [_P, c_int, c_float, _P, _P, _P]),
+    "mil_tm_landmarks_bwd": (c_int, [_P, _P, c_int, c_float, _P, _P]),
+    "mil_tm_pinv_init": (c_int, [_P] * 4 + [_P]),
+    "mil_tm_pinv_init_bwd": (c_int, [_P] * 6 + [_P]),
+    "mil_tm_resconv": (c_int, [_P, _P, c_int, _P, _P]),
+    "mil_tm_resconv_bwd": (c_int, [_P, _P, _P, c_int, _P, _P, _P]),
+    "mil_tm_ppeg_fwd": (c_int, [_P, c_int] + [_P] * 7 + [_P]),
+    "mil_tm_ppeg_bwd": (c_int, [_P, _P, c_int] + [_P] * 6 + [_P]),
 }
 
 STAGE_DROPBITS, STAGE_GATE_FWD, STAGE_POOL, STAGE_TAIL, STAGE_GATE_BWD, STAGE_REDUCE, STAGE_ADAM = 1, 2, 4, 8, 16, 32, 64

@@ -19,7 +19,8 @@ def create_arg_parser(argv=None):
     p.add_argument("--modality", default=["pathology"], type=arg_as_list, help="subset of ['CT', 'pathology', 'CI'] ('CT': the encoder's feature map is a synthetic input)")
     p.add_argument("--alignment_base", default="CI", type=str)
     p.add_argument("--model_CT", default="resnetMC3_18", type=str)
-    p.add_argument("--model_pathology", default="ABMIL", type=str)
+    p.add_argument("--model_pathology", default="ABMIL", type=str,
+                   help="image_only: ABMIL or TransMIL (Nystrom attention + PPEG; autograd path only); fusion: ABMIL")
     p.add_argument("--model_CI", default="CLIP", type=str)
     p.add_argument("--aggregator", default="ABMIL", type=str)
     p.add_argument("--CI_prompt_version", default="single", type=str, help="single (1 note) | devided (10 prompts)")

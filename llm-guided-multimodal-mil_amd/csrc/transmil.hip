@@ -1,0 +1,478 @@
+// TransMIL (reference: model/dim1/TransMIL.py + the nystrom_attention package its TransLayer builds), MI355X path.
+//
+// The Nystrom core of one bag is a chain of per-head products with the three softmax maps materialised
+// (A1 [n_pad, 256], A2 [256, 256], A3 [256, n_pad] per head), so every stage here is either
+//  - a batched fp32-MFMA product over general strides (k_tm_bgemm): the per-head operands are read straight out of the
+//    merged [n_pad, 3 x 512] q|k|v rows of to_qkv, and the results are written straight into merged-head rows, with the
+//    `c I - P` epilogue of the Newton-Schulz pseudo-inverse and split-K (atomic accumulation) for the long-K products;
+//  - a row-wise pass (softmax fwd/bwd, landmark means, the 33-tap residual conv on v, the pseudo-inverse's scale), or
+//  - the PPEG depthwise 7 x 7 (the 7 / 5 / 3 kernels and the identity folded into one) and the row gather of the
+//    sequence assembly ([cls | tokens | repeats], front zero pad).
+// Heads fixed at 8 x 64 (TransLayer: dim 512, dim_head 64), 256 landmarks, conv kernel 33.
+#include <hip/hip_runtime.h>
+
+#include "mil_common.h"
+#include "../../include/mil_hip.h"
+
+namespace {
+
+constexpr int TM_H = 8, TM_DH = 64, TM_D = 512, TM_QKV = 3 * TM_D, TM_M = 256, TM_CONV = 33;
+constexpr int BG_BK = 16, BG_LD = 64 + 4;
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// C[b] = alpha A[b] B[b] + beta D[b] + diag I (D = C when null; D[b] laid out like C[b]), element (i, k) of A[b] at
+// A + b sAb + i sAi + k sAk (likewise B, C).
+// 64 x 64 tile, 2 x 2 waves of one 32 x 32 MFMA accumulator each, K staged 16 at a time through LDS (k-major images,
+// the register copy of the next slice loaded while the current one is multiplied).  blockIdx.z = batch * splits + split;
+// splits > 1 adds the partial products atomically (the caller has C initialised; beta must be 1, D null).
+__global__ __launch_bounds__(256) void k_tm_bgemm(const float* __restrict__ A, long sAb, long sAi, long sAk,
+                                                  const float* __restrict__ B, long sBb, long sBk, long sBj, float* C,
+                                                  long sCb, long sCi, long sCj, const float* D, int M, int N, int K,
+                                                  float alpha, float beta, float diag, int splits) {
+    __shared__ float as[BG_BK][BG_LD];
+    __shared__ float bs[BG_BK][BG_LD];
+    const int bz = blockIdx.z / splits, split = blockIdx.z % splits;
+    const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wi = wave >> 1, wj = wave & 1, r = lane & 31, h = lane >> 5;
+    A += (long)bz * sAb;
+    B += (long)bz * sBb;
+    C += (long)bz * sCb;
+    if (D != nullptr) D += (long)bz * sCb;
+    const int kslices = (K + BG_BK - 1) / BG_BK;
+    const int per = (kslices + splits - 1) / splits;
+    const int s0 = split * per, s1 = min(kslices, s0 + per);
+    const bool a_krow = sAk == 1, b_jrow = sBj == 1;
+
+    float ra[4], rb[4];
+    auto load = [&](int ks) {
+        const int k0 = ks * BG_BK;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int e = tid + 256 * p;
+            const int ai = a_krow ? e >> 4 : e & 63, ak = a_krow ? e & 15 : e >> 6;
+            const int gi = i0 + ai, gk = k0 + ak;
+            ra[p] = (gi < M && gk < K) ? A[gi * sAi + gk * sAk] : 0.f;
+            const int bj = b_jrow ? e & 63 : e >> 4, bk = b_jrow ? e >> 6 : e & 15;
+            const int gj = j0 + bj, gk2 = k0 + bk;
+            rb[p] = (gj < N && gk2 < K) ? B[gk2 * sBk + gj * sBj] : 0.f;
+        }
+    };
+    auto store = [&]() {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int e = tid + 256 * p;
+            const int ai = a_krow ? e >> 4 : e & 63, ak = a_krow ? e & 15 : e >> 6;
+            as[ak][ai] = ra[p];
+            const int bj = b_jrow ? e & 63 : e >> 4, bk = b_jrow ? e >> 6 : e & 15;
+            bs[bk][bj] = rb[p];
+        }
+    };
+
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    if (s0 < s1) load(s0);
+    for (int ks = s0; ks < s1; ++ks) {
+        store();
+        __syncthreads();
+        if (ks + 1 < s1) load(ks + 1);
+#pragma unroll
+        for (int kk = 0; kk < BG_BK / 2; ++kk)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[2 * kk + h][32 * wi + r], bs[2 * kk + h][32 * wj + r], acc, 0, 0, 0);
+        __syncthreads();
+    }
+
+    const int col = j0 + 32 * wj + r;
+    if (col >= N) return;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int row = i0 + 32 * wi + mfma32_row(i, h);
+        if (row >= M) continue;
+        float* cp = C + row * sCi + col * sCj;
+        float v = alpha * acc[i];
+        if (splits == 1) {
+            if (beta != 0.f) v += beta * (D != nullptr ? D[row * sCi + col * sCj] : *cp);
+            if (row == col) v += diag;
+            *cp = v;
+        } else {
+            if (row == col && split == 0) v += diag;
+            atomicAdd(cp, v);
+        }
+    }
+}
+
+// in place: x[row] = softmax(x[row]); one wave per row
+__global__ __launch_bounds__(256) void k_tm_softmax(float* x, long rows, int cols) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    float* p = x + row * cols;
+    float m = -INFINITY;
+    for (int j = lane; j < cols; j += 64) m = fmaxf(m, p[j]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int j = lane; j < cols; j += 64) s += __expf(p[j] - m);
+    s = wave_sum(s);
+    const float inv = 1.f / s;
+    for (int j = lane; j < cols; j += 64) p[j] = __expf(p[j] - m) * inv;
+}
+
+// in place: dp[row] = p (dp - <p, dp>)
+__global__ __launch_bounds__(256) void k_tm_softmax_bwd(const float* p, float* dp, long rows, int cols) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float* pr = p + row * cols;
+    float* dr = dp + row * cols;
+    float s = 0.f;
+    for (int j = lane; j < cols; j += 64) s += pr[j] * dr[j];
+    s = wave_sum(s);
+    for (int j = lane; j < cols; j += 64) dr[j] = pr[j] * (dr[j] - s);
+}
+
+// dst[r] = idx[r] >= 0 ? src[idx[r]] : idx[r] == -2 ? extra : 0
+__global__ __launch_bounds__(256) void k_tm_gather(const float* __restrict__ src, const float* __restrict__ extra,
+                                                   const int32_t* __restrict__ idx, int E, float* __restrict__ dst) {
+    const int r = blockIdx.x, id = idx[r];
+    const float* s = id >= 0 ? src + (long)id * E : extra;
+    for (int c = threadIdx.x; c < E; c += 256) dst[(long)r * E + c] = (id >= 0 || id == -2) ? s[c] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_tm_gather_bwd(const float* __restrict__ ddst, const int32_t* __restrict__ idx, int E,
+                                                       float* dsrc, float* dextra) {
+    const int r = blockIdx.x, id = idx[r];
+    if (id == -1 || (id == -2 && dextra == nullptr)) return;
+    float* d = id >= 0 ? dsrc + (long)id * E : dextra;
+    for (int c = threadIdx.x; c < E; c += 256) atomicAdd(d + c, ddst[(long)r * E + c]);
+}
+
+// qL [8, 256, 64] = qscale * mean of l consecutive q rows, kL the same of k (no scale); thread per (landmark, q|k column)
+__global__ __launch_bounds__(256) void k_tm_landmarks(const float* __restrict__ qkv, int l, float qscale, float* qL, float* kL) {
+    const int j = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;        // c < 1024
+    float s = 0.f;
+    for (int t = 0; t < l; ++t) s += qkv[(long)(j * l + t) * TM_QKV + c];
+    const int cc = c & (TM_D - 1), hh = cc >> 6, d = cc & 63;
+    if (c < TM_D) qL[(hh * TM_M + j) * TM_DH + d] = s * (qscale / l);
+    else kL[(hh * TM_M + j) * TM_DH + d] = s / l;
+}
+
+// dqkv[i][q | k column] += coef * d(qL | kL)[head][i / l][d]
+__global__ __launch_bounds__(256) void k_tm_landmarks_bwd(const float* __restrict__ dqL, const float* __restrict__ dkL, int l,
+                                                          float qscale, float* dqkv) {
+    const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    const int cc = c & (TM_D - 1), hh = cc >> 6, d = cc & 63, j = i / l;
+    const float g = c < TM_D ? dqL[(hh * TM_M + j) * TM_DH + d] * (qscale / l) : dkL[(hh * TM_M + j) * TM_DH + d] / l;
+    dqkv[(long)i * TM_QKV + c] += g;
+}
+
+// per head h (one workgroup each): out[3 + h] = max row abs-sum, out[11 + h] = max column abs-sum, arg[1 + h] = h * 256 +
+// column of the largest column sum (first on ties).  Rows: one wave per row, coalesced; columns: one thread per column.
+__global__ __launch_bounds__(256) void k_tm_pinv_scale(const float* __restrict__ A2, float* out, int32_t* arg) {
+    __shared__ float sr[4], sc[256];
+    __shared__ int si[256];
+    const int t = threadIdx.x, hh = blockIdx.x, lane = t & 63, wv = t >> 6;
+    const float* a = A2 + (long)hh * TM_M * TM_M;
+    float mr = 0.f;
+    for (int i = wv; i < TM_M; i += 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(a + i * TM_M + 4 * lane);
+        mr = fmaxf(mr, wave_sum(fabsf(v[0]) + fabsf(v[1]) + fabsf(v[2]) + fabsf(v[3])));
+    }
+    float cs = 0.f;
+    for (int j = 0; j < TM_M; ++j) cs += fabsf(a[j * TM_M + t]);
+    if (lane == 0) sr[wv] = mr;
+    sc[t] = cs;
+    si[t] = hh * TM_M + t;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            const float c2 = sc[t + o];
+            const int i2 = si[t + o];
+            if (c2 > sc[t] || (c2 == sc[t] && i2 < si[t])) { sc[t] = c2; si[t] = i2; }
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[3 + hh] = fmaxf(fmaxf(sr[0], sr[1]), fmaxf(sr[2], sr[3]));
+        out[3 + TM_H + hh] = sc[0];
+        arg[1 + hh] = si[0];
+    }
+}
+
+// the bag's scale from the 8 heads' maxima (every thread, from cache), then Z0[h][i][j] = A2[h][j][i] / scale; the first
+// thread stores out[0] = max row abs-sum x max column abs-sum, out[1] / out[2] the two factors, arg[0] the arg-max column
+__global__ __launch_bounds__(256) void k_tm_pinv_init(const float* __restrict__ A2, float* scale, int32_t* arg, float* Z) {
+    float mr = 0.f, mc = -1.f;
+    int ic = 0;
+#pragma unroll
+    for (int hh = 0; hh < TM_H; ++hh) {
+        mr = fmaxf(mr, scale[3 + hh]);
+        if (scale[3 + TM_H + hh] > mc) { mc = scale[3 + TM_H + hh]; ic = arg[1 + hh]; }
+    }
+    const float sv = mr * mc;
+    const int e = blockIdx.x * 256 + threadIdx.x;              // < 8 * 256 * 256
+    const int hh = e >> 16, i = (e >> 8) & 255, j = e & 255;
+    Z[e] = A2[(hh << 16) + (j << 8) + i] / sv;
+    if (e == 0) {
+        scale[0] = sv;
+        scale[1] = mr;
+        scale[2] = mc;
+        arg[0] = ic;
+    }
+}
+
+// ws[0] += <dZ0, Z0> over 2048-element chunks (ws caller-zeroed)
+__global__ __launch_bounds__(256) void k_tm_pinv_dot(const float* __restrict__ dZ0, const float* __restrict__ Z0, float* ws) {
+    __shared__ float red[4];
+    const int base = blockIdx.x * 2048;
+    float s = 0.f;
+    for (int e = base + threadIdx.x; e < base + 2048; e += 256) s += dZ0[e] * Z0[e];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(ws, red[0] + red[1] + red[2] + red[3]);
+}
+
+// dA2[h][i][j] += dZ0[h][j][i] / s
+__global__ __launch_bounds__(256) void k_tm_pinv_init_bwd_t(const float* __restrict__ dZ0, const float* __restrict__ scale,
+                                                            float* dA2) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int hh = e >> 16, i = (e >> 8) & 255, j = e & 255;
+    dA2[e] += dZ0[(hh << 16) + (j << 8) + i] / scale[0];
+}
+
+// the scale's gradient ds = -<dZ0, Z0> / s (ws[0], k_tm_pinv_dot) goes to the arg-max column through its column-sum
+// factor: dA2[h*][i][j*] += ds * (max row abs-sum) (A2 > 0 after softmax, so |.|' = 1).  One workgroup, one thread per row.
+__global__ __launch_bounds__(256) void k_tm_pinv_init_bwd_s(const float* __restrict__ ws, const float* __restrict__ scale,
+                                                            const int32_t* __restrict__ arg, float* dA2) {
+    const int t = threadIdx.x;
+    const float ds = -ws[0] / scale[0];
+    const int hh = arg[0] >> 8, jc = arg[0] & 255;
+    dA2[(hh << 16) + (t << 8) + jc] += ds * scale[1];
+}
+
+// out[i][c] += sum_t w[head][t] v[i + t - 16][c] (v = columns 1024.. of qkv, zero outside [0, n_pad))
+__global__ __launch_bounds__(256) void k_tm_resconv(const float* __restrict__ qkv, const float* __restrict__ w, int n, float* out) {
+    const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x, hh = c >> 6;
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < TM_CONV; ++t) {
+        const int ii = i + t - TM_CONV / 2;
+        if (ii >= 0 && ii < n) s += w[hh * TM_CONV + t] * qkv[(long)ii * TM_QKV + 2 * TM_D + c];
+    }
+    out[(long)i * TM_D + c] += s;
+}
+
+// dv[i][c] += sum_t w[head][t] dout[i - t + 16][c], into the v columns of dqkv
+__global__ __launch_bounds__(256) void k_tm_resconv_bwd_dv(const float* __restrict__ dout, const float* __restrict__ w, int n,
+                                                           float* dqkv) {
+    const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x, hh = c >> 6;
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < TM_CONV; ++t) {
+        const int ii = i - t + TM_CONV / 2;
+        if (ii >= 0 && ii < n) s += w[hh * TM_CONV + t] * dout[(long)ii * TM_D + c];
+    }
+    dqkv[(long)i * TM_QKV + 2 * TM_D + c] += s;
+}
+
+// dw[head][t] += sum over a chunk of rows i and d of dout[i][head, d] v[i + t - 16][head, d]; block (head * 33 + t, chunk)
+constexpr int RC_CHUNK = 256;
+__global__ __launch_bounds__(256) void k_tm_resconv_bwd_dw(const float* __restrict__ dout, const float* __restrict__ qkv, int n,
+                                                           float* dw) {
+    __shared__ float red[4];
+    const int hh = blockIdx.x / TM_CONV, t = blockIdx.x % TM_CONV;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = hh * TM_DH + lane;
+    const int r0 = blockIdx.y * RC_CHUNK, r1 = min(n, r0 + RC_CHUNK);
+    float s = 0.f;
+    for (int i = r0 + wv; i < r1; i += 4) {
+        const int ii = i + t - TM_CONV / 2;
+        if (ii >= 0 && ii < n) s += dout[(long)i * TM_D + c] * qkv[(long)ii * TM_QKV + 2 * TM_D + c];
+    }
+    s = wave_sum(s);
+    if (lane == 0) red[wv] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(dw + blockIdx.x, red[0] + red[1] + red[2] + red[3]);
+}
+
+// PPEG: y[1 + i s + j][c] = bias[c] + sum_{a,b < 7} Wf[c][a][b] x[1 + (i + a - 3) s + (j + b - 3)][c], y[0] = x[0];
+// Wf = W7 + pad(W5) + pad(W3) + delta, bias = b7 + b5 + b3.  flip = 1: the transposed map (dx from dy, no bias).
+constexpr int PPEG_COLS = 8;      // grid columns per workgroup: s rows x 2 channel halves x ceil(s / 8) workgroups
+__device__ __forceinline__ void tm_ppeg_fold(const float* W7, const float* W5, const float* W3, int c, float* wf) {
+#pragma unroll
+    for (int a = 0; a < 7; ++a)
+#pragma unroll
+        for (int b = 0; b < 7; ++b) {
+            float v = W7[c * 49 + a * 7 + b];
+            if (a >= 1 && a < 6 && b >= 1 && b < 6) v += W5[c * 25 + (a - 1) * 5 + (b - 1)];
+            if (a >= 2 && a < 5 && b >= 2 && b < 5) v += W3[c * 9 + (a - 2) * 3 + (b - 2)];
+            if (a == 3 && b == 3) v += 1.f;
+            wf[a * 7 + b] = v;
+        }
+}
+
+__global__ __launch_bounds__(256) void k_tm_ppeg(const float* __restrict__ x, int s, const float* __restrict__ W7,
+                                                 const float* __restrict__ b7, const float* __restrict__ W5,
+                                                 const float* __restrict__ b5, const float* __restrict__ W3,
+                                                 const float* __restrict__ b3, int flip, float* __restrict__ y) {
+    const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    float wf[49];
+    tm_ppeg_fold(W7, W5, W3, c, wf);
+    const float bias = flip ? 0.f : b7[c] + b5[c] + b3[c];
+    if (i == 0 && blockIdx.z == 0) y[c] = x[c];
+    const int j0 = blockIdx.z * PPEG_COLS, j1 = min(s, j0 + PPEG_COLS);
+    for (int j = j0; j < j1; ++j) {
+        float acc = bias;
+#pragma unroll
+        for (int a = 0; a < 7; ++a) {
+            const int ii = flip ? i - (a - 3) : i + (a - 3);
+            if (ii < 0 || ii >= s) continue;
+#pragma unroll
+            for (int b = 0; b < 7; ++b) {
+                const int jj = flip ? j - (b - 3) : j + (b - 3);
+                if (jj < 0 || jj >= s) continue;
+                acc += wf[a * 7 + b] * x[(long)(1 + ii * s + jj) * TM_D + c];
+            }
+        }
+        y[(long)(1 + i * s + j) * TM_D + c] = acc;
+    }
+}
+
+// dWf[c][tap] (tap < 49) and db[c] (tap 49) += sums over a chunk of 8 grid rows; thread per (tap, channel)
+constexpr int PPEG_ROWS = 8;
+__global__ __launch_bounds__(256) void k_tm_ppeg_dw(const float* __restrict__ dy, const float* __restrict__ x, int s, float* dWf,
+                                                    float* db) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= 50 * TM_D) return;
+    const int tap = e / TM_D, c = e % TM_D, a = tap / 7 - 3, b = tap % 7 - 3;
+    const int r0 = blockIdx.y * PPEG_ROWS, r1 = min(s, r0 + PPEG_ROWS);
+    float acc = 0.f;
+    for (int i = r0; i < r1; ++i) {
+        if (tap == 49) {
+            for (int j = 0; j < s; ++j) acc += dy[(long)(1 + i * s + j) * TM_D + c];
+            continue;
+        }
+        const int ii = i + a;
+        if (ii < 0 || ii >= s) continue;
+        for (int j = max(0, -b); j < min(s, s - b); ++j)
+            acc += dy[(long)(1 + i * s + j) * TM_D + c] * x[(long)(1 + ii * s + j + b) * TM_D + c];
+    }
+    if (tap == 49) atomicAdd(db + c, acc);
+    else atomicAdd(dWf + c * 49 + tap, acc);
+}
+
+inline int launch_rc() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MIL_OK : (int)e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mil_tm_bgemm(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C, long sCb,
+                 long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta, float diag,
+                 int splits, void* stream) {
+    if (!A || !B || !C || batch <= 0 || M <= 0 || N <= 0 || K <= 0 || splits <= 0 ||
+        (splits > 1 && (beta != 1.f || D != nullptr)))
+        return MIL_EINVAL;
+    if ((M + 63) / 64 > 65535 || (long)batch * splits > 65535) return MIL_EINVAL;
+    dim3 grid((N + 63) / 64, (M + 63) / 64, batch * splits);
+    hipLaunchKernelGGL(k_tm_bgemm, grid, dim3(256), 0, (hipStream_t)stream, A, sAb, sAi, sAk, B, sBb, sBk, sBj, C, sCb, sCi,
+                       sCj, D, M, N, K, alpha, beta, diag, splits);
+    return launch_rc();
+}
+
+int mil_tm_softmax_rows(float* x, long rows, int cols, void* stream) {
+    if (!x || rows <= 0 || cols <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_softmax, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, rows, cols);
+    return launch_rc();
+}
+
+int mil_tm_softmax_rows_bwd(const float* p, float* dp, long rows, int cols, void* stream) {
+    if (!p || !dp || rows <= 0 || cols <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_softmax_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, dp, rows, cols);
+    return launch_rc();
+}
+
+int mil_tm_row_gather(const float* src, const float* extra, const int32_t* idx, int rows, int E, float* dst, void* stream) {
+    if (!src || !idx || !dst || rows <= 0 || E <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_gather, dim3(rows), dim3(256), 0, (hipStream_t)stream, src, extra, idx, E, dst);
+    return launch_rc();
+}
+
+int mil_tm_row_gather_bwd(const float* ddst, const int32_t* idx, int rows, int E, float* dsrc, float* dextra, void* stream) {
+    if (!ddst || !idx || !dsrc || rows <= 0 || E <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_gather_bwd, dim3(rows), dim3(256), 0, (hipStream_t)stream, ddst, idx, E, dsrc, dextra);
+    return launch_rc();
+}
+
+int mil_tm_landmarks(const float* qkv, int n_pad, float qscale, float* qL, float* kL, void* stream) {
+    if (!qkv || !qL || !kL || n_pad <= 0 || n_pad % TM_M) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_landmarks, dim3(TM_M, 4), dim3(256), 0, (hipStream_t)stream, qkv, n_pad / TM_M, qscale, qL, kL);
+    return launch_rc();
+}
+
+int mil_tm_landmarks_bwd(const float* dqL, const float* dkL, int n_pad, float qscale, float* dqkv, void* stream) {
+    if (!dqL || !dkL || !dqkv || n_pad <= 0 || n_pad % TM_M) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_landmarks_bwd, dim3(n_pad, 4), dim3(256), 0, (hipStream_t)stream, dqL, dkL, n_pad / TM_M, qscale, dqkv);
+    return launch_rc();
+}
+
+int mil_tm_pinv_init(const float* A2, float* scale, int32_t* arg, float* Z0, void* stream) {
+    if (!A2 || !scale || !arg || !Z0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_pinv_scale, dim3(TM_H), dim3(256), 0, (hipStream_t)stream, A2, scale, arg);
+    hipLaunchKernelGGL(k_tm_pinv_init, dim3(TM_H * TM_M * TM_M / 256), dim3(256), 0, (hipStream_t)stream, A2, scale, arg, Z0);
+    return launch_rc();
+}
+
+int mil_tm_pinv_init_bwd(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
+                         void* stream) {
+    if (!dZ0 || !Z0 || !scale || !arg || !dA2 || !ws) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_pinv_init_bwd_t, dim3(TM_H * TM_M * TM_M / 256), dim3(256), 0, (hipStream_t)stream, dZ0, scale, dA2);
+    hipLaunchKernelGGL(k_tm_pinv_dot, dim3(TM_H * TM_M * TM_M / 2048), dim3(256), 0, (hipStream_t)stream, dZ0, Z0, ws);
+    hipLaunchKernelGGL(k_tm_pinv_init_bwd_s, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, scale, arg, dA2);
+    return launch_rc();
+}
+
+int mil_tm_resconv(const float* qkv, const float* w, int n_pad, float* out, void* stream) {
+    if (!qkv || !w || !out || n_pad <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_resconv, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, qkv, w, n_pad, out);
+    return launch_rc();
+}
+
+int mil_tm_resconv_bwd(const float* dout, const float* qkv, const float* w, int n_pad, float* dqkv, float* dw, void* stream) {
+    if (!dout || !qkv || !w || !dqkv || !dw || n_pad <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dv, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, dout, w, n_pad, dqkv);
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dw, dim3(TM_H * TM_CONV, (n_pad + RC_CHUNK - 1) / RC_CHUNK), dim3(256), 0,
+                       (hipStream_t)stream, dout, qkv, n_pad, dw);
+    return launch_rc();
+}
+
+int mil_tm_ppeg_fwd(const float* x, int s, const float* W7, const float* b7, const float* W5, const float* b5, const float* W3,
+                    const float* b3, float* y, void* stream) {
+    if (!x || !W7 || !b7 || !W5 || !b5 || !W3 || !b3 || !y || s <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_ppeg, dim3(s, 2, (s + PPEG_COLS - 1) / PPEG_COLS), dim3(256), 0, (hipStream_t)stream, x, s, W7, b7, W5, b5, W3, b3, 0, y);
+    return launch_rc();
+}
+
+int mil_tm_ppeg_bwd(const float* dy, const float* x, int s, const float* W7, const float* W5, const float* W3, float* dx,
+                    float* dWf, float* db, void* stream) {
+    if (!dy || !x || !W7 || !W5 || !W3 || !dx || !dWf || !db || s <= 0) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_ppeg, dim3(s, 2, (s + PPEG_COLS - 1) / PPEG_COLS), dim3(256), 0, (hipStream_t)stream, dy, s, W7, W7, W5, W5, W3, W3, 1, dx);
+    hipLaunchKernelGGL(k_tm_ppeg_dw, dim3((50 * TM_D + 255) / 256, (s + PPEG_ROWS - 1) / PPEG_ROWS), dim3(256), 0,
+                       (hipStream_t)stream, dy, x, s, dWf, db);
+    return launch_rc();
+}
+
+}  // extern "C"

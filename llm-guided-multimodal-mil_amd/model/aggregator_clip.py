@@ -1,6 +1,6 @@
 """Image-only variant (reference: model/aggregator_clip.py:6-118, pathology branch :109-118):
-`forward(x_list) -> (bag_embedding [B, L], sigmoid(fc(bag_embedding)) [B, C])` with ABMIL straight on
-the patch features.  This is BASELINE config 2's model; `trainer.ImageOnlyTrainer` is its fused step."""
+`forward(x_list) -> (bag_embedding [B, F], sigmoid(fc(bag_embedding)) [B, C])` with ABMIL (F = L) or TransMIL (F = 512,
+--model_pathology TransMIL) straight on the patch features.  This is BASELINE config 2's model; `trainer.ImageOnlyTrainer` is its fused step."""
 from typing import List, Optional
 
 import torch
@@ -8,22 +8,31 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .dim1 import ABMIL
+from .dim1 import ABMIL, TransMIL
 
 
 class aggregator(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
-        if list(args.modality) != ["pathology"] or getattr(args, "model_pathology", "ABMIL") != "ABMIL":
-            raise NotImplementedError("aggregator_clip: only modality ['pathology'] with ABMIL is on the built path")
+        which = getattr(args, "model_pathology", "ABMIL")
+        if list(args.modality) != ["pathology"] or which not in ("ABMIL", "TransMIL"):
+            raise NotImplementedError("aggregator_clip: only modality ['pathology'] with ABMIL or TransMIL is on the built path")
         L = int(getattr(args, "patch_dim", 768))                     # aggregator_clip.py:36
-        self.extractor_pathology = ABMIL(args, L=L)
-        self.fc = nn.Sequential(nn.Dropout(0.25), nn.Linear(L, args.num_classes))
+        if which == "TransMIL":
+            # aggregator_clip.py:47-52: the extractor gives h [B, 512] (its cls row), the head is Linear(512, C)
+            self.extractor_pathology = TransMIL(n_classes=args.num_classes, L=L)
+            F_out = self.extractor_pathology.D
+        else:
+            self.extractor_pathology = ABMIL(args, L=L)
+            F_out = L
+        self.fc = nn.Sequential(nn.Dropout(0.25), nn.Linear(F_out, args.num_classes))
         self.last_logits: Optional[torch.Tensor] = None
 
     def forward(self, x_list: List[torch.Tensor], lengths=None):
         M = self.extractor_pathology(x_list[0], lengths)
+        if isinstance(M, tuple):                     # TransMIL: (h, [attn0, attn1])
+            M = M[0]
         h = M
         if self.training and M.shape[1] % 32 == 0:
             # Dropout(.25) in front of the head (aggregator_clip.py / aggregator.py:129) from the SAME stream as the fused

@@ -1,0 +1,156 @@
+"""TransMIL (reference: model/dim1/TransMIL.py:8-107 with nystrom_attention's NystromAttention in its TransLayer), MI355X path.
+
+Same constructor, parameter names and output `(h [B, 512], [attn0, attn1])`.  Input: flat rows [R, L] plus per-bag lengths, or
+[B, N, L] / [N, L].  Each bag runs alone (its own square padding, front pad and landmarks): a batch is B independent bags.
+The one deliberate difference from upstream is there for B > 1 only: the pseudo-inverse's starting scale (max row sum x max
+column sum of softmax(qL kL^T)) is taken per bag over its 8 heads, where upstream takes it over the whole batch.
+
+Hot path: _fc1 / to_qkv / to_out on mil_gemm (ops.linear_act), LayerNorm on mil_layernorm_*, the Nystrom core, PPEG and the
+sequence assembly on csrc/transmil.hip (ops.nystrom_core, ops.tm_ppeg, ops.tm_row_gather).  Train mode: to_out's Dropout(0.1)
+draws Philox keep bits from the module's seed and a device pass counter, as ABMIL's masks do."""
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+import torch.nn as nn
+
+from ... import ops
+
+TM_DROP_P = 0.1
+
+
+def geometry(N: int) -> dict:
+    """Per-bag shapes: grid side s, repeated rows add, sequence rows seq = s^2 + 1 (cls first), n_pad = 256 ceil(seq / 256),
+    landmark group l = n_pad / 256, front zero pad rows."""
+    s = int(math.ceil(math.sqrt(N)))
+    add = s * s - N
+    seq = s * s + 1
+    n_pad = ops.TM_M * -(-seq // ops.TM_M)
+    return dict(N=N, s=s, add=add, seq=seq, n_pad=n_pad, l=n_pad // ops.TM_M, pad=n_pad - seq)
+
+
+class NystromAttention(nn.Module):
+    """Parameters of nystrom_attention.NystromAttention(dim=512, dim_head=64, heads=8, num_landmarks=256, pinv_iterations=6,
+    residual=True, dropout=0.1): to_qkv (no bias), to_out = Linear + Dropout, res_conv = depthwise (33, 1) over the heads."""
+
+    def __init__(self, dim: int = 512, heads: int = 8, dim_head: int = 64, dropout: float = TM_DROP_P):
+        super().__init__()
+        self.heads = heads
+        self.to_qkv = nn.Linear(dim, 3 * heads * dim_head, bias=False)
+        self.to_out = nn.Sequential(nn.Linear(heads * dim_head, dim), nn.Dropout(dropout))
+        self.res_conv = nn.Conv2d(heads, heads, (ops.TM_CONV, 1), padding=(ops.TM_CONV // 2, 0), groups=heads, bias=False)
+
+
+class TransLayer(nn.Module):
+    def __init__(self, norm_layer=nn.LayerNorm, dim: int = 512):
+        super().__init__()
+        self.norm = norm_layer(dim)
+        self.attn = NystromAttention(dim=dim)
+
+    def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn: bool):
+        """x [seq, 512] of one bag -> (x + to_out(Nystrom(LN(x)))[last seq rows], attn map or None)."""
+        a = self.attn
+        ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
+        xp = ops.tm_row_gather(ln, None, pad_idx)                                   # zero rows in front: [n_pad, 512]
+        qkv = ops.linear_act(xp, a.to_qkv.weight, None)
+        o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn)
+        o = o[g["pad"]:]
+        lin = a.to_out[0]
+        if bits is None:
+            y = ops.linear_act(o, lin.weight, lin.bias, residual=x)
+        else:
+            y = x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
+        return y, attn
+
+
+class PPEG(nn.Module):
+    def __init__(self, dim: int = 512):
+        super().__init__()
+        self.proj = nn.Conv2d(dim, dim, 7, 1, 7 // 2, groups=dim)
+        self.proj1 = nn.Conv2d(dim, dim, 5, 1, 5 // 2, groups=dim)
+        self.proj2 = nn.Conv2d(dim, dim, 3, 1, 3 // 2, groups=dim)
+
+    def run(self, x: torch.Tensor, s: int) -> torch.Tensor:
+        return ops.tm_ppeg(x, s, self.proj.weight, self.proj.bias, self.proj1.weight, self.proj1.bias, self.proj2.weight,
+                           self.proj2.bias)
+
+
+class TransMIL(nn.Module):
+    def __init__(self, n_classes: int, L: int = 768, D: int = 512, K: int = 1):
+        super().__init__()
+        if D != ops.TM_D or K != 1:
+            raise NotImplementedError("the HIP TransMIL kernels are built for D=512 (8 heads x 64), K=1 (the reference's values)")
+        self.L, self.D, self.K = L, D, K
+        self.pos_layer = PPEG(dim=D)
+        self._fc1 = nn.Sequential(nn.Linear(L, D), nn.ReLU())
+        self.cls_token = nn.Parameter(torch.randn(1, 1, D))
+        self.n_classes = n_classes
+        self.layer1 = TransLayer(dim=D)
+        self.layer2 = TransLayer(dim=D)
+        self.norm = nn.LayerNorm(D)
+        self._fc2 = nn.Linear(D, n_classes)          # upstream keeps it but never calls it (TransMIL.py:99-104)
+        self._drop_seed: Optional[int] = None
+        self._drop_ctr: Optional[torch.Tensor] = None
+        self.last_bits: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None
+        self.force_bits: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None   # tests: masks supplied from outside
+
+    def _drop_state(self, device):
+        if self._drop_seed is None:
+            self._drop_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if self._drop_ctr is None or self._drop_ctr.device != device:
+            self._drop_ctr = torch.zeros(1, device=device, dtype=torch.int32)
+
+    def _bits(self, b: int, seq: int, device):
+        """Keep bits of the two Dropout(0.1) of bag b: key seed ^ layer, stream offset 2 b (+1) + the device pass counter."""
+        if self.force_bits is not None:
+            return self.force_bits[b]
+        return tuple(ops.dropout_keep_bits(seq, self.D, TM_DROP_P, self._drop_seed ^ (0x5472616E734D494C + j), 2 * b + j, device,
+                                           offset_dev=self._drop_ctr) for j in range(2))
+
+    def forward(self, x: torch.Tensor, lengths: Optional[Sequence[int]] = None, need_attn: bool = False):
+        if x.dim() == 2 and lengths is None:
+            x = x.unsqueeze(0)
+        if x.dim() == 3:
+            B, N, L = x.shape
+            lengths = [N] * B
+            x = x.reshape(B * N, L)
+        lengths = [int(n) for n in lengths]
+        if min(lengths) < 1 or sum(lengths) != x.shape[0]:
+            raise ValueError(f"TransMIL: lengths {lengths} do not cover the {x.shape[0]} rows")
+        dev = x.device
+        h = ops.linear_act(x, self._fc1[0].weight, self._fc1[0].bias, "relu")        # [R, 512]
+        geo = [geometry(n) for n in lengths]
+        # [cls | tokens | first `add` tokens again] per bag, one gather for all bags; index -2 = the cls row
+        idx, off = [], 0
+        for g in geo:
+            idx += [-2] + list(range(off, off + g["N"])) + list(range(off, off + g["add"]))
+            off += g["N"]
+        idx_dev = torch.tensor(idx, dtype=torch.int32).to(dev, non_blocking=True)
+        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev)
+        train = self.training
+        if train:
+            self._drop_state(dev)
+        cls_rows, attn0, attn1, bits_used = [], [], [], []
+        row = 0
+        for b, g in enumerate(geo):
+            xb = seqs[row:row + g["seq"]]
+            row += g["seq"]
+            pad_idx = torch.tensor([-1] * g["pad"] + list(range(g["seq"])), dtype=torch.int32).to(dev, non_blocking=True)
+            bits = self._bits(b, g["seq"], dev) if train else (None, None)
+            bits_used.append(bits)
+            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn)
+            xb = self.pos_layer.run(xb, g["s"])
+            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn)
+            cls_rows.append(xb[:1])
+            attn0.append(a0)
+            attn1.append(a1)
+        if train and self.force_bits is None:
+            ops.counter_add(self._drop_ctr, 1)
+        self.last_bits = bits_used if train else None
+        hc = cls_rows[0] if len(cls_rows) == 1 else torch.cat(cls_rows, 0)
+        out = ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps)     # norm of the cls rows only
+        if not need_attn:
+            return out, [None, None]
+        if len(geo) == 1:
+            return out, [attn0[0].unsqueeze(0), attn1[0].unsqueeze(0)]
+        return out, [attn0, attn1]                   # ragged bags: one [8, n_pad, n_pad] map per bag

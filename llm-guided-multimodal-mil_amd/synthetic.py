@@ -71,6 +71,27 @@ def image_only_params(seed: int = 1234, L: int = 512, D: int = 192, C: int = 2) 
     return p
 
 
+def transmil_params(seed: int = 1234, L: int = 768, C: int = 2, D: int = 512, prefix: str = "") -> Params:
+    """model/dim1/TransMIL.py state_dict with nn-default magnitudes: Linear / Conv2d U(-1/sqrt(fan_in), +), cls_token N(0, 1),
+    LayerNorms 1 / 0 with the small seeded jitter of _put_ln (heads 8 x 64, res_conv (33, 1) per head)."""
+    g = _gen(seed)
+    p: Params = {}
+    for name, k in (("pos_layer.proj", 7), ("pos_layer.proj1", 5), ("pos_layer.proj2", 3)):
+        bound = 1.0 / k
+        p[prefix + name + ".weight"] = _uniform(g, (D, 1, k, k), bound)
+        p[prefix + name + ".bias"] = _uniform(g, (D,), bound)
+    _put_linear(p, g, prefix + "_fc1.0", D, L)
+    p[prefix + "cls_token"] = _normal(g, (1, 1, D), 1.0)
+    for layer in ("layer1", "layer2"):
+        _put_ln(p, g, f"{prefix}{layer}.norm", D)
+        p[f"{prefix}{layer}.attn.to_qkv.weight"] = _uniform(g, (3 * D, D), 1.0 / math.sqrt(D))
+        _put_linear(p, g, f"{prefix}{layer}.attn.to_out.0", D, D)
+        p[f"{prefix}{layer}.attn.res_conv.weight"] = _uniform(g, (8, 1, 33, 1), 1.0 / math.sqrt(33))
+    _put_ln(p, g, prefix + "norm", D)
+    _put_linear(p, g, prefix + "_fc2", C, D)
+    return p
+
+
 def attention_params(p: Params, g: torch.Generator, name: str, E: int, internal: int) -> None:
     """model/sam/transformer.py:413-416."""
     _put_linear(p, g, name + ".q_proj", internal, E)

@@ -47,6 +47,11 @@ def main_worker(local_rank: int, nprocs: int, args):
         gpu = int(args.gpu.split(",")[local_rank])
     else:
         world, rank, gpu = env_world()
+    if args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL" and (
+            args.fused_step or getattr(args, "hip_graph", 0)):
+        # the fused ImageOnlyTrainer is ABMIL's step, and TransMIL's per-bag geometry (square padding, n_pad) is built on
+        # the host every forward, which a captured graph cannot replay
+        raise ValueError("--model_pathology TransMIL runs on the autograd path only: drop --fused_step / --hip_graph")
     torch.cuda.set_device(gpu)
     dev = torch.device("cuda", gpu)
     if world > 1:
