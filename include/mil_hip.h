@@ -61,7 +61,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 6 */
+int mil_abi_version(void);   /* 7 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -329,6 +329,10 @@ int mil_gate_bwd_input_pool(const float* gates, const float* ds, const float* w,
  * arithmetic as the fp32 entry points on rounded inputs (model/dim1/ABMIL.py:47-59); the deviation from
  * the fp32 oracle is reported, the 1e-3 bar applies to the fp32 path.  L % 64 == 0 (gate), L in {512,1024} (pool). */
 int mil_cast_bf16(const float* src, uint16_t* dst, size_t n, void* stream);
+/* Three-piece split of the gate weights for the split-bf16 gate forward: Wp[(k/16)][q][(k/8)%2][n][k%8] = piece q of row n
+ * of [Wv; Wu] (n < 192: Wv) at column k, w = p0 + p1 + p2 exactly with p0 = bf16(w), p1 = bf16(w - p0), p2 = bf16(w - p0 - p1)
+ * (round to nearest even; p1 = p2 = 0 for a non-finite w).  L % 32 == 0, 16-byte aligned pointers. */
+int mil_gate_pieces(const float* Wv, const float* Wu, uint16_t* Wp, int L, void* stream);
 /* gates (fp32 [R, 384], nullable) and/or gates16 (bf16 [R, 384], nullable): the saved {V | U}.  The bf16 form is what
  * mil_gate_bwd_params_bf16 reads: half the bytes of the largest tensor of the step, written with 16-byte stores. */
 int mil_gate_scores_fwd_bf16(const uint16_t* x, const uint16_t* Wv, const float* bv, const uint16_t* Wu,
@@ -858,6 +862,9 @@ typedef struct mil_image_only_step {
     int32_t* done_dev;              /* nullable, with adam_step_dev: [1] sign-off word, zero before the first step and left zero by
                                      * every step - the fold launch that applies Adam then advances adam_step_dev itself (its last
                                      * workgroup to read the step number does it) instead of a one-thread launch behind it */
+    const uint16_t* Wp;             /* nullable, fp32 x: three-piece bf16 planes of [Wv; Wu] (mil_gate_pieces layout, 3 * 384 * L
+                                     * halves).  Given, the gate forward runs its split-bf16 MFMA loop and every Adam update this
+                                     * call applies rewrites the planes; NULL: the fp32-MFMA gate forward */
 } mil_image_only_step;
 
 int mil_image_only_step_run(const mil_image_only_step* a, void* stream);

@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -65,6 +65,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_patch_drop_select": (c_int, [_P, _P, _P, c_int, c_int, c_uint64, c_uint64, _P, _P]),
     "mil_cohort_feed": (c_int, [_P, _P, _P, _P, _P, _P]),
     "mil_cast_bf16": (c_int, [_P, _P, c_size_t, _P]),
+    "mil_gate_pieces": (c_int, [_P, _P, _P, c_int, _P]),
     "mil_gate_scores_fwd_bf16": (c_int, [_P] * 9 + [c_int, c_int, c_int, _P, _P, c_float, _P]),
     "mil_attn_pool_partial_bf16": (c_int, [_P] * 3 + [c_int, c_int, _P, _P, c_float, _P]),
     "mil_attn_pool_partial_h_bf16": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P, c_float, _P, c_float, _P]),
@@ -228,7 +229,7 @@ class ImageOnlyStep(ctypes.Structure):
         + [(n, _P) for n in ("param_flat", "grad_flat", "exp_avg", "exp_avg_sq")]
         + [("n_param", c_uint64), ("adam_step", c_int32), ("adam_step_dev", _P)]
         + [(n, c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale")]
-        + [("lr_dev", _P), ("tail_ws", _P), ("done_dev", _P)])
+        + [("lr_dev", _P), ("tail_ws", _P), ("done_dev", _P), ("Wp", _P)])
 
 
 _lib = None

@@ -5,6 +5,37 @@
 #define GR_NG 384
 #define GR_NB 16          // lanes per bias / w / b output in the reduce
 
+// Three-piece split-bf16 form of an fp32 value (the gate forward's MFMA operands, k_gate_fwd2<.., PW = true>):
+// v = p0 + p1 + p2 exactly, p0 = bf16(v), p1 = bf16(v - p0), p2 = bf16(v - p0 - p1) (round to nearest even).  A non-finite v
+// keeps p0 = bf16(v) (the infinity / NaN itself) and p1 = p2 = 0, so the split adds no NaN of its own; a finite v beyond the
+// largest bf16 (|v| >= 2^128 (1 - 2^-9)) rounds to p0 = +-inf the same way.
+__device__ __forceinline__ unsigned short gp_bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
+__device__ __forceinline__ float gp_bf16_val(unsigned short b) { return __uint_as_float(((unsigned)b) << 16); }
+__device__ __forceinline__ void gp_split3(float v, unsigned short& p0, unsigned short& p1, unsigned short& p2) {
+    p0 = gp_bf16_bits(v);
+    float r = v - gp_bf16_val(p0);
+    r = __builtin_isfinite(r) ? r : 0.f;
+    p1 = gp_bf16_bits(r);
+    p2 = gp_bf16_bits(r - gp_bf16_val(p1));
+}
+// Layout of the weight pieces Wp of [Wv; Wu] (gate row n in 0..383, Wu rows from 192): [L/16][3 pieces][2 halves][384][8]
+// bf16 - one 36 KiB block per 16-deep K slice, in the order the forward's LDS image holds it (a straight copy by LDS-DMA),
+// element (n, k) of piece q at this index.
+#define GP_SLICE_ELEMS (3 * 2 * GR_NG * 8)
+__host__ __device__ __forceinline__ size_t gp_index(int q, int n, int k) {
+    return (size_t)(k >> 4) * GP_SLICE_ELEMS + ((size_t)(q * 2 + ((k >> 3) & 1)) * GR_NG + n) * 8 + (k & 7);
+}
+// the pieces of four consecutive k (k % 4 == 0) of gate row n: three 8-byte stores
+__device__ __forceinline__ void gp_store4(unsigned short* __restrict__ Wp, int n, int k, const f32x4 v) {
+    ushort4 o[3];
+    gp_split3(v[0], o[0].x, o[1].x, o[2].x);
+    gp_split3(v[1], o[0].y, o[1].y, o[2].y);
+    gp_split3(v[2], o[0].z, o[1].z, o[2].z);
+    gp_split3(v[3], o[0].w, o[1].w, o[2].w);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) *reinterpret_cast<ushort4*>(Wp + gp_index(q, n, k)) = o[q];
+}
+
 // Parameter gradients of the head (model/aggregator.py:128-131: z = M Wf^T + bf):  dWf[c][j] = sum_b dz[b][c] M[b][j],
 // dbf[c] = sum_b dz[b][c], plus the step's loss = sum_b loss_bag[b].  A handful of workgroups of latency-bound work that
 // depends only on the fused per-bag tail: it rides at the end of the gate reduce launch (blocks >= first) instead of
@@ -84,9 +115,11 @@ static __global__ __launch_bounds__(256) void k_gate_bwd_reduce(const float* __r
                                                                 float wscale, int head_first = 1 << 30,
                                                                 HeadBwdArgs head = HeadBwdArgs{}, AdamFuse ad_in = AdamFuse{},
                                                                 unsigned short* __restrict__ Wv16 = nullptr,
-                                                                unsigned short* __restrict__ Wu16 = nullptr) {
+                                                                unsigned short* __restrict__ Wu16 = nullptr,
+                                                                unsigned short* __restrict__ Wp = nullptr) {
     // Wv16 / Wu16 (bf16-storage step with Adam applied here): the bf16 shadows of the gate weights the forward reads are
-    // refreshed by the thread that has just updated their fp32 masters - no cast launches after the update
+    // refreshed by the thread that has just updated their fp32 masters - no cast launches after the update.  Wp (fp32 step
+    // with Adam applied here): the same for the three-piece planes of the split-bf16 gate forward.
     __shared__ float bcs[2];
     const int L4 = L / 4;
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -156,6 +189,8 @@ static __global__ __launch_bounds__(256) void k_gate_bwd_reduce(const float* __r
             o.w = __builtin_bit_cast(unsigned short, (__bf16)pnew[3]);
             *reinterpret_cast<ushort4*>((ii < 64 ? Wv16 : Wu16) + woff) = o;
         }
+        if (Wp != nullptr && ad.param != nullptr)
+            gp_store4(Wp, (ii < 64 ? 0 : MIL_GATE_D) + (int)(woff / L), 4 * c4, pnew);
     } else if (idx < nW + GR_NB * (3 * 192 + 1)) {
         // bias / w / b: GR_NB lanes per output, each sums every GR_NB-th slab (loads in flight), then a fixed-order
         // shuffle fold.  (One thread per output walked the S * NJ slabs of the low-VALU kernel serially: 9.5 us.)

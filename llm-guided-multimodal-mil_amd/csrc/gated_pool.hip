@@ -7,6 +7,7 @@
 //   * scores -> softmax over the bag -> A.x (and ds in the backward) stream x once: HBM-bound.
 #include "mil_common.h"
 #include "philox.h"
+#include "gate_reduce.h"
 #include <type_traits>
 
 // ================================================================================ K1a gate forward
@@ -220,15 +221,34 @@ struct GateFwdPool {
     float mscale;
 };
 
-template <bool DROP, bool GEN, int PQ>
+// PW (split-bf16 main loop, the default of the fp32 one-call step; MIL_GATE_PIECES=0 keeps the f32-MFMA loop above): the
+// contraction runs on v_mfma_f32_32x32x16_bf16 over three-piece bf16 operands, x = x0 + x1 + x2 and W = w0 + w1 + w2 (each
+// split exact, gp_split3), keeping the six cross terms (p, q) with p + q <= 2: per 16 k and output tile six bf16 MFMAs of 32
+// cycles (192) where the f32 MFMA takes 512.  The dropped terms x1w2, x2w1, x2w2 are below 2^-24 relative.  Same
+// workgroup shape, epilogue, keep draw and pool pass as the f32 loop; only the K loop differs.
+//   * K slices are 16 deep (one bf16 MFMA), double-buffered: per buffer an x image [128][16] fp32 (64-byte rows, 16-byte
+//     chunk c of row `row` at c ^ ((row >> 2) & 3): conflict-free for the ds_read_b128 lane groups) and the W piece block
+//     [3][2][384][8] bf16 of the slice (36 KiB, gp_index: copied as it lies in Wp).  2 x 44 KiB; 32-deep slices would need
+//     2 x 88 KiB, over the 160 KiB of a CU.
+//   * W pieces are precomputed (Wp, refreshed by the optimizer, gate_reduce.h); x is split after the fragment read, in
+//     registers, by both waves that share a row tile (the VALU work hides under the bf16 MFMAs).
+//   * dropped elements are zeroed before the split (all three pieces 0); 1/(1-p) stays in the epilogue.
+//   * non-finite x: x0 = x, x1 = x2 = 0 (gp_split3).  A product term x0 * w_q with w_q == 0 still makes an infinite x a
+//     NaN in that gate column, where the f32 loop gives +-inf (tanh/sigmoid then +-1 / 0 / 1): rows with an infinite
+//     feature are not carried through this path with the f32 loop's values.
+#define GP_XS_BYTES (GF_TM * 16 * 4)             /* one x buffer            (8 KiB) */
+#define GP_WS_BYTES (GP_SLICE_ELEMS * 2)         /* one W piece block      (36 KiB) */
+typedef __bf16 gp_bf16x8 __attribute__((ext_vector_type(8)));
+template <bool DROP, bool GEN, int PQ, bool PW = false>
 __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, const float* __restrict__ Wv,
                                                    const float* __restrict__ bv, const float* __restrict__ Wu,
                                                    const float* __restrict__ bu, const float* __restrict__ wvec,
                                                    const float* __restrict__ battn, float* __restrict__ scores,
                                                    float* __restrict__ gates, int R, int L,
                                                    const uint32_t* __restrict__ xbits, float xscale, GateFwdGen gen,
-                                                   GateFwdPool pool) {
-    __shared__ __attribute__((aligned(16))) float smem[2 * (GF_TM + GF_NG) * 32];      // [2] x buffers, then [2] W buffers
+                                                   GateFwdPool pool, const unsigned short* __restrict__ Wp = nullptr) {
+    constexpr int SMEM_FLOATS = PW ? (2 * (GP_XS_BYTES + GP_WS_BYTES)) / 4 : 2 * (GF_TM + GF_NG) * 32;
+    __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];                  // [2] x buffers, then [2] W buffers
     __shared__ __attribute__((aligned(16))) uint32_t mlds[GEN ? GF_TM * 32 : 4];       // keep words [128][nslice <= 32]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -317,8 +337,23 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[c][u][i] = 0.f;
 
+    if constexpr (PW) {
+        // slice 0 of the split-bf16 loop: x rows 16w .. 16w + 15 and W piece blocks w, w + 8, .. (same map as its dma16)
+        const int xrow = 16 * wave + (lane >> 2);
+        const __amdgpu_buffer_rsrc_t srd_p = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, GP_WS_BYTES, MIL_SRD_FLAGS);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_x, (lds_void*)(uintptr_t)(lds0 + (unsigned)(wave * 1024)), 16,
+                                                 (xrow * L + 4 * ((lane & 3) ^ ((xrow >> 2) & 3))) * 4, 0, 0, 0);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) dma_piece(i, 0, 0);
+        for (int i = 0; i < 5; ++i) {
+            const int p = wave + 8 * i;
+            if (i < 4 || p < 36)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p, (lds_void*)(uintptr_t)(lds0 + (unsigned)(2 * GP_XS_BYTES + p * 1024)),
+                                                         16, lane * 16, p * 1024, 0, 0);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) dma_piece(i, 0, 0);
+    }
     __syncthreads();                                   // hipcc drains the DMA (vmcnt(0)) in front of the barrier
     if (GEN) mnext = mlds[vmask];
 
@@ -372,6 +407,7 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
             }
         }
     };
+    if constexpr (!PW) {
     int s = 0;
     for (; s + 1 < nslice; s += 2) {
         slice(s, std::integral_constant<int, 0>{});
@@ -382,6 +418,82 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
     if (s < nslice) {
         slice(s, std::integral_constant<int, 0>{});
         __syncthreads();
+    }
+    } else {
+        // ---- split-bf16 K loop (see the comment above the kernel): 16-deep slices, buffer = slice parity
+        const int n16 = L / 16;
+        const int xrow = 16 * wave + (lane >> 2);                         // x DMA: wave w fills rows 16w .. 16w + 15
+        const int xsrc = (xrow * L + 4 * ((lane & 3) ^ ((xrow >> 2) & 3))) * 4;
+        const __amdgpu_buffer_rsrc_t srd_p = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, n16 * GP_WS_BYTES, MIL_SRD_FLAGS);
+        auto dma16 = [&](int buf, int s16) {
+            const unsigned xdst = lds0 + (unsigned)(buf * GP_XS_BYTES + wave * 1024);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_x, (lds_void*)(uintptr_t)xdst, 16, xsrc, s16 * 64, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {                                 // 36 W pieces of 1 KiB: 4 or 5 per wave
+                const int p = wave + 8 * i;
+                if (i < 4 || p < 36) {
+                    const unsigned wdst = lds0 + (unsigned)(2 * GP_XS_BYTES + buf * GP_WS_BYTES + p * 1024);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p, (lds_void*)(uintptr_t)wdst, 16, lane * 16,
+                                                             s16 * GP_WS_BYTES + p * 1024, 0, 0);
+                }
+            }
+        };
+        const unsigned xr = lds0 + (unsigned)((32 * wr + r) * 64);
+        const unsigned pa0 = xr + 16u * (unsigned)((2 * h) ^ ((r >> 2) & 3));
+        const unsigned pa1 = xr + 16u * (unsigned)((2 * h + 1) ^ ((r >> 2) & 3));
+        const unsigned pb = lds0 + (unsigned)(2 * GP_XS_BYTES + (h * GF_NG + 96 * wc + r) * 16);
+        // one 16-deep slice from buffer `buf`; mw = keep bits of this lane's 8 k in bits 0..7
+        auto slice16 = [&](int s16, unsigned mw, auto buf_c) {
+            constexpr int buf = decltype(buf_c)::value;
+            const f32x4 xa0 = *(lds_cf4*)(uintptr_t)(pa0 + (unsigned)(buf * GP_XS_BYTES));
+            const f32x4 xa1 = *(lds_cf4*)(uintptr_t)(pa1 + (unsigned)(buf * GP_XS_BYTES));
+            f32x4 bq[3][3][2];                                            // [piece][c][u], smallest piece first
+#pragma unroll
+            for (int q = 2; q >= 0; --q)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+                        bq[q][c][u] = *(lds_cf4*)(uintptr_t)(pb + (unsigned)(buf * GP_WS_BYTES + (q * 2 * GF_NG + u * 192 + 32 * c) * 16));
+            // the next slice goes to the other buffer (after this slice's reads in program order: no LDS wait in between)
+            dma16(buf ^ 1, min(s16 + 1, n16 - 1));
+            gp_bf16x8 ap[3];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float v = j < 4 ? xa0[j] : xa1[j - 4];
+                if (DROP) v = keep_if(v, mw, j);
+                unsigned short p0, p1, p2;
+                gp_split3(v, p0, p1, p2);
+                ap[0][j] = __builtin_bit_cast(__bf16, p0);
+                ap[1][j] = __builtin_bit_cast(__bf16, p1);
+                ap[2][j] = __builtin_bit_cast(__bf16, p2);
+            }
+            // cross terms (p, q), p + q <= 2, smallest first; the B piece q of every tile is read before its first use
+            constexpr int TP[6] = {0, 1, 2, 0, 1, 0}, TQ[6] = {2, 1, 0, 1, 0, 0};
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+                        acc[c][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[TP[t]], __builtin_bit_cast(gp_bf16x8, bq[TQ[t]][c][u]),
+                                                                            acc[c][u], 0, 0, 0);
+            // keep the MFMAs in front of the barrier (and its DMA drain): the next slice's DMA lands under them
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        for (int s = 0; s < nslice; ++s) {                                // 32-deep steps: one keep word, two slices
+            unsigned mw = 0;
+            if (DROP) {
+                mw = mnext;
+                const int s1 = min(s + 1, nslice - 1);
+                if (GEN) mnext = mlds[vmask + s1];
+                else mnext = __builtin_amdgcn_raw_buffer_load_b32(srd_m, vmask, s1 * 4, 0);
+            }
+            slice16(2 * s, mw >> (8 * h), std::integral_constant<int, 0>{});
+            __syncthreads();
+            slice16(2 * s + 1, mw >> (16 + 8 * h), std::integral_constant<int, 1>{});
+            __syncthreads();
+        }
     }
 
     // fused pool pass: the x rows of this wave's tile are requested NOW (they depend on nothing the epilogue computes), so
@@ -1521,7 +1633,7 @@ static inline int split_plan(int R, int L, int* KC_out) {
     return (R + kc - 1) / kc;
 }
 
-extern "C" int mil_abi_version(void) { return 6; }
+extern "C" int mil_abi_version(void) { return 7; }
 
 // Small batches (the authors train with ONE bag per GPU: R = 1 000 - 15 000 rows): 128-row tiles would leave most CUs
 // idle (8 workgroups for 1024 patches, each walking all of K: the kernel takes its full ~100 us for 1/32 of the
@@ -1719,7 +1831,7 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
                                 const float* w, const float* b, float* scores, float* gates, int R, int L, int D,
                                 const uint32_t* xbits, float xscale, const GateFwdGen* gen, void* stream,
                                 const GateFwdPool* pool = nullptr, int* fused = nullptr, const int32_t* rows_dev = nullptr,
-                                const TileMapJob* tmap = nullptr) {
+                                const TileMapJob* tmap = nullptr, const uint16_t* Wp = nullptr) {
     if (!x || !Wv || !bv || !Wu || !bu || !w || !b || !scores) return MIL_EINVAL;
     if (D != MIL_GATE_D || L <= 0 || (L % GF_BK) != 0 || R < 0) return MIL_EINVAL;
     if (R == 0) return MIL_OK;
@@ -1751,6 +1863,16 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
 #endif
     if (fused != nullptr) *fused = 0;
     const GateFwdPool nopool{};
+    // Wp (three-piece bf16 planes of [Wv; Wu], gp_index layout): the split-bf16 K loop of k_gate_fwd2
+#define GF2_LAUNCH(D_, G_, PQ_, R_, ...)                                                                                       \
+    do {                                                                                                                       \
+        if (Wp != nullptr)                                                                                                     \
+            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_, true>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, \
+                               gates, R_, L, __VA_ARGS__, (const unsigned short*)Wp);                                          \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, \
+                               R_, L, __VA_ARGS__);                                                                            \
+    } while (0)
     // the pool partial pass rides in the forward's epilogue when every row goes through k_gate_fwd2 and every tile of the
     // map is a full, aligned 32-row tile (T * 32 == R: tile t = rows 32 t ..)
     const bool pool_in = pool != nullptr && fused != nullptr && !r32 && tail == 0 && fwd2 && L == 512 && (R % 32) == 0 &&
@@ -1763,12 +1885,10 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
             { const int rc_ = tmap_alone(); if (rc_ != MIL_OK) return rc_; }
             const int grid = (R + GF_TM - 1) / GF_TM;
             if (pool_in && gen->mbits_out != nullptr) {
-                hipLaunchKernelGGL((k_gate_fwd2<true, true, 2>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates,
-                                   R, L, gen->xbits_out, xscale, *gen, *pool);
+                GF2_LAUNCH((true), (true), 2, R, gen->xbits_out, xscale, *gen, *pool);
                 *fused = 1;
             } else {
-                hipLaunchKernelGGL((k_gate_fwd2<true, true, 0>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates,
-                                   R, L, gen->xbits_out, xscale, *gen, nopool);
+                GF2_LAUNCH((true), (true), 0, R, gen->xbits_out, xscale, *gen, nopool);
             }
             MIL_CHECK_LAUNCH();
             return MIL_OK;
@@ -1798,19 +1918,15 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
     const int grid = (Rm + GF_TM - 1) / GF_TM;
     const GateFwdGen nogen{};
     if (pool_in && xbits && pool->mbits) {
-        hipLaunchKernelGGL((k_gate_fwd2<true, false, 2>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L,
-                           xbits, xscale, nogen, *pool);
+        GF2_LAUNCH((true), (false), 2, Rm, xbits, xscale, nogen, *pool);
         *fused = 1;
     } else if (pool_in && !xbits && !pool->mbits) {
-        hipLaunchKernelGGL((k_gate_fwd2<false, false, 2>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L,
-                           xbits, 1.0f, nogen, *pool);
+        GF2_LAUNCH((false), (false), 2, Rm, xbits, 1.0f, nogen, *pool);
         *fused = 1;
     } else if (fwd2 && xbits)
-        hipLaunchKernelGGL((k_gate_fwd2<true, false, 0>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L,
-                           xbits, xscale, nogen, nopool);
+        GF2_LAUNCH((true), (false), 0, Rm, xbits, xscale, nogen, nopool);
     else if (fwd2)
-        hipLaunchKernelGGL((k_gate_fwd2<false, false, 0>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L,
-                           xbits, 1.0f, nogen, nopool);
+        GF2_LAUNCH((false), (false), 0, Rm, xbits, 1.0f, nogen, nopool);
     else if (xbits)
         hipLaunchKernelGGL(k_gate_fwd<true>, dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L, xbits,
                            xscale);
@@ -1837,6 +1953,8 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
     }
     return MIL_OK;
 }
+
+#undef GF2_LAUNCH
 
 extern "C" int mil_gate_scores_fwd(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
                                    const float* w, const float* b, float* scores, float* gates, int R, int L, int D,
@@ -1866,7 +1984,7 @@ extern "C" int mil_gate_scores_fwd_draw(const float* x, const float* Wv, const f
 int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
                       const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
                       uint32_t* mbits, int B, uint64_t seed, uint64_t mseed, uint64_t offset, const int32_t* offset_dev,
-                      const int32_t* rows_dev, void* stream, const TileMapJob* tmap) {
+                      const int32_t* rows_dev, void* stream, const TileMapJob* tmap, const uint16_t* Wp) {
     if (draw) {
         if (!xbits || (L % 64) != 0 || (mbits && B <= 0)) return MIL_EINVAL;
         GateFwdGen g{};
@@ -1880,10 +1998,10 @@ int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const fl
         g.offset = offset;
         g.offset_dev = offset_dev;
         return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, nullptr, xscale, &g, stream, nullptr,
-                                    nullptr, rows_dev, tmap);
+                                    nullptr, rows_dev, tmap, Wp);
     }
     return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, xbits, xscale, nullptr, stream, nullptr,
-                                nullptr, rows_dev, tmap);
+                                nullptr, rows_dev, tmap, Wp);
 }
 
 // Internal (step.hip): gate forward with the pool partial pass in its epilogue when the batch allows it; *fused says
@@ -1893,7 +2011,7 @@ int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const f
                        const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
                        uint32_t* mbits, float mscale, int B, uint64_t seed, uint64_t mseed, uint64_t offset,
                        const int32_t* offset_dev, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
-                       int* fused, void* stream) {
+                       int* fused, void* stream, const uint16_t* Wp) {
     GateFwdPool pl{};
     pl.tile_map = tile_map;
     pl.partials = partials;
@@ -1914,9 +2032,11 @@ int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const f
         g.mseed_hi = (uint32_t)(mseed >> 32);
         g.offset = offset;
         g.offset_dev = offset_dev;
-        return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, nullptr, xscale, &g, stream, &pl, fused);
+        return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, nullptr, xscale, &g, stream, &pl, fused,
+                                    nullptr, nullptr, Wp);
     }
-    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, xbits, xscale, nullptr, stream, &pl, fused);
+    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, xbits, xscale, nullptr, stream, &pl, fused,
+                                nullptr, nullptr, Wp);
 }
 
 static int launch_pool_partial(const float* x, const float* scores, const int32_t* tile_map, int T, int L,
@@ -2146,7 +2266,8 @@ int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* 
                                    float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
                                    float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
                                    float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
-                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done = nullptr);
+                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done = nullptr,
+                                   uint16_t* Wp = nullptr);
 
 // mil_gate_bwd_reduce_head with Adam applied by the threads that produce the final gradients (world size 1: nothing sits
 // between the gradient and the update): param_flat / exp_avg / exp_avg_sq are indexed like grad_flat, in which dWv .. dbf all
@@ -2169,7 +2290,8 @@ int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* 
                                    float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
                                    float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
                                    float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
-                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done) {
+                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done,
+                                   uint16_t* Wp) {
     if (!workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db || !dz || !M || !dWf || !dbf) return MIL_EINVAL;
     if (!param_flat || !grad_flat || !exp_avg || !exp_avg_sq || (step_dev == nullptr && step < 1)) return MIL_EINVAL;
     if (step_dev != nullptr) step = 1;
@@ -2195,7 +2317,29 @@ int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* 
                       (float)sqrt(bc2), step_dev, lr, lr_dev, step_dev ? done : nullptr};
     hipLaunchKernelGGL(k_gate_bwd_reduce, dim3(nred + nhead), dim3(256), 0, (hipStream_t)stream, workspace,
                        workspace + (size_t)S * GF_NG * L, S, use_dw2(R, L) ? S * (L / 128) : S, L, dWv, dbv, dWu, dbu, dw, db,
-                       accumulate, xscale, nred, head, ad);
+                       accumulate, xscale, nred, head, ad, nullptr, nullptr, (unsigned short*)Wp);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// The three-piece bf16 planes of [Wv; Wu] the split-bf16 gate forward reads (gp_index layout, 3 * 384 * L halves), formed
+// from the fp32 masters.  The one-call step keeps them current itself after every update it applies; a caller that
+// writes the parameters another way calls this once afterwards.
+__global__ __launch_bounds__(256) void k_gate_pieces(const float* __restrict__ Wv, const float* __restrict__ Wu,
+                                                     unsigned short* __restrict__ Wp, int L) {
+    const int L4 = L / 4;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= GF_NG * L4) return;
+    const int n = idx / L4, k = 4 * (idx % L4);
+    const float* src = (n < MIL_GATE_D ? Wv + (size_t)n * L : Wu + (size_t)(n - MIL_GATE_D) * L) + k;
+    gp_store4(Wp, n, k, *reinterpret_cast<const f32x4*>(src));
+}
+
+extern "C" int mil_gate_pieces(const float* Wv, const float* Wu, uint16_t* Wp, int L, void* stream) {
+    if (!Wv || !Wu || !Wp || L <= 0 || (L % 32) != 0) return MIL_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(Wv) | reinterpret_cast<uintptr_t>(Wu) | reinterpret_cast<uintptr_t>(Wp)) & 15) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_gate_pieces, dim3((GF_NG * (L / 4) + 255) / 256), dim3(256), 0, (hipStream_t)stream, Wv, Wu,
+                       (unsigned short*)Wp, L);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

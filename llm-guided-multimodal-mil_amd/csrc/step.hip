@@ -13,13 +13,13 @@ int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const f
                        const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
                        uint32_t* mbits, float mscale, int B, uint64_t seed, uint64_t mseed, uint64_t offset,
                        const int32_t* offset_dev, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
-                       int* fused, void* stream);
+                       int* fused, void* stream, const uint16_t* Wp);
 
 // gated_pool.hip: gate forward of a bucketed batch - tiles beyond the true row count (rows_dev) are skipped
 int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
                       const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
                       uint32_t* mbits, int B, uint64_t seed, uint64_t mseed, uint64_t offset, const int32_t* offset_dev,
-                      const int32_t* rows_dev, void* stream, const TileMapJob* tmap);
+                      const int32_t* rows_dev, void* stream, const TileMapJob* tmap, const uint16_t* Wp);
 
 // gated_pool.hip: split-K fold + head gradients + Adam in one launch, the step number on the host or in a device counter
 int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu,
@@ -27,7 +27,8 @@ int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* 
                                    float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
                                    float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
                                    float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
-                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done);
+                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done,
+                                   uint16_t* Wp);
 
 // gated_pool_bf16.hip: bf16-MFMA weight gradient whose fold launch carries the head gradients, the loss and (param_flat != NULL)
 // Adam + the refresh of the bf16 weight shadows
@@ -95,6 +96,8 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
     const uint32_t* xbits = train ? a->xbits : nullptr;
     const uint32_t* mbits = train ? a->mbits : nullptr;
     const bool use_h = a->hrow != nullptr && grads && a->C <= 4;
+    // fp32 x with weight pieces: the gate forward runs its split-bf16 K loop (k_gate_fwd2<.., PW = true>)
+    const uint16_t* Wp = (!a->x_bf16 && a->Wp) ? a->Wp : nullptr;
     bool adam_in_reduce = false;
     int pool_fused = 0;
 
@@ -142,11 +145,17 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
             rc = gate_fwd_with_pool((const float*)a->x, a->Wv, a->bv, a->Wu, a->bu, a->w, a->b, a->scores, gates, a->R, a->L,
                                     draw_in_fwd ? 1 : 0, a->xbits, xscale, a->mbits, mscale, a->B, a->seed,
                                     a->seed ^ 0x9E3779B97F4A7C15ull, a->offset, a->offset_dev, a->tile_map, a->T, a->partials,
-                                    a->Wf, a->hrow, &pool_fused, stream);
+                                    a->Wf, a->hrow, &pool_fused, stream, Wp);
         else if (a->bag_len_dev && a->rows_dev)
             rc = gate_fwd_rows_dev((const float*)a->x, a->Wv, a->bv, a->Wu, a->bu, a->w, a->b, a->scores, gates, a->R, a->L,
                                    draw_in_fwd ? 1 : 0, a->xbits, xscale, a->mbits, a->B, a->seed, a->seed ^ 0x9E3779B97F4A7C15ull,
-                                   a->offset, a->offset_dev, a->rows_dev, stream, tmap_with_fwd ? &tmj : nullptr);
+                                   a->offset, a->offset_dev, a->rows_dev, stream, tmap_with_fwd ? &tmj : nullptr, Wp);
+        else if (Wp != nullptr)
+            // the plain forward (keep bits drawn in the kernel or given) on the split-bf16 K loop: no tile map, no bucket rows
+            rc = gate_fwd_rows_dev((const float*)a->x, a->Wv, a->bv, a->Wu, a->bu, a->w, a->b, a->scores, gates, a->R, a->L,
+                                   draw_in_fwd ? 1 : 0, draw_in_fwd ? a->xbits : const_cast<uint32_t*>(xbits), xscale, a->mbits,
+                                   a->B, a->seed, a->seed ^ 0x9E3779B97F4A7C15ull, a->offset, a->offset_dev, nullptr, stream,
+                                   nullptr, Wp);
         else if (draw_in_fwd)
             rc = mil_gate_scores_fwd_draw((const float*)a->x, a->Wv, a->bv, a->Wu, a->bu, a->w, a->b, a->scores, gates, a->R,
                                           a->L, MIL_GATE_D, a->xbits, xscale, a->mbits, a->B, a->seed,
@@ -240,7 +249,8 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
                                                     a->accumulate, xscale, a->dz, Mhead, a->dWf, a->dbf, a->B, a->C, a->loss_bag,
                                                     a->loss_out, a->param_flat, a->grad_flat, (size_t)a->n_param, a->exp_avg,
                                                     a->exp_avg_sq, a->adam_step, a->adam_step_dev, a->lr, a->lr_dev, a->beta1,
-                                                    a->beta2, a->eps, a->weight_decay, a->grad_scale, stream, a->done_dev);
+                                                    a->beta2, a->eps, a->weight_decay, a->grad_scale, stream, a->done_dev,
+                                                    const_cast<uint16_t*>(a->Wp));
                 // the device counter moves on after the update, as mil_adam_step_counted does - by the fold launch itself when
                 // the caller gave it a sign-off word (done_dev), by a one-thread launch otherwise
                 if (rc == MIL_OK && a->adam_step_dev && !a->done_dev) rc = mil_counter_add(a->adam_step_dev, 1, stream);
@@ -265,6 +275,11 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
             rc = mil_adam_step(a->param_flat, a->grad_flat, a->exp_avg, a->exp_avg_sq, (size_t)a->n_param, a->adam_step, a->lr,
                                a->beta1, a->beta2, a->eps, a->weight_decay, a->grad_scale, stream);
         if (rc != MIL_OK) return rc;
+        if (!a->x_bf16 && a->Wp) {
+            // the split-bf16 forward's weight pieces follow their fp32 masters here, once per update
+            rc = mil_gate_pieces(a->Wv, a->Wu, const_cast<uint16_t*>(a->Wp), a->L, stream);
+            if (rc != MIL_OK) return rc;
+        }
         if (a->x_bf16) {
             // the bf16 shadows of the gate weights follow their fp32 masters here, once per update, instead of being
             // re-cast in front of every forward (two launches per pass in round 1)

@@ -119,6 +119,11 @@ class ImageOnlyTrainer:
         self._keep = None                        # tensors the current struct points at (x, y, layout)
         self._w16: Optional[Dict[str, torch.Tensor]] = None
         self._w16_version, self._param_version = -1, 0
+        # fp32 x: three-piece bf16 planes of [Wv; Wu] for the split-bf16 gate forward (MIL_GATE_PIECES=0: the fp32-MFMA
+        # forward).  The step rewrites them with every update it applies; host-side writes are followed up by _pieces()
+        self._wp: Optional[torch.Tensor] = None
+        self._wp_version = -1
+        self.gate_pieces = os.environ.get("MIL_GATE_PIECES", "1") != "0"
         self._graph = None
         self.last = {}
         if self.world > 1:      # DDP broadcasts rank 0's parameters at wrap time (train_ddp.py:79)
@@ -142,6 +147,17 @@ class ImageOnlyTrainer:
                 ops.cast_bf16(fp.p(k), out=t)
             self._w16_version = self._param_version
         return self._w16
+
+    def _pieces(self):
+        fp = self.fp
+        Wv, Wu = fp.p("aggregator.attention_V.0.weight"), fp.p("aggregator.attention_U.0.weight")
+        if self._wp is None:
+            self._wp = torch.empty(3 * 2 * Wv.numel(), device=self.device, dtype=torch.int16)
+        if self._wp_version != self._param_version and not torch.cuda.is_current_stream_capturing():
+            rc = _lib.lib().mil_gate_pieces(Wv.data_ptr(), Wu.data_ptr(), self._wp.data_ptr(), Wv.shape[1], ops._stream())
+            _lib.check(rc, "mil_gate_pieces")
+            self._wp_version = self._param_version
+        return self._wp
 
     def _fill(self, x: torch.Tensor, layout: BagLayout, y: Optional[torch.Tensor], global_bags: Optional[int]):
         """(Re)build the C struct for this batch; cached while the same tensors / layout come back."""
@@ -184,6 +200,8 @@ class ImageOnlyTrainer:
         if b16:
             w16 = self._shadows()
             a.Wv16, a.Wu16 = w16[names["Wv"]].data_ptr(), w16[names["Wu"]].data_ptr()
+        elif self.gate_pieces and L % 32 == 0:
+            a.Wp = self._pieces().data_ptr()
         a.loss_out = self.loss_sum.data_ptr()
         grads = y is not None
         st = dict(scores=self._buf("scores", R), partials=self._buf("partials", T * (L + 2)),
@@ -242,6 +260,8 @@ class ImageOnlyTrainer:
 
     def _run(self, a, stages: int, keep=None):
         self._sync_lr()
+        if a.Wp and self._wp_version != self._param_version:
+            self._pieces()                          # parameters written on the host since the planes were formed
         keep = self._keep if keep is None else keep
         # plain single-segment layout with every bag a multiple of 32 rows: the pool partial pass may ride in the forward launch
         if getattr(keep[2], "aligned32", False) and (stages & _lib.STAGE_GATE_FWD) and (stages & _lib.STAGE_POOL):
@@ -287,6 +307,8 @@ class ImageOnlyTrainer:
         self._param_version += 1
         if a.x_bf16:
             self._w16_version = self._param_version     # step.hip re-cast the shadows right after the update
+        if a.Wp:
+            self._wp_version = self._param_version      # ... and rewrote the weight pieces
 
     def reduce_and_step(self, a=None, keep=None):
         """One all-reduce(sum) of the flat gradient over RCCL, then Adam.  The local loss was already
@@ -307,6 +329,8 @@ class ImageOnlyTrainer:
             self._param_version += 1
             if a.x_bf16:
                 self._w16_version = self._param_version
+            if a.Wp:
+                self._wp_version = self._param_version
         elif last:
             self.reduce_and_step()
         self._micro = 0 if last else self._micro + 1
@@ -383,6 +407,9 @@ class ImageOnlyTrainer:
         a2 = _lib.ImageOnlyStep.from_buffer_copy(a)
         scratch = [fp.flat.clone(), fp.exp_avg.clone(), fp.exp_avg_sq.clone()]
         a2.param_flat, a2.exp_avg, a2.exp_avg_sq = (t.data_ptr() for t in scratch)
+        if a2.Wp:                                   # the update rewrites the weight pieces: those of the scratch copy
+            scratch.append(self._wp.clone())
+            a2.Wp = scratch[-1].data_ptr()
         a2.adam_step_dev, a2.adam_step, a2.lr, a2.x_bf16 = None, 1, self.lr, 0
         rc = _lib.lib().mil_image_only_step_time(ctypes.byref(a2), _lib.STAGE_ADAM, warm, iters, ctypes.byref(ms), ops._stream())
         _lib.check(rc, "mil_image_only_step_time")
@@ -403,6 +430,9 @@ class ImageOnlyTrainer:
         a2 = _lib.ImageOnlyStep.from_buffer_copy(a)
         scratch = [fp.flat.clone(), fp.exp_avg.clone(), fp.exp_avg_sq.clone()]
         a2.param_flat, a2.exp_avg, a2.exp_avg_sq = (t.data_ptr() for t in scratch)
+        if a2.Wp:                                   # the update rewrites the weight pieces: those of the scratch copy
+            scratch.append(self._wp.clone())
+            a2.Wp = scratch[-1].data_ptr()
         a2.adam_step_dev, a2.lr_dev, a2.adam_step, a2.lr, a2.accumulate = None, None, 1, self.lr, 0
         S = _lib
         fwd = S.STAGE_TILEMAP | S.STAGE_DROPBITS | S.STAGE_GATE_FWD
@@ -501,6 +531,8 @@ class ImageOnlyTrainer:
         if g["adam"]:
             self.step_count += 1
             self._param_version += 1
+            if g["args"].Wp:
+                self._wp_version = self._param_version
         else:
             # the optimizer stage runs on the GRAPH's own descriptor: self._args / _args_key / _keep still describe the last
             # eager batch, and _fill() must keep returning that struct for that key (a replay that overwrote
