@@ -7,6 +7,7 @@ from mil_amd import _lib, ops
 from mil_amd import synthetic as syn
 from mil_amd.bags import BagLayout
 from mil_amd.trainer import ImageOnlyTrainer
+from step_ref import gates_ref, keep_from_bits, max_err, step_route
 
 pytestmark = pytest.mark.gpu
 
@@ -38,6 +39,22 @@ def device_pieces(Wv: torch.Tensor, Wu: torch.Tensor) -> torch.Tensor:
     rc = _lib.lib().mil_gate_pieces(Wv.data_ptr(), Wu.data_ptr(), out.data_ptr(), Wv.shape[1], ops._stream())
     _lib.check(rc, "mil_gate_pieces")
     return out
+
+
+def _pw_forward_matches_float64(tr, seed):
+    """A forward of 32 x 1024 rows - the split-bf16 K loop, which reads the weight pieces - against float64 from the
+    trainer's current masters."""
+    dev = torch.device("cuda")
+    L, lengths = tr.fp.p(WV).shape[1], [1024] * 32
+    assert step_route(sum(lengths), L, 2, tr.train_mode, aligned32=True)["main"] == "fwd2_pw"
+    x = torch.randn(sum(lengths), L, device=dev, generator=torch.Generator(device=dev).manual_seed(seed))
+    tr.forward(x, BagLayout.make(lengths, dev), syn.make_labels(seed, len(lengths)).to(dev))
+    torch.cuda.synchronize()
+    keep = keep_from_bits(tr.last["xbits"], L) if tr.train_mode else None
+    rs, rg = gates_ref(x, tr.fp.state_dict(), keep)
+    es, eg = max_err(tr.last["scores"], rs), max_err(tr.last["gates"], rg)
+    print(f"32 x 1024 forward on the planes: scores {es:.1e} gates {eg:.1e}")
+    assert es <= 1e-5 and eg <= 1e-5, (es, eg)
 
 
 def test_pieces_sum_back_exactly():
@@ -80,12 +97,14 @@ def test_trainer_planes_follow_the_masters(fused_adam):
             tr.reduce_and_step()                # MIL_STAGE_ADAM on its own
     torch.cuda.synchronize()
     assert torch.equal(tr._wp.cpu(), pieces_layout(tr.fp.p(WV).cpu(), tr.fp.p(WU).cpu()))
+    _pw_forward_matches_float64(tr, 7)
     # a host-side parameter write is followed by a fresh split before the next step reads the planes
     sd = {k: v.clone() * 0.5 for k, v in tr.fp.state_dict().items()}
     tr.load_model_state_dict(sd)
     tr.forward(x, lay)
     torch.cuda.synchronize()
     assert torch.equal(tr._wp.cpu(), pieces_layout(tr.fp.p(WV).cpu(), tr.fp.p(WU).cpu()))
+    _pw_forward_matches_float64(tr, 8)
 
 
 def _ref64(x, p, keep=None):
@@ -141,13 +160,15 @@ def test_accuracy_against_float64(shape, train):
 
 def test_one_step_agrees_with_fp32_mfma_path():
     dev = torch.device("cuda")
-    L, lengths = 512, [1024] * 8
+    L, lengths = 512, [1024] * 32
     p = syn.image_only_params(95, L=L)
     x = torch.randn(sum(lengths), L, generator=torch.Generator().manual_seed(6)).to(dev)
     y = syn.make_labels(74, len(lengths)).to(dev)
     lay = BagLayout.make(lengths, dev)
     out = {}
     for pieces in (True, False):
+        # 32 x 1024 rows: both arms run k_gate_fwd2 (split-bf16 and fp32-MFMA K loops), not the 32-row kernel
+        assert step_route(sum(lengths), L, 2, True, aligned32=True, pieces=pieces)["main"] == ("fwd2_pw" if pieces else "fwd2")
         tr = ImageOnlyTrainer(p, dev, lr=1e-3, train_mode=True)
         tr.gate_pieces = pieces
         loss, prob = tr.train_step(x, lay, y)
