@@ -61,7 +61,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 7 */
+int mil_abi_version(void);   /* 8 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -874,6 +874,49 @@ int mil_image_only_step_run(const mil_image_only_step* a, void* stream);
  * are issued from C, so a 10 us kernel is not timed behind 30 us of interpreter. */
 int mil_image_only_step_time(const mil_image_only_step* a, uint32_t stages, int warm, int iters, float* ms_out,
                              void* stream);
+
+/* Which kernels the fp32 gate step launches for a shape: the plan the gate forward and the weight gradient execute,
+ * as a host-only query (no launch, no allocation; with ncu > 0 no device call at all).
+ *   main        the kernel that carries the rows: k_gate_fwd_r32 (fewer 128-row tiles than 3/4 of the CUs), k_gate_fwd2 on
+ *               its fp32-MFMA K loop or (weight pieces given) its split-bf16 loop, or the L > 4096 k_gate_fwd
+ *   rt          row tiles per workgroup of that r32 launch (0: main is not r32)
+ *   tail        rows beyond whole rounds of the grid that leave the main kernel: SMALL (1 .. MIL_SMALL_ROWS rows beyond
+ *               whole rounds of 128-row tiles, gates saved) or BIG (up to 1024); tail_rows of them go to tail_kernel
+ *               (mil_linear_small_fwd + k_gate_tail_scores without keep bits, else the r32 kernel with tail_rt)
+ *   bits        keep bits: none, given by the caller, drawn inside k_gate_fwd2 or by a generator launch in front of it
+ *   pool_fused  the pool partial pass runs in k_gate_fwd2's epilogue
+ *   dw, S, kc   weight-gradient kernel, its row chunks (split-K factor) and rows per chunk (L % 128 == 0, else dw = -1) */
+#define MIL_ROUTE_MAIN_R32 0
+#define MIL_ROUTE_MAIN_FWD2 1
+#define MIL_ROUTE_MAIN_FWD2_PW 2
+#define MIL_ROUTE_MAIN_LEGACY 3
+#define MIL_ROUTE_TAIL_NONE 0
+#define MIL_ROUTE_TAIL_SMALL 1
+#define MIL_ROUTE_TAIL_BIG 2
+#define MIL_ROUTE_TAIL_KERNEL_NONE 0
+#define MIL_ROUTE_TAIL_KERNEL_LINEAR_SMALL 1
+#define MIL_ROUTE_TAIL_KERNEL_R32 2
+#define MIL_ROUTE_BITS_NONE 0
+#define MIL_ROUTE_BITS_GIVEN 1
+#define MIL_ROUTE_BITS_IN_KERNEL 2
+#define MIL_ROUTE_BITS_GENERATOR 3
+#define MIL_ROUTE_DW_KG1 0         /* k_gate_bwd_dw<.., KG = 1> */
+#define MIL_ROUTE_DW_KG2 1         /* k_gate_bwd_dw<.., KG = 2> */
+#define MIL_ROUTE_DW2 2            /* k_gate_bwd_dw2 */
+typedef struct mil_gate_route {
+    int32_t main, rt;
+    int32_t tail, tail_rows, tail_kernel, tail_rt;
+    int32_t bits, pool_fused;
+    int32_t dw, S, kc;
+} mil_gate_route;
+/* R rows (a bucketed batch: its capacity), L % 32 == 0, C classes.  save_gates: the forward keeps the gates (a step with
+ * labels).  keep: MIL_ROUTE_BITS_NONE (eval), _GIVEN, or any other value for "to be drawn by this step".  pieces: weight
+ * pieces (Wp) given.  fused_pool: the caller asks for the pool pass in the forward's epilogue (MIL_STAGE_POOL_FUSED and
+ * what mil_image_only_step_run requires with it: C == 2, not bucketed, hrow given) and the tile map is all full, aligned tiles.
+ * bucketed: rows_dev given.  C and bucketed complete the description of the step; today's plan does not depend on them.
+ * ncu: compute units to plan for, <= 0: those of the current device. */
+int mil_gate_step_route(int R, int L, int C, int save_gates, int keep, int pieces, int fused_pool, int bucketed, int ncu,
+                        mil_gate_route* out);
 
 /* torch.nn.CosineEmbeddingLoss()(x1, x2, target = +1), mean over the B rows, forward + backward in one launch: the optional
  * 'textCosSim' term between the text-aligned tokens x_CT2CI and x_Pth2CI (reference train_ddp.py:102,266,325-329).

@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -60,6 +60,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_gate_bwd_input_pool": (c_int, [_P] * 5 + [c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P, _P]),
     "mil_image_only_step_run": (c_int, [_P, _P]),
     "mil_image_only_step_time": (c_int, [_P, c_uint32, c_int, c_int, _P, _P]),
+    "mil_gate_step_route": (c_int, [c_int] * 9 + [_P]),
     "mil_image_only_step_profile": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "mil_image_only_step_profile_rot": (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "mil_patch_drop_select": (c_int, [_P, _P, _P, c_int, c_int, c_uint64, c_uint64, _P, _P]),
@@ -197,6 +198,13 @@ class SmallDwDesc(ctypes.Structure):
     _fields_ = [("dy", c_void_p), ("yv", c_void_p), ("x", c_void_p), ("dW", c_void_p), ("db", c_void_p),
                 ("lddy", c_int32), ("ldyv", c_int32), ("ldx", c_int32), ("lddw", c_int32), ("act", c_int32),
                 ("M", c_int32), ("N", c_int32), ("K", c_int32)]
+
+
+class GateRoute(ctypes.Structure):
+    """Mirror of mil_gate_route (include/mil_hip.h, with the MIL_ROUTE_* values of its fields); layout checked against the
+    header by tests/test_abi.py."""
+    _fields_ = [(n, c_int32) for n in ("main", "rt", "tail", "tail_rows", "tail_kernel", "tail_rt", "bits", "pool_fused",
+                                       "dw", "S", "kc")]
 
 
 SMALL_DW_MAX = 32

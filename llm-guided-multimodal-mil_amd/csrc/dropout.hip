@@ -18,7 +18,7 @@
 //   p_drop = 0.5 : word w of the bit tensor = output word (w & 3) of block (w >> 2)            (1 random bit / element)
 //   p_drop = 0.25: word w = ~(out[2 (w & 1)] & out[2 (w & 1) + 1]) of block (w >> 1)          (dropped iff 2 bits set)
 //   otherwise    : element e kept iff out[e & 3] of block (e >> 2) >= p_drop * 2^32            (32 random bits / element)
-#include "mil_common.h"
+#include "mil_internal.h"
 #include "philox.h"
 
 // mode 0: p = 0.5, mode 1: p = 0.25, mode 2: generic threshold.  One thread per 128-bit Philox block.

@@ -213,3 +213,45 @@ static __global__ __launch_bounds__(256) void k_gate_bwd_reduce(const float* __r
         adam_fused(ad, dst, v);
     }
 }
+
+// ---- host side: the one place that launches the fold
+// SB as above.  head (nullable): the head's parameter gradients and the loss as appended workgroups; ad (nullable): Adam
+// on the spot, with the bf16 shadows Wv16 / Wu16 or the weight pieces Wp of the gate weights rewritten by the same threads.
+static inline int launch_gate_bwd_reduce(const float* part, const float* pbias, int S, int SB, int L, float* dWv, float* dbv,
+                                         float* dWu, float* dbu, float* dw, float* db, int accumulate, float wscale,
+                                         hipStream_t st, const HeadBwdArgs* head = nullptr, const AdamFuse* ad = nullptr,
+                                         uint16_t* Wv16 = nullptr, uint16_t* Wu16 = nullptr, uint16_t* Wp = nullptr) {
+    const int nthreads = GR_NG * (L / 4) + GR_NB * (3 * 192 + 1);
+    const int nred = (nthreads + 255) / 256, nhead = head ? head->C * ((head->L + 63) / 64) + 1 : 0;
+    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3(nred + nhead), dim3(256), 0, st, part, pbias, S, SB, L, dWv, dbv, dWu, dbu, dw, db,
+                       accumulate, wscale, head ? nred : 1 << 30, head ? *head : HeadBwdArgs{}, ad ? *ad : AdamFuse{},
+                       (unsigned short*)Wv16, (unsigned short*)Wu16, (unsigned short*)Wp);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// The AdamFuse of a fold launch that updates the parameters it has the gradients of: every gradient must lie inside the
+// flat buffer (16-byte aligned where it is stored as float4), and `step` >= 1 is the update's number unless a device
+// counter (step_dev) carries it.  MIL_EINVAL otherwise.
+static inline int gate_adam_fuse(const float* dWv, const float* dbv, const float* dWu, const float* dbu, const float* dw,
+                                 const float* db, const HeadBwdArgs& head, float* param_flat, const float* grad_flat,
+                                 size_t n_param, float* exp_avg, float* exp_avg_sq, int step, const int* step_dev, float lr,
+                                 const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                 int* done, AdamFuse* out) {
+    if (!param_flat || !grad_flat || !exp_avg || !exp_avg_sq || (step_dev == nullptr && step < 1)) return MIL_EINVAL;
+    const float* outs[8] = {dWv, dbv, dWu, dbu, dw, db, head.dWf, head.dbf};
+    const size_t lens[8] = {(size_t)192 * head.L, 192, (size_t)192 * head.L, 192, 192, 1, (size_t)head.C * head.L, (size_t)head.C};
+    for (int i = 0; i < 8; ++i)
+        if (outs[i] < grad_flat || outs[i] + lens[i] > grad_flat + n_param) return MIL_EINVAL;
+    if (((dWv - grad_flat) | (dWu - grad_flat)) & 3) return MIL_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(param_flat) | reinterpret_cast<uintptr_t>(grad_flat) | reinterpret_cast<uintptr_t>(exp_avg) |
+         reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+        return MIL_EINVAL;
+    if (step_dev != nullptr) step = 1;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    // the kernel forms the same single-precision quotient k_adam forms (lr / (float)bc1): the two routes stay bit-identical
+    *out = AdamFuse{param_flat, grad_flat, exp_avg, exp_avg_sq, (float)bc1, beta1, beta2, eps, weight_decay, grad_scale,
+                    (float)sqrt(bc2), step_dev, lr, lr_dev, step_dev ? done : nullptr};
+    return MIL_OK;
+}

@@ -5,7 +5,7 @@
 //   * gate GEMMs  x[R,L] . [Wv;Wu]^T -> [R,384] and its transpose-product in the backward are
 //     dense fp32 contractions: v_mfma_f32_32x32x2_f32 (exact f32, 157 TFLOP/s roof).
 //   * scores -> softmax over the bag -> A.x (and ds in the backward) stream x once: HBM-bound.
-#include "mil_common.h"
+#include "mil_internal.h"
 #include "philox.h"
 #include "gate_reduce.h"
 #include <type_traits>
@@ -1614,26 +1614,7 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2(const float* __restrict__ 
 #include "gate_reduce.h"
 
 // ================================================================================ host entry points
-// KG = 2 (two K groups per 512-thread workgroup, one workgroup per CU) once a row chunk is at least 512 rows deep
-static inline int split_kg(int R, int L) {
-#if defined(GB_NO_KG2)
-    return 1;
-#endif
-    const int NJ = L / 128;
-    const int smax = (MIL_NUM_CU) / (3 * NJ);
-    return (smax >= 1 && R / smax >= 512) ? 2 : 1;
-}
-static inline int split_plan(int R, int L, int* KC_out) {
-    const int NJ = L / 128;
-    int smax = (2 * MIL_NUM_CU / split_kg(R, L)) / (3 * NJ);
-    if (smax < 1) smax = 1;
-    int kc = ((R + smax - 1) / smax + GB_BKR - 1) / GB_BKR * GB_BKR;
-    if (kc < GB_BKR) kc = GB_BKR;
-    *KC_out = kc;
-    return (R + kc - 1) / kc;
-}
-
-extern "C" int mil_abi_version(void) { return 7; }
+extern "C" int mil_abi_version(void) { return 8; }
 
 // Small batches (the authors train with ONE bag per GPU: R = 1 000 - 15 000 rows): 128-row tiles would leave most CUs
 // idle (8 workgroups for 1024 patches, each walking all of K: the kernel takes its full ~100 us for 1/32 of the
@@ -1784,10 +1765,8 @@ __global__ __launch_bounds__(GS_THREADS) void k_gate_fwd_r32(const float* __rest
     }
 }
 
-// Tile quantisation: with one 128-row workgroup per CU, R = k * 256 * 128 + (a few rows) costs a whole extra round of
-// the grid for one workgroup (config 3: 32 bags x (1024 patches + 2 tokens) = 256.5 tiles -> 2x the kernel time).
-// When the rows beyond a whole number of rounds fit the few-rows linear (<= 64), they take that path instead:
-// V and U through mil_linear_small_fwd straight into the gates buffer, then one tiny scoring launch.
+// The few rows beyond whole rounds of the grid (gate_route_plan, MIL_ROUTE_TAIL_SMALL): scores from the V, U that
+// mil_linear_small_fwd wrote into the gates buffer.
 __global__ __launch_bounds__(64) void k_gate_tail_scores(const float* __restrict__ gates, const float* __restrict__ wvec,
                                                          const float* __restrict__ battn, float* __restrict__ scores) {
     const int row = blockIdx.x, lane = threadIdx.x;
@@ -1799,17 +1778,113 @@ __global__ __launch_bounds__(64) void k_gate_tail_scores(const float* __restrict
     if (lane == 0) scores[row] = v + battn[0];
 }
 
+// ---- the route plan: which kernels the fp32 gate step launches for a shape, decided here and nowhere else
+// (mil_gate_route, include/mil_hip.h).  Pure host arithmetic: no HIP call, the CU count comes in as a parameter.
+struct GateRouteIn {
+    int R, L;
+    bool save_gates;        // `gates` is written (the small tail keeps V, U there)
+    int keep;               // MIL_ROUTE_BITS_NONE, _GIVEN, or _GENERATOR for "to be drawn" (the plan says where)
+    bool pieces;            // weight pieces Wp given
+    bool fused_pool;        // the caller wants the pool partial pass in the epilogue and its tile map is all full, aligned tiles
+};
+struct GateDwPlan {
+    int dw, S, kc;          // MIL_ROUTE_DW_*, row chunks (split-K factor), rows per chunk
+};
+// rows beyond whole rounds of 128-row tiles that fit the few-rows kernels (shared with the input gradient below)
 static inline int gate_tail_rows(int R, int tiles_per_round) {
     const int tail = R % GF_TM, full = R / GF_TM;
     return (tail >= 1 && tail <= MIL_SMALL_ROWS && full >= tiles_per_round && full % tiles_per_round == 0) ? tail : 0;
 }
+static inline int gate_r32_rt(int rows, int ncu) {
+    const int tiles = (rows + GS_TM - 1) / GS_TM;
+    return tiles <= ncu ? 1 : tiles <= 2 * ncu ? 2 : 3;
+}
+// The weight-gradient part of the plan: it depends on the shape alone (L % 128 == 0).  KG = 2 (two K groups per 512-thread
+// workgroup, one workgroup per CU) once a row chunk is at least 512 rows deep; with fp32 x and offsets within 32 bits that
+// is the low-VALU kernel (k_gate_bwd_dw2; bf16 x stays on k_gate_bwd_dw<true, 2>)
+static GateDwPlan gate_dw_plan(int R, int L, int ncu) {
+    const int NJ = L / 128;
+    GateDwPlan d{};
+    int kg = 1;
+#if !defined(GB_NO_KG2)
+    if (ncu / (3 * NJ) >= 1 && R / (ncu / (3 * NJ)) >= 512) kg = 2;
+#endif
+    d.dw = kg == 2 ? MIL_ROUTE_DW_KG2 : MIL_ROUTE_DW_KG1;
+#if !defined(GB_NO_DW2)
+    if (kg == 2 && (long long)R * L < (1ll << 29)) d.dw = MIL_ROUTE_DW2;
+#endif
+    int smax = (2 * ncu / kg) / (3 * NJ);
+    if (smax < 1) smax = 1;
+    d.kc = ((R + smax - 1) / smax + GB_BKR - 1) / GB_BKR * GB_BKR;
+    if (d.kc < GB_BKR) d.kc = GB_BKR;
+    d.S = (R + d.kc - 1) / d.kc;
+    return d;
+}
+static mil_gate_route gate_route_plan(const GateRouteIn& in, int ncu) {
+    const int R = in.R, L = in.L;
+    mil_gate_route p{};
+    // fewer 128-row tiles than 3/4 of the CUs: 32-row tiles (4x the workgroups, each a quarter of the time), RT of them per
+    // workgroup - the smallest count that covers the rows in one round of one-workgroup-per-CU launches
+    const bool r32 = (R + GF_TM - 1) / GF_TM < (3 * ncu) / 4;
+#if defined(GF_NO_FWD2)
+    const bool fwd2 = false;
+#else
+    const bool fwd2 = L <= 4096;                 // 128 rows x L floats must stay inside the 32-bit buffer offsets (and int math)
+#endif
+    p.main = r32 ? MIL_ROUTE_MAIN_R32 : !fwd2 ? MIL_ROUTE_MAIN_LEGACY : in.pieces ? MIL_ROUTE_MAIN_FWD2_PW : MIL_ROUTE_MAIN_FWD2;
+    p.rt = r32 ? gate_r32_rt(R, ncu) : 0;
+    if (!r32) {
+        // Tile quantisation: with one 128-row workgroup per CU, R = k * ncu * 128 + (a few rows) costs a whole extra round
+        // of the grid for one workgroup (config 3: 32 bags x (1024 patches + 2 tokens) = 256.5 tiles -> 2x the kernel time).
+        // When the rows beyond a whole number of rounds fit the few-rows linear (<= 64), they take that path instead.
+        // Otherwise a last round that would hold only a few workgroups (T text tokens per bag appended to 32 x 1024 patches:
+        // 259 tiles on 256 CUs): every row beyond the whole rounds, up to 1024 of them, goes through the 32-row kernel
+        // (10 workgroups of a quarter of the time)
+        const int few = in.save_gates ? gate_tail_rows(R, ncu) : 0, per_round = GF_TM * ncu, over = R % per_round;
+        if (few > 0) {
+            p.tail = MIL_ROUTE_TAIL_SMALL;
+            p.tail_rows = few;
+        } else if (R >= per_round && over > 0 && over <= 1024) {
+            p.tail = MIL_ROUTE_TAIL_BIG;
+            p.tail_rows = over;
+        }
+    }
+    if (p.tail != MIL_ROUTE_TAIL_NONE) {
+        // the 32-row kernel applies the keep bits while staging; the few-rows linear has no such input
+        const bool small_linear = p.tail == MIL_ROUTE_TAIL_SMALL && in.keep == MIL_ROUTE_BITS_NONE;
+        p.tail_kernel = small_linear ? MIL_ROUTE_TAIL_KERNEL_LINEAR_SMALL : MIL_ROUTE_TAIL_KERNEL_R32;
+        p.tail_rt = small_linear ? 0 : gate_r32_rt(p.tail_rows, ncu);
+    }
+    const bool all_fwd2 = !r32 && p.tail == MIL_ROUTE_TAIL_NONE && fwd2;        // every row goes through k_gate_fwd2
+    // the forward kernel can draw the keep bits itself when a workgroup's [128][L/32] words fit its LDS slot; otherwise the
+    // stand-alone generator runs first
+    p.bits = in.keep == MIL_ROUTE_BITS_NONE || in.keep == MIL_ROUTE_BITS_GIVEN ? in.keep
+             : all_fwd2 && L <= 1024 && (L % 128) == 0 ? MIL_ROUTE_BITS_IN_KERNEL : MIL_ROUTE_BITS_GENERATOR;
+    p.pool_fused = in.fused_pool && all_fwd2 && L == 512 && (R % 32) == 0;      // the pool partial pass in the epilogue
+    p.dw = -1;
+    if ((L % 128) == 0) {
+        const GateDwPlan d = gate_dw_plan(R, L, ncu);
+        p.dw = d.dw;
+        p.S = d.S;
+        p.kc = d.kc;
+    }
+    return p;
+}
+
+// C and bucketed describe the step for the caller's benefit; the plan does not depend on them (whether the fused pool is
+// asked for at all - C == 2, not bucketed, the stage bits - is the caller's rule, mil_image_only_step_run's in step.hip)
+extern "C" int mil_gate_step_route(int R, int L, int C, int save_gates, int keep, int pieces, int fused_pool, int bucketed,
+                                   int ncu, mil_gate_route* out) {
+    if (!out || R <= 0 || L <= 0 || (L % GF_BK) != 0 || C <= 0) return MIL_EINVAL;
+    if (keep != MIL_ROUTE_BITS_NONE && keep != MIL_ROUTE_BITS_GIVEN) keep = MIL_ROUTE_BITS_GENERATOR;
+    (void)bucketed;
+    *out = gate_route_plan(GateRouteIn{R, L, save_gates != 0, keep, pieces != 0, fused_pool != 0}, ncu > 0 ? ncu : MIL_NUM_CU);
+    return MIL_OK;
+}
 
 static int launch_gate_fwd_r32(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
                                const float* w, const float* b, float* scores, float* gates, int R, int L,
-                               const uint32_t* xbits, float xscale, hipStream_t st, const int32_t* rows_dev = nullptr) {
-    // row tiles per workgroup: the smallest count that covers R in one round of one-workgroup-per-CU launches
-    const int tiles = (R + GS_TM - 1) / GS_TM;
-    const int rt = tiles <= MIL_NUM_CU ? 1 : tiles <= 2 * MIL_NUM_CU ? 2 : 3;
+                               const uint32_t* xbits, float xscale, int rt, hipStream_t st, const int32_t* rows_dev = nullptr) {
     const dim3 grid((R + GS_TM * rt - 1) / (GS_TM * rt));
     const float xs = xbits ? xscale : 1.0f;
 #define R32_LAUNCH(D_, RT_) hipLaunchKernelGGL((k_gate_fwd_r32<D_, RT_>), grid, dim3(GS_THREADS), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, xbits, xs, rows_dev)
@@ -1820,13 +1895,11 @@ static int launch_gate_fwd_r32(const float* x, const float* Wv, const float* bv,
     return MIL_OK;
 }
 
-int dropout_keep_bits_pair(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed, uint64_t offset,
-                           const int32_t* offset_dev, void* stream);
-int dropout_keep_bits_pair_tilemap(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed,
-                                   uint64_t offset, const int32_t* offset_dev, const TileMapJob& tm, void* stream);
-extern "C" int mil_build_tile_map(const int32_t* bag_len, int B, int32_t* tile_map, int32_t* bag_tile_off, int32_t* rows_out,
-                                  int T_cap, void* stream);      // dropout.hip
-
+// gen: the keep bits are drawn by this call (in the forward kernel or by a generator launch in front of it: the plan
+// says which), else xbits (nullable) are given.  pool + fused: the caller wants the pool partial pass in the epilogue;
+// *fused says whether it ran there.  tmap: the step's tile map is still to be built (it writes rows_dev, which the
+// forward reads): it rides on the generator launch where there is one, and is a launch of its own in front of the
+// forward otherwise.  Wp (three-piece bf16 planes of [Wv; Wu], gp_index layout): the split-bf16 K loop of k_gate_fwd2.
 static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
                                 const float* w, const float* b, float* scores, float* gates, int R, int L, int D,
                                 const uint32_t* xbits, float xscale, const GateFwdGen* gen, void* stream,
@@ -1836,125 +1909,81 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
     if (D != MIL_GATE_D || L <= 0 || (L % GF_BK) != 0 || R < 0) return MIL_EINVAL;
     if (R == 0) return MIL_OK;
     hipStream_t st = (hipStream_t)stream;
-    // tmap: the step's tile map is still to be built (it writes rows_dev, which this launch reads): it rides on the generator
-    // launch where there is one, and is a launch of its own in front of the forward otherwise
-    bool tmap_done = tmap == nullptr;
-    auto tmap_alone = [&]() -> int {
-        if (tmap_done) return MIL_OK;
-        tmap_done = true;
-        return mil_build_tile_map(tmap->bag_len, tmap->B, tmap->tile_map, tmap->bag_tile_off, tmap->rows_out, tmap->T_cap, stream);
-    };
-    const bool r32 = (R + GF_TM - 1) / GF_TM < (3 * MIL_NUM_CU) / 4;
-    int tail = (!r32 && gates != nullptr) ? gate_tail_rows(R, MIL_NUM_CU) : 0;   // the tail path keeps V, U in `gates`
-    if (!r32 && tail == 0) {
-        // A last round that would hold only a few workgroups (T text tokens per bag appended to 32 x 1024 patches: 259
-        // tiles on 256 CUs) costs a whole round: every row beyond the whole rounds, up to 1024 of them, goes through the
-        // 32-row kernel instead (10 workgroups of a quarter of the time)
-        const int per_round = GF_TM * MIL_NUM_CU;
-        const int over = R % per_round;
-        if (R >= per_round && over > 0 && over <= 1024) tail = -over;       // negative: "large tail", always the 32-row kernel
-    }
-    const bool big_tail = tail < 0;
-    if (big_tail) tail = -tail;
-#if defined(GF_NO_FWD2)
-    const bool fwd2 = false;
-#else
-    const bool fwd2 = L <= 4096;                 // 128 rows x L floats must stay inside the 32-bit buffer offsets (and int math)
-#endif
     if (fused != nullptr) *fused = 0;
-    const GateFwdPool nopool{};
-    // Wp (three-piece bf16 planes of [Wv; Wu], gp_index layout): the split-bf16 K loop of k_gate_fwd2
-#define GF2_LAUNCH(D_, G_, PQ_, R_, ...)                                                                                       \
-    do {                                                                                                                       \
-        if (Wp != nullptr)                                                                                                     \
-            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_, true>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, \
-                               gates, R_, L, __VA_ARGS__, (const unsigned short*)Wp);                                          \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_>), dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, \
-                               R_, L, __VA_ARGS__);                                                                            \
-    } while (0)
-    // the pool partial pass rides in the forward's epilogue when every row goes through k_gate_fwd2 and every tile of the
-    // map is a full, aligned 32-row tile (T * 32 == R: tile t = rows 32 t ..)
-    const bool pool_in = pool != nullptr && fused != nullptr && !r32 && tail == 0 && fwd2 && L == 512 && (R % 32) == 0 &&
-                         pool->T * MIL_POOL_TILE == R && pool->tile_map && pool->partials && pool->Wf && pool->hrow;
-    if (gen != nullptr) {
-        // the forward kernel can draw the keep bits itself when every row goes through k_gate_fwd2 and a workgroup's
-        // [128][L/32] words fit its LDS slot; otherwise the stand-alone generator runs first
-        const bool in_kernel = !r32 && tail == 0 && fwd2 && L <= 1024 && (L % 128) == 0;
-        if (in_kernel) {
-            { const int rc_ = tmap_alone(); if (rc_ != MIL_OK) return rc_; }
-            const int grid = (R + GF_TM - 1) / GF_TM;
-            if (pool_in && gen->mbits_out != nullptr) {
-                GF2_LAUNCH((true), (true), 2, R, gen->xbits_out, xscale, *gen, *pool);
-                *fused = 1;
-            } else {
-                GF2_LAUNCH((true), (true), 0, R, gen->xbits_out, xscale, *gen, nopool);
-            }
-            MIL_CHECK_LAUNCH();
-            return MIL_OK;
-        }
-        int rc;
-        if (gen->mbits_out != nullptr && !tmap_done) {
-            rc = dropout_keep_bits_pair_tilemap(gen->xbits_out, R, gen->mbits_out, gen->B, L,
-                                                ((uint64_t)gen->seed_hi << 32) | gen->seed_lo,
-                                                ((uint64_t)gen->mseed_hi << 32) | gen->mseed_lo, gen->offset, gen->offset_dev, *tmap,
-                                                stream);
-            tmap_done = true;
+    // the fused pool pass needs every tile of the map full and aligned (T * 32 == R: tile t = rows 32 t ..) and the head's
+    // keep words where the patch rows have theirs
+    const bool pool_ok = pool != nullptr && fused != nullptr && pool->T * MIL_POOL_TILE == R && pool->tile_map &&
+                         pool->partials && pool->Wf && pool->hrow &&
+                         (gen ? gen->mbits_out != nullptr : (xbits != nullptr) == (pool->mbits != nullptr));
+    const int keep = gen ? MIL_ROUTE_BITS_GENERATOR : xbits ? MIL_ROUTE_BITS_GIVEN : MIL_ROUTE_BITS_NONE;
+    const mil_gate_route p = gate_route_plan(GateRouteIn{R, L, gates != nullptr, keep, Wp != nullptr, pool_ok}, MIL_NUM_CU);
+
+    int rc = MIL_OK;
+    if (p.bits == MIL_ROUTE_BITS_GENERATOR) {
+        const uint64_t seed = ((uint64_t)gen->seed_hi << 32) | gen->seed_lo, mseed = ((uint64_t)gen->mseed_hi << 32) | gen->mseed_lo;
+        if (gen->mbits_out != nullptr && tmap != nullptr) {
+            rc = dropout_keep_bits_pair_tilemap(gen->xbits_out, R, gen->mbits_out, gen->B, L, seed, mseed, gen->offset,
+                                                gen->offset_dev, *tmap, stream);
+            tmap = nullptr;
         } else if (gen->mbits_out != nullptr)
-            rc = dropout_keep_bits_pair(gen->xbits_out, R, gen->mbits_out, gen->B, L, ((uint64_t)gen->seed_hi << 32) | gen->seed_lo,
-                                        ((uint64_t)gen->mseed_hi << 32) | gen->mseed_lo, gen->offset, gen->offset_dev, stream);
+            rc = dropout_keep_bits_pair(gen->xbits_out, R, gen->mbits_out, gen->B, L, seed, mseed, gen->offset, gen->offset_dev, stream);
         else
-            rc = mil_dropout_keep_bits(gen->xbits_out, R, L, 0.5f, ((uint64_t)gen->seed_hi << 32) | gen->seed_lo, gen->offset,
-                                       gen->offset_dev, stream);
+            rc = mil_dropout_keep_bits(gen->xbits_out, R, L, 0.5f, seed, gen->offset, gen->offset_dev, stream);
         if (rc != MIL_OK) return rc;
         xbits = gen->xbits_out;
     }
-    { const int rc_ = tmap_alone(); if (rc_ != MIL_OK) return rc_; }
-    if (r32) {
-        // fewer 128-row tiles than 3/4 of the CUs: 32-row tiles (4x the workgroups, each a quarter of the time)
-        return launch_gate_fwd_r32(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, xbits, xscale, st, rows_dev);
+    if (tmap != nullptr) {
+        rc = mil_build_tile_map(tmap->bag_len, tmap->B, tmap->tile_map, tmap->bag_tile_off, tmap->rows_out, tmap->T_cap, stream);
+        if (rc != MIL_OK) return rc;
     }
-    const int Rm = R - tail;
-    const int grid = (Rm + GF_TM - 1) / GF_TM;
-    const GateFwdGen nogen{};
-    if (pool_in && xbits && pool->mbits) {
-        GF2_LAUNCH((true), (false), 2, Rm, xbits, xscale, nogen, *pool);
-        *fused = 1;
-    } else if (pool_in && !xbits && !pool->mbits) {
-        GF2_LAUNCH((false), (false), 2, Rm, xbits, 1.0f, nogen, *pool);
-        *fused = 1;
-    } else if (fwd2 && xbits)
-        GF2_LAUNCH((true), (false), 0, Rm, xbits, xscale, nogen, nopool);
-    else if (fwd2)
-        GF2_LAUNCH((false), (false), 0, Rm, xbits, 1.0f, nogen, nopool);
-    else if (xbits)
-        hipLaunchKernelGGL(k_gate_fwd<true>, dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L, xbits,
-                           xscale);
-    else
-        hipLaunchKernelGGL(k_gate_fwd<false>, dim3(grid), dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L, xbits,
-                           1.0f);
+    if (p.main == MIL_ROUTE_MAIN_R32)
+        return launch_gate_fwd_r32(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, xbits, xscale, p.rt, st, rows_dev);
+
+    const bool draw = p.bits == MIL_ROUTE_BITS_IN_KERNEL;
+    if (draw) xbits = gen->xbits_out;
+    const int Rm = R - p.tail_rows;
+    const dim3 grid((Rm + GF_TM - 1) / GF_TM);
+    const float xs = xbits ? xscale : 1.0f;
+    if (p.main == MIL_ROUTE_MAIN_LEGACY) {
+        if (xbits) hipLaunchKernelGGL(k_gate_fwd<true>, grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L, xbits, xs);
+        else hipLaunchKernelGGL(k_gate_fwd<false>, grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L, xbits, xs);
+    } else {
+        const GateFwdGen fgen = draw ? *gen : GateFwdGen{};
+        const GateFwdPool fpool = p.pool_fused ? *pool : GateFwdPool{};
+#define GF2_LAUNCH(D_, G_, PQ_)                                                                                                \
+    do {                                                                                                                       \
+        if (p.main == MIL_ROUTE_MAIN_FWD2_PW)                                                                                  \
+            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_, true>), grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, \
+                               Rm, L, xbits, xs, fgen, fpool, (const unsigned short*)Wp);                                      \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_>), grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, \
+                               L, xbits, xs, fgen, fpool);                                                                     \
+    } while (0)
+        if (draw) { if (p.pool_fused) GF2_LAUNCH(true, true, 2); else GF2_LAUNCH(true, true, 0); }
+        else if (xbits) { if (p.pool_fused) GF2_LAUNCH(true, false, 2); else GF2_LAUNCH(true, false, 0); }
+        else { if (p.pool_fused) GF2_LAUNCH(false, false, 2); else GF2_LAUNCH(false, false, 0); }
+#undef GF2_LAUNCH
+    }
+    if (p.pool_fused) *fused = 1;
     MIL_CHECK_LAUNCH();
-    if (tail > 0 && (xbits || big_tail)) {
-        // train mode: the few rows beyond whole rounds go through the 32-row kernel (it applies the keep bits while staging)
+    if (p.tail_kernel == MIL_ROUTE_TAIL_KERNEL_R32)
         return launch_gate_fwd_r32(x + (size_t)Rm * L, Wv, bv, Wu, bu, w, b, scores + Rm,
-                                   gates ? gates + (size_t)Rm * GF_NG : nullptr, tail, L,
-                                   xbits ? xbits + (size_t)Rm * (L / 32) : nullptr, xscale, st);
-    }
-    if (tail > 0) {
+                                   gates ? gates + (size_t)Rm * GF_NG : nullptr, p.tail_rows, L,
+                                   xbits ? xbits + (size_t)Rm * (L / 32) : nullptr, xscale, p.tail_rt, st);
+    if (p.tail_kernel == MIL_ROUTE_TAIL_KERNEL_LINEAR_SMALL) {
+        // V and U through mil_linear_small_fwd straight into the gates buffer, then one tiny scoring launch
         const float* xt = x + (size_t)Rm * L;
         float* gt = gates + (size_t)Rm * GF_NG;
-        int rc = mil_linear_small_fwd(xt, L, Wv, L, bv, 1 /* tanh */, nullptr, 0, gt, GF_NG, tail, MIL_GATE_D, L, stream);
+        rc = mil_linear_small_fwd(xt, L, Wv, L, bv, 1 /* tanh */, nullptr, 0, gt, GF_NG, p.tail_rows, MIL_GATE_D, L, stream);
         if (rc != MIL_OK) return rc;
-        rc = mil_linear_small_fwd(xt, L, Wu, L, bu, 4 /* sigmoid */, nullptr, 0, gt + MIL_GATE_D, GF_NG, tail, MIL_GATE_D, L,
+        rc = mil_linear_small_fwd(xt, L, Wu, L, bu, 4 /* sigmoid */, nullptr, 0, gt + MIL_GATE_D, GF_NG, p.tail_rows, MIL_GATE_D, L,
                                   stream);
         if (rc != MIL_OK) return rc;
-        hipLaunchKernelGGL(k_gate_tail_scores, dim3(tail), dim3(64), 0, st, gt, w, b, scores + Rm);
+        hipLaunchKernelGGL(k_gate_tail_scores, dim3(p.tail_rows), dim3(64), 0, st, gt, w, b, scores + Rm);
         MIL_CHECK_LAUNCH();
     }
     return MIL_OK;
 }
-
-#undef GF2_LAUNCH
 
 extern "C" int mil_gate_scores_fwd(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
                                    const float* w, const float* b, float* scores, float* gates, int R, int L, int D,
@@ -1962,11 +1991,8 @@ extern "C" int mil_gate_scores_fwd(const float* x, const float* Wv, const float*
     return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, D, xbits, xscale, nullptr, stream);
 }
 
-extern "C" int mil_gate_scores_fwd_draw(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
-                                        const float* w, const float* b, float* scores, float* gates, int R, int L, int D,
-                                        uint32_t* xbits_out, float xscale, uint32_t* mbits_out, int B, uint64_t seed,
-                                        uint64_t mseed, uint64_t offset, const int32_t* offset_dev, void* stream) {
-    if (!xbits_out || (L % 64) != 0 || (mbits_out && B <= 0)) return MIL_EINVAL;
+static GateFwdGen gate_fwd_gen(uint32_t* xbits_out, uint32_t* mbits_out, int B, uint64_t seed, uint64_t mseed, uint64_t offset,
+                               const int32_t* offset_dev) {
     GateFwdGen g{};
     g.xbits_out = xbits_out;
     g.mbits_out = mbits_out;
@@ -1977,41 +2003,34 @@ extern "C" int mil_gate_scores_fwd_draw(const float* x, const float* Wv, const f
     g.mseed_hi = (uint32_t)(mseed >> 32);
     g.offset = offset;
     g.offset_dev = offset_dev;
-    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, D, nullptr, xscale, &g, stream);
+    return g;
 }
 
-// Internal (step.hip): the gate forward of a bucketed batch (rows_dev = true row count on the device; R = capacity).
+extern "C" int mil_gate_scores_fwd_draw(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
+                                        const float* w, const float* b, float* scores, float* gates, int R, int L, int D,
+                                        uint32_t* xbits_out, float xscale, uint32_t* mbits_out, int B, uint64_t seed,
+                                        uint64_t mseed, uint64_t offset, const int32_t* offset_dev, void* stream) {
+    if (!xbits_out || (L % 64) != 0 || (mbits_out && B <= 0)) return MIL_EINVAL;
+    const GateFwdGen gen = gate_fwd_gen(xbits_out, mbits_out, B, seed, mseed, offset, offset_dev);
+    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, D, nullptr, xscale, &gen, stream);
+}
+
 int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
                       const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
                       uint32_t* mbits, int B, uint64_t seed, uint64_t mseed, uint64_t offset, const int32_t* offset_dev,
                       const int32_t* rows_dev, void* stream, const TileMapJob* tmap, const uint16_t* Wp) {
-    if (draw) {
-        if (!xbits || (L % 64) != 0 || (mbits && B <= 0)) return MIL_EINVAL;
-        GateFwdGen g{};
-        g.xbits_out = xbits;
-        g.mbits_out = mbits;
-        g.B = B;
-        g.seed_lo = (uint32_t)seed;
-        g.seed_hi = (uint32_t)(seed >> 32);
-        g.mseed_lo = (uint32_t)mseed;
-        g.mseed_hi = (uint32_t)(mseed >> 32);
-        g.offset = offset;
-        g.offset_dev = offset_dev;
-        return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, nullptr, xscale, &g, stream, nullptr,
-                                    nullptr, rows_dev, tmap, Wp);
-    }
-    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, xbits, xscale, nullptr, stream, nullptr,
-                                nullptr, rows_dev, tmap, Wp);
+    if (draw && (!xbits || (L % 64) != 0 || (mbits && B <= 0))) return MIL_EINVAL;
+    const GateFwdGen gen = gate_fwd_gen(xbits, mbits, B, seed, mseed, offset, offset_dev);
+    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, draw ? nullptr : xbits, xscale,
+                                draw ? &gen : nullptr, stream, nullptr, nullptr, rows_dev, tmap, Wp);
 }
 
-// Internal (step.hip): gate forward with the pool partial pass in its epilogue when the batch allows it; *fused says
-// whether partials / hrow were produced (otherwise the caller runs the stand-alone pool pass).  seed / mseed / offset as
-// mil_gate_scores_fwd_draw when draw != 0 (train mode, keep bits drawn by the kernel), else xbits / mbits are inputs.
 int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
                        const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
                        uint32_t* mbits, float mscale, int B, uint64_t seed, uint64_t mseed, uint64_t offset,
                        const int32_t* offset_dev, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
                        int* fused, void* stream, const uint16_t* Wp) {
+    if (draw && (!xbits || !mbits || (L % 64) != 0 || B <= 0)) return MIL_EINVAL;
     GateFwdPool pl{};
     pl.tile_map = tile_map;
     pl.partials = partials;
@@ -2020,23 +2039,9 @@ int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const f
     pl.hrow = hrow;
     pl.mbits = draw ? nullptr : mbits;
     pl.mscale = mscale;
-    if (draw) {
-        if (!xbits || !mbits || (L % 64) != 0 || B <= 0) return MIL_EINVAL;
-        GateFwdGen g{};
-        g.xbits_out = xbits;
-        g.mbits_out = mbits;
-        g.B = B;
-        g.seed_lo = (uint32_t)seed;
-        g.seed_hi = (uint32_t)(seed >> 32);
-        g.mseed_lo = (uint32_t)mseed;
-        g.mseed_hi = (uint32_t)(mseed >> 32);
-        g.offset = offset;
-        g.offset_dev = offset_dev;
-        return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, nullptr, xscale, &g, stream, &pl, fused,
-                                    nullptr, nullptr, Wp);
-    }
-    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, xbits, xscale, nullptr, stream, &pl, fused,
-                                nullptr, nullptr, Wp);
+    const GateFwdGen gen = gate_fwd_gen(xbits, mbits, B, seed, mseed, offset, offset_dev);
+    return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, draw ? nullptr : xbits, xscale,
+                                draw ? &gen : nullptr, stream, &pl, fused, nullptr, nullptr, Wp);
 }
 
 static int launch_pool_partial(const float* x, const float* scores, const int32_t* tile_map, int T, int L,
@@ -2137,10 +2142,10 @@ extern "C" int mil_attn_pool_bwd(const float* x, const float* scores, const floa
 
 template <bool XB16>
 static void launch_gate_bwd_dw(const void* x, const float* gates, const float* ds, const float* w, float* part, float* pbias,
-                               int R, int L, int kc, int NJ, int S, const uint32_t* xbits, hipStream_t st,
+                               int R, int L, int kc, int NJ, int S, int kg, const uint32_t* xbits, hipStream_t st,
                                const int32_t* rows_dev = nullptr) {
     const dim3 grid(S * 3 * NJ);
-    if (split_kg(R, L) == 2) {
+    if (kg == 2) {
         if (xbits) hipLaunchKernelGGL((k_gate_bwd_dw<XB16, 2, true>), grid, dim3(512), 0, st, x, gates, ds, w, part, pbias, R, L, kc, NJ, xbits, rows_dev);
         else hipLaunchKernelGGL((k_gate_bwd_dw<XB16, 2, false>), grid, dim3(512), 0, st, x, gates, ds, w, part, pbias, R, L, kc, NJ, xbits, rows_dev);
     } else {
@@ -2149,20 +2154,11 @@ static void launch_gate_bwd_dw(const void* x, const float* gates, const float* d
     }
 }
 
-// fp32 x, two K groups per workgroup, offsets within 32 bits: the low-VALU kernel (k_gate_bwd_dw2)
-static inline bool use_dw2(int R, int L) {
-#if defined(GB_NO_DW2)
-    return false;
-#endif
-    return split_kg(R, L) == 2 && (long long)R * L < (1ll << 29);
-}
 static inline size_t gate_bwd_ws_floats(int S, int L) { return (size_t)S * GF_NG * L + (size_t)S * (L / 128) * 4 * 192; }
 
 extern "C" size_t mil_gate_bwd_workspace_floats(int R, int L) {
     if (R <= 0 || L <= 0 || (L % 128) != 0) return 0;
-    int kc;
-    const int S = split_plan(R, L, &kc);
-    return gate_bwd_ws_floats(S, L);
+    return gate_bwd_ws_floats(gate_dw_plan(R, L, MIL_NUM_CU).S, L);
 }
 
 // The two launches of mil_gate_bwd_params as separate entry points (bench.py times the MFMA kernel alone).
@@ -2171,12 +2167,11 @@ static int gate_bwd_partials_impl(const float* x, const float* gates, const floa
                                   const int32_t* rows_dev, void* stream) {
     if (!x || !gates || !ds || !w || !workspace) return MIL_EINVAL;
     if (D != MIL_GATE_D || L <= 0 || (L % 128) != 0 || R <= 0) return MIL_EINVAL;
-    int kc;
-    const int S = split_plan(R, L, &kc);
+    const GateDwPlan p = gate_dw_plan(R, L, MIL_NUM_CU);
+    const int S = p.S, kc = p.kc, NJ = L / 128;
     if (workspace_floats < gate_bwd_ws_floats(S, L)) return MIL_ENOSPC;
-    const int NJ = L / 128;
-    if (use_dw2(R, L)) {
-        float* pb = workspace + (size_t)S * GF_NG * L;
+    float* pb = workspace + (size_t)S * GF_NG * L;
+    if (p.dw == MIL_ROUTE_DW2) {
         if (xbits)
             hipLaunchKernelGGL(k_gate_bwd_dw2<true>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,
                                R, L, kc, NJ, xbits, rows_dev);
@@ -2186,7 +2181,7 @@ static int gate_bwd_partials_impl(const float* x, const float* gates, const floa
         MIL_CHECK_LAUNCH();
         return MIL_OK;
     }
-    launch_gate_bwd_dw<false>((const void*)x, gates, ds, w, workspace, workspace + (size_t)S * GF_NG * L, R, L, kc, NJ, S, xbits,
+    launch_gate_bwd_dw<false>((const void*)x, gates, ds, w, workspace, pb, R, L, kc, NJ, S, p.dw == MIL_ROUTE_DW_KG2 ? 2 : 1, xbits,
                               (hipStream_t)stream, rows_dev);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
@@ -2206,18 +2201,21 @@ extern "C" int mil_gate_bwd_partials_rows(const float* x, const float* gates, co
     return gate_bwd_partials_impl(x, gates, ds, w, R, L, D, workspace, workspace_floats, xbits, rows_dev, stream);
 }
 
+// The fold of the workspace gate_bwd_partials_impl filled for (R, L): the same plan gives its layout
+static int gate_bwd_fold(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu, float* dw, float* db,
+                         int accumulate, float wscale, void* stream, const HeadBwdArgs* head = nullptr,
+                         const AdamFuse* ad = nullptr, uint16_t* Wp = nullptr) {
+    const GateDwPlan p = gate_dw_plan(R, L, MIL_NUM_CU);
+    return launch_gate_bwd_reduce(workspace, workspace + (size_t)p.S * GF_NG * L, p.S, p.dw == MIL_ROUTE_DW2 ? p.S * (L / 128) : p.S,
+                                  L, dWv, dbv, dWu, dbu, dw, db, accumulate, wscale, (hipStream_t)stream, head, ad, nullptr,
+                                  nullptr, Wp);
+}
+
 extern "C" int mil_gate_bwd_reduce(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu,
                                    float* dw, float* db, int accumulate, float xscale, void* stream) {
     if (!workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db) return MIL_EINVAL;
     if (L <= 0 || (L % 128) != 0 || R <= 0) return MIL_EINVAL;
-    int kc;
-    const int S = split_plan(R, L, &kc);
-    const int nthreads = GF_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3((nthreads + 255) / 256), dim3(256), 0, (hipStream_t)stream, workspace,
-                       workspace + (size_t)S * GF_NG * L, S, use_dw2(R, L) ? S * (L / 128) : S, L, dWv, dbv, dWu, dbu, dw, db,
-                       accumulate, xscale);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    return gate_bwd_fold(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xscale, stream);
 }
 
 extern "C" int mil_gate_bwd_params_head(const float* x, const float* gates, const float* ds, const float* w, int R, int L,
@@ -2229,16 +2227,8 @@ extern "C" int mil_gate_bwd_params_head(const float* x, const float* gates, cons
     if (B <= 0 || C <= 0 || C > 32 || (loss_bag && !loss_out)) return MIL_EINVAL;
     const int rc = mil_gate_bwd_partials(x, gates, ds, w, R, L, D, workspace, workspace_floats, xbits, stream);
     if (rc != MIL_OK) return rc;
-    int kc;
-    const int S = split_plan(R, L, &kc);
-    const int nthreads = GF_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    const int nred = (nthreads + 255) / 256, nhead = C * ((L + 63) / 64) + 1;
     const HeadBwdArgs head{dz, M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
-    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3(nred + nhead), dim3(256), 0, (hipStream_t)stream, workspace,
-                       workspace + (size_t)S * GF_NG * L, S, use_dw2(R, L) ? S * (L / 128) : S, L, dWv, dbv, dWu, dbu, dw, db,
-                       accumulate, xbits ? xscale : 1.0f, nred, head);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    return gate_bwd_fold(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xbits ? xscale : 1.0f, stream, &head);
 }
 
 // The reduce launch of mil_gate_bwd_params_head alone (split-K fold + the head's parameter gradients as appended
@@ -2249,25 +2239,9 @@ extern "C" int mil_gate_bwd_reduce_head(const float* workspace, int R, int L, fl
                                         void* stream) {
     if (!workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db || !dz || !M || !dWf || !dbf) return MIL_EINVAL;
     if (L <= 0 || (L % 128) != 0 || R <= 0 || B <= 0 || C <= 0 || C > 32 || (loss_bag && !loss_out)) return MIL_EINVAL;
-    int kc;
-    const int S = split_plan(R, L, &kc);
-    const int nthreads = GF_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    const int nred = (nthreads + 255) / 256, nhead = C * ((L + 63) / 64) + 1;
     const HeadBwdArgs head{dz, M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
-    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3(nred + nhead), dim3(256), 0, (hipStream_t)stream, workspace,
-                       workspace + (size_t)S * GF_NG * L, S, use_dw2(R, L) ? S * (L / 128) : S, L, dWv, dbv, dWu, dbu, dw, db,
-                       accumulate, xscale, nred, head);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    return gate_bwd_fold(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xscale, stream, &head);
 }
-
-int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu,
-                                   float* dw, float* db, int accumulate, float xscale, const float* dz, const float* M,
-                                   float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
-                                   float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
-                                   float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
-                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done = nullptr,
-                                   uint16_t* Wp = nullptr);
 
 // mil_gate_bwd_reduce_head with Adam applied by the threads that produce the final gradients (world size 1: nothing sits
 // between the gradient and the update): param_flat / exp_avg / exp_avg_sq are indexed like grad_flat, in which dWv .. dbf all
@@ -2283,8 +2257,6 @@ extern "C" int mil_gate_bwd_reduce_head_adam(const float* workspace, int R, int 
                                           lr, nullptr, beta1, beta2, eps, weight_decay, grad_scale, stream);
 }
 
-// step_dev != NULL: the update's number is (*step_dev + 1), read on the device (hipGraph replay); the counter is advanced by
-// this launch itself when `done` (a zeroed sign-off word) is given, else by the caller afterwards.  Internal (step.hip).
 int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu,
                                    float* dw, float* db, int accumulate, float xscale, const float* dz, const float* M,
                                    float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
@@ -2293,33 +2265,13 @@ int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* 
                                    float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done,
                                    uint16_t* Wp) {
     if (!workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db || !dz || !M || !dWf || !dbf) return MIL_EINVAL;
-    if (!param_flat || !grad_flat || !exp_avg || !exp_avg_sq || (step_dev == nullptr && step < 1)) return MIL_EINVAL;
-    if (step_dev != nullptr) step = 1;
     if (L <= 0 || (L % 128) != 0 || R <= 0 || B <= 0 || C <= 0 || C > 32 || (loss_bag && !loss_out)) return MIL_EINVAL;
-    // every gradient this launch produces must lie inside the flat buffer (16-byte aligned where it is stored as float4)
-    const float* outs[8] = {dWv, dbv, dWu, dbu, dw, db, dWf, dbf};
-    const size_t lens[8] = {(size_t)192 * L, 192, (size_t)192 * L, 192, 192, 1, (size_t)C * L, (size_t)C};
-    for (int i = 0; i < 8; ++i)
-        if (outs[i] < grad_flat || outs[i] + lens[i] > grad_flat + n_param) return MIL_EINVAL;
-    if (((dWv - grad_flat) | (dWu - grad_flat)) & 3) return MIL_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(param_flat) | reinterpret_cast<uintptr_t>(grad_flat) | reinterpret_cast<uintptr_t>(exp_avg) |
-         reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
-        return MIL_EINVAL;
-    int kc;
-    const int S = split_plan(R, L, &kc);
-    const int nthreads = GF_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    const int nred = (nthreads + 255) / 256, nhead = C * ((L + 63) / 64) + 1;
     const HeadBwdArgs head{dz, M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    // the kernel forms the same single-precision quotient k_adam forms (lr / (float)bc1): the two routes stay bit-identical
-    const AdamFuse ad{param_flat, grad_flat, exp_avg, exp_avg_sq, (float)bc1, beta1, beta2, eps, weight_decay, grad_scale,
-                      (float)sqrt(bc2), step_dev, lr, lr_dev, step_dev ? done : nullptr};
-    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3(nred + nhead), dim3(256), 0, (hipStream_t)stream, workspace,
-                       workspace + (size_t)S * GF_NG * L, S, use_dw2(R, L) ? S * (L / 128) : S, L, dWv, dbv, dWu, dbu, dw, db,
-                       accumulate, xscale, nred, head, ad, nullptr, nullptr, (unsigned short*)Wp);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    AdamFuse ad{};
+    const int rc = gate_adam_fuse(dWv, dbv, dWu, dbu, dw, db, head, param_flat, grad_flat, n_param, exp_avg, exp_avg_sq, step, step_dev,
+                                  lr, lr_dev, beta1, beta2, eps, weight_decay, grad_scale, done, &ad);
+    if (rc != MIL_OK) return rc;
+    return gate_bwd_fold(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xscale, stream, &head, &ad, Wp);
 }
 
 // The three-piece bf16 planes of [Wv; Wu] the split-bf16 gate forward reads (gp_index layout, 3 * 384 * L halves), formed
@@ -2360,21 +2312,16 @@ extern "C" int mil_gate_bwd_params_x16(const uint16_t* x, const float* gates, co
                                        float xscale, void* stream) {
     if (!x || !gates || !ds || !w || !workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db) return MIL_EINVAL;
     if (D != MIL_GATE_D || L <= 0 || (L % 128) != 0 || R <= 0) return MIL_EINVAL;
-    int kc;
-    const int S = split_plan(R, L, &kc);
-    const size_t need = gate_bwd_ws_floats(S, L);
-    if (workspace_floats < need) return MIL_ENOSPC;
+    const GateDwPlan p = gate_dw_plan(R, L, MIL_NUM_CU);          // bf16 x: k_gate_bwd_dw<true, KG> where fp32 x would take k_gate_bwd_dw2
+    const int S = p.S;
+    if (workspace_floats < gate_bwd_ws_floats(S, L)) return MIL_ENOSPC;
     float* part = workspace;
     float* pbias = workspace + (size_t)S * GF_NG * L;
-    const int NJ = L / 128;
     hipStream_t st = (hipStream_t)stream;
-    launch_gate_bwd_dw<true>((const void*)x, gates, ds, w, part, pbias, R, L, kc, NJ, S, xbits, st);
+    launch_gate_bwd_dw<true>((const void*)x, gates, ds, w, part, pbias, R, L, p.kc, L / 128, S, p.dw == MIL_ROUTE_DW_KG1 ? 1 : 2, xbits,
+                             st);
     MIL_CHECK_LAUNCH();
-    const int nthreads = GF_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3((nthreads + 255) / 256), dim3(256), 0, st, part, pbias, S, S, L, dWv, dbv, dWu,
-                       dbu, dw, db, accumulate, xbits ? xscale : 1.0f);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    return launch_gate_bwd_reduce(part, pbias, S, S, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xbits ? xscale : 1.0f, st);
 }
 
 // ================================================================================ K1 backward: gate dx (MFMA)

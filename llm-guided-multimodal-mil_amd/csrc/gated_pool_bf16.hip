@@ -9,7 +9,7 @@
 //                     version of the transposed product is the next step)
 #include <stdlib.h>
 
-#include "mil_common.h"
+#include "mil_internal.h"
 #include "gate_reduce.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1542,22 +1542,13 @@ int gate_bwd_params_bf16_tail(const uint16_t* x, const uint16_t* gates, const fl
     if (!x || !gates || !ds || !w || !workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db) return MIL_EINVAL;
     if (!dz || !M || !dWf || !dbf || B <= 0 || C <= 0 || C > 32 || (loss_bag && !loss_out)) return MIL_EINVAL;
     if (L <= 0 || (L % 256) != 0 || R <= 0) return MIL_EINVAL;
+    const HeadBwdArgs head{dz, M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
     AdamFuse ad{};
     if (param_flat != nullptr) {
-        if (!grad_flat || !exp_avg || !exp_avg_sq || !Wv16 || !Wu16 || (step_dev == nullptr && step < 1)) return MIL_EINVAL;
-        const float* outs[8] = {dWv, dbv, dWu, dbu, dw, db, dWf, dbf};
-        const size_t lens[8] = {(size_t)192 * L, 192, (size_t)192 * L, 192, 192, 1, (size_t)C * L, (size_t)C};
-        for (int i = 0; i < 8; ++i)
-            if (outs[i] < grad_flat || outs[i] + lens[i] > grad_flat + n_param) return MIL_EINVAL;
-        if (((dWv - grad_flat) | (dWu - grad_flat)) & 3) return MIL_EINVAL;
-        if ((reinterpret_cast<uintptr_t>(param_flat) | reinterpret_cast<uintptr_t>(grad_flat) |
-             reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
-            return MIL_EINVAL;
-        if (step_dev != nullptr) step = 1;
-        const double bc1 = 1.0 - pow((double)beta1, (double)step);
-        const double bc2 = 1.0 - pow((double)beta2, (double)step);
-        ad = AdamFuse{param_flat, grad_flat, exp_avg, exp_avg_sq, (float)bc1, beta1, beta2, eps, weight_decay, grad_scale,
-                      (float)sqrt(bc2), step_dev, lr, lr_dev, step_dev ? done : nullptr};
+        if (!Wv16 || !Wu16) return MIL_EINVAL;
+        const int rc = gate_adam_fuse(dWv, dbv, dWu, dbu, dw, db, head, param_flat, grad_flat, n_param, exp_avg, exp_avg_sq, step,
+                                      step_dev, lr, lr_dev, beta1, beta2, eps, weight_decay, grad_scale, done, &ad);
+        if (rc != MIL_OK) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     int S;
@@ -1566,13 +1557,8 @@ int gate_bwd_params_bf16_tail(const uint16_t* x, const uint16_t* gates, const fl
     const int rc_dw = launch_gate_bwd_dw16(x, gates, ds, w, workspace, workspace_floats, R, L, xbits, st, &S, &pbias);
     if (rc_dw != MIL_OK) return rc_dw;
     MIL_CHECK_LAUNCH();
-    const int nthreads = HB_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    const int nred = (nthreads + 255) / 256, nhead = C * ((L + 63) / 64) + 1;
-    const HeadBwdArgs head{dz, M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
-    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3(nred + nhead), dim3(256), 0, st, part, pbias, S, S, L, dWv, dbv, dWu, dbu, dw, db,
-                       accumulate, xbits ? xscale : 1.0f, nred, head, ad, param_flat ? Wv16 : nullptr, param_flat ? Wu16 : nullptr);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    return launch_gate_bwd_reduce(part, pbias, S, S, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xbits ? xscale : 1.0f, st, &head,
+                                  &ad, param_flat ? Wv16 : nullptr, param_flat ? Wu16 : nullptr);
 }
 
 extern "C" int mil_gate_bwd_params_bf16(const uint16_t* x, const uint16_t* gates, const float* ds, const float* w, int R,
@@ -1588,9 +1574,5 @@ extern "C" int mil_gate_bwd_params_bf16(const uint16_t* x, const uint16_t* gates
     const int rc_dw = launch_gate_bwd_dw16(x, gates, ds, w, workspace, workspace_floats, R, L, xbits, st, &S, &pbias);
     if (rc_dw != MIL_OK) return rc_dw;
     MIL_CHECK_LAUNCH();
-    const int nthreads = HB_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    hipLaunchKernelGGL(k_gate_bwd_reduce, dim3((nthreads + 255) / 256), dim3(256), 0, st, part, pbias, S, S, L, dWv, dbv, dWu,
-                       dbu, dw, db, accumulate, xbits ? xscale : 1.0f);
-    MIL_CHECK_LAUNCH();
-    return MIL_OK;
+    return launch_gate_bwd_reduce(part, pbias, S, S, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xbits ? xscale : 1.0f, st);
 }

@@ -16,7 +16,7 @@
 // read with ds_read_b32 at row 8t+4h+jj: both use the same k order, so modes mix freely.
 // Staging is branch-free (indices clamped, out-of-range k zeroed by a mask applied at LDS-write
 // time) and issued as 8 pieces between MFMA groups; registers hold the slice after next.
-#include "mil_common.h"
+#include "mil_internal.h"
 
 #define LG_BK 32
 #define LG_KS 36       // k-contiguous image row stride (words)
@@ -688,9 +688,6 @@ extern "C" size_t mil_linear_bwd_params_workspace_floats(int rows, int n_out, in
     if (S2 > S) S = S2;
     return (size_t)S * n_out * k_in + (size_t)S * n_out;
 }
-
-int mil_gemm_tn2_rows(const float* dY, int lddy, const float* Y, int ldy, int act, const float* X, int ldx, int rows, int N, int K,
-                      float* partial, float* cs_partial, const int32_t* rows_dev, void* stream);      // linear_nt2.hip
 
 // rows_dev (nullable): device int32 with the true number of rows (<= rows: the capacity of a bucket) - the rows behind it
 // carry zero gradients, and the tall-activation kernel then spreads only the true rows over its workgroups.

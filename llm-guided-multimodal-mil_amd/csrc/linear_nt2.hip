@@ -10,7 +10,7 @@
 // k-group reads 2 + 4 fragments for 32 MFMAs and a 32-deep slice is 128 MFMAs per wave between two barriers; LDS 2 x (32 +
 // 32) KB.  32 768 x 512 (fc_pathology) is exactly 256 workgroups = one round of the chip.
 // Epilogue: bias, tanh / ReLU (v_rcp-based tanh as in the gate kernels), 128-byte row segments per store instruction.
-#include "mil_common.h"
+#include "mil_internal.h"
 #include <type_traits>
 
 typedef __attribute__((address_space(3))) void nt2_lds_void;

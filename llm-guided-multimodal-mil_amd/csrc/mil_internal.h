@@ -1,0 +1,57 @@
+// Functions one .hip file defines and another calls that are not part of the C ABI (include/mil_hip.h).  Included by the
+// defining file as well, so the compiler holds every definition against the one prototype; default arguments live here only.
+#pragma once
+#include "mil_common.h"
+
+// ---- gated_pool.hip (called from step.hip)
+// Gate forward with the pool partial pass in its epilogue when the batch allows it; *fused says whether partials / hrow
+// were produced (otherwise the caller runs the stand-alone pool pass).  draw != 0 (train mode): the keep bits are drawn
+// by this call into xbits / mbits (seed / mseed / offset as mil_gate_scores_fwd_draw), else xbits / mbits are inputs.
+int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
+                       const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
+                       uint32_t* mbits, float mscale, int B, uint64_t seed, uint64_t mseed, uint64_t offset,
+                       const int32_t* offset_dev, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
+                       int* fused, void* stream, const uint16_t* Wp);
+// Gate forward of a bucketed batch (rows_dev = true row count on the device, R = capacity; NULL: a plain batch); tmap: the
+// tile map is still to be built and goes along (on the generator launch where there is one).
+int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
+                      const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
+                      uint32_t* mbits, int B, uint64_t seed, uint64_t mseed, uint64_t offset, const int32_t* offset_dev,
+                      const int32_t* rows_dev, void* stream, const TileMapJob* tmap, const uint16_t* Wp);
+// Split-K fold + head gradients + Adam in one launch.  step_dev != NULL: the update's number is (*step_dev + 1), read on
+// the device (hipGraph replay); the counter is advanced by this launch itself when `done` (a zeroed sign-off word) is
+// given, else by the caller afterwards.  Wp: the weight pieces of the split-bf16 forward, rewritten with the update.
+int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu,
+                                   float* dw, float* db, int accumulate, float xscale, const float* dz, const float* M,
+                                   float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
+                                   float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
+                                   float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
+                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream,
+                                   int* done = nullptr, uint16_t* Wp = nullptr);
+
+// ---- gated_pool_bf16.hip (called from step.hip)
+// bf16-MFMA weight gradient whose fold launch carries the head gradients, the loss and (param_flat != NULL) Adam + the
+// refresh of the bf16 weight shadows
+int gate_bwd_params_bf16_tail(const uint16_t* x, const uint16_t* gates, const float* ds, const float* w, int R, int L,
+                              float* workspace, size_t workspace_floats, float* dWv, float* dbv, float* dWu, float* dbu,
+                              float* dw, float* db, int accumulate, const uint32_t* xbits, float xscale, const float* dz,
+                              const float* M, float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
+                              float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg, float* exp_avg_sq,
+                              int step, const int* step_dev, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                              float weight_decay, float grad_scale, uint16_t* Wv16, uint16_t* Wu16, void* stream, int* done);
+// bf16 gate forward with the pool partial pass in its epilogue when the batch allows (*fused as gate_fwd_with_pool)
+int gate_fwd_bf16_with_pool(const uint16_t* x, const uint16_t* Wv, const float* bv, const uint16_t* Wu, const float* bu,
+                            const float* w, const float* b, float* scores, uint16_t* gates16, int R, int L, const uint32_t* xbits,
+                            float xscale, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
+                            const uint32_t* mbits, float mscale, int* fused, void* stream);
+
+// ---- dropout.hip (called from gated_pool.hip, step.hip)
+// both keep-bit tensors of a step in one launch; _tilemap: mil_build_tile_map rides along as one more workgroup
+int dropout_keep_bits_pair(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed, uint64_t offset,
+                           const int32_t* offset_dev, void* stream);
+int dropout_keep_bits_pair_tilemap(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed,
+                                   uint64_t offset, const int32_t* offset_dev, const TileMapJob& tm, void* stream);
+
+// ---- linear_nt2.hip (called from linear.hip)
+int mil_gemm_tn2_rows(const float* dY, int lddy, const float* Y, int ldy, int act, const float* X, int ldx, int rows, int N, int K,
+                      float* partial, float* cs_partial, const int32_t* rows_dev, void* stream);

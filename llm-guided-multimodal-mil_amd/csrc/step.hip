@@ -6,51 +6,7 @@
 // call is capture-safe (the host mirror replays it from a hipGraph for tiny one-bag steps) and costs one foreign call.
 #include <stdlib.h>
 
-#include "mil_common.h"
-
-// gated_pool.hip: gate forward + (when the batch allows) the pool partial pass in the same launch
-int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
-                       const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
-                       uint32_t* mbits, float mscale, int B, uint64_t seed, uint64_t mseed, uint64_t offset,
-                       const int32_t* offset_dev, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
-                       int* fused, void* stream, const uint16_t* Wp);
-
-// gated_pool.hip: gate forward of a bucketed batch - tiles beyond the true row count (rows_dev) are skipped
-int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu, const float* w,
-                      const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
-                      uint32_t* mbits, int B, uint64_t seed, uint64_t mseed, uint64_t offset, const int32_t* offset_dev,
-                      const int32_t* rows_dev, void* stream, const TileMapJob* tmap, const uint16_t* Wp);
-
-// gated_pool.hip: split-K fold + head gradients + Adam in one launch, the step number on the host or in a device counter
-int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu,
-                                   float* dw, float* db, int accumulate, float xscale, const float* dz, const float* M,
-                                   float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
-                                   float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
-                                   float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
-                                   float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done,
-                                   uint16_t* Wp);
-
-// gated_pool_bf16.hip: bf16-MFMA weight gradient whose fold launch carries the head gradients, the loss and (param_flat != NULL)
-// Adam + the refresh of the bf16 weight shadows
-int gate_bwd_params_bf16_tail(const uint16_t* x, const uint16_t* gates, const float* ds, const float* w, int R, int L,
-                              float* workspace, size_t workspace_floats, float* dWv, float* dbv, float* dWu, float* dbu,
-                              float* dw, float* db, int accumulate, const uint32_t* xbits, float xscale, const float* dz,
-                              const float* M, float* dWf, float* dbf, int B, int C, const float* loss_bag, float* loss_out,
-                              float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg, float* exp_avg_sq,
-                              int step, const int* step_dev, float lr, const float* lr_dev, float beta1, float beta2, float eps,
-                              float weight_decay, float grad_scale, uint16_t* Wv16, uint16_t* Wu16, void* stream, int* done);
-
-// gated_pool_bf16.hip: bf16 gate forward with the pool partial pass in its epilogue when the batch allows
-int gate_fwd_bf16_with_pool(const uint16_t* x, const uint16_t* Wv, const float* bv, const uint16_t* Wu, const float* bu,
-                            const float* w, const float* b, float* scores, uint16_t* gates16, int R, int L, const uint32_t* xbits,
-                            float xscale, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
-                            const uint32_t* mbits, float mscale, int* fused, void* stream);
-
-// dropout.hip: both keep-bit tensors of a step in one launch
-int dropout_keep_bits_pair(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed, uint64_t offset,
-                           const int32_t* offset_dev, void* stream);
-int dropout_keep_bits_pair_tilemap(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed,
-                                   uint64_t offset, const int32_t* offset_dev, const TileMapJob& tm, void* stream);
+#include "mil_internal.h"
 
 static int step_check(const mil_image_only_step* a) {
     if (!a || a->struct_bytes != sizeof(mil_image_only_step)) return MIL_EINVAL;

@@ -1,10 +1,13 @@
 """Test helpers for the fp32 image-only step (csrc/step.hip, mil_image_only_step_run): a mirror of the host rules that
-pick its gate-forward and weight-gradient kernels, and a plain float64 restatement of the whole step (gates, scores,
-softmax pool, head, loss and the gradients of all eight parameters) that runs on the device."""
+pick its gate-forward and weight-gradient kernels, the library's own statement of them (mil_gate_step_route) in the
+mirror's terms, and a plain float64 restatement of the whole step (gates, scores, softmax pool, head, loss and the
+gradients of all eight parameters) that runs on the device."""
+import ctypes
 import os
 
 import torch
 
+from mil_amd import _lib
 from mil_amd.trainer import PARAM_ORDER
 
 WV, BV = "aggregator.attention_V.0.weight", "aggregator.attention_V.0.bias"
@@ -22,67 +25,107 @@ def num_cu() -> int:
 
 
 def r32_rt(R: int, ncu: int) -> int:
-    """Row tiles per k_gate_fwd_r32 workgroup (launch_gate_fwd_r32, gated_pool.hip:1810-1812)."""
+    """Row tiles per k_gate_fwd_r32 workgroup (gated_pool.hip: gate_r32_rt)."""
     tiles = (R + GS_TM - 1) // GS_TM
     return 1 if tiles <= ncu else 2 if tiles <= 2 * ncu else 3
 
 
 def split_kg(R: int, L: int, ncu: int) -> int:
-    """gated_pool.hip:1618-1625."""
+    """K groups per weight-gradient workgroup (gated_pool.hip: the dw part of gate_route_plan)."""
     smax = ncu // (3 * (L // 128))
     return 2 if smax >= 1 and R // smax >= 512 else 1
 
 
 def dw_route(R: int, L: int, ncu: int) -> str:
-    """The fp32 weight-gradient kernel (gate_bwd_partials_impl, gated_pool.hip:2153-2158, 2178-2190)."""
+    """The fp32 weight-gradient kernel (gate_route_plan, launched by gate_bwd_partials_impl)."""
     kg = split_kg(R, L, ncu)
     return "dw2" if kg == 2 and R * L < (1 << 29) else f"dw<{kg}>"
 
 
+def dw_split(R: int, L: int, ncu: int):
+    """(S, kc): row chunks of the weight gradient's split-K and rows per chunk, a multiple of 32 (gate_route_plan)."""
+    smax = max((2 * ncu // split_kg(R, L, ncu)) // (3 * (L // 128)), 1)
+    kc = max(((R + smax - 1) // smax + 31) // 32 * 32, 32)
+    return (R + kc - 1) // kc, kc
+
+
 def step_route(R: int, L: int, C: int, train: bool, *, aligned32: bool = False, bucketed: bool = False,
-               pieces: bool = True, ncu: int = None) -> dict:
+               pieces: bool = True, ncu: int = None, given_bits: bool = False) -> dict:
     """Which kernels ImageOnlyTrainer.forward(x, layout, y) + backward() launch for the fp32 step with labels (gates
     saved).  R is the bucket capacity for a bucketed (DeviceBagLayout) batch.
 
-    main:   'r32' (k_gate_fwd_r32), 'fwd2_pw' (k_gate_fwd2<.., PW = true>) or 'fwd2' (its fp32-MFMA K loop)
+    main:   'r32' (k_gate_fwd_r32), 'fwd2_pw' (k_gate_fwd2<.., PW = true>), 'fwd2' (its fp32-MFMA K loop) or 'legacy'
+            (k_gate_fwd, L > 4096)
     rt:     RT of the r32 launch that carries the whole batch
     tail:   None, 'small' (rows beyond whole rounds, <= 64) or 'big' (<= 1024 rows beyond whole rounds)
+    tail_rows: rows that leave the main kernel for the tail kernel (0: none)
     tail_kernel / tail_rt: 'linear_small' (mil_linear_small_fwd + k_gate_tail_scores) or 'r32' and its RT
-    bits:   train mode only: 'in_kernel' (drawn by k_gate_fwd2<.., GEN = true>) or 'generator' (a launch of its own)
+    bits:   train mode only: 'in_kernel' (drawn by k_gate_fwd2<.., GEN = true>) or 'generator' (a launch of its own);
+            given_bits (not train: the gate forward alone, with keep bits the caller made): 'given'
     pool:   'fused' (pool partial pass in k_gate_fwd2's epilogue) or 'alone' (k_pool_partial)
     dw:     'dw<1>', 'dw<2>' (k_gate_bwd_dw<.., KG>) or 'dw2' (k_gate_bwd_dw2)
+    S, kc:  row chunks of the weight gradient's split-K, rows per chunk
     """
     ncu = ncu or num_cu()
-    # step.hip:88-167: the entry point
-    fuse_env = os.environ.get("MIL_FUSE_POOL", "1")[:1] != "0"
-    fused_entry = aligned32 and C == 2 and not bucketed and fuse_env          # step.hip:142-143 (use_h: C <= 4)
-    pw = pieces and L % 32 == 0                                               # trainer.py:203, step.hip:100
-    # gated_pool.hip gate_scores_fwd_impl
-    r32 = (R + GF_TM - 1) // GF_TM < (3 * ncu) // 4                           # :1847
+    fused_entry = _fused_entry(C, aligned32, bucketed)
+    pw = pieces and L % 32 == 0                       # trainer.py: ImageOnlyTrainer.gate_pieces; step.hip: Wp
+    # gated_pool.hip: gate_route_plan
+    r32 = (R + GF_TM - 1) // GF_TM < (3 * ncu) // 4
     tail, big = 0, False
     if not r32:
         t, full = R % GF_TM, R // GF_TM
-        if 1 <= t <= SMALL_ROWS and full >= ncu and full % ncu == 0:           # :1802-1805, :1848
+        if 1 <= t <= SMALL_ROWS and full >= ncu and full % ncu == 0:           # gate_tail_rows
             tail = t
         else:
-            over = R % (GF_TM * ncu)                                            # :1849-1856
+            over = R % (GF_TM * ncu)
             if R >= GF_TM * ncu and 0 < over <= 1024:
                 tail, big = over, True
-    fwd2 = L <= 4096                                                            # :1862
-    pool_in = fused_entry and not r32 and tail == 0 and fwd2 and L == 512 and R % 32 == 0      # :1878-1879
-    in_kernel = not r32 and tail == 0 and fwd2 and L <= 1024 and L % 128 == 0                 # :1883
-    out = dict(main="r32" if r32 else ("fwd2_pw" if pw else "fwd2"), rt=r32_rt(R, ncu) if r32 else None,
-               tail=None, tail_kernel=None, tail_rt=None, bits=None, pool="fused" if pool_in else "alone",
-               dw=dw_route(R, L, ncu))
+    fwd2 = L <= 4096
+    pool_in = fused_entry and not r32 and tail == 0 and fwd2 and L == 512 and R % 32 == 0
+    in_kernel = not r32 and tail == 0 and fwd2 and L <= 1024 and L % 128 == 0
+    S, kc = dw_split(R, L, ncu)
+    out = dict(main="r32" if r32 else "legacy" if not fwd2 else ("fwd2_pw" if pw else "fwd2"),
+               rt=r32_rt(R, ncu) if r32 else None, tail=None, tail_rows=tail, tail_kernel=None, tail_rt=None, bits=None,
+               pool="fused" if pool_in else "alone", dw=dw_route(R, L, ncu), S=S, kc=kc)
     if tail:
         out["tail"] = "big" if big else "small"
-        if big or train:                                                        # :1937-1942
+        if big or train or given_bits:             # keep bits: the 32-row kernel applies them while staging
             out["tail_kernel"], out["tail_rt"] = "r32", r32_rt(tail, ncu)
-        else:                                                                   # :1943-1953
+        else:
             out["tail_kernel"] = "linear_small"
     if train:
         out["bits"] = "in_kernel" if in_kernel else "generator"
+    elif given_bits:
+        out["bits"] = "given"
     return out
+
+
+def _fused_entry(C: int, aligned32: bool, bucketed: bool) -> bool:
+    """Whether mil_image_only_step_run asks for the pool pass in the forward's epilogue at all (step.hip: the
+    gate_fwd_with_pool branch; use_h holds for C <= 4 with labels)."""
+    fuse_env = os.environ.get("MIL_FUSE_POOL", "1")[:1] != "0"
+    return aligned32 and C == 2 and not bucketed and fuse_env
+
+
+_MAIN = ("r32", "fwd2", "fwd2_pw", "legacy")                  # MIL_ROUTE_MAIN_*
+_TAIL = (None, "small", "big")                                # MIL_ROUTE_TAIL_*
+_TAIL_KERNEL = (None, "linear_small", "r32")                  # MIL_ROUTE_TAIL_KERNEL_*
+_BITS = (None, "given", "in_kernel", "generator")             # MIL_ROUTE_BITS_*
+_DW = ("dw<1>", "dw<2>", "dw2")                               # MIL_ROUTE_DW_*
+
+
+def lib_route(R: int, L: int, C: int, train: bool, *, aligned32: bool = False, bucketed: bool = False,
+              pieces: bool = True, ncu: int = None, given_bits: bool = False) -> dict:
+    """The library's own route for the same step (mil_gate_step_route: the plan its launches execute), in step_route's
+    terms.  ncu None: the library plans for the device it runs on."""
+    p = _lib.GateRoute()
+    keep = _BITS.index("generator" if train else "given" if given_bits else None)
+    rc = _lib.lib().mil_gate_step_route(R, L, C, 1, keep, int(pieces),
+                                        int(_fused_entry(C, aligned32, bucketed)), int(bucketed), ncu or 0, ctypes.byref(p))
+    assert rc == 0, rc
+    return dict(main=_MAIN[p.main], rt=p.rt or None, tail=_TAIL[p.tail], tail_kernel=_TAIL_KERNEL[p.tail_kernel],
+                tail_rt=p.tail_rt or None, bits=_BITS[p.bits], pool="fused" if p.pool_fused else "alone", dw=_DW[p.dw] if p.dw >= 0 else None,
+                S=p.S, kc=p.kc, tail_rows=p.tail_rows)
 
 
 # ------------------------------------------------------------------------------------------ float64 reference

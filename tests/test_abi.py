@@ -53,10 +53,10 @@ def test_tile_map_ragged():
 
 
 @pytest.mark.parametrize("cname,pyname", [("mil_image_only_step", "ImageOnlyStep"), ("mil_small_dw_desc", "SmallDwDesc"),
-                                          ("mil_cohort_feed_desc", "CohortFeedDesc")])
+                                          ("mil_cohort_feed_desc", "CohortFeedDesc"), ("mil_gate_route", "GateRoute")])
 def test_struct_layouts_match_the_header(tmp_path, cname, pyname):
-    """The ctypes mirrors of the C structs (the one-call step, the grouped weight-gradient descriptor) against the C compiler's
-    view of include/mil_hip.h."""
+    """The ctypes mirrors of the C structs (the one-call step, the grouped weight-gradient descriptor, the gate step's route)
+    against the C compiler's view of include/mil_hip.h."""
     import ctypes
     import subprocess
     from mil_amd import _lib

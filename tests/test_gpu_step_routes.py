@@ -1,6 +1,7 @@
 """GPU: every gate-forward and weight-gradient route of the fp32 one-call step (mil_image_only_step_run) against a float64
-restatement of the step, element by element.  Each case names the kernels it is meant to reach, and tests/step_ref.py
-mirrors the host rules that choose them, so a shape cannot drift to another kernel unnoticed.
+restatement of the step, element by element.  Each case names the kernels it is meant to reach; tests/step_ref.py mirrors
+the host rules that choose them and the library states the plan its launches execute (mil_gate_step_route): both must
+give the named route, so a shape cannot drift to another kernel unnoticed.
 
 Bounds: scores, gates and logits max|got - ref| <= 1e-5 max|ref|; every gradient <= 1e-4 max|ref|; loss within 1e-5
 relative; top-1 equal.  On the split-bf16 (PW) cases the forward's error is also at most 1.5x that of the fp32-MFMA K loop
@@ -11,7 +12,7 @@ import torch
 from mil_amd import synthetic as syn
 from mil_amd.bags import BagLayout, bucket_rows
 from mil_amd.trainer import PARAM_ORDER, ImageOnlyTrainer, RaggedImageOnlyStepper
-from step_ref import WB, WW, gates_ref, keep_from_bits, max_err, step_ref, step_route
+from step_ref import WB, WW, gates_ref, keep_from_bits, lib_route, max_err, step_ref, step_route
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -95,6 +96,9 @@ def _route_case(tag, lengths, L, C, want, train):
     lay = BagLayout.make(lengths, DEV)
     have = step_route(R, L, C, train, aligned32=lay.aligned32)
     assert {k: have[k] for k in want} == want, (tag, have)
+    planned = lib_route(R, L, C, train, aligned32=lay.aligned32)
+    print(f"{tag}: library route {planned}")
+    assert {k: planned[k] for k in want} == want, (tag, planned)
     p = syn.image_only_params(300 + L + C, L=L, C=C)
     x = _randn(R, L, R + L)
     y = syn.make_labels(R, len(lengths), C).to(DEV)
@@ -165,6 +169,9 @@ def test_bucketed_pw_step_ignores_the_rows_beyond_the_batch(cap, train):
     want = dict(PW, bits="in_kernel" if train else None)
     have = step_route(cap, L, C, train, bucketed=True)
     assert {k: have[k] for k in want} == want, have
+    planned = lib_route(cap, L, C, train, bucketed=True)
+    print(f"bucket {cap} {'train' if train else 'eval'}: library route {planned}")
+    assert {k: planned[k] for k in want} == want, planned
     p = syn.image_only_params(71, L=L)
     x = _randn(n, L, 72)
     y = syn.make_labels(73, len(lengths)).to(DEV)
