@@ -978,6 +978,16 @@ int mil_tm_softmax_rows_bwd(const float* p, float* dp, long rows, int cols, void
  * Backward: dsrc[idx[r]] += ddst[r] (atomic, repeated indices add), dextra likewise; both caller-initialised. */
 int mil_tm_row_gather(const float* src, const float* extra, const int32_t* idx, int rows, int E, float* dst, void* stream);
 int mil_tm_row_gather_bwd(const float* ddst, const int32_t* idx, int rows, int E, float* dsrc, float* dextra, void* stream);
+/* The gather index of the sequence assembly from bag lengths ON THE DEVICE, for a step replayed from a hipGraph: s_of_bag is a
+ * HOST array of B <= 16 grid sides (by value in the launch: what the graph is keyed by), len_dev [B] the lengths, bag b's rows
+ * packed behind those of the bags in front (off_b = len[0] + .. + len[b-1]).  Bag b gets 1 + s_b^2 entries: -2 (cls),
+ * off_b .. off_b + N_b - 1, off_b .. off_b + s_b^2 - N_b - 1; idx_rows (the extent of idx_out) must cover their sum.
+ * rows_dev_out [1] (nullable) = sum of the lengths.  A length outside ((s_b - 1)^2, s_b^2] is clamped into it, so no index
+ * leaves the sum of s_b^2 rows, and flag_dev [1] (nullable) is set to 1 (never cleared here).
+ * x_tail (nullable): [x_rows, L] floats, x_rows >= sum of s_b^2, L % 4 == 0, 16-byte aligned - rows from the sum of the
+ * lengths on are zeroed (what an earlier step left behind the bags of this one). */
+int mil_tm_seq_index(const int32_t* len_dev, int B, const int32_t* s_of_bag, int32_t* idx_out, int idx_rows, int32_t* rows_dev_out,
+                     int32_t* flag_dev, float* x_tail, int x_rows, int L, void* stream);
 /* Landmarks: qL, kL [8, 256, 64] = means of l = n_pad / 256 consecutive rows of q (times qscale) and k, zero pad rows
  * counted.  Backward: dqkv's q and k columns += the spread-out landmark gradients. */
 int mil_tm_landmarks(const float* qkv, int n_pad, float qscale, float* qL, float* kL, void* stream);

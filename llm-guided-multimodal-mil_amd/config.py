@@ -20,7 +20,8 @@ def create_arg_parser(argv=None):
     p.add_argument("--alignment_base", default="CI", type=str)
     p.add_argument("--model_CT", default="resnetMC3_18", type=str)
     p.add_argument("--model_pathology", default="ABMIL", type=str,
-                   help="image_only: ABMIL or TransMIL (Nystrom attention + PPEG; autograd path only); fusion: ABMIL")
+                   help="image_only: ABMIL or TransMIL (Nystrom attention + PPEG; autograd path, replayed from hipGraphs with "
+                        "--transmil_graph 1); fusion: ABMIL")
     p.add_argument("--model_CI", default="CLIP", type=str)
     p.add_argument("--aggregator", default="ABMIL", type=str)
     p.add_argument("--CI_prompt_version", default="single", type=str, help="single (1 note) | devided (10 prompts)")
@@ -89,6 +90,12 @@ def create_arg_parser(argv=None):
                         "(3 / 6 cross terms: ~3e-6 / fp32-level relative error, 2.3x / 1.45x the fp32 GEMM rate)")
     p.add_argument("--hip_graph", type=int, default=0, help="autograd path: capture forward + backward of a repeating "
                    "batch shape in a hipGraph and replay it (graph_step.py); meant for the one-bag-per-GPU regime")
+    p.add_argument("--transmil_graph", type=int, default=0, help="image_only + --model_pathology TransMIL: replay the step "
+                   "from one hipGraph per grid side s = ceil(sqrt(N)), bag lengths and the gather index on the device "
+                   "(transmil_step.RaggedTransMILStepper); feeds from the HBM-resident cohort when --resident_cohort 1 fits.  "
+                   "test_ddp.py: its per-bag eval forward is replayed the same way (the model built by build_model does it)")
+    p.add_argument("--transmil_max_graphs", type=int, default=0, help="--transmil_graph 1: most graphs kept (0 = the "
+                   "stepper's default); a grid side beyond the cap runs eagerly")
     p.add_argument("--flat_adam", type=int, default=1, help="autograd path: parameters in one flat buffer, one gradient "
                    "all-reduce and one Adam launch per step (optim.FlatAdam); 0 = torch DDP + torch.optim.Adam")
     return p.parse_args(argv)

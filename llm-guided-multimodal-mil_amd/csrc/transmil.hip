@@ -157,6 +157,59 @@ __global__ __launch_bounds__(256) void k_tm_gather_bwd(const float* __restrict__
     for (int c = threadIdx.x; c < E; c += 256) atomicAdd(d + c, ddst[(long)r * E + c]);
 }
 
+// Grid sides of up to TM_MAX_BAGS bags, by value: what a captured step of those sides is keyed by.  The lengths are read from
+// the device, so one graph per tuple of sides serves every bag with (s - 1)^2 < N <= s^2.
+constexpr int TM_MAX_BAGS = 16;
+struct TmSides {
+    int s[TM_MAX_BAGS];
+};
+
+// length of bag b as the index may use it: clamped into its side's bucket, so that no index leaves the capacity
+__device__ __forceinline__ int tm_len(const int32_t* __restrict__ len_dev, const TmSides& sd, int b) {
+    const int s = sd.s[b], lo = (s - 1) * (s - 1) + 1, hi = s * s;
+    return min(max(len_dev[b], lo), hi);
+}
+
+// idx[r] of the sequence assembly, thread per entry: bag b owns 1 + s_b^2 entries, [-2 | off .. off + N - 1 | off .. off +
+// add - 1] with off = the rows of the bags in front (bags are packed back to back by their true lengths).  Thread 0 also
+// writes the true row count and raises `flag` when a length lies outside its bucket (sticky: never cleared here).
+__global__ __launch_bounds__(256) void k_tm_seq_index(const int32_t* __restrict__ len_dev, int B, TmSides sd, int total,
+                                                      int32_t* __restrict__ idx, int32_t* __restrict__ rows_out,
+                                                      int32_t* __restrict__ flag) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r == 0) {
+        int rows = 0, bad = 0;
+        for (int b = 0; b < B; ++b) {
+            const int n = tm_len(len_dev, sd, b);
+            bad |= n != len_dev[b];
+            rows += n;
+        }
+        if (rows_out) rows_out[0] = rows;
+        if (bad && flag) flag[0] = 1;
+    }
+    if (r >= total) return;
+    int b = 0, first = 0, off = 0;
+    for (; b < B - 1; ++b) {
+        const int seq = 1 + sd.s[b] * sd.s[b];
+        if (r < first + seq) break;
+        first += seq;
+        off += tm_len(len_dev, sd, b);
+    }
+    const int j = r - first, n = tm_len(len_dev, sd, b);
+    idx[r] = j == 0 ? -2 : (j <= n ? off + j - 1 : off + j - 1 - n);
+}
+
+// x rows [sum of the lengths, x_rows) <- 0: the rows of a slot behind this step's bags hold an earlier step's data
+__global__ __launch_bounds__(256) void k_tm_zero_tail(const int32_t* __restrict__ len_dev, int B, TmSides sd, float* __restrict__ x,
+                                                      int x_rows, int L) {
+    int rows = 0;
+    for (int b = 0; b < B; ++b) rows += tm_len(len_dev, sd, b);
+    const int row = x_rows - 1 - (int)blockIdx.x;
+    if (row < rows || row < 0) return;
+    float4* p = reinterpret_cast<float4*>(x + (long)row * L);
+    for (int c = threadIdx.x; c < L / 4; c += 256) p[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 // qL [8, 256, 64] = qscale * mean of l consecutive q rows, kL the same of k (no scale); thread per (landmark, q|k column)
 __global__ __launch_bounds__(256) void k_tm_landmarks(const float* __restrict__ qkv, int l, float qscale, float* qL, float* kL) {
     const int j = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;        // c < 1024
@@ -414,6 +467,30 @@ int mil_tm_row_gather(const float* src, const float* extra, const int32_t* idx, 
 int mil_tm_row_gather_bwd(const float* ddst, const int32_t* idx, int rows, int E, float* dsrc, float* dextra, void* stream) {
     if (!ddst || !idx || !dsrc || rows <= 0 || E <= 0) return MIL_EINVAL;
     hipLaunchKernelGGL(k_tm_gather_bwd, dim3(rows), dim3(256), 0, (hipStream_t)stream, ddst, idx, E, dsrc, dextra);
+    return launch_rc();
+}
+
+int mil_tm_seq_index(const int32_t* len_dev, int B, const int32_t* s_of_bag, int32_t* idx_out, int idx_rows, int32_t* rows_dev_out,
+                     int32_t* flag_dev, float* x_tail, int x_rows, int L, void* stream) {
+    if (!len_dev || !s_of_bag || !idx_out || B <= 0 || B > TM_MAX_BAGS) return MIL_EINVAL;
+    TmSides sd{};
+    long total = 0, cap = 0, slack = 0;
+    for (int b = 0; b < B; ++b) {
+        const int s = s_of_bag[b];
+        if (s < 1 || s > 4096) return MIL_EINVAL;
+        sd.s[b] = s;
+        total += 1 + (long)s * s;
+        cap += (long)s * s;
+        slack += 2 * (long)s - 2;                    // s^2 minus the shortest length of the side, (s - 1)^2 + 1
+    }
+    if (total > idx_rows) return MIL_EINVAL;
+    if (x_tail && (x_rows < cap || L <= 0 || (L & 3) || (reinterpret_cast<uintptr_t>(x_tail) & 15))) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_seq_index, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, len_dev, B, sd,
+                       (int)total, idx_out, rows_dev_out, flag_dev);
+    const long tail = x_tail ? (long)x_rows - cap + slack : 0;     // most rows that can lie behind the bags
+    if (tail > 0)
+        hipLaunchKernelGGL(k_tm_zero_tail, dim3((unsigned)(tail < x_rows ? tail : x_rows)), dim3(256), 0, (hipStream_t)stream, len_dev,
+                           B, sd, x_tail, x_rows, L);
     return launch_rc();
 }
 

@@ -31,9 +31,15 @@ class _Entry:
 
 
 class GraphedStep:
-    def __init__(self, params: Sequence[torch.nn.Parameter], max_graphs: int = 4, warmup: int = 2):
+    def __init__(self, params: Sequence[torch.nn.Parameter], max_graphs: int = 4, warmup: int = 2, share_pool: bool = False,
+                 backward: bool = True):
+        """share_pool: every graph of this object allocates from ONE private memory pool (only one of them replays at a
+        time, so their intermediates may overlap; outputs and gradients stay live and are never shared) - for steppers that
+        hold many graphs (one per TransMIL grid side).  backward=False: the body is a forward only (evaluation)."""
         self.params: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
         self.max_graphs, self.warmup = max_graphs, warmup
+        self.pool = torch.cuda.graph_pool_handle() if share_pool else None
+        self.backward = bool(backward)
         self._graphs: Dict[tuple, _Entry] = {}
         self._seen: Dict[tuple, int] = {}
         self.replays = 0
@@ -54,8 +60,7 @@ class GraphedStep:
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             self._drop_grads()
-            out = body(*inputs)
-            ops.backward(out[0])
+            out = self._pass(body, inputs)
             if after_backward is not None:
                 after_backward()
             out = tuple(o.detach() for o in out)
@@ -63,7 +68,15 @@ class GraphedStep:
         self.eager_steps += 1
         return out
 
-    def _capture(self, inputs, body, after_backward=None) -> _Entry:
+    def _pass(self, body, inputs):
+        if not self.backward:
+            with torch.no_grad():
+                return body(*inputs)
+        out = body(*inputs)
+        ops.backward(out[0])
+        return out
+
+    def _capture(self, inputs, body, after_backward=None, before_capture=None) -> _Entry:
         ent = _Entry()
         ent.inputs = [t.clone() for t in inputs]
         cur = torch.cuda.current_stream()
@@ -75,13 +88,14 @@ class GraphedStep:
             with torch.cuda.stream(self.stream):
                 for _ in range(self.warmup):      # caches (segment maps, positional rows, split weights) fill here
                     self._drop_grads()
-                    ops.backward(body(*ent.inputs)[0])
+                    self._pass(body, ent.inputs)
+                if before_capture is not None:    # device state the warm-up passes moved (a dropout pass counter) goes back
+                    before_capture()
             cur.wait_stream(self.stream)
             self._drop_grads()                    # backward inside the capture then allocates / adopts, never accumulates
             ent.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ent.graph, stream=self.stream):
-                out = body(*ent.inputs)
-                ops.backward(out[0])
+            with torch.cuda.graph(ent.graph, stream=self.stream, **({"pool": self.pool} if self.pool is not None else {})):
+                out = self._pass(body, ent.inputs)
                 if after_backward is not None:      # e.g. a counted FlatAdam step: the optimizer inside the graph (the
                     after_backward()                # warm-up passes above leave it out - they must not train)
         ent.keep = keep
@@ -89,10 +103,12 @@ class GraphedStep:
         ent.grads = [p.grad for p in self.params]
         return ent
 
-    def run(self, key, inputs: Sequence[torch.Tensor], body: Callable[..., Tuple[torch.Tensor, ...]], after_backward=None):
+    def run(self, key, inputs: Sequence[torch.Tensor], body: Callable[..., Tuple[torch.Tensor, ...]], after_backward=None,
+            before_capture=None):
         """body(*inputs) -> (loss, *others); returns that tuple with loss.backward() done.  after_backward(): runs right
         after the backward on the same stream, and INSIDE the captured graph - for an optimizer whose step number and
-        learning rate live on the device (optim.FlatAdam(counted=True)), so that a whole training step is one replay."""
+        learning rate live on the device (optim.FlatAdam(counted=True)), so that a whole training step is one replay.
+        before_capture(): runs on the same stream between the warm-up passes and the capture."""
         sig = (key, tuple((tuple(t.shape), t.dtype) for t in inputs))
         ent = self._graphs.get(sig)
         if ent is None:
@@ -101,7 +117,7 @@ class GraphedStep:
                 if len(self._seen) > 4096:
                     self._seen.clear()
                 return self._eager(inputs, body, after_backward)
-            ent = self._graphs[sig] = self._capture(inputs, body, after_backward)
+            ent = self._graphs[sig] = self._capture(inputs, body, after_backward, before_capture)
         for dst, src in zip(ent.inputs, inputs):
             dst.copy_(src, non_blocking=True)
         ent.graph.replay()

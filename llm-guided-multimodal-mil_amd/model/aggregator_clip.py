@@ -28,9 +28,22 @@ class aggregator(nn.Module):
             F_out = L
         self.fc = nn.Sequential(nn.Dropout(0.25), nn.Linear(F_out, args.num_classes))
         self.last_logits: Optional[torch.Tensor] = None
+        # --transmil_graph 1 (train_ddp.build_model sets it): an eval-mode, no-grad forward of ONE bag - what test_ddp.py
+        # runs per sample - is replayed from the hipGraph of the bag's grid side (transmil_step.RaggedTransMILStepper)
+        self.graph_eval = False
+        self._eval_stepper = None
 
-    def forward(self, x_list: List[torch.Tensor], lengths=None):
-        M = self.extractor_pathology(x_list[0], lengths)
+    def forward(self, x_list: List[torch.Tensor], lengths=None, geom=None):
+        """geom (TransMIL only, model/dim1/TransMIL.py: DeviceGeometry): the capture-safe forward over a slot's static input,
+        bag geometry on the device - the body trainer.RaggedTransMILStepper replays from a hipGraph."""
+        x0 = x_list[0]
+        if (self.graph_eval and geom is None and not self.training and not torch.is_grad_enabled() and x0.is_cuda
+                and (x0.dim() == 2 or x0.shape[0] == 1) and (lengths is None or len(lengths) == 1)):
+            return self._replayed_eval(x0.reshape(-1, x0.shape[-1]), lengths)
+        if geom is not None:
+            M = self.extractor_pathology(x_list[0], None, geom=geom)
+        else:
+            M = self.extractor_pathology(x_list[0], lengths)
         if isinstance(M, tuple):                     # TransMIL: (h, [attn0, attn1])
             M = M[0]
         h = M
@@ -47,3 +60,17 @@ class aggregator(nn.Module):
         p, z = ops.head_sigmoid(h, self.fc[1].weight, self.fc[1].bias)
         self.last_logits = z
         return M, p
+
+    def _replayed_eval(self, x: torch.Tensor, lengths=None):
+        """One bag [n, L] (rows [0, lengths[0]) of it) through the evaluation stepper: copied into the side's static input,
+        forward replayed.  The results are the graph's static tensors, valid until that side's next forward."""
+        if self._eval_stepper is None:
+            from ..transmil_step import RaggedTransMILStepper
+            self._eval_stepper = RaggedTransMILStepper(self, None, B=1, backward=False)
+        st = self._eval_stepper
+        n = int(lengths[0]) if lengths is not None else x.shape[0]
+        slot = st.slot([n])
+        slot.x[:n].copy_(x[:n], non_blocking=True)
+        _, prob = st.step(slot, [n])
+        self.last_logits = slot.last["logits"]
+        return slot.last["h"], prob

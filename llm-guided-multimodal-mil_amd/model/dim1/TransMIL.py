@@ -29,6 +29,66 @@ def geometry(N: int) -> dict:
     return dict(N=N, s=s, add=add, seq=seq, n_pad=n_pad, l=n_pad // ops.TM_M, pad=n_pad - seq)
 
 
+def bucket_side(N: int) -> int:
+    """Grid side s of a bag of N rows, (s - 1)^2 < N <= s^2, in integer arithmetic: the key of a captured step."""
+    if N < 1:
+        raise ValueError("TransMIL: a bag needs at least one row")
+    return math.isqrt(N - 1) + 1
+
+
+def side_geometry(s: int) -> dict:
+    """What geometry(N) gives for every N of side s: all shapes but N and add."""
+    seq = s * s + 1
+    n_pad = ops.TM_M * -(-seq // ops.TM_M)
+    return dict(s=s, seq=seq, n_pad=n_pad, l=n_pad // ops.TM_M, pad=n_pad - seq)
+
+
+def seq_index_entry(j: int, N: int, off: int) -> int:
+    """Entry j (0 <= j <= s^2) of a bag's part of the sequence index: -2 = the cls row, then the bag's N rows (the first of
+    them row `off` of the flat input), then its first s^2 - N rows again.  csrc/transmil.hip: k_tm_seq_index evaluates this
+    per entry from the lengths on the device."""
+    return -2 if j == 0 else (off + j - 1 if j <= N else off + j - 1 - N)
+
+
+def seq_index(lengths: Sequence[int]) -> List[int]:
+    """The index of the sequence assembly for bags packed back to back: per bag [cls | tokens | first `add` tokens again]."""
+    idx, off = [], 0
+    for n in lengths:
+        add = bucket_side(n) ** 2 - n
+        idx += [-2] + list(range(off, off + n)) + list(range(off, off + add))
+        off += n
+    return idx
+
+
+def pad_index(g: dict) -> List[int]:
+    """Front zero pad of one bag's rows to n_pad: -1 = a zero row.  Depends on the side only."""
+    return [-1] * g["pad"] + list(range(g["seq"]))
+
+
+class DeviceGeometry:
+    """The part of a forward's geometry that a replayed step cannot build on the host: the grid side of every bag (host
+    ints, fixed per captured graph), the gather index and the true row count on the device (ops.tm_seq_index writes both
+    from the lengths in `len_dev`), the per-side pad index (static) and the out-of-bucket flag."""
+
+    def __init__(self, sides: Sequence[int], device, pad_cache: Optional[dict] = None, flag: Optional[torch.Tensor] = None):
+        self.sides = tuple(int(s) for s in sides)
+        self.cap = sum(s * s for s in self.sides)                         # rows of the flat input buffer
+        i32 = dict(device=device, dtype=torch.int32)
+        self.len_dev = torch.zeros(len(self.sides), **i32)
+        self.idx = torch.zeros(sum(1 + s * s for s in self.sides), **i32)
+        self.rows_dev = torch.zeros(1, **i32)
+        self.flag = flag if flag is not None else torch.zeros(1, **i32)
+        self.pad_idx = pad_cache if pad_cache is not None else {}
+        for s in self.sides:
+            if s not in self.pad_idx:
+                self.pad_idx[s] = torch.tensor(pad_index(side_geometry(s)), dtype=torch.int32).to(device)
+
+    def update(self, x_tail: Optional[torch.Tensor] = None):
+        """Index and row count from the lengths now in len_dev; x_tail: the slot's input buffer, its rows behind the bags zeroed."""
+        ops.tm_seq_index(self.len_dev, self.sides, self.idx, self.rows_dev, self.flag, x_tail)
+        return self
+
+
 class NystromAttention(nn.Module):
     """Parameters of nystrom_attention.NystromAttention(dim=512, dim_head=64, heads=8, num_landmarks=256, pinv_iterations=6,
     residual=True, dropout=0.1): to_qkv (no bias), to_out = Linear + Dropout, res_conv = depthwise (33, 1) over the heads."""
@@ -107,25 +167,37 @@ class TransMIL(nn.Module):
         return tuple(ops.dropout_keep_bits(seq, self.D, TM_DROP_P, self._drop_seed ^ (0x5472616E734D494C + j), 2 * b + j, device,
                                            offset_dev=self._drop_ctr) for j in range(2))
 
-    def forward(self, x: torch.Tensor, lengths: Optional[Sequence[int]] = None, need_attn: bool = False):
-        if x.dim() == 2 and lengths is None:
-            x = x.unsqueeze(0)
-        if x.dim() == 3:
-            B, N, L = x.shape
-            lengths = [N] * B
-            x = x.reshape(B * N, L)
-        lengths = [int(n) for n in lengths]
-        if min(lengths) < 1 or sum(lengths) != x.shape[0]:
-            raise ValueError(f"TransMIL: lengths {lengths} do not cover the {x.shape[0]} rows")
+    def forward(self, x: torch.Tensor, lengths: Optional[Sequence[int]] = None, need_attn: bool = False,
+                geom: Optional[DeviceGeometry] = None):
+        """geom: the capture-safe form (RaggedTransMILStepper).  x is then the slot's whole [sum s^2, L] buffer, the bags packed
+        at its front, and nothing below touches the host: sides from geom, index / row count / pad index on the device."""
         dev = x.device
-        h = ops.linear_act(x, self._fc1[0].weight, self._fc1[0].bias, "relu")        # [R, 512]
-        geo = [geometry(n) for n in lengths]
-        # [cls | tokens | first `add` tokens again] per bag, one gather for all bags; index -2 = the cls row
-        idx, off = [], 0
-        for g in geo:
-            idx += [-2] + list(range(off, off + g["N"])) + list(range(off, off + g["add"]))
-            off += g["N"]
-        idx_dev = torch.tensor(idx, dtype=torch.int32).to(dev, non_blocking=True)
+        if geom is not None:
+            if x.dim() != 2 or x.shape[0] != geom.cap:
+                raise ValueError(f"TransMIL: geom of sides {geom.sides} wants a [{geom.cap}, L] input, got {tuple(x.shape)}")
+            if self.training and (self._drop_seed is None or self._drop_ctr is None or self._drop_ctr.device != dev):
+                raise ValueError("TransMIL: fix the dropout stream (_drop_state) before a forward with geom")
+            # _fc1 runs over the slot's capacity.  The rows behind the true count hold an earlier step's data: they are never
+            # gathered, so their gradient rows are zero, but 0 x NaN in _fc1's weight gradient would still poison it.
+            # ops.tm_seq_index (geom.update) has ZEROED that tail of x, which holds for every kernel _fc1 dispatches to;
+            # rows_dev on top lets the tall kernels skip the tiles behind the count (the few-rows kernels ignore it).
+            h = ops.linear_act(x, self._fc1[0].weight, self._fc1[0].bias, "relu", rows_dev=geom.rows_dev)
+            geo = [side_geometry(s) for s in geom.sides]
+            idx_dev = geom.idx
+        else:
+            if x.dim() == 2 and lengths is None:
+                x = x.unsqueeze(0)
+            if x.dim() == 3:
+                B, N, L = x.shape
+                lengths = [N] * B
+                x = x.reshape(B * N, L)
+            lengths = [int(n) for n in lengths]
+            if min(lengths) < 1 or sum(lengths) != x.shape[0]:
+                raise ValueError(f"TransMIL: lengths {lengths} do not cover the {x.shape[0]} rows")
+            h = ops.linear_act(x, self._fc1[0].weight, self._fc1[0].bias, "relu")        # [R, 512]
+            geo = [geometry(n) for n in lengths]
+            # [cls | tokens | first `add` tokens again] per bag, one gather for all bags; index -2 = the cls row
+            idx_dev = torch.tensor(seq_index(lengths), dtype=torch.int32).to(dev, non_blocking=True)
         seqs = ops.tm_row_gather(h, self.cls_token, idx_dev)
         train = self.training
         if train:
@@ -135,7 +207,10 @@ class TransMIL(nn.Module):
         for b, g in enumerate(geo):
             xb = seqs[row:row + g["seq"]]
             row += g["seq"]
-            pad_idx = torch.tensor([-1] * g["pad"] + list(range(g["seq"])), dtype=torch.int32).to(dev, non_blocking=True)
+            if geom is not None:
+                pad_idx = geom.pad_idx[g["s"]]
+            else:
+                pad_idx = torch.tensor(pad_index(g), dtype=torch.int32).to(dev, non_blocking=True)
             bits = self._bits(b, g["seq"], dev) if train else (None, None)
             bits_used.append(bits)
             xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn)

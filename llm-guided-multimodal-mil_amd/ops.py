@@ -2460,6 +2460,22 @@ def tm_row_gather(src, extra, idx):
     return _TmRowGather.apply(src, extra, idx)
 
 
+def tm_seq_index(len_dev, sides, idx_out, rows_dev=None, flag=None, x_tail=None):
+    """idx_out (device int32, at least sum(1 + s^2) entries) <- tm_row_gather's index of the sequence assembly, from the bag
+    lengths on the device (len_dev int32 [B]) and the bags' grid sides (host ints: the launch shape); rows_dev [1] <- the
+    sum of the lengths; flag [1] <- 1 if a length lies outside its side's bucket (it is clamped, nothing is written out of
+    range); x_tail [rows >= sum(s^2), L]: its rows behind the bags are zeroed.  One launch (two with x_tail), no host sync."""
+    sides = [int(s) for s in sides]
+    arr = (ctypes.c_int32 * len(sides))(*sides)
+    if x_tail is not None and (x_tail.dtype != torch.float32 or not x_tail.is_contiguous()):
+        raise _lib.MilHipError("tm_seq_index: x_tail must be a contiguous float32 tensor")
+    rc = _lib.lib().mil_tm_seq_index(_p(len_dev), len(sides), arr, _p(idx_out), idx_out.numel(), _p(rows_dev), _p(flag),
+                                     _p(x_tail), x_tail.shape[0] if x_tail is not None else 0,
+                                     x_tail.shape[1] if x_tail is not None else 0, _stream())
+    _lib.check(rc, "mil_tm_seq_index")
+    return idx_out
+
+
 class _TmPPEG(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, s: int, W7, b7, W5, b5, W3, b3):

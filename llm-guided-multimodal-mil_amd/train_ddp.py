@@ -38,7 +38,11 @@ def build_model(args):
             args.patch_dim = int(args.synthetic[1])
     else:
         from .model.utils import get_model
-    return get_model(args)
+    model = get_model(args)
+    if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
+            and getattr(args, "transmil_graph", 0)):
+        model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward
+    return model
 
 
 def main_worker(local_rank: int, nprocs: int, args):
@@ -49,9 +53,16 @@ def main_worker(local_rank: int, nprocs: int, args):
         world, rank, gpu = env_world()
     if args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL" and (
             args.fused_step or getattr(args, "hip_graph", 0)):
-        # the fused ImageOnlyTrainer is ABMIL's step, and TransMIL's per-bag geometry (square padding, n_pad) is built on
-        # the host every forward, which a captured graph cannot replay
+        # the fused ImageOnlyTrainer is ABMIL's step, and --hip_graph keys its graphs by the exact bag lengths, under which a
+        # ragged TransMIL cohort never replays: its graph path is --transmil_graph 1 (one graph per grid side, bag geometry on
+        # the device: transmil_step.RaggedTransMILStepper)
         raise ValueError("--model_pathology TransMIL runs on the autograd path only: drop --fused_step / --hip_graph")
+    tm_graph = (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
+                and bool(getattr(args, "transmil_graph", 0)))
+    if getattr(args, "transmil_graph", 0) and not tm_graph:
+        raise ValueError("--transmil_graph 1 is the graph path of --variant image_only --model_pathology TransMIL")
+    if tm_graph and (args.learnablePrompt or not getattr(args, "flat_adam", 1)):
+        raise ValueError("--transmil_graph 1 needs --flat_adam 1 (the counted FlatAdam rides inside the graph)")
     torch.cuda.set_device(gpu)
     dev = torch.device("cuda", gpu)
     if world > 1:
@@ -71,6 +82,7 @@ def main_worker(local_rank: int, nprocs: int, args):
     args.lr = lr0
 
     fused = args.fused_step and args.variant == "image_only"
+    tstepper = None
     if fused:
         from .trainer import ImageOnlyTrainer
         sd = model.state_dict()
@@ -111,8 +123,9 @@ def main_worker(local_rank: int, nprocs: int, args):
             # included, so step number and learning rate live on the device
             bucketed = (bool(getattr(args, "hip_graph", 0)) and args.variant != "image_only" and prompts <= 12
                         and list(args.modality) in (["pathology"], ["CT", "pathology"]))
+            # --transmil_graph 1 at world size 1: the same, inside the per-side graphs of transmil_step.RaggedTransMILStepper
             optimizer = FlatAdam(trainable, lr=lr0, betas=(args.b1, args.b2), weight_decay=1e-7, world_size=world,
-                                 counted=bucketed)
+                                 counted=bucketed or (tm_graph and world == 1))
         else:
             optimizer = torch.optim.Adam(trainable, lr=lr0, betas=(args.b1, args.b2), weight_decay=1e-7)
         if flat_opt and world > 1:
@@ -145,7 +158,13 @@ def main_worker(local_rank: int, nprocs: int, args):
                 from . import ops
                 loss_ = loss_ + ops.cosine_embedding_loss(toks[0].squeeze(1), toks[1].squeeze(1))
             return loss_
-        graphed = fstepper = None
+        graphed = fstepper = tstepper = None
+        if tm_graph:
+            # TransMIL, one ragged bag per GPU: bag lengths on the device, one graph per grid side s = ceil(sqrt(N)); Adam
+            # inside the graph at world size 1, the all-reduce and the update outside otherwise
+            from .transmil_step import RaggedTransMILStepper
+            tstepper = RaggedTransMILStepper(model, optimizer, B=per_gpu, drop_seed=args.seed,
+                                             max_graphs=int(getattr(args, "transmil_max_graphs", 0)) or None)
         CT_SHAPE = (512, 160, 2, 2)          # synthetic stand-in for the CT encoder's feature map (aggregator.py:139-140)
         if (getattr(args, "hip_graph", 0) and flat_opt and args.variant != "image_only" and prompts <= 12
                 and list(args.modality) in (["pathology"], ["CT", "pathology"])):
@@ -180,7 +199,7 @@ def main_worker(local_rank: int, nprocs: int, args):
     # per-epoch patch drop drawn on the device, every step fed by ONE gather launch into the bucket's static buffers -
     # instead of the reference's per-step np.load + random.sample + pad + H2D copy (dataset.py:366-393, train_ddp.py:274-293)
     cohort = None
-    any_stepper = (stepper if fused else fstepper)
+    any_stepper = (stepper if fused else (fstepper or tstepper))
     if any_stepper is not None and getattr(args, "resident_cohort", 1):
         from .cohort import DeviceCohort
         lens_all = ([int(v) for v in data.lengths] if hasattr(data, "lengths") else None)
@@ -189,7 +208,7 @@ def main_worker(local_rank: int, nprocs: int, args):
             lens_all = [int(_np.load(os.path.join(data.root, k + ".npy"), mmap_mode="r").shape[0]) for k in data.keys]
         if DeviceCohort.fits(DeviceCohort.bytes_needed(lens_all, args.patch_dim), dev):
             cohort = DeviceCohort.from_dataset(data, dev, seed=args.seed, augmentation=bool(getattr(args, "augmentation", 1)))
-            if not fused and not fstepper.tower_inside:
+            if not fused and fstepper is not None and not fstepper.tower_inside:
                 # --cache_text 1: every note's frozen-tower embedding once, as a device table the feed launch reads
                 with torch.no_grad():
                     cohort.set_text(torch.cat([model.clinic_extractor(cohort.ids[i:i + 32]) for i in range(0, cohort.nb, 32)], 0))
@@ -224,6 +243,13 @@ def main_worker(local_rank: int, nprocs: int, args):
                     cohort.feed(take, slot.x, slot.layout.bag_len_dev, slot.y)
                     loss, prob = stepper.step(slot, ks, on_device=True)
                     y, nb_ = slot.y, len(take)
+                elif tstepper is not None:
+                    for g in optimizer.param_groups:
+                        g["lr"] = lr
+                    slot = tstepper.slot(ks)
+                    cohort.feed(take, slot.x, slot.len_dev, slot.y)
+                    loss, prob = tstepper.step(slot, ks, on_device=True)
+                    y, nb_ = slot.y, len(take)
                 else:
                     for g in optimizer.param_groups:
                         g["lr"] = lr
@@ -242,7 +268,7 @@ def main_worker(local_rank: int, nprocs: int, args):
                         slot = None
                 if slot is not None:
                     if it % 10 == 0 or it == steps - 1:
-                        losses.update(float(loss.detach()), nb_)
+                        losses.update(tstepper.read_loss(loss) if tstepper is not None else float(loss.detach()), nb_)
                         accs.update(float(calculate_accuracy(prob.detach(), y)), nb_)
                         bt.update(time.time() - end)
                         progress.display(it)
@@ -287,6 +313,14 @@ def main_worker(local_rank: int, nprocs: int, args):
                     else:
                         fstepper.encode_notes(slot, batch["CI"].to(dev))                  # --cache_text 1: a lookup per note
                     loss, prob, _ = fstepper.step(slot, lengths)
+                elif tstepper is not None and len(lengths) == per_gpu:
+                    slot = tstepper.slot(lengths)                                         # host-fed: the side's static inputs
+                    r0 = 0
+                    for b, n in enumerate(lengths):
+                        slot.x[r0:r0 + n].copy_(x[b, :n], non_blocking=True)
+                        r0 += n
+                    slot.y.copy_(y, non_blocking=True)
+                    loss, prob = tstepper.step(slot, lengths)
                 elif graphed is not None:
                     key = (tuple(int(v) for v in lengths), args.variant)
                     if args.variant == "image_only":

@@ -1,7 +1,14 @@
 """TransMIL image-only extractor (--model_pathology TransMIL): one bag of N patches, eval forward and forward + backward (BCE
 through the aggregator_clip head), HIP path against the torch restatement (tests/transmil_ref.py, fp32) on the same GPU in the
 same process.  Median of --reps timed regions; GF per step from the shapes (transmil_flops below); fraction of the 157.3 TF
-fp32 MFMA peak.  Prints one JSON line per N."""
+fp32 MFMA peak.  Prints one JSON line per N.
+
+--graph: per N, the TRAINING step (model.train(), BCE, backward, counted FlatAdam) eager - the module called with host
+lengths, as train_ddp.py's autograd path runs it - next to the same step replayed from the side's hipGraph
+(transmil_step.RaggedTransMILStepper): same bag, same region count, same process; the spread of the eager regions and the
+memory of the graph's pool are reported with it.
+--ragged K: K bags drawn from U[2000, 15592] in turn through the stepper: ms/step, replay / eager counts, eager steps after a
+key's second visit (must be 0), graphs, the memory of their shared pool and the free memory the whole run took."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -41,15 +48,124 @@ def timed(fn, reps, warm):
     return sorted(ts)[len(ts) // 2]
 
 
+def graph_rows(a, dev, args):
+    from mil_amd import ops
+    from mil_amd.optim import FlatAdam
+    from mil_amd.transmil_step import RaggedTransMILStepper
+    bce = torch.nn.BCELoss()
+    y = syn.make_labels(3, 1).to(dev)
+    for N in a.N:
+        torch.manual_seed(1234)
+        m_e = get_model(args).to(dev).train()
+        torch.manual_seed(1234)
+        m_r = get_model(args).to(dev).train()
+        o_e = FlatAdam(list(m_e.parameters()), lr=1e-5, counted=True)
+        o_r = FlatAdam(list(m_r.parameters()), lr=1e-5, counted=True)
+        st = RaggedTransMILStepper(m_r, o_r, B=1, drop_seed=1)
+        x = syn.make_bags(N, 1, N, 768)[0].to(dev)
+        slot = st.slot([N])
+        slot.x[:N].copy_(x)
+        slot.y.copy_(y)
+
+        def eager():
+            o_e.zero_grad()
+            _, prob = m_e([x], [N])
+            ops.backward(bce(prob, y))
+            o_e.step()
+
+        def replay():
+            st.step(slot, [N])
+
+        for _ in range(3):                        # eager visit, capture, first replay
+            replay()
+        assert st.n_graphs == 1
+        ts = region_times(eager, a.reps, a.warmup)
+        tr = region_times(replay, a.reps, a.warmup)
+        med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+        print(json.dumps(dict(N=N, side=slot.sides[0], eager_ms=round(med(ts), 3), eager_min_ms=round(min(ts), 3),
+                              eager_max_ms=round(max(ts), 3), replay_ms=round(med(tr), 3), replay_min_ms=round(min(tr), 3),
+                              replay_max_ms=round(max(tr), 3), graph_mib=round(list(st.graph_bytes.values())[0] / 2 ** 20, 1),
+                              replays=st.replays, eager_steps=st.eager_steps)), flush=True)
+        del st, slot, m_e, m_r, o_e, o_r
+        torch.cuda.empty_cache()
+
+
+def ragged_run(a, dev, args):
+    import time
+    from mil_amd.optim import FlatAdam
+    from mil_amd.transmil_step import RaggedTransMILStepper
+    torch.manual_seed(1234)
+    model = get_model(args).to(dev).train()
+    opt = FlatAdam(list(model.parameters()), lr=1e-5, counted=True)
+    st = RaggedTransMILStepper(model, opt, B=1, drop_seed=1, max_graphs=a.max_graphs or None)
+    lens = [int(v) for v in torch.randint(2000, 15593, (a.ragged,), generator=torch.Generator().manual_seed(a.seed))]
+    pool = torch.randn((15592, 768), generator=torch.Generator().manual_seed(2)).to(dev)
+    y = syn.make_labels(3, 1).to(dev)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(dev)[0]
+    visits, late_eager, t_replay, n_replay = {}, 0, 0.0, 0
+    t0 = time.perf_counter()
+    for n in lens:
+        slot = st.slot([n])
+        slot.x[:n].copy_(pool[:n], non_blocking=True)
+        slot.y.copy_(y, non_blocking=True)
+        v = visits[slot.sides] = visits.get(slot.sides, 0) + 1
+        e0, g0 = st.eager_steps, st.n_graphs
+        if v > 2:
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+        st.step(slot, [n])
+        if v > 2:
+            torch.cuda.synchronize()
+            t_replay += time.perf_counter() - t1
+            n_replay += 1
+            late_eager += st.eager_steps - e0
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    held = free0 - torch.cuda.mem_get_info(dev)[0]
+    slots = sum(s.x.numel() * 4 for s in st.slots.values())
+    print(json.dumps(dict(ragged=a.ragged, sides=len(visits), graphs=st.n_graphs, replays=st.replays, eager_steps=st.eager_steps,
+                          eager_after_second_visit=late_eager, ms_per_step_all=round(1e3 * wall / a.ragged, 3),
+                          ms_per_replayed_step=round(1e3 * t_replay / max(1, n_replay), 3), replayed_timed=n_replay,
+                          held_gib=round(held / 2 ** 30, 3), slot_inputs_gib=round(slots / 2 ** 30, 3),
+                          graph_pool_gib=round(st.pool_bytes() / 2 ** 30, 3),
+                          largest_capture_mib=round(max(st.graph_bytes.values(), default=0) / 2 ** 20, 1))), flush=True)
+
+
+def region_times(fn, reps, warm):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        torch.cuda.synchronize()
+        ts.append(s.elapsed_time(e))
+    return ts
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, nargs="+", default=[2000, 7600, 15592])
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no_torch", action="store_true", help="skip the torch restatement")
+    ap.add_argument("--graph", action="store_true", help="training step per N: eager next to the replayed hipGraph")
+    ap.add_argument("--ragged", type=int, default=0, help="K bags from U[2000, 15592] in turn through the graph stepper")
+    ap.add_argument("--max_graphs", type=int, default=0, help="--ragged: the stepper's graph cap (0 = its default)")
+    ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
     args = SimpleNamespace(modality=["pathology"], model_pathology="TransMIL", num_classes=2, patch_dim=768, variant="image_only")
+    if a.graph or a.ragged:
+        if a.graph:
+            graph_rows(a, dev, args)
+        if a.ragged:
+            ragged_run(a, dev, args)
+        return
     torch.manual_seed(1234)
     model = get_model(args).to(dev).eval()        # eval: dropout off, gradients still flow
     p = {k.replace("extractor_pathology.", ""): v.detach() for k, v in model.state_dict().items()}
