@@ -974,7 +974,8 @@ int mil_tm_bgemm(const float* A, long sAb, long sAi, long sAk, const float* B, l
 /* In place over contiguous rows: x = softmax(x) per row; backward dp = p (dp - <p, dp>). */
 int mil_tm_softmax_rows(float* x, long rows, int cols, void* stream);
 int mil_tm_softmax_rows_bwd(const float* p, float* dp, long rows, int cols, void* stream);
-/* Sequence assembly: dst[r] = src[idx[r]] (idx >= 0), the row `extra` (idx == -2) or zeros (idx == -1); rows of E floats.
+/* Sequence assembly: dst[r] = src[idx[r]] (idx >= 0), the row `extra` (idx == -2; zeros when
+ * `extra` is null) or zeros (idx == -1); rows of E floats.
  * Backward: dsrc[idx[r]] += ddst[r] (atomic, repeated indices add), dextra likewise; both caller-initialised. */
 int mil_tm_row_gather(const float* src, const float* extra, const int32_t* idx, int rows, int E, float* dst, void* stream);
 int mil_tm_row_gather_bwd(const float* ddst, const int32_t* idx, int rows, int E, float* dsrc, float* dextra, void* stream);

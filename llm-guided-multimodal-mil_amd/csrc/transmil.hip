@@ -17,7 +17,7 @@
 namespace {
 
 constexpr int TM_H = 8, TM_DH = 64, TM_D = 512, TM_QKV = 3 * TM_D, TM_M = 256, TM_CONV = 33;
-constexpr int BG_BK = 16, BG_LD = 64 + 4;
+constexpr int BG_BK = 16, BG_LD = 64 + 4, BG_FOLD = 32;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -79,9 +79,11 @@ __global__ __launch_bounds__(256) void k_tm_bgemm(const float* __restrict__ A, l
         }
     };
 
-    f32x16 acc;
+    // two levels: the MFMA chain runs over BG_FOLD slices (512 of K), then folds into `tot` - one running fp32 sum over a
+    // K of 7936 loses 19 x what the float32 product on the CPU loses (tests/test_gpu_transmil_stages.py, docs/lab_notes.md)
+    f32x16 acc, tot;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int i = 0; i < 16; ++i) acc[i] = tot[i] = 0.f;
     if (s0 < s1) load(s0);
     for (int ks = s0; ks < s1; ++ks) {
         store();
@@ -90,8 +92,14 @@ __global__ __launch_bounds__(256) void k_tm_bgemm(const float* __restrict__ A, l
 #pragma unroll
         for (int kk = 0; kk < BG_BK / 2; ++kk)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[2 * kk + h][32 * wi + r], bs[2 * kk + h][32 * wj + r], acc, 0, 0, 0);
+        if (((ks - s0) & (BG_FOLD - 1)) == BG_FOLD - 1) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { tot[i] += acc[i]; acc[i] = 0.f; }
+        }
         __syncthreads();
     }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] += tot[i];
 
     const int col = j0 + 32 * wj + r;
     if (col >= N) return;
@@ -141,12 +149,12 @@ __global__ __launch_bounds__(256) void k_tm_softmax_bwd(const float* p, float* d
     for (int j = lane; j < cols; j += 64) dr[j] = pr[j] * (dr[j] - s);
 }
 
-// dst[r] = idx[r] >= 0 ? src[idx[r]] : idx[r] == -2 ? extra : 0
+// dst[r] = idx[r] >= 0 ? src[idx[r]] : idx[r] == -2 && extra ? extra : 0 (a null `extra` reads as a row of zeros)
 __global__ __launch_bounds__(256) void k_tm_gather(const float* __restrict__ src, const float* __restrict__ extra,
                                                    const int32_t* __restrict__ idx, int E, float* __restrict__ dst) {
     const int r = blockIdx.x, id = idx[r];
-    const float* s = id >= 0 ? src + (long)id * E : extra;
-    for (int c = threadIdx.x; c < E; c += 256) dst[(long)r * E + c] = (id >= 0 || id == -2) ? s[c] : 0.f;
+    const float* s = id >= 0 ? src + (long)id * E : (id == -2 ? extra : nullptr);
+    for (int c = threadIdx.x; c < E; c += 256) dst[(long)r * E + c] = s != nullptr ? s[c] : 0.f;
 }
 
 __global__ __launch_bounds__(256) void k_tm_gather_bwd(const float* __restrict__ ddst, const int32_t* __restrict__ idx, int E,

@@ -75,6 +75,10 @@ def test_nystrom_core_fwd_bwd(n_pad):
     assert rel(qd.grad, qr.grad) < 2e-3                  # all rows: the pad rows' q / k / v gradients too
     assert rel(qd.grad[:pad], qr.grad[:pad]) < 2e-3
     assert rel(wd.grad, wr.grad) < 2e-3
+    # the same per q / k / v block, pad rows and conv halo: one norm over dqkv is a statement about dv alone (|dv| is 12 x
+    # |dq| at n_pad 512 and 1760 x at 7936)
+    got = {"out": o.detach(), "dqkv": qd.grad, "dw": wd.grad.reshape(R.H, R.CONV)}
+    R.hold("core", f"n_pad {n_pad}", got, R.core_run(qkv, w, dO), R.core_run(qkv, w, dO, torch.float32), R.core_blocks(n_pad, pad))
 
 
 @pytest.mark.parametrize("N", [7, 250, 1000])
@@ -98,6 +102,10 @@ def test_ppeg_and_gather_fwd_bwd(N):
     assert rel(xd.grad, xr.grad) < 1e-5
     for k in p:
         assert rel(pd[k].grad, pr[k].grad) < 1e-4, k
+    # cls row, border ring of width 3 and interior of the grid each on their own
+    blocks = {"y": R.ppeg_blocks(geo["s"]), "dx": R.ppeg_blocks(geo["s"])}
+    R.hold("ppeg", f"N {N}", {"y": y.detach(), "dx": xd.grad}, R.ppeg_run(p, x, dy, geo["s"]),
+           R.ppeg_run(p, x, dy, geo["s"], torch.float32), blocks)
     # sequence assembly: [cls | tokens | first add tokens again], the repeats' gradients add
     h = torch.randn((N, 512), generator=g)
     cls = torch.randn((1, 1, 512), generator=g)
@@ -143,9 +151,19 @@ def _check_bag(net, p, x, tol_h=1e-4, tol_g=2e-3, keeps=None):
         assert rel(prm.grad, pr[k].grad) < tol_g, (k, rel(prm.grad, pr[k].grad))
         worst = max(worst, rel(prm.grad, pr[k].grad))
     print(f"restatement N={x.shape[0]}: h {rel(h[0], h_ref):.2e} worst grad {worst:.2e}")
+    # to_qkv.weight.grad by its q, k and v row blocks (as one tensor it is the v block's), against what the float32
+    # restatement loses on the CPU
+    x32 = x.float().clone().requires_grad_(True)
+    p32 = {k: v.float().clone().requires_grad_(True) for k, v in p.items()}
+    h32, _ = R.transmil(x32, p32, None if keeps is None else [k.float() for k in keeps])
+    (h32 * gw.float()).sum().backward()
+    grads = dict(net.named_parameters())
+    for layer in ("layer1", "layer2"):
+        k = f"{layer}.attn.to_qkv.weight"
+        R.hold("module", f"N {x.shape[0]} {k}", {"g": grads[k].grad}, {"g": pr[k].grad}, {"g": p32[k].grad}, {"g": R.wqkv_blocks()})
 
 
-@pytest.mark.parametrize("N", [7, 250, 1000, 2000])
+@pytest.mark.parametrize("N", [7, 250, 1000, 2000, 1, 2, 256, 257])      # 1: s = 1; 256: add = 0; 257: the largest add
 def test_module_eval_against_restatement(N):
     net, p = _model()
     net.eval()
