@@ -18,6 +18,21 @@ __device__ __forceinline__ void gp_split3(float v, unsigned short& p0, unsigned 
     p1 = gp_bf16_bits(r);
     p2 = gp_bf16_bits(r - gp_bf16_val(p1));
 }
+// Transposing fragment read of a k-major bf16 LDS image (rows = k, WB_S elements apart), shared by k_gate_bwd_dw_bf16 and
+// k_gate_bwd_dw2_pieces; the lane mapping and the conflict-free stride are described at k_gate_bwd_dw_bf16.
+#define WB_S 160
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+typedef unsigned short gp_u16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ gp_u16x8 tr_frag(const unsigned short* img, int row, int col) {
+    // 8 consecutive rows [row, row + 8) of column (col + lane column), as one 32x32x16 operand fragment
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + row * WB_S + col));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (row + 4) * WB_S + col));
+    gp_u16x8 f;
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
+    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
+    return f;
+}
 // Layout of the weight pieces Wp of [Wv; Wu] (gate row n in 0..383, Wu rows from 192): [L/16][3 pieces][2 halves][384][8]
 // bf16 - one 36 KiB block per 16-deep K slice, in the order the forward's LDS image holds it (a straight copy by LDS-DMA),
 // element (n, k) of piece q at this index.

@@ -1352,6 +1352,68 @@ __global__ __launch_bounds__(256 * KG) void k_gate_bwd_dw(const void* __restrict
 }
 
 
+// The epilogue shared by k_gate_bwd_dw2 and k_gate_bwd_dw2_pieces (512 threads: two K groups x four waves, wave (wi, wj) of
+// either group holding a partial 64 x 64 tile of the same output; smem_all = the 128 KiB staging area, dead by now).
+// partial tile -> part[s][128m + 64wi + row][j0 + 64wj + col]: every wave writes its 64 x 64 tile row-major into its own
+// 16 KB of its group's half; the two waves that own the same tile (one per K group) each fold and store half of its rows
+// with 16-byte stores.
+__device__ __forceinline__ void dw2_store_tile(float* smem_all, const f32x16 (&acc)[2][2], float* __restrict__ part, int s, int m,
+                                               int L, int j0, int grp, int wave, int lane) {
+    const int wi = wave >> 1, wj = wave & 1, r = lane & 31, h = lane >> 5;
+    float* tw = smem_all + grp * (2 * 2 * GB_BKR * 128) + wave * (64 * 64);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) tw[(32 * a + mfma32_row(i, h)) * 64 + 32 * b + r] = acc[a][b][i];
+    __syncthreads();
+    float* pt = part + ((size_t)s * GF_NG + 128 * m + 64 * wi) * L + j0 + 64 * wj;
+    const int c4 = lane & 15, rr = lane >> 4;
+    const float* t0 = smem_all + wave * (64 * 64);
+    const float* t1 = smem_all + (2 * 2 * GB_BKR * 128) + wave * (64 * 64);
+#pragma unroll
+    for (int pass = 0; pass < 8; ++pass) {
+        const int row = 4 * (pass + 8 * grp) + rr;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(t0 + row * 64 + 4 * c4) +
+                        *reinterpret_cast<const f32x4*>(t1 + row * 64 + 4 * c4);
+        *reinterpret_cast<f32x4*>(pt + (size_t)row * L + 4 * c4) = v;
+    }
+}
+// bias / w / b partials: every (s, jt) workgroup publishes the sums of its share of the slices -> pbias[s][jt][4][192].
+// arow_all (0..31), ad4: the thread's row group and float4 column of the dPre staging map.
+__device__ __forceinline__ void dw2_publish_sums(float* smem_all, float* __restrict__ pbias, int s, int NJ, int jt, int m,
+                                                 int arow_all, int ad4, const f32x4 acc_bv, const f32x4 acc_bu,
+                                                 const f32x4 acc_w, float acc_ds) {
+    float* redf = smem_all;   // [32 row groups][3][64]
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        redf[(arow_all * 3 + 0) * 64 + 4 * ad4 + e] = acc_bv[e];
+        redf[(arow_all * 3 + 1) * 64 + 4 * ad4 + e] = acc_bu[e];
+        redf[(arow_all * 3 + 2) * 64 + 4 * ad4 + e] = acc_w[e];
+    }
+    __syncthreads();
+    float* pb = pbias + ((size_t)s * NJ + jt) * 4 * 192;
+    if (threadIdx.x < 192) {
+        const int which = threadIdx.x / 64, d = threadIdx.x % 64;
+        float v = 0.f;
+#pragma unroll
+        for (int g = 0; g < 32; ++g) v += redf[(g * 3 + which) * 64 + d];
+        pb[which * 192 + 64 * m + d] = v;
+    }
+    if (m == 0) {
+        __syncthreads();
+        redf[threadIdx.x] = acc_ds;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float v = 0.f;
+            for (int g = 0; g < 512; g += 16) v += redf[g];
+            pb[3 * 192] = v;
+        }
+    }
+}
+
 // ================================================================================ K1 backward: gate dW, "VALU diet" form
 // Same product, tiling, split-K layout, k order and outputs (bit for bit) as k_gate_bwd_dw<false, 2, *>; what changes is
 // how little VECTOR-ALU work the main loop carries.  Measured on MI355X (tools/mfma_valu_mix.hip): unlike the bf16 MFMAs,
@@ -1553,62 +1615,212 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2(const float* __restrict__ 
         __syncthreads();
     }
 
-    // partial tile -> part[s][128m + 64wi + row][j0 + 64wj + col]: every wave writes its 64 x 64 tile row-major into its own
-    // 16 KB of its group's (now dead) staging area; the two waves that own the same tile (one per K group) each fold
-    // and store half of its rows with 16-byte stores.
-    {
-        float* tw = smem + wave * (64 * 64);
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) tw[(32 * a + mfma32_row(i, h)) * 64 + 32 * b + r] = acc[a][b][i];
-        __syncthreads();
-        float* pt = part + ((size_t)s * GF_NG + 128 * m + 64 * wi) * L + j0 + 64 * wj;
-        const int c4 = lane & 15, rr = lane >> 4;
-        const float* t0 = smem_all + wave * (64 * 64);
-        const float* t1 = smem_all + (2 * 2 * GB_BKR * 128) + wave * (64 * 64);
-#pragma unroll
-        for (int pass = 0; pass < 8; ++pass) {
-            const int row = 4 * (pass + 8 * grp) + rr;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(t0 + row * 64 + 4 * c4) +
-                            *reinterpret_cast<const f32x4*>(t1 + row * 64 + 4 * c4);
-            *reinterpret_cast<f32x4*>(pt + (size_t)row * L + 4 * c4) = v;
-        }
-    }
+    dw2_store_tile(smem_all, acc, part, s, m, L, j0, grp, wave, lane);
+    dw2_publish_sums(smem_all, pbias, s, NJ, jt, m, arow + 16 * grp, ad4, acc_bv, acc_bu, acc_w, acc_ds);
+}
 
-    // bias / w / b partials: every (s, jt) workgroup publishes the sums of its share of the slices -> pbias[s][jt][4][192]
+// ================================================================================ K1 backward: gate dW, split-bf16 K loop
+// The product of k_gate_bwd_dw2 with its K loop on v_mfma_f32_32x32x16_bf16, as the forward's PW loop: every staged fp32
+// value - dPreV / dPreU built from gates, ds, w and the keep-masked x - is split ONCE, while it is staged, into three exact
+// bf16 pieces (gp_split3: a dropped element is zeroed first, a row beyond the chunk reads as zero, a zero splits to three
+// zeros, a non-finite value keeps p0 = the inf / NaN and p1 = p2 = 0), and the contraction keeps the six cross terms (p, q)
+// with p + q <= 2, smallest first: 192 matrix cycles per 16 k and tile where the f32 MFMA takes 512.  Grid, split-K chunks,
+// XCD order, rows_dev clamp, part / pbias layout and the spreading of the bias / w / b sums (fp32 VALU on the unsplit
+// values) are those of k_gate_bwd_dw2; MIL_DW_PIECES=0 keeps that kernel.
+// LDS image: three pieces take 6 B per element, so two K groups with 32-row slices of their own (the f32 kernel's 128 KiB)
+// would need 192 KiB.  Here ONE stage pair serves all eight waves: a stage is a 32-row slice of both operands, 3 pieces x
+// [32][WB_S = 160] bf16 each (k-major as in memory; fragments come transposed from ds_read_b64_tr_b16, tr_frag) = 60 KiB,
+// two stages 120 KiB.  The "K groups" are the two 16-row halves of every slice: waves 0-3 multiply rows 0-15, waves 4-7 rows
+// 16-31, each wave on a 64 x 64 tile (12 fragments, 24 MFMAs per slice), and the epilogue folds the two halves as before.
+// Every element is staged (and split) once per workgroup, by 512 threads instead of 256.
+// Pipeline: one barrier per slice, in the MIDDLE of its 24 MFMAs.  Before it the wave lays the staging of slice sl + 1
+// (split + LDS writes, then the global loads of slice sl + 2) between the twelve MFMAs of the small terms; after it the
+// fragments of slice sl + 1 are read into the other register set under the twelve MFMAs of the large terms (the bf16 MFMA
+// hides VALU and LDS issue, tools/mfma_valu_mix.hip).
+#define GQ_PSZ (GB_BKR * WB_S)          /* one piece of one operand: [32][160] bf16 (10 KiB) */
+#define GQ_BUF (6 * GQ_PSZ)             /* one stage: dPre pieces 0..2, x pieces 0..2 (60 KiB) */
+template <bool DROP>
+__global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __restrict__ x, const float* __restrict__ gates,
+                                                             const float* __restrict__ ds, const float* __restrict__ wvec,
+                                                             float* __restrict__ part, float* __restrict__ pbias, int R, int L,
+                                                             int KC, int NJ, const uint32_t* __restrict__ xbits,
+                                                             const int32_t* __restrict__ rows_dev) {
+    // 128 KiB: the two stages take 120 KiB, the epilogue's eight 64 x 64 fp32 tiles all of it
+    __shared__ __attribute__((aligned(16))) float smem_all[2 * 2 * 2 * GB_BKR * 128];
+    static_assert(2 * GQ_BUF * 2 <= (int)sizeof(smem_all), "stages exceed the LDS image");
+    unsigned short* const img = reinterpret_cast<unsigned short*>(smem_all);
+    if (rows_dev != nullptr) R = min(R, __builtin_amdgcn_readfirstlane(rows_dev[0]));      // bucketed batches: true row count on the device
+    const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));               // which 16 rows of every slice
+    const int T = threadIdx.x, tid = T & 255, lane = tid & 63, wave = tid >> 6;
+    const int wi = wave >> 1, wj = wave & 1;
+    const int h = lane >> 5;
+    const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;                  // transpose-read address roles
+    int bid = blockIdx.x;
     {
-        float* redf = smem_all;   // [32 row groups][3][64]
-        const int arow_all = arow + 16 * grp;
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            redf[(arow_all * 3 + 0) * 64 + 4 * ad4 + e] = acc_bv[e];
-            redf[(arow_all * 3 + 1) * 64 + 4 * ad4 + e] = acc_bu[e];
-            redf[(arow_all * 3 + 2) * 64 + 4 * ad4 + e] = acc_w[e];
-        }
-        __syncthreads();
-        float* pb = pbias + ((size_t)s * NJ + jt) * 4 * 192;
-        if (threadIdx.x < 192) {
-            const int which = threadIdx.x / 64, d = threadIdx.x % 64;
-            float v = 0.f;
-#pragma unroll
-            for (int g = 0; g < 32; ++g) v += redf[(g * 3 + which) * 64 + d];
-            pb[which * 192 + 64 * m + d] = v;
-        }
-        if (m == 0) {
-            __syncthreads();
-            redf[threadIdx.x] = acc_ds;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                float v = 0.f;
-                for (int g = 0; g < 512; g += 16) v += redf[g];
-                pb[3 * 192] = v;
-            }
-        }
+        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
+        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
     }
+    const int jt = bid % NJ, m = (bid / NJ) % 3, s = bid / (3 * NJ);
+    const int j0 = jt * 128;
+    const int rbeg = min(s * KC, R), rend = min(R, rbeg + KC);
+    const int nloop = (rend - rbeg + GB_BKR - 1) / GB_BKR;
+
+    // per-lane byte offsets inside a slice (loop invariants)
+    const int xrow = T >> 5, xc4 = T & 31;        // x: rows xrow + 16i (i < 2), 16-byte chunk xc4 of the 128-column tile
+    const int arow = T >> 4, ad4 = T & 15;        // gates: row arow, d = 64m + 4 ad4
+    const int LW = L >> 5;
+    int vx[2], vm[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        vx[i] = ((xrow + 16 * i) * L + j0 + 4 * xc4) * 4;
+        vm[i] = ((xrow + 16 * i) * LW + ((j0 + 4 * xc4) >> 5)) * 4;
+    }
+    const int vg = (arow * GF_NG + 64 * m + 4 * ad4) * 4, vd = arow * 4;
+    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wvec + 64 * m + 4 * ad4);
+    unsigned short* const xw = img + 3 * GQ_PSZ + xrow * WB_S + 4 * xc4;     // + buf * GQ_BUF + 16 i * WB_S; piece q: + q * GQ_PSZ
+    unsigned short* const aw = img + arow * WB_S + 4 * ad4;                  // V columns 0..63; U: + 64
+    const int frow = 16 * grp + 8 * h + tq;
+    const int acol = 64 * wi + 16 * tg + 4 * tp;                             // + 32 a
+    const int bcol = 64 * wj + 16 * tg + 4 * tp;                             // + 32 b
+
+    u32x4_t rx[2], rv, ru;
+    unsigned rm[2] = {0, 0};
+    float rds;
+    f32x4 rt;
+    f32x4 acc_bv = {0, 0, 0, 0}, acc_bu = {0, 0, 0, 0}, acc_w = {0, 0, 0, 0};
+    float acc_ds = 0.f;
+
+    // resources of slice `row0`: rows >= rend are out of range -> the loads return zeros
+    auto xload = [&](int i, int row0) {
+        const int left = max(rend - row0, 0);
+        rx[i] = __builtin_amdgcn_raw_buffer_load_b128(
+            __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)row0 * L), 0, left * L * 4, MIL_SRD_FLAGS), vx[i], 0, 0);
+        if (DROP)
+            rm[i] = __builtin_amdgcn_raw_buffer_load_b32(
+                __builtin_amdgcn_make_buffer_rsrc((void*)(xbits + (size_t)row0 * LW), 0, left * LW * 4, MIL_SRD_FLAGS), vm[i], 0, 0);
+    };
+    auto aload = [&](int row0) {
+        const int left = max(rend - row0, 0);
+        const __amdgpu_buffer_rsrc_t g =
+            __builtin_amdgcn_make_buffer_rsrc((void*)(gates + (size_t)row0 * GF_NG), 0, left * GF_NG * 4, MIL_SRD_FLAGS);
+        rv = __builtin_amdgcn_raw_buffer_load_b128(g, vg, 0, 0);
+        ru = __builtin_amdgcn_raw_buffer_load_b128(g, vg + 192 * 4, 0, 0);
+        rds = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+            __builtin_amdgcn_make_buffer_rsrc((void*)(ds + row0), 0, left * 4, MIL_SRD_FLAGS), vd, 0, 0));
+    };
+    auto put3 = [&](unsigned short* dst, const f32x4 v) {          // four columns of one row: one 8-byte store per piece
+        ushort4 o[3];
+        gp_split3(v[0], o[0].x, o[1].x, o[2].x);
+        gp_split3(v[1], o[0].y, o[1].y, o[2].y);
+        gp_split3(v[2], o[0].z, o[1].z, o[2].z);
+        gp_split3(v[3], o[0].w, o[1].w, o[2].w);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) *reinterpret_cast<ushort4*>(dst + q * GQ_PSZ) = o[q];
+    };
+    auto xwrite = [&](int i, int buf) {
+        f32x4 v = __builtin_bit_cast(f32x4, rx[i]);
+        if (DROP) {
+            const unsigned mm = rm[i] >> (4 * (xc4 & 7));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = keep_if(v[e], mm, e);
+        }
+        put3(xw + buf * GQ_BUF + 16 * i * WB_S, v);
+    };
+    auto awrite_v = [&](int buf) {                  // dPreV = a - (a V) V,  a = ds w U
+        const f32x4 v = __builtin_bit_cast(f32x4, rv);
+        const f32x4 a = (rds * w4) * __builtin_bit_cast(f32x4, ru);
+        const f32x4 t = a * v;
+        rt = t;
+        put3(aw + buf * GQ_BUF, a - t * v);
+    };
+    auto awrite_u = [&](int buf, bool pub) {        // dPreU = t - t U,  t = ds w U V
+        const f32x4 t = rt, u = __builtin_bit_cast(f32x4, ru);
+        const f32x4 pu = t - t * u;
+        put3(aw + buf * GQ_BUF + 64, pu);
+        if (pub) {                                    // scalar branch: this slice's sums belong to this workgroup
+            const f32x4 v = __builtin_bit_cast(f32x4, rv);
+            acc_bv += (rds * w4) * u - t * v;
+            acc_bu += pu;
+            acc_w += (rds * v) * u;
+            if (ad4 == 0) acc_ds += rds;
+        }
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+
+    gp_u16x8 fa[2][3][2], fb[2][3][2];              // [register set][piece][tile]
+    auto frags = [&](auto set_c, int buf) {         // smallest piece first: the small terms are multiplied first
+        constexpr int set = decltype(set_c)::value;
+        const unsigned short* ai = img + buf * GQ_BUF;
+#pragma unroll
+        for (int p = 2; p >= 0; --p) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a) fa[set][p][a] = tr_frag(ai + p * GQ_PSZ, frow, acol + 32 * a);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) fb[set][p][b] = tr_frag(ai + (3 + p) * GQ_PSZ, frow, bcol + 32 * b);
+        }
+    };
+
+    // prologue: slice 0 -> stage 0 -> fragment set 0, slice 1 -> registers
+    xload(0, rbeg); xload(1, rbeg); aload(rbeg);
+    xwrite(0, 0); xwrite(1, 0); awrite_v(0); awrite_u(0, jt == 0);
+    xload(0, rbeg + GB_BKR); xload(1, rbeg + GB_BKR); aload(rbeg + GB_BKR);
+    __syncthreads();
+    frags(std::integral_constant<int, 0>{}, 0);
+
+    // cross terms (p, q) of dPre piece p and x piece q, p + q <= 2, smallest first (the forward's order)
+    auto slice = [&](int sl, auto set_c) {
+        constexpr int set = decltype(set_c)::value;      // fragment set = stage of slice sl
+        constexpr int TP[6] = {0, 1, 2, 0, 1, 0}, TQ[6] = {2, 1, 0, 1, 0, 0};
+        const int row2 = rbeg + (sl + 2) * GB_BKR;
+        const bool pub = ((sl + 1) % NJ) == jt;          // the slice being staged now is sl + 1
+        auto mfma = [&](int t, int g) {
+            const int a = g >> 1, b = g & 1;
+            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gp_bf16x8, fa[set][TP[t]][a]),
+                                                                __builtin_bit_cast(gp_bf16x8, fb[set][TQ[t]][b]), acc[a][b], 0, 0, 0);
+        };
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                mfma(t, g);
+                __builtin_amdgcn_sched_barrier(0);
+                switch (4 * t + g) {                     // seven staging parts behind the first MFMAs
+                    case 0: xwrite(0, set ^ 1); break;
+                    case 1: xload(0, row2); break;
+                    case 2: xwrite(1, set ^ 1); break;
+                    case 3: xload(1, row2); break;
+                    case 4: awrite_v(set ^ 1); break;
+                    case 5: awrite_u(set ^ 1, pub); break;
+                    case 6: aload(row2); break;
+                    default: break;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        __syncthreads();                                 // stage set ^ 1 holds slice sl + 1; every wave has read stage `set`
+        if (sl + 1 < nloop) frags(std::integral_constant<int, set ^ 1>{}, set ^ 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 3; t < 6; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) mfma(t, g);
+    };
+    int sl = 0;
+    for (; sl + 1 < nloop; sl += 2) {
+        slice(sl, std::integral_constant<int, 0>{});
+        slice(sl + 1, std::integral_constant<int, 1>{});
+    }
+    if (sl < nloop) slice(sl, std::integral_constant<int, 0>{});
+    __syncthreads();                                     // the stages are dead from here on
+
+    dw2_store_tile(smem_all, acc, part, s, m, L, j0, grp, wave, lane);
+    dw2_publish_sums(smem_all, pbias, s, NJ, jt, m, arow, ad4, acc_bv, acc_bu, acc_w, acc_ds);
 }
 
 #include "gate_reduce.h"
@@ -2161,6 +2373,14 @@ extern "C" size_t mil_gate_bwd_workspace_floats(int R, int L) {
     return gate_bwd_ws_floats(gate_dw_plan(R, L, MIL_NUM_CU).S, L);
 }
 
+// The K loop of the dw2 route: the split-bf16 kernel (k_gate_bwd_dw2_pieces) unless MIL_DW_PIECES=0 asks for the f32-MFMA
+// one.  Read per call (under a hipGraph: at capture), so A/B runs and tests toggle it inside one process; the route plan,
+// the workspace and the fold are the same for both.
+static inline bool dw_pieces_on() {
+    const char* e = getenv("MIL_DW_PIECES");
+    return e == nullptr || atoi(e) != 0;
+}
+
 // The two launches of mil_gate_bwd_params as separate entry points (bench.py times the MFMA kernel alone).
 static int gate_bwd_partials_impl(const float* x, const float* gates, const float* ds, const float* w, int R, int L,
                                   int D, float* workspace, size_t workspace_floats, const uint32_t* xbits,
@@ -2171,6 +2391,16 @@ static int gate_bwd_partials_impl(const float* x, const float* gates, const floa
     const int S = p.S, kc = p.kc, NJ = L / 128;
     if (workspace_floats < gate_bwd_ws_floats(S, L)) return MIL_ENOSPC;
     float* pb = workspace + (size_t)S * GF_NG * L;
+    if (p.dw == MIL_ROUTE_DW2 && dw_pieces_on()) {
+        if (xbits)
+            hipLaunchKernelGGL(k_gate_bwd_dw2_pieces<true>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,
+                               R, L, kc, NJ, xbits, rows_dev);
+        else
+            hipLaunchKernelGGL(k_gate_bwd_dw2_pieces<false>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,
+                               R, L, kc, NJ, xbits, rows_dev);
+        MIL_CHECK_LAUNCH();
+        return MIL_OK;
+    }
     if (p.dw == MIL_ROUTE_DW2) {
         if (xbits)
             hipLaunchKernelGGL(k_gate_bwd_dw2<true>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,

@@ -889,19 +889,8 @@ __global__ __launch_bounds__(256) void k_pool_bwd_ds_bf16(const u16* __restrict_
 // neither HBM nor prefetch depth: per slice the CU moves 96 KB of transpose reads + 48 KB of staging writes through LDS
 // (~1400 clk at the LDS rates) against 1024 MFMA clk, with the fragment reads of each k-step exposed (no register room
 // to double-buffer 6 fragments next to 128 accumulators at two waves per SIMD).
-#define WB_S 160
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-__device__ __forceinline__ u16x8 tr_frag(const u16* img, int row, int col) {
-    // 8 consecutive rows [row, row + 8) of column (col + lane column), as one 32x32x16 operand fragment
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + row * WB_S + col));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (row + 4) * WB_S + col));
-    u16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
+// WB_S (the 160-element row stride) and tr_frag live in gate_reduce.h: the split-bf16 weight gradient of the fp32 step
+// (k_gate_bwd_dw2_pieces, gated_pool.hip) reads its images the same way.
 
 __device__ __forceinline__ ushort4 pack_bf16x4(const f32x4 v) {
     ushort4 o;
