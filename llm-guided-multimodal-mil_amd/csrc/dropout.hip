@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void k_dropout_keep_bits_pair(uint32_t* __rest
     }
 }
 
-// Internal (step.hip, gated_pool.hip): mil_dropout_keep_bits(xbits, R, L, 0.5, seed ..) + (mbits, B, L, 0.25, mseed ..)
+// Internal (step.hip, gate_fwd.hip): mil_dropout_keep_bits(xbits, R, L, 0.5, seed ..) + (mbits, B, L, 0.25, mseed ..)
 static int keep_bits_pair_impl(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed,
                                uint64_t offset, const int32_t* offset_dev, int32_t* advance, int32_t* done, uint32_t mdelta,
                                void* stream, TileMapJob tm = TileMapJob{nullptr, 0, nullptr, nullptr, nullptr, 0}) {

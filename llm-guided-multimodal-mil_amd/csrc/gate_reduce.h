@@ -5,19 +5,6 @@
 #define GR_NG 384
 #define GR_NB 16          // lanes per bias / w / b output in the reduce
 
-// Three-piece split-bf16 form of an fp32 value (the gate forward's MFMA operands, k_gate_fwd2<.., PW = true>):
-// v = p0 + p1 + p2 exactly, p0 = bf16(v), p1 = bf16(v - p0), p2 = bf16(v - p0 - p1) (round to nearest even).  A non-finite v
-// keeps p0 = bf16(v) (the infinity / NaN itself) and p1 = p2 = 0, so the split adds no NaN of its own; a finite v beyond the
-// largest bf16 (|v| >= 2^128 (1 - 2^-9)) rounds to p0 = +-inf the same way.
-__device__ __forceinline__ unsigned short gp_bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
-__device__ __forceinline__ float gp_bf16_val(unsigned short b) { return __uint_as_float(((unsigned)b) << 16); }
-__device__ __forceinline__ void gp_split3(float v, unsigned short& p0, unsigned short& p1, unsigned short& p2) {
-    p0 = gp_bf16_bits(v);
-    float r = v - gp_bf16_val(p0);
-    r = __builtin_isfinite(r) ? r : 0.f;
-    p1 = gp_bf16_bits(r);
-    p2 = gp_bf16_bits(r - gp_bf16_val(p1));
-}
 // Transposing fragment read of a k-major bf16 LDS image (rows = k, WB_S elements apart), shared by k_gate_bwd_dw_bf16 and
 // k_gate_bwd_dw2_pieces; the lane mapping and the conflict-free stride are described at k_gate_bwd_dw_bf16.
 #define WB_S 160
@@ -32,23 +19,6 @@ __device__ __forceinline__ gp_u16x8 tr_frag(const unsigned short* img, int row, 
     f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
     f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
     return f;
-}
-// Layout of the weight pieces Wp of [Wv; Wu] (gate row n in 0..383, Wu rows from 192): [L/16][3 pieces][2 halves][384][8]
-// bf16 - one 36 KiB block per 16-deep K slice, in the order the forward's LDS image holds it (a straight copy by LDS-DMA),
-// element (n, k) of piece q at this index.
-#define GP_SLICE_ELEMS (3 * 2 * GR_NG * 8)
-__host__ __device__ __forceinline__ size_t gp_index(int q, int n, int k) {
-    return (size_t)(k >> 4) * GP_SLICE_ELEMS + ((size_t)(q * 2 + ((k >> 3) & 1)) * GR_NG + n) * 8 + (k & 7);
-}
-// the pieces of four consecutive k (k % 4 == 0) of gate row n: three 8-byte stores
-__device__ __forceinline__ void gp_store4(unsigned short* __restrict__ Wp, int n, int k, const f32x4 v) {
-    ushort4 o[3];
-    gp_split3(v[0], o[0].x, o[1].x, o[2].x);
-    gp_split3(v[1], o[0].y, o[1].y, o[2].y);
-    gp_split3(v[2], o[0].z, o[1].z, o[2].z);
-    gp_split3(v[3], o[0].w, o[1].w, o[2].w);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) *reinterpret_cast<ushort4*>(Wp + gp_index(q, n, k)) = o[q];
 }
 
 // Parameter gradients of the head (model/aggregator.py:128-131: z = M Wf^T + bf):  dWf[c][j] = sum_b dz[b][c] M[b][j],

@@ -1,6 +1,6 @@
 // K1, bf16-storage variant (BASELINE config 5: large bags, N=4096, D=1024): x and the gate weights are held
 // in bf16, every accumulation (gate pre-activations, scores, softmax, pooled sum, gradients) stays fp32.
-// Same arithmetic as gated_pool.hip (reference model/dim1/ABMIL.py:47-59) on rounded inputs; parity with the
+// Same arithmetic as the fp32 stage files (reference model/dim1/ABMIL.py:47-59) on rounded inputs; parity with the
 // fp32 oracle is REPORTED (max |dlogit|), the 1e-3 bar applies to the fp32 path.
 //
 //   k_gate_fwd_bf16   v_mfma_f32_32x32x16_bf16: 16x the fp32 MFMA rate, so this kernel sits at the HBM/L2 ridge
@@ -384,9 +384,6 @@ __global__ __launch_bounds__(512) void k_gate_fwd_bf16_deep(const u16* __restric
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
-#if defined(HC_STAMP)
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime(), sr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     const int fx = (r >> 2) & 3;       // rows 64 wr + 32 q + r and 32 (..) + r: (row >> 2) & 3 == (r >> 2) & 3
     // Per slice: 12 B fragments j = 6 ks + 2 c + u, each feeding two MFMAs (row tiles q = 0, 1).  B fragments rotate
     // through three register slots and are read two ahead of their use; the A pair of k-step 1 is read during
@@ -413,7 +410,6 @@ __global__ __launch_bounds__(512) void k_gate_fwd_bf16_deep(const u16* __restric
             mw[0] = mp[0];
             mw[1] = mp[32 * 4];
         }
-#if !defined(HC_PHASED_LOOP)
         u16x8 a[2][2], bs[3];
         auto read_a = [&](int ks) {
             const int ch = 8 * ((2 * ks + h) ^ fx);
@@ -447,54 +443,10 @@ __global__ __launch_bounds__(512) void k_gate_fwd_bf16_deep(const u16* __restric
             acc[1][c][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[ks][1]), bf, acc[1][c][u], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#else
-        // Phased k-step (round 2): ALL eight fragments of a k-step are read as one block, then its twelve MFMAs run as one
-        // uninterrupted cluster at raised priority.  With the fragments trickling in one per MFMA pair (round 1) the two
-        // waves of a SIMD stayed in lockstep - both waiting on LDS, then both multiplying: MFMA busy 0.37.  A contiguous
-        // read block and a contiguous 384-cycle cluster let them fall into alternation on their own: the matrix pipe
-        // serialises the two clusters once, and from then on one wave reads while the other multiplies.
-        u16x8 a[2], bq[6];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int ch = 8 * ((2 * ks + h) ^ fx);
-            a[0] = *reinterpret_cast<const u16x8*>(xa + ch);
-            a[1] = *reinterpret_cast<const u16x8*>(xa + 32 * HC_BK + ch);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) bq[j] = *reinterpret_cast<const u16x8*>(wb + ((j & 1) * 192 + 32 * (j >> 1)) * HC_BK + ch);
-#if !defined(HC_ABL_NOW)
-            if (ks == 0) { dma_w(0, wnew, kw); dma_w(1, wnew, kw); dma_w(2, wnew, kw); }
-#endif
-#if !defined(HC_ABL_NOX)
-            if (ks == 1) { dma_x(0, xnew, kx); dma_x(1, xnew, kx); }
-#endif
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const bf16x8 bf = __builtin_bit_cast(bf16x8, bq[j]);
-#if !defined(HC_ABL_NOMFMA)
-                acc[0][j >> 1][j & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]), bf, acc[0][j >> 1][j & 1], 0, 0, 0);
-                acc[1][j >> 1][j & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]), bf, acc[1][j >> 1][j & 1], 0, 0, 0);
-#else
-                asm volatile("" ::"v"(bf), "v"(a[0]), "v"(a[1]));
-#endif
-            }
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#endif
-#if defined(HC_ABL_NOW) && defined(HC_ABL_NOX)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#elif defined(HC_ABL_NOW)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // ablation: x pieces only (2 per slice): x of s + 1 landed
-#elif defined(HC_ABL_NOX)
-        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");     // ablation: weight pieces only (3 per slice)
-#else
         // everything issued before the previous slice's x pieces has landed (a slice that opened with a keep-word piece has
         // one more operation behind them)
         if (mask_slice) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-#endif
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         xs = xs == HC_NX - 1 ? 0 : xs + 1;
@@ -503,9 +455,6 @@ __global__ __launch_bounds__(512) void k_gate_fwd_bf16_deep(const u16* __restric
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the clamped tail pieces must not land on the scratch below
     __builtin_amdgcn_s_barrier();
 
-#if defined(HC_STAMP)
-    const unsigned long long st1 = __builtin_amdgcn_s_memtime(), sr1 = __builtin_amdgcn_s_memrealtime();
-#endif
     float* sred = reinterpret_cast<float*>(smem) + 8 * (32 * 192) / 2;       // [2][256], behind the eight gate tiles
     u16* tile_lds = smem + wave * (32 * 192);                               // this wave's [32][192] bf16 tile (12 KB)
     // fused pool pass: this wave's tile, its row registers and the loader.  Buffer q2 holds the 512-column block q2 of the
@@ -668,13 +617,6 @@ __global__ __launch_bounds__(512) void k_gate_fwd_bf16_deep(const u16* __restric
             }
         }
     }
-#if defined(HC_STAMP)
-    if (tid == 0 && GMODE == 2) {      // diagnostic build: (loop cycles, loop 100 MHz ticks, epilogue cycles, start tick) per workgroup
-        const unsigned long long st2 = __builtin_amdgcn_s_memtime();
-        float* dbg = reinterpret_cast<float*>(gates16) + 4 * blockIdx.x;
-        dbg[0] = (float)(st1 - st0); dbg[1] = (float)(sr1 - sr0); dbg[2] = (float)(st2 - st1); dbg[3] = (float)(sr0 & 0xffffff);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------- pool stages, bf16 x
@@ -890,7 +832,7 @@ __global__ __launch_bounds__(256) void k_pool_bwd_ds_bf16(const u16* __restrict_
 // (~1400 clk at the LDS rates) against 1024 MFMA clk, with the fragment reads of each k-step exposed (no register room
 // to double-buffer 6 fragments next to 128 accumulators at two waves per SIMD).
 // WB_S (the 160-element row stride) and tr_frag live in gate_reduce.h: the split-bf16 weight gradient of the fp32 step
-// (k_gate_bwd_dw2_pieces, gated_pool.hip) reads its images the same way.
+// (k_gate_bwd_dw2_pieces, gate_bwd_dw.hip) reads its images the same way.
 
 __device__ __forceinline__ ushort4 pack_bf16x4(const f32x4 v) {
     ushort4 o;
@@ -960,40 +902,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     unsigned rxm[WB_SETS][DROP ? 8 : 1];
     auto xload = [&](int z, int i, int rs) {
         const int gr = min(rs + xrow + 8 * i, rend - 1);
-#if !defined(WB_ABL_NOX)       // ablation builds (tools/build_variants.sh + tools/kbench_dw16.py): times only, results meaningless
         rx[z][i] = *reinterpret_cast<const u16x8*>(x + (size_t)gr * L + j0 + 8 * xc);
-#else
-        asm volatile("" : "+v"(rx[z][i]) : "v"(gr));
-#endif
         if (DROP) rxm[z][i] = xbits[(size_t)gr * (L >> 5) + ((j0 + 8 * xc) >> 5)];
     };
     auto xwrite = [&](int z, int i, int buf) {
         // columns 0..127 -> panel 0, 128..255 -> panel 1 (each panel is its own 160-stride image)
         u16* dst = xb + buf * BSZ + (xc >> 4) * ASZ + (xrow + 8 * i) * WB_S + 8 * (xc & 15);
-#if !defined(WB_ABL_NOXW)
         *reinterpret_cast<u16x8*>(dst) = DROP ? keep_bf16x8_b(rx[z][i], rxm[z][i] >> (8 * (xc & 3))) : rx[z][i];
-#else
-        asm volatile("" ::"v"(rx[z][i]), "v"(dst));
-#endif
     };
     auto aload = [&](int z, int i, int rs, bool live) {
         const int gr = rs + arow + 16 * i;
         const int gc = min(gr, rend - 1);
         const u16* gp = gates + (size_t)gc * HB_NG + 64 * m + 4 * ad4;
-#if !defined(WB_ABL_NOG)
         hv[z][i] = *reinterpret_cast<const ushort4*>(gp);
         hu[z][i] = *reinterpret_cast<const ushort4*>(gp + 192);
         rds[z][i] = ds[gc];
-#else
-        asm volatile("" : "+v"(hv[z][i]), "+v"(hu[z][i]), "+v"(rds[z][i]) : "v"(gp));
-#endif
         rmask[z][i] = (live && gr < rend) ? 1.f : 0.f;
     };
     auto awrite = [&](int z, int i, int buf) {
-#if defined(WB_ABL_NOAW)
-        asm volatile("" ::"v"(hv[z][i]), "v"(hu[z][i]), "v"(rds[z][i]), "v"(buf));
-        return;
-#endif
         const f32x4 v = {bf16_to_f32(hv[z][i].x), bf16_to_f32(hv[z][i].y), bf16_to_f32(hv[z][i].z), bf16_to_f32(hv[z][i].w)};
         const f32x4 u = {bf16_to_f32(hu[z][i].x), bf16_to_f32(hu[z][i].y), bf16_to_f32(hu[z][i].z), bf16_to_f32(hu[z][i].w)};
         const float dsv = rds[z][i] * rmask[z][i];
@@ -1053,17 +979,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         u16x8 fa[2][2], fb[2][4];                                // [register set][tile]
         auto frags = [&](int ks, int q) {
             const int row = 16 * ks + 8 * h + tq;
-#if !defined(WB_ABL_NOFRAG)
 #pragma unroll
             for (int a = 0; a < 2; ++a) fa[q][a] = tr_frag(ai, row, acol + 32 * a);
 #pragma unroll
             for (int b = 0; b < 4; ++b) fb[q][b] = tr_frag(bi, row, bcol + 32 * b);
-#else
-#pragma unroll
-            for (int a = 0; a < 2; ++a) asm volatile("" : "+v"(fa[q][a]) : "v"(row), "v"(ai));
-#pragma unroll
-            for (int b = 0; b < 4; ++b) asm volatile("" : "+v"(fb[q][b]) : "v"(bi));
-#endif
         };
         // twelve staging parts of the next slice, three per k-step
         auto stage = [&](int p) {
@@ -1080,12 +999,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
-#if !defined(WB_ABL_NOMFMA)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[q][a]),
                                                                         __builtin_bit_cast(bf16x8, fb[q][b]), acc[a][b], 0, 0, 0);
-#else
-                    asm volatile("" : "+v"(acc[a][b]) : "v"(fa[q][a]), "v"(fb[q][b]));
-#endif
                     const int g = a * 4 + b;                     // 8 MFMAs per k-step: a staging part behind #1, #3, #5
                     if (g == 1 || g == 3 || g == 5) {
                         __builtin_amdgcn_sched_barrier(0);

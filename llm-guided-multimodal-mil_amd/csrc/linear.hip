@@ -123,7 +123,6 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int l
     // keeps consecutive logical tiles on one XCD, dispatched within a few slots of each other.  (Times are unchanged on
     // MI355X - the Infinity Cache already absorbs the cross-XCD re-reads; the order only spares L2 -> fabric traffic.)
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-#if !defined(LG_NOXCD)
     {
         const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy * gridDim.z;
         int lin = bx + gx * (by + gy * bz);
@@ -133,7 +132,6 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int l
         by = (lin / gx) % gy;
         bz = lin / (gx * gy);
     }
-#endif
     int i0 = by * 128;
     const int j0 = bx * 128;
     int kbeg = bz * kchunk, kend = min(K, kbeg + kchunk);
@@ -498,12 +496,10 @@ static bool tail_plan(int M, int N, int K, int a_mode, int* rows_main, int* S_ou
 extern "C" size_t mil_gemm_workspace_floats(int M, int N, int K, int a_mode) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     int kchunk, rows_main, S_tail;
-#if !defined(LG_NO_TILE64N)
     {
         int S64;
         if (small_tile_plan(M, N, K, a_mode, &S64, &kchunk)) return S64 > 1 ? (size_t)S64 * M * N : 0;
     }
-#endif
     if (tail_plan(M, N, K, a_mode, &rows_main, &S_tail, &kchunk)) return (size_t)S_tail * (M - rows_main) * N;
     const int S = splitk_plan(M, N, K, a_mode, &kchunk);
     return S > 1 ? (size_t)S * M * N : 0;
@@ -522,7 +518,6 @@ static int gemm_impl(const float* A, int lda, int a_mode, const float* B, int ld
     if (b_mode == 1 && (N < 4 || (N & 3))) return MIL_EINVAL;
     if (a_mode == 1 && b_mode == 0) return MIL_EINVAL;             // TT form is never needed
     hipStream_t st = (hipStream_t)stream;
-#if !defined(LG_NO_NT2)
     if (a_mode == 0 && b_mode == 0 && residual == nullptr && !accumulate && aux_mode == AUX_NONE && act <= ACT_RELU &&
         ldc >= N && mil_gemm_nt2_ok(lda, ldb, M, N, K) && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0) {
         // tall NT product whose 256 x 256 tiles fill whole rounds of the chip (fc_pathology: 32 768 x 512 = 256 tiles): the
@@ -532,8 +527,6 @@ static int gemm_impl(const float* A, int lda, int a_mode, const float* B, int ld
         if (rows_dev == nullptr && tiles >= (3 * MIL_NUM_CU) / 4 && 8 * tiles >= 7 * rounds * MIL_NUM_CU)
             return mil_gemm_nt2(A, lda, B, ldb, C, ldc, M, N, K, bias, act, stream);
     }
-#endif
-#if !defined(LG_NO_TILE64)
     if (a_mode == 0) {
         // Tall products take 64 x 128 tiles (gemm64.h: three workgroups per CU = 768 slots) as soon as those fill half
         // of the chip: finer rounds and a third resident workgroup beat the 128-row tile on every shape measured
@@ -551,8 +544,6 @@ static int gemm_impl(const float* A, int lda, int a_mode, const float* B, int ld
             return MIL_OK;
         }
     }
-#endif
-#if !defined(LG_NO_TILE64N)
     {
         // a few hundred rows: 64 x 64 tiles, K split over blockIdx.z when the tiles alone leave CUs idle (gemm64.h)
         int S64, kc64;
@@ -573,7 +564,6 @@ static int gemm_impl(const float* A, int lda, int a_mode, const float* B, int ld
             return MIL_OK;
         }
     }
-#endif
     {
         int rows_main, S_tail, kc_tail;
         if (workspace != nullptr && tail_plan(M, N, K, a_mode, &rows_main, &S_tail, &kc_tail) &&
@@ -700,7 +690,6 @@ extern "C" int mil_linear_bwd_params_rows(const float* dY, int lddy, const float
     if (act != ACT_NONE && Y == nullptr) return MIL_EINVAL;
     if (workspace_floats < mil_linear_bwd_params_workspace_floats(rows, n_out, k_in)) return MIL_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
-#if !defined(LG_NO_TN2)
     if (mil_gemm_tn2_ok(lddy, Y ? ldy : lddy, ldx, rows, n_out, k_in) &&
         ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0) {
         // tall activation, whole 128 x 128 output tiles: the low-VALU split-rows kernel (linear_nt2.hip), same partial layout
@@ -716,7 +705,6 @@ extern "C" int mil_linear_bwd_params_rows(const float* dY, int lddy, const float
         MIL_CHECK_LAUNCH();
         return MIL_OK;
     }
-#endif
     int kchunk;
     int S = splitk_plan(n_out, k_in, rows, 1, &kchunk);
     if (S < 1) { S = 1; kchunk = rows; }

@@ -1,4 +1,4 @@
-// K3a, tall NT products on the low-VALU pipeline of k_gate_fwd2 (gated_pool.hip):  C[M, N] = act(A[M, K] W[N, K]^T + bias)
+// K3a, tall NT products on the low-VALU pipeline of k_gate_fwd2 (gate_fwd.hip):  C[M, N] = act(A[M, K] W[N, K]^T + bias)
 // with both operands K-contiguous (nn.Linear on a tall activation: fc_pathology, model/aggregator.py:47, 141-149).
 //
 // The f32 MFMA does not hide vector-ALU instructions (tools/mfma_valu_mix.hip: every VALU instruction between two
@@ -179,7 +179,7 @@ extern "C" int mil_gemm_nt2(const float* A, int lda, const float* W, int ldw, fl
 // ================================================================================ tall TN products (weight gradients)
 // dW[n][k] = sum_rows G[row][n] X[row][k],  G = dY (.) act'(Y),  plus db[n] = sum_rows G[row][n]: the parameter half of a
 // Linear layer's backward on a tall activation (fc_pathology: 32 768 rows, 512 x 768 outputs), split over the rows.
-// The low-VALU form of k_gate_bwd_dw2 (gated_pool.hip) with both operands staged alike: 512 threads = two K groups x four
+// The low-VALU form of k_gate_bwd_dw2 (gate_bwd_dw.hip) with both operands staged alike: 512 threads = two K groups x four
 // waves x (2 x 2) MFMA tiles on a 128 (n) x 128 (k) output tile; global operands through buffer resources whose base
 // advances by scalar ALU (rows beyond the chunk read as zeros: no clamps, no masks), LDS images [32 rows][128] with their
 // 32-column blocks in the order {0, 2, 1, 3} so that one ds_read2st64_b32 fetches both operand values of a k-step, staging

@@ -30,6 +30,9 @@ static inline int mil_num_cu() {
 // linear sweep over more than that leaves nothing useful behind): its loads carry the nontemporal hint.
 #define MIL_STREAM_BYTES ((size_t)192 << 20)
 
+#define GF_NG 384                     /* columns of a saved gate row: V (0 .. 191), then U (192 .. 383) */
+#define MIL_SRD_FLAGS 0x00020000      /* raw buffer resource word 3 as hipcc's examples build it for gfx950 */
+
 #define MIL_CHECK_LAUNCH()                               \
     do {                                                 \
         hipError_t e_ = hipGetLastError();               \
@@ -248,6 +251,44 @@ __device__ __forceinline__ f32x4 adam_fused4(const AdamFuse& ad, const float* gp
 // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)   (dtype independent on gfx950).
 __device__ __forceinline__ int mfma32_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
+// Dropout keep bits applied to an fp32 value: all-ones if bit `b` of m is set, else 0 (v_bfe_i32: a one-bit signed field)
+__device__ __forceinline__ unsigned bitmask1(unsigned m, int b) { return (unsigned)__builtin_amdgcn_sbfe((int)m, b, 1); }
+__device__ __forceinline__ float keep_if(float v, unsigned m, int b) {
+    return __uint_as_float(__float_as_uint(v) & bitmask1(m, b));
+}
+
+// Three-piece split-bf16 form of an fp32 value (the MFMA operands of k_gate_fwd2<.., PW = true> and k_gate_bwd_dw2_pieces):
+// v = p0 + p1 + p2 exactly, p0 = bf16(v), p1 = bf16(v - p0), p2 = bf16(v - p0 - p1) (round to nearest even).  A non-finite v
+// keeps p0 = bf16(v) (the infinity / NaN itself) and p1 = p2 = 0, so the split adds no NaN of its own; a finite v beyond the
+// largest bf16 (|v| >= 2^128 (1 - 2^-9)) rounds to p0 = +-inf the same way.
+typedef __bf16 gp_bf16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ unsigned short gp_bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
+__device__ __forceinline__ float gp_bf16_val(unsigned short b) { return __uint_as_float(((unsigned)b) << 16); }
+__device__ __forceinline__ void gp_split3(float v, unsigned short& p0, unsigned short& p1, unsigned short& p2) {
+    p0 = gp_bf16_bits(v);
+    float r = v - gp_bf16_val(p0);
+    r = __builtin_isfinite(r) ? r : 0.f;
+    p1 = gp_bf16_bits(r);
+    p2 = gp_bf16_bits(r - gp_bf16_val(p1));
+}
+// Layout of the weight pieces Wp of [Wv; Wu] (gate row n in 0..383, Wu rows from 192): [L/16][3 pieces][2 halves][384][8]
+// bf16 - one 36 KiB block per 16-deep K slice, in the order the forward's LDS image holds it (a straight copy by LDS-DMA),
+// element (n, k) of piece q at this index.
+#define GP_SLICE_ELEMS (3 * 2 * GF_NG * 8)
+__host__ __device__ __forceinline__ size_t gp_index(int q, int n, int k) {
+    return (size_t)(k >> 4) * GP_SLICE_ELEMS + ((size_t)(q * 2 + ((k >> 3) & 1)) * GF_NG + n) * 8 + (k & 7);
+}
+// the pieces of four consecutive k (k % 4 == 0) of gate row n: three 8-byte stores
+__device__ __forceinline__ void gp_store4(unsigned short* __restrict__ Wp, int n, int k, const f32x4 v) {
+    ushort4 o[3];
+    gp_split3(v[0], o[0].x, o[1].x, o[2].x);
+    gp_split3(v[1], o[0].y, o[1].y, o[2].y);
+    gp_split3(v[2], o[0].z, o[1].z, o[2].z);
+    gp_split3(v[3], o[0].w, o[1].w, o[2].w);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) *reinterpret_cast<ushort4*>(Wp + gp_index(q, n, k)) = o[q];
+}
+
 struct TileMapJob {            // mil_build_tile_map's arguments as an optional rider of another launch (bag_len == NULL: none)
     const int32_t* bag_len;
     int B;
@@ -258,7 +299,7 @@ struct TileMapJob {            // mil_build_tile_map's arguments as an optional 
 };
 
 // Tile map of a batch whose bag lengths live on the device (one workgroup of 256 threads; see k_build_tile_map in
-// gated_pool.hip): shared by that kernel and by the generator launch that carries it as an extra workgroup (dropout.hip).
+// attn_pool.hip): shared by that kernel and by the generator launch that carries it as an extra workgroup (dropout.hip).
 __device__ __forceinline__ void build_tile_map_block(const int32_t* __restrict__ bag_len, int B, int32_t* __restrict__ tile_map,
                                                      int32_t* __restrict__ bag_tile_off, int32_t* __restrict__ rows_out,
                                                      int T_cap) {

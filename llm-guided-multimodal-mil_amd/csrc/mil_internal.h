@@ -3,7 +3,12 @@
 #pragma once
 #include "mil_common.h"
 
-// ---- gated_pool.hip (called from step.hip)
+#define MIL_HIDDEN __attribute__((visibility("hidden")))      /* host planners: not among the library's dynamic symbols */
+
+// ---- gate_fwd.hip (called from step.hip, gate_bwd_dx.hip)
+// Rows beyond whole rounds of 128-row tiles (tiles_per_round of them per round of the grid) that take the few-rows
+// kernels instead of one more round: 1 .. MIL_SMALL_ROWS, or 0
+MIL_HIDDEN int gate_tail_rows(int R, int tiles_per_round);
 // Gate forward with the pool partial pass in its epilogue when the batch allows it; *fused says whether partials / hrow
 // were produced (otherwise the caller runs the stand-alone pool pass).  draw != 0 (train mode): the keep bits are drawn
 // by this call into xbits / mbits (seed / mseed / offset as mil_gate_scores_fwd_draw), else xbits / mbits are inputs.
@@ -18,6 +23,13 @@ int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const fl
                       const float* b, float* scores, float* gates, int R, int L, int draw, uint32_t* xbits, float xscale,
                       uint32_t* mbits, int B, uint64_t seed, uint64_t mseed, uint64_t offset, const int32_t* offset_dev,
                       const int32_t* rows_dev, void* stream, const TileMapJob* tmap, const uint16_t* Wp);
+
+// ---- gate_bwd_dw.hip (called from gate_fwd.hip, step.hip)
+// The weight-gradient part of the route plan for (R, L) on ncu compute units; the same plan sizes the workspace
+struct GateDwPlan {
+    int dw, S, kc;          // MIL_ROUTE_DW_*, row chunks (split-K factor), rows per chunk
+};
+MIL_HIDDEN GateDwPlan gate_dw_plan(int R, int L, int ncu);
 // Split-K fold + head gradients + Adam in one launch.  step_dev != NULL: the update's number is (*step_dev + 1), read on
 // the device (hipGraph replay); the counter is advanced by this launch itself when `done` (a zeroed sign-off word) is
 // given, else by the caller afterwards.  Wp: the weight pieces of the split-bf16 forward, rewritten with the update.
@@ -45,7 +57,7 @@ int gate_fwd_bf16_with_pool(const uint16_t* x, const uint16_t* Wv, const float* 
                             float xscale, const int32_t* tile_map, int T, float* partials, const float* Wf, float* hrow,
                             const uint32_t* mbits, float mscale, int* fused, void* stream);
 
-// ---- dropout.hip (called from gated_pool.hip, step.hip)
+// ---- dropout.hip (called from gate_fwd.hip, step.hip)
 // both keep-bit tensors of a step in one launch; _tilemap: mil_build_tile_map rides along as one more workgroup
 int dropout_keep_bits_pair(uint32_t* xbits, int R, uint32_t* mbits, int B, int L, uint64_t seed, uint64_t mseed, uint64_t offset,
                            const int32_t* offset_dev, void* stream);

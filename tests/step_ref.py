@@ -15,7 +15,7 @@ WU, BU = "aggregator.attention_U.0.weight", "aggregator.attention_U.0.bias"
 WW, WB = "aggregator.attention_weights.weight", "aggregator.attention_weights.bias"
 WF, BF = "fc.1.weight", "fc.1.bias"
 
-GF_TM = 128          # rows per k_gate_fwd2 workgroup (gated_pool.hip GF_TM)
+GF_TM = 128          # rows per k_gate_fwd2 workgroup (gate_fwd.hip GF_TM)
 GS_TM = 32           # rows per k_gate_fwd_r32 row tile (GS_TM)
 SMALL_ROWS = 64      # MIL_SMALL_ROWS
 
@@ -25,13 +25,13 @@ def num_cu() -> int:
 
 
 def r32_rt(R: int, ncu: int) -> int:
-    """Row tiles per k_gate_fwd_r32 workgroup (gated_pool.hip: gate_r32_rt)."""
+    """Row tiles per k_gate_fwd_r32 workgroup (gate_fwd.hip: gate_r32_rt)."""
     tiles = (R + GS_TM - 1) // GS_TM
     return 1 if tiles <= ncu else 2 if tiles <= 2 * ncu else 3
 
 
 def split_kg(R: int, L: int, ncu: int) -> int:
-    """K groups per weight-gradient workgroup (gated_pool.hip: the dw part of gate_route_plan)."""
+    """K groups per weight-gradient workgroup (gate_bwd_dw.hip: gate_dw_plan)."""
     smax = ncu // (3 * (L // 128))
     return 2 if smax >= 1 and R // smax >= 512 else 1
 
@@ -69,7 +69,7 @@ def step_route(R: int, L: int, C: int, train: bool, *, aligned32: bool = False, 
     ncu = ncu or num_cu()
     fused_entry = _fused_entry(C, aligned32, bucketed)
     pw = pieces and L % 32 == 0                       # trainer.py: ImageOnlyTrainer.gate_pieces; step.hip: Wp
-    # gated_pool.hip: gate_route_plan
+    # gate_fwd.hip: gate_route_plan
     r32 = (R + GF_TM - 1) // GF_TM < (3 * ncu) // 4
     tail, big = 0, False
     if not r32:

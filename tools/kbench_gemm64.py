@@ -1,5 +1,6 @@
 """Text-tower shapes of the learnable-prompt step (about 10 k live rows): mil_gemm as dispatched (64-row tiles where they
-fill the chip better) against a build without them (tools/variants/lib_DLG_NO_TILE64.so via MIL_HIP_LIB)."""
+fill the chip better).  The 128-row figures it was compared with came from a build of commit 8457148 or earlier with the
+64-row route compiled out, loaded through MIL_HIP_LIB (tools/README.md: dropped variants live in the history)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mil_amd
