@@ -61,7 +61,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 8 */
+int mil_abi_version(void);   /* 9 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1013,6 +1013,16 @@ int mil_tm_ppeg_fwd(const float* x, int s, const float* W7, const float* b7, con
                     const float* b3, float* y, void* stream);
 int mil_tm_ppeg_bwd(const float* dy, const float* x, int s, const float* W7, const float* W5, const float* W3, float* dx,
                     float* dWf, float* db, void* stream);
+/* Per-patch attention of the cls token: the cls row (padded row `pad` = n_pad - s^2 - 1) of the map A1 Z A3 that the
+ * Nystrom core stands for, folded onto the bag's patches, without forming the [8, n_pad, n_pad] map.  A1 [8, n_pad, 256] and
+ * A3 [8, 256, n_pad] softmaxed, Z [8, 256, 256] the last pseudo-inverse iterate.  out [8, s^2]:
+ *   out[h][i] = P[h][pad][pad + 1 + i] + (i < s^2 - N ? P[h][pad][pad + 1 + N + i] : 0) for i < N (a patch the square padding
+ *   repeats gets the sum of its two keys), 0 for N <= i < s^2; the front-pad and cls columns are left out.
+ * N: `n` when len_dev is null ((s - 1)^2 < n <= s^2 or MIL_EINVAL), else len_dev[bag] read on the device and clamped into
+ * that bucket (mil_tm_seq_index raises the flag for such a length).  t_ws: 8 x 256 floats of workspace.  Two launches on
+ * `stream`, no host sync. */
+int mil_tm_cls_attn(const float* A1, const float* Z, const float* A3, int n_pad, int pad, int s, int n, const int32_t* len_dev,
+                    int bag, float* t_ws, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -186,6 +186,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_resconv_bwd": (c_int, [_P, _P, _P, c_int, _P, _P, _P]),
     "mil_tm_ppeg_fwd": (c_int, [_P, c_int] + [_P] * 7 + [_P]),
     "mil_tm_ppeg_bwd": (c_int, [_P, _P, c_int] + [_P] * 6 + [_P]),
+    "mil_tm_cls_attn": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
 }
 
 STAGE_DROPBITS, STAGE_GATE_FWD, STAGE_POOL, STAGE_TAIL, STAGE_GATE_BWD, STAGE_REDUCE, STAGE_ADAM = 1, 2, 4, 8, 16, 32, 64

@@ -96,6 +96,15 @@ def create_arg_parser(argv=None):
                    "test_ddp.py: its per-bag eval forward is replayed the same way (the model built by build_model does it)")
     p.add_argument("--transmil_max_graphs", type=int, default=0, help="--transmil_graph 1: most graphs kept (0 = the "
                    "stepper's default); a grid side beyond the cap runs eagerly")
+    p.add_argument("--save_patch_attn", type=str, default="", help="test_ddp.py, image_only + --model_pathology TransMIL: write "
+                   "DIR/<bag key or index>.npy per bag, float32 [2, 8, N] = layers x heads x patches, the cls token's attention "
+                   "to each patch (a repeated patch's two keys summed; not renormalised), bags in the order test_ddp.py runs "
+                   "them.  Works with and without --transmil_graph 1; the files are written when the run ends")
     p.add_argument("--flat_adam", type=int, default=1, help="autograd path: parameters in one flat buffer, one gradient "
                    "all-reduce and one Adam launch per step (optim.FlatAdam); 0 = torch DDP + torch.optim.Adam")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.save_patch_attn and (args.variant != "image_only" or args.model_pathology != "TransMIL"):
+        # refused here, before an entry point touches the GPU
+        raise ValueError("--save_patch_attn writes TransMIL's cls-token attention: it needs --variant image_only "
+                         "--model_pathology TransMIL (ABMIL keeps its scores in extractor_pathology.last_scores)")
+    return args

@@ -432,6 +432,89 @@ __global__ __launch_bounds__(256) void k_tm_ppeg_dw(const float* __restrict__ dy
     else atomicAdd(dWf + c * 49 + tap, acc);
 }
 
+// Per-patch cls-token attention: the cls row (padded row `pad`) of A1 Z A3 without the [n_pad, n_pad] map, in two launches.
+// t[h][:] = A1[h][pad][:] Z[h] comes from a tiny launch of its own (8 x 4 workgroups into an [8, 256] workspace) rather than
+// a per-workgroup recompute: every workgroup of the stream below would otherwise re-read its head's 256 KiB of Z.
+// Workgroup (64 columns of Z, head); wave w sums k in [64 w, 64 w + 64), the four partial sums are added in a fixed order.
+__global__ __launch_bounds__(256) void k_tm_cls_t(const float* __restrict__ A1, const float* __restrict__ Z, int n_pad, int pad,
+                                                  float* __restrict__ t) {
+    __shared__ float red[4][64];
+    const int hh = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = blockIdx.x * 64 + lane;
+    const float* a = A1 + ((long)hh * n_pad + pad) * TM_M + 64 * wv;
+    const float* z = Z + ((long)hh * TM_M + 64 * wv) * TM_M + j;
+    float s = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < 64; ++k) s += a[k] * z[k * TM_M];
+    red[wv][lane] = s;
+    __syncthreads();
+    if (wv == 0) t[hh * TM_M + j] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+
+// out[h][i] = sum_m t[h][m] (A3[h][m][pad + 1 + i] + (i < add ? A3[h][m][pad + 1 + N + i] : 0)) for i < N, 0 for N <= i < s^2:
+// a repeated patch gets the sum of its two keys.  One pass over the sequence columns of A3 with lanes along the column
+// index; the front-pad columns and the cls column are never read.  Workgroup (64 V patches, head): the thread of patches
+// i0 .. i0 + V - 1 forms both of their column sums over the 64 rows of its wave, the four waves' partial sums are added in a
+// fixed order.  V = 4 (16-byte loads) wants pad + 1 = n_pad - s^2 a multiple of 4, i.e. an even side; the repeats' columns
+// start at N, so their loads are wide only where N % 4 == 0 and the whole group lies below add.
+// len_dev != null: N is bag `bag`'s length on the device, clamped into the side's bucket as k_tm_seq_index does (which also
+// raises the out-of-bucket flag), so no column index leaves [pad + 1, n_pad).
+template <int V>
+__global__ __launch_bounds__(256) void k_tm_cls_row(const float* __restrict__ t, const float* __restrict__ A3, int n_pad, int pad,
+                                                    int s, int n_host, const int32_t* __restrict__ len_dev, int bag,
+                                                    float* __restrict__ out) {
+    __shared__ float red[4][64 * V];
+    const int S2 = s * s;
+    const int N = len_dev != nullptr ? min(max(len_dev[bag], (s - 1) * (s - 1) + 1), S2) : n_host;
+    const int add = S2 - N;
+    const int hh = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int i0 = (blockIdx.x * 64 + lane) * V;
+    const bool p_on = i0 < N, r_on = i0 < add;                       // i0 < N <= S2: every primary load stays in the row
+    const bool r_wide = V == 4 && (N & 3) == 0 && i0 + V <= add;
+    const float* tt = t + hh * TM_M + 64 * wv;
+    const float* a = A3 + ((long)hh * TM_M + 64 * wv) * n_pad + pad + 1 + i0;
+    float acc[V], rep[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = rep[v] = 0.f;
+    if (p_on) {
+#pragma unroll 8
+        for (int m = 0; m < 64; ++m) {
+            const float tm = tt[m];
+            const float* row = a + (long)m * n_pad;
+            if constexpr (V == 4) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(row);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[v] += tm * x[v];
+            } else {
+                acc[0] += tm * row[0];
+            }
+            if (r_on) {
+                if constexpr (V == 4) {
+                    if (r_wide) {
+                        const f32x4 y = *reinterpret_cast<const f32x4*>(row + N);
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) rep[v] += tm * y[v];
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < 4; ++v)
+                            if (i0 + v < add) rep[v] += tm * row[N + v];
+                    }
+                } else {
+                    rep[0] += tm * row[N];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) red[wv][lane * V + v] = acc[v] + rep[v];
+    __syncthreads();
+    if (wv != 0) return;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const int i = i0 + v, e = lane * V + v;
+        if (i < S2) out[(long)hh * S2 + i] = i < N ? (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]) : 0.f;
+    }
+}
+
 inline int launch_rc() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MIL_OK : (int)e;
@@ -557,6 +640,23 @@ int mil_tm_ppeg_bwd(const float* dy, const float* x, int s, const float* W7, con
     hipLaunchKernelGGL(k_tm_ppeg, dim3(s, 2, (s + PPEG_COLS - 1) / PPEG_COLS), dim3(256), 0, (hipStream_t)stream, dy, s, W7, W7, W5, W5, W3, W3, 1, dx);
     hipLaunchKernelGGL(k_tm_ppeg_dw, dim3((50 * TM_D + 255) / 256, (s + PPEG_ROWS - 1) / PPEG_ROWS), dim3(256), 0,
                        (hipStream_t)stream, dy, x, s, dWf, db);
+    return launch_rc();
+}
+
+int mil_tm_cls_attn(const float* A1, const float* Z, const float* A3, int n_pad, int pad, int s, int n, const int32_t* len_dev,
+                    int bag, float* t_ws, float* out, void* stream) {
+    if (!A1 || !Z || !A3 || !t_ws || !out || n_pad <= 0 || n_pad % TM_M || s < 1 || s > 4096) return MIL_EINVAL;
+    const long S2 = (long)s * s;
+    if (pad < 0 || (long)pad + 1 + S2 != n_pad) return MIL_EINVAL;
+    if (len_dev != nullptr ? (bag < 0 || bag >= TM_MAX_BAGS) : (n > S2 || n <= (long)(s - 1) * (s - 1))) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_cls_t, dim3(TM_M / 64, TM_H), dim3(256), 0, (hipStream_t)stream, A1, Z, n_pad, pad, t_ws);
+    const bool wide = (s & 1) == 0 && !(reinterpret_cast<uintptr_t>(A3) & 15);
+    if (wide)
+        hipLaunchKernelGGL(k_tm_cls_row<4>, dim3((unsigned)((S2 + 255) / 256), TM_H), dim3(256), 0, (hipStream_t)stream, t_ws, A3,
+                           n_pad, pad, s, n, len_dev, bag, out);
+    else
+        hipLaunchKernelGGL(k_tm_cls_row<1>, dim3((unsigned)((S2 + 63) / 64), TM_H), dim3(256), 0, (hipStream_t)stream, t_ws, A3,
+                           n_pad, pad, s, n, len_dev, bag, out);
     return launch_rc();
 }
 

@@ -32,6 +32,45 @@ class aggregator(nn.Module):
         # runs per sample - is replayed from the hipGraph of the bag's grid side (transmil_step.RaggedTransMILStepper)
         self.graph_eval = False
         self._eval_stepper = None
+        # TransMIL only (ABMIL keeps extractor_pathology.last_scores and ignores this): the forward also asks the extractor for
+        # need_attn="cls" and leaves [a0, a1] - per layer a list with one [8, N_b] tensor per bag, the cls token's attention
+        # to each patch - in last_patch_attn; the returned tuple does not change
+        self.patch_attn = False
+        self.last_patch_attn = None
+        self._attn_dir, self._attn_names, self._attn_kept, self._attn_done = None, None, [], 0
+
+    ATTN_KEEP_BYTES = 1 << 30
+
+    def save_patch_attn_to(self, directory: str, names=None):
+        """--save_patch_attn (train_ddp.build_model): every eval-mode, no-grad forward from here on keeps its bags' attention
+        as one [2, 8, N] tensor ON THE DEVICE (one small device copy; the results of a replayed forward are the graph's static
+        tensors), and flush_patch_attn() - registered to run when the process ends - copies them to the host and writes
+        DIR/<names[i] or i>.npy, float32, bags numbered in the order they ran.  So an entry point that times each forward
+        (test_ddp.py) has no host copy and no file inside its bracket.  Beyond ATTN_KEEP_BYTES kept, a forward flushes first."""
+        import atexit
+        import os
+        os.makedirs(directory, exist_ok=True)
+        self._attn_dir, self._attn_names = directory, (list(names) if names is not None else None)
+        self.patch_attn = True
+        atexit.register(self.flush_patch_attn)
+
+    def flush_patch_attn(self):
+        import os
+        import numpy as np
+        for a in self._attn_kept:
+            i = self._attn_done
+            name = str(self._attn_names[i]) if self._attn_names is not None and i < len(self._attn_names) else str(i)
+            np.save(os.path.join(self._attn_dir, name + ".npy"), a.float().cpu().numpy())
+            self._attn_done += 1
+        self._attn_kept = []
+
+    def _keep_patch_attn(self):
+        if self._attn_dir is None or self.training or torch.is_grad_enabled():
+            return
+        if sum(a.numel() for a in self._attn_kept) * 4 > self.ATTN_KEEP_BYTES:
+            self.flush_patch_attn()
+        a0, a1 = self.last_patch_attn
+        self._attn_kept += [torch.stack([x, y]) for x, y in zip(a0, a1)]
 
     def forward(self, x_list: List[torch.Tensor], lengths=None, geom=None):
         """geom (TransMIL only, model/dim1/TransMIL.py: DeviceGeometry): the capture-safe forward over a slot's static input,
@@ -40,11 +79,16 @@ class aggregator(nn.Module):
         if (self.graph_eval and geom is None and not self.training and not torch.is_grad_enabled() and x0.is_cuda
                 and (x0.dim() == 2 or x0.shape[0] == 1) and (lengths is None or len(lengths) == 1)):
             return self._replayed_eval(x0.reshape(-1, x0.shape[-1]), lengths)
+        want = "cls" if self.patch_attn and isinstance(self.extractor_pathology, TransMIL) else False
         if geom is not None:
-            M = self.extractor_pathology(x_list[0], None, geom=geom)
+            M = self.extractor_pathology(x_list[0], None, geom=geom, need_attn=want)
+        elif want:
+            M = self.extractor_pathology(x_list[0], lengths, need_attn=want)
         else:
             M = self.extractor_pathology(x_list[0], lengths)
         if isinstance(M, tuple):                     # TransMIL: (h, [attn0, attn1])
+            if want:
+                self.last_patch_attn = M[1]
             M = M[0]
         h = M
         if self.training and M.shape[1] % 32 == 0:
@@ -59,6 +103,8 @@ class aggregator(nn.Module):
             h = F.dropout(M, 0.25, True)
         p, z = ops.head_sigmoid(h, self.fc[1].weight, self.fc[1].bias)
         self.last_logits = z
+        if want and geom is None:
+            self._keep_patch_attn()
         return M, p
 
     def _replayed_eval(self, x: torch.Tensor, lengths=None):
@@ -73,4 +119,7 @@ class aggregator(nn.Module):
         slot.x[:n].copy_(x[:n], non_blocking=True)
         _, prob = st.step(slot, [n])
         self.last_logits = slot.last["logits"]
+        if slot.last["patch_attn"] is not None:     # the side's static [8, s^2] tensors, cut to the bag
+            self.last_patch_attn = [[a[:, :n] for a in layer] for layer in slot.last["patch_attn"]]
+            self._keep_patch_attn()
         return slot.last["h"], prob

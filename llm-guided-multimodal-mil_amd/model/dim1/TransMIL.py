@@ -1,6 +1,7 @@
 """TransMIL (reference: model/dim1/TransMIL.py:8-107 with nystrom_attention's NystromAttention in its TransLayer), MI355X path.
 
-Same constructor, parameter names and output `(h [B, 512], [attn0, attn1])`.  Input: flat rows [R, L] plus per-bag lengths, or
+Same constructor, parameter names and output `(h [B, 512], [attn0, attn1])` (need_attn: the whole maps, or "cls" for the cls
+token's per-patch attention at any bag size).  Input: flat rows [R, L] plus per-bag lengths, or
 [B, N, L] / [N, L].  Each bag runs alone (its own square padding, front pad and landmarks): a batch is B independent bags.
 The one deliberate difference from upstream is there for B > 1 only: the pseudo-inverse's starting scale (max row sum x max
 column sum of softmax(qL kL^T)) is taken per bag over its 8 heads, where upstream takes it over the whole batch.
@@ -107,13 +108,17 @@ class TransLayer(nn.Module):
         self.norm = norm_layer(dim)
         self.attn = NystromAttention(dim=dim)
 
-    def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn: bool):
-        """x [seq, 512] of one bag -> (x + to_out(Nystrom(LN(x)))[last seq rows], attn map or None)."""
+    def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn, cls: Optional[dict] = None):
+        """x [seq, 512] of one bag -> (x + to_out(Nystrom(LN(x)))[last seq rows], attn map / cls attention [8, s^2] / None).
+        cls: the bag length for need_attn="cls", dict(n=N) or dict(len_dev=.., bag=b)."""
         a = self.attn
         ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         xp = ops.tm_row_gather(ln, None, pad_idx)                                   # zero rows in front: [n_pad, 512]
         qkv = ops.linear_act(xp, a.to_qkv.weight, None)
-        o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn)
+        if cls is not None:
+            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, pad=g["pad"], s=g["s"], **cls)
+        else:
+            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn)
         o = o[g["pad"]:]
         lin = a.to_out[0]
         if bits is None:
@@ -167,10 +172,17 @@ class TransMIL(nn.Module):
         return tuple(ops.dropout_keep_bits(seq, self.D, TM_DROP_P, self._drop_seed ^ (0x5472616E734D494C + j), 2 * b + j, device,
                                            offset_dev=self._drop_ctr) for j in range(2))
 
-    def forward(self, x: torch.Tensor, lengths: Optional[Sequence[int]] = None, need_attn: bool = False,
+    def forward(self, x: torch.Tensor, lengths: Optional[Sequence[int]] = None, need_attn=False,
                 geom: Optional[DeviceGeometry] = None):
         """geom: the capture-safe form (RaggedTransMILStepper).  x is then the slot's whole [sum s^2, L] buffer, the bags packed
-        at its front, and nothing below touches the host: sides from geom, index / row count / pad index on the device."""
+        at its front, and nothing below touches the host: sides from geom, index / row count / pad index on the device.
+        need_attn: False -> (h, [None, None]); True -> the layers' whole [8, n_pad, n_pad] maps (n_pad^2 memory: small bags
+        only); "cls" -> (h, [a0, a1]), a_l a list with one [8, N_b] tensor per bag: what the cls token gives each patch in
+        layer l, a repeated patch's two keys summed (ops.tm_cls_attention; any bag size, train or eval).  With geom each entry is
+        the static [8, s_b^2] tensor, zeros behind the bag's length on the device."""
+        if not (isinstance(need_attn, bool) or (isinstance(need_attn, str) and need_attn == "cls")):
+            raise ValueError(f"TransMIL: need_attn must be False, True or 'cls', got {need_attn!r}")
+        want_cls = not isinstance(need_attn, bool)
         dev = x.device
         if geom is not None:
             if x.dim() != 2 or x.shape[0] != geom.cap:
@@ -213,9 +225,14 @@ class TransMIL(nn.Module):
                 pad_idx = torch.tensor(pad_index(g), dtype=torch.int32).to(dev, non_blocking=True)
             bits = self._bits(b, g["seq"], dev) if train else (None, None)
             bits_used.append(bits)
-            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn)
+            cls = None
+            if want_cls:
+                cls = dict(len_dev=geom.len_dev, bag=b) if geom is not None else dict(n=g["N"])
+            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls)
             xb = self.pos_layer.run(xb, g["s"])
-            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn)
+            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls)
+            if want_cls and geom is None:
+                a0, a1 = a0[:, :g["N"]], a1[:, :g["N"]]
             cls_rows.append(xb[:1])
             attn0.append(a0)
             attn1.append(a1)
@@ -226,6 +243,8 @@ class TransMIL(nn.Module):
         out = ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps)     # norm of the cls rows only
         if not need_attn:
             return out, [None, None]
+        if want_cls:
+            return out, [attn0, attn1]
         if len(geo) == 1:
             return out, [attn0[0].unsqueeze(0), attn1[0].unsqueeze(0)]
         return out, [attn0, attn1]                   # ragged bags: one [8, n_pad, n_pad] map per bag

@@ -2508,7 +2508,30 @@ def tm_ppeg(x, s: int, W7, b7, W5, b5, W3, b3):
     return _TmPPEG.apply(x, s, W7, b7, W5, b5, W3, b3)
 
 
-def _tm_fwd(qkv, w, need_attn: bool):
+def tm_cls_attention(A1, Z, A3, pad: int, s: int, n=None, len_dev=None, bag: int = 0):
+    """Per-patch attention of the cls token out of the Nystrom factors, without the [8, n_pad, n_pad] map (mil_tm_cls_attn):
+    A1 [8, n_pad, 256] and A3 [8, 256, n_pad] softmaxed, Z [8, 256, 256] as _tm_fwd holds them, pad = n_pad - s^2 - 1 the cls
+    row.  With P = A1 Z A3: out[h, i] = P[h, pad, pad + 1 + i] + (i < s^2 - N ? P[h, pad, pad + 1 + N + i] : 0) for i < N - a
+    patch the square padding repeats gets the sum of its two keys - and 0 for N <= i < s^2; not renormalised (the Nystrom
+    approximation can go negative).  N is the host int `n`, or len_dev[bag] read on the device (clamped into the side's
+    bucket) for a replayed step.  Returns [8, s^2] fp32; 8 x 256 floats of workspace, two launches, no host sync."""
+    if (n is None) == (len_dev is None):
+        raise ValueError("tm_cls_attention: give the bag length either as n or as len_dev (+ bag)")
+    A1, Z, A3 = _f32c(A1, "A1"), _f32c(Z, "Z"), _f32c(A3, "A3")
+    n_pad = A3.shape[-1]
+    if tuple(A1.shape) != (TM_H, n_pad, TM_M) or tuple(Z.shape) != (TM_H, TM_M, TM_M) or tuple(A3.shape) != (TM_H, TM_M, n_pad):
+        raise _lib.MilHipError(f"tm_cls_attention: A1 {tuple(A1.shape)} / Z {tuple(Z.shape)} / A3 {tuple(A3.shape)} outside the built shape")
+    if len_dev is not None and (len_dev.dtype != torch.int32 or not 0 <= int(bag) < len_dev.numel()):
+        raise _lib.MilHipError("tm_cls_attention: len_dev must be int32 and hold entry `bag`")
+    out = torch.empty((TM_H, int(s) * int(s)), device=A3.device, dtype=torch.float32)
+    t = torch.empty((TM_H, TM_M), device=A3.device, dtype=torch.float32)
+    rc = _lib.lib().mil_tm_cls_attn(_p(A1), _p(Z), _p(A3), n_pad, int(pad), int(s), int(n) if n is not None else 0, _p(len_dev),
+                                    int(bag), _p(t), _p(out), _stream())
+    _lib.check(rc, "mil_tm_cls_attn")
+    return out
+
+
+def _tm_fwd(qkv, w, need_attn, cls=None):
     n = qkv.shape[0]
     dev = qkv.device
     f32 = dict(device=dev, dtype=torch.float32)
@@ -2550,7 +2573,9 @@ def _tm_fwd(qkv, w, need_attn: bool):
     rc = _lib.lib().mil_tm_resconv(_p(qkv), _p(w), n, _p(O), _stream())
     _lib.check(rc, "mil_tm_resconv")
     attn = None
-    if need_attn:           # A1 Z A3 [8, n_pad, n_pad] (nystrom_attention return_attn), forward only
+    if need_attn == "cls":  # the cls row of that map folded onto the patches, [8, s^2]: no map is formed
+        attn = tm_cls_attention(A1, Z, A3, **cls)
+    elif need_attn:         # A1 Z A3 [8, n_pad, n_pad] (nystrom_attention return_attn), forward only
         T = tm_bgemm(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
         attn = tm_bgemm(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
     saved = (qL, kL, A1, A2, A3, W, U, Z, scale, arg, Zs, Xs, T2s, T3s)
@@ -2612,12 +2637,12 @@ def _tm_bwd(dO, qkv, w, saved):
 
 class _NystromCore(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, w, need_attn: bool):
+    def forward(ctx, qkv, w, need_attn, cls=None):
         qkv = _f32c(qkv, "qkv")
         w = _f32c(w, "res_conv.weight")
         if qkv.shape[1] != 3 * TM_D or qkv.shape[0] % TM_M or w.numel() != TM_H * TM_CONV:
             raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
-        O, attn, saved = _tm_fwd(qkv, w, need_attn)
+        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls)
         ctx.saved = saved
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
@@ -2630,10 +2655,18 @@ class _NystromCore(torch.autograd.Function):
         qkv, w = ctx.saved_tensors
         dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved)
         ctx.saved = None
-        return dqkv, dw.reshape(ctx.w_shape), None
+        return dqkv, dw.reshape(ctx.w_shape), None, None
 
 
-def nystrom_core(qkv, w, need_attn: bool = False):
+def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0):
     """qkv [n_pad, 1536] (to_qkv of the front-zero-padded rows, n_pad % 256 == 0), w = res_conv.weight [8, 1, 33, 1] ->
-    (out [n_pad, 512] merged heads before to_out, attn [8, n_pad, n_pad] or None)."""
-    return _NystromCore.apply(qkv, w, need_attn)
+    (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
+    [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
+    as keywords: pad, s and the length as n or as len_dev (+ bag).  attn carries no gradient in any mode."""
+    if isinstance(need_attn, bool):
+        return _NystromCore.apply(qkv, w, need_attn, None)
+    if not (isinstance(need_attn, str) and need_attn == "cls"):
+        raise ValueError(f"nystrom_core: need_attn must be False, True or 'cls', got {need_attn!r}")
+    if pad is None or s is None or (n is None) == (len_dev is None):
+        raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
+    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)))

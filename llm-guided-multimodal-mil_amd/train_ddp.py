@@ -42,6 +42,15 @@ def build_model(args):
     if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
             and getattr(args, "transmil_graph", 0)):
         model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward
+    save = getattr(args, "save_patch_attn", "") or ""
+    if save:
+        if args.variant != "image_only" or getattr(args, "model_pathology", "ABMIL") != "TransMIL":
+            raise ValueError("--save_patch_attn needs --variant image_only --model_pathology TransMIL")
+        names = None
+        if getattr(args, "path_data_pathology", ""):          # on-disk cohort: the files carry the bag keys, in test order
+            from .dataset import load_cohort
+            names = list(load_cohort(args, "test", 1)[0].keys)
+        model.save_patch_attn_to(save, names)
     return model
 
 

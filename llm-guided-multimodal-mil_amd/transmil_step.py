@@ -108,12 +108,15 @@ class RaggedTransMILStepper:
             for pair in m.extractor_pathology.last_bits:
                 out += list(pair)
             out.append(m.last_mbits)
+        if getattr(m, "patch_attn", False):               # [8, s_b^2] per layer and bag, zeros behind the length on the device
+            out += list(m.last_patch_attn[0]) + list(m.last_patch_attn[1])
         return tuple(out)
 
     def step(self, slot, lengths: Sequence[int], on_device: bool = False):
         """One step on the bags packed at the front of slot.x.  on_device: the lengths already sit in slot.len_dev (the
-        cohort's feed launch wrote them); otherwise they are copied there.  Returns (loss, prob); slot.last holds h, logits
-        and, in train mode, the keep bits - static tensors of the key's graph once it replays."""
+        cohort's feed launch wrote them); otherwise they are copied there.  Returns (loss, prob); slot.last holds h, logits,
+        in train mode the keep bits and, when model.patch_attn is set, patch_attn = [a0, a1] (per layer one [8, s_b^2] tensor per
+        bag, zeros from the bag's length on) - static tensors of the key's graph once it replays."""
         lengths = [int(n) for n in lengths]
         if tuple(bucket_side(n) for n in lengths) != slot.sides:
             raise ValueError(f"RaggedTransMILStepper: lengths {lengths} do not belong to the slot of sides {slot.sides}")
@@ -121,7 +124,9 @@ class RaggedTransMILStepper:
             slot.len_dev.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=True)
         m = self.model
         training = bool(m.training)
-        key = ("transmil-sides", slot.sides, training, self.backward)
+        attn = bool(getattr(m, "patch_attn", False))
+        # a graph captured without the attention outputs is never replayed for a request with them, and the other way round
+        key = ("transmil-sides", slot.sides, training, self.backward) + (("patch_attn",) if attn else ())
         body = lambda: self._body(slot)      # noqa: E731
         ctr = m.extractor_pathology._drop_ctr
         # the warm-up passes in front of a capture draw masks too: the pass counter goes back, so the stream of a replayed
@@ -137,7 +142,9 @@ class RaggedTransMILStepper:
             self.graph_bytes[key], self._pool_seen = now - self._pool_seen, now
         if self.opt is not None and not in_graph:
             self.opt.step()
-        slot.last = dict(h=out[2], logits=out[3], bits=list(out[4:]) if training else None)
+        na = 2 * self.B if attn else 0
+        slot.last = dict(h=out[2], logits=out[3], bits=list(out[4:len(out) - na]) if training else None,
+                         patch_attn=[list(out[len(out) - na:len(out) - self.B]), list(out[len(out) - self.B:])] if attn else None)
         return out[0], out[1]
 
     def pool_bytes(self) -> int:

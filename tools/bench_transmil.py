@@ -8,7 +8,9 @@ lengths, as train_ddp.py's autograd path runs it - next to the same step replaye
 (transmil_step.RaggedTransMILStepper): same bag, same region count, same process; the spread of the eager regions and the
 memory of the graph's pool are reported with it.
 --ragged K: K bags drawn from U[2000, 15592] in turn through the stepper: ms/step, replay / eager counts, eager steps after a
-key's second visit (must be 0), graphs, the memory of their shared pool and the free memory the whole run took."""
+key's second visit (must be 0), graphs, the memory of their shared pool and the free memory the whole run took.
+--attn cls: per N, the eval forward without attention and with the per-patch cls attention (need_attn="cls"), and the peak
+allocated bytes of both, in one process."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -132,6 +134,35 @@ def ragged_run(a, dev, args):
                           largest_capture_mib=round(max(st.graph_bytes.values(), default=0) / 2 ** 20, 1))), flush=True)
 
 
+def attn_rows(a, dev, args):
+    """Per N, in one process: the eval forward (no grad) of the extractor without attention and with need_attn="cls", the
+    median of --reps regions each with the spread of the plain one, and the peak allocated bytes of one forward of each."""
+    torch.manual_seed(1234)
+    net = get_model(args).to(dev).eval().extractor_pathology
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    for N in a.N:
+        x = syn.make_bags(N, 1, N, 768)[0].to(dev)
+        run = {want: (lambda want=want: net(x, [N], need_attn=want)) for want in (False, "cls")}
+        res = dict(N=N, n_pad=geometry(N)["n_pad"])
+        with torch.no_grad():
+            for want, tag in ((False, "fwd"), ("cls", "fwd_cls"), (False, "fwd_again")):
+                ts = region_times(run[want], a.reps, a.warmup)
+                res.update({tag + "_ms": round(med(ts), 3), tag + "_min_ms": round(min(ts), 3), tag + "_max_ms": round(max(ts), 3)})
+            for want, tag in ((False, "fwd"), ("cls", "fwd_cls")):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                out = run[want]()
+                torch.cuda.synchronize()
+                res[tag + "_peak_mib"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 3)
+                del out
+        res["cls_cost_pct"] = round(100.0 * (res["fwd_cls_ms"] - res["fwd_ms"]) / res["fwd_ms"], 2)
+        res["full_map_mib_per_layer"] = round(8 * res["n_pad"] ** 2 * 4 / 2 ** 20, 1)
+        print(json.dumps(res), flush=True)
+        del x
+        torch.cuda.empty_cache()
+
+
 def region_times(fn, reps, warm):
     for _ in range(warm):
         fn()
@@ -156,10 +187,15 @@ def main():
     ap.add_argument("--graph", action="store_true", help="training step per N: eager next to the replayed hipGraph")
     ap.add_argument("--ragged", type=int, default=0, help="K bags from U[2000, 15592] in turn through the graph stepper")
     ap.add_argument("--max_graphs", type=int, default=0, help="--ragged: the stepper's graph cap (0 = its default)")
+    ap.add_argument("--attn", choices=["cls"], default=None, help="eval forward per N with and without the per-patch cls "
+                    "attention (need_attn='cls'): ms and peak allocated bytes of both")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
     args = SimpleNamespace(modality=["pathology"], model_pathology="TransMIL", num_classes=2, patch_dim=768, variant="image_only")
+    if a.attn:
+        attn_rows(a, dev, args)
+        return
     if a.graph or a.ragged:
         if a.graph:
             graph_rows(a, dev, args)
