@@ -574,7 +574,10 @@ int mil_attn_rows_bwd_general(const float* q, const float* k, const float* v, co
                               float* workspace, void* stream);
 /* "pool" form: <= 16 queries per bag over many keys (token->image attention: an H-head attention pool over
  * the patches).  tile_map int32 [ntiles][3] = {bag, key0, nkeys <= 64}, bag_tile_off [B+1].
- * forward workspace: ntiles * 16 * (H*C + 2*H) floats; backward workspace: ntiles * 16 * H*C floats. */
+ * forward workspace: ntiles * 16 * (H*C + 2*H) floats; backward workspace: ntiles * 16 * H*C floats.
+ * Zero keys: a bag whose tile range is empty gives o = 0, lse = -inf and dq = 0 (the rows form likewise: o = 0, lse = -inf
+ * for a bag without keys).  A tile {bag, key0, 0} - the padding of a capacity bucket - reads row key0 at most, never a row in
+ * front of it, leaves the partial (m = -inf, l = 0, acc = 0), and adds nothing to a bag that has another, non-empty tile. */
 int mil_attn_pool_fwd_mh(const float* q, const float* k, const float* v, const int32_t* q_off,
                          const int32_t* tile_map, const int32_t* bag_tile_off, int ntiles, int B, int Tmax, int H,
                          int C, float* o, float* lse, float* workspace, void* stream);
@@ -653,7 +656,8 @@ int mil_value_proj(const float* pooled, const float* Wv, const float* bv, int B,
 int mil_value_proj_pad(const float* pooled, const float* Wv, const float* bv, int B, int H, int C, int E, int T, int THp,
                        float* o, void* stream);
 /* Fewer launches on the token-side chain (each dependent launch costs ~4 us whatever it computes):
- *   mil_absorbed_pool_value_fwd   mil_absorbed_pool_fwd whose merge launch also forms o = Wv pooled + bv [B, H C]
+ *   mil_absorbed_pool_value_fwd   mil_absorbed_pool_fwd whose merge launch also forms o = Wv pooled + bv [B, H C]; pooled and
+ *                                 lse are bit-identical to mil_absorbed_pool_fwd's (one merge kernel serves both)
  *   mil_value_proj_bwd            dpooled [B, H, E], dWv [H C, E], dbv [H C] (nullable) from do [B, H C] in one launch
  * (mil_absorb_query_bwd likewise runs both of its halves in one launch when both are requested). */
 int mil_absorbed_pool_value_fwd(const float* keys, const float* pe, const float* Qp, const int32_t* k_off,

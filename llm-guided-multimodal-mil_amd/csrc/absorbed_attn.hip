@@ -11,7 +11,7 @@
 //
 // Kernels (E = 512 = 64 lanes x 8, H <= 8, head dim c, rows tiled 64 per workgroup, split-N partials + merge):
 //   k_absorb_query / _bwd     Qp[b][h][:] = sum_c qp[b][hc + c'] Wk[hc + c'][:]
-//   k_apool_partial / _merge  online-softmax pool of the keys under H absorbed queries
+//   k_apool_partial / _merge_value  online-softmax pool of the keys under H absorbed queries
 //   k_apool_dots / _bwd_apply per row: recompute a_h[n] (MFMA dots); dkeys, and per-tile partial of dQp
 //   k_value_proj / _bwd       o[b][hc + c'] = Wv[hc + c'] . pooled[b][h] + bv
 #include "mil_common.h"
@@ -315,54 +315,6 @@ __global__ __launch_bounds__(256, 2) void k_apool_partial(const float* __restric
             pml[((size_t)g * AP_H + lane) * 2 + 1] = (lh_lds[0][lane] + lh_lds[1][lane]) + (lh_lds[2][lane] + lh_lds[3][lane]);
         }
     }
-}
-
-// merge over a bag's tiles: pooled[b][h][:], lse[b][h].   grid (B, H), block E/4 threads
-__global__ void k_apool_merge(const float* __restrict__ pacc, const float* __restrict__ pml,
-                              const int32_t* __restrict__ bag_tile_off, int E, float* __restrict__ pooled,
-                              float* __restrict__ lse) {
-    const int b = blockIdx.x, h = blockIdx.y, j4 = threadIdx.x;
-    const int g0 = bag_tile_off[b], g1 = bag_tile_off[b + 1];
-    float m = -INFINITY;
-    {
-        int g = g0;
-        for (; g + 8 <= g1; g += 8) {                 // eight loads in flight per pass: the merge is pure latency
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = pml[((size_t)(g + u) * AP_H + h) * 2];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) m = fmaxf(m, t[u]);
-        }
-        for (; g < g1; ++g) m = fmaxf(m, pml[((size_t)g * AP_H + h) * 2]);
-    }
-    float l = 0.f;
-    f32x4 acc = {0, 0, 0, 0};
-    {
-        int g = g0;
-        for (; g + 8 <= g1; g += 8) {
-            float2 ml[8];
-            f32x4 t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                ml[u] = *reinterpret_cast<const float2*>(pml + ((size_t)(g + u) * AP_H + h) * 2);
-                t[u] = *reinterpret_cast<const f32x4*>(pacc + ((size_t)(g + u) * AP_H + h) * E + 4 * j4);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float sc = __expf(ml[u].x - m);
-                l += sc * ml[u].y;
-                acc += sc * t[u];
-            }
-        }
-        for (; g < g1; ++g) {
-            const float sc = __expf(pml[((size_t)g * AP_H + h) * 2] - m);
-            l += sc * pml[((size_t)g * AP_H + h) * 2 + 1];
-            acc += sc * *reinterpret_cast<const f32x4*>(pacc + ((size_t)g * AP_H + h) * E + 4 * j4);
-        }
-    }
-    const float inv = g1 > g0 ? 1.0f / l : 0.f;
-    *reinterpret_cast<f32x4*>(pooled + ((size_t)b * AP_H + h) * E + 4 * j4) = acc * inv;
-    if (j4 == 0) lse[b * AP_H + h] = g1 > g0 ? m + logf(l) : -INFINITY;
 }
 
 // ---------------------------------------------------------------------------------------------- absorbed pool, backward
@@ -1165,12 +1117,15 @@ __global__ __launch_bounds__(512) void k_value_proj_bwd(const float* __restrict_
         }
 }
 
-// k_apool_merge followed by k_value_proj in one launch: grid (B, H), 1024 threads = 8 groups x E / 4 column threads.
+// The merge over a bag's tiles (pooled[b][h][:], lse[b][h]), VALUE: followed by k_value_proj in the same launch: grid (B, H),
+// 1024 threads = 8 groups x E / 4 column threads.  mil_absorbed_pool_fwd launches VALUE = false, so both forwards add the tile
+// partials in the same order and their pooled / lse are bit-identical (a merge in tile order was not, from two tiles on).
 // Group q merges the bag's tiles g0 + q, g0 + q + 8, ... against the bag-wide maximum (formed first by all threads), the
 // eight partial sums are folded through LDS in group order; pooled[b][h] goes to global memory (the backward needs it) and
 // stays in LDS for the head's C outputs of the value projection (first 256 threads).  With ONE long bag per batch (the
 // authors' regime: ~200 tiles) the single-group form walked every tile in turn: 31 us per attention site.
 #define AMV_G 8
+template <bool VALUE>
 __global__ __launch_bounds__(1024) void k_apool_merge_value(const float* __restrict__ pacc, const float* __restrict__ pml,
                                                             const int32_t* __restrict__ bag_tile_off, int E,
                                                             float* __restrict__ pooled, float* __restrict__ lse,
@@ -1185,7 +1140,7 @@ __global__ __launch_bounds__(1024) void k_apool_merge_value(const float* __restr
     // requested now, they arrive under the merge - behind the last barrier they were four more round trips
     const int per = 256 / C, vc = (tid & 255) / per, vpart = (tid & 255) % per;
     f32x4 wvr[16];                                             // C = 32: 16 pieces of 16 bytes per thread, C = 64: 8
-    if (tid < 256) {
+    if (VALUE && tid < 256) {
         const float* w = Wv + (size_t)(h * C + vc) * E;
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
@@ -1240,6 +1195,7 @@ __global__ __launch_bounds__(1024) void k_apool_merge_value(const float* __restr
         if (j4 == 0) lse[b * AP_H + h] = g1 > g0 ? m + logf(lt) : -INFINITY;
         *reinterpret_cast<f32x4*>(&pl[0][4 * j4]) = v;
     }
+    if (!VALUE) return;
     __syncthreads();
     if (tid >= 256) return;
     const int c = vc, part = vpart;
@@ -1607,7 +1563,8 @@ extern "C" int mil_absorbed_pool_fwd(const float* keys, const float* pe, const f
                            LnbrFwd{});
         MIL_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_apool_merge, dim3(B, AP_H), dim3(E / 4), 0, st, pacc, pml, bag_tile_off, E, pooled, lse);
+    hipLaunchKernelGGL(k_apool_merge_value<false>, dim3(B, AP_H), dim3(1024), 0, st, pacc, pml, bag_tile_off, E, pooled, lse,
+                       (const float*)nullptr, (const float*)nullptr, C, (float*)nullptr);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
@@ -1630,7 +1587,7 @@ extern "C" int mil_absorbed_pool_value_fwd(const float* keys, const float* pe, c
                            LnbrFwd{});
         MIL_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_apool_merge_value, dim3(B, AP_H), dim3(1024), 0, st, pacc, pml, bag_tile_off, E, pooled, lse, Wv, bv, C, o);
+    hipLaunchKernelGGL(k_apool_merge_value<true>, dim3(B, AP_H), dim3(1024), 0, st, pacc, pml, bag_tile_off, E, pooled, lse, Wv, bv, C, o);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
@@ -1700,7 +1657,7 @@ extern "C" int mil_lnbr_absorbed_pool_value_fwd(const float* x, const float* o, 
                            pacc, pml, LnbrFwd{x, o, gamma, beta, eps, y, stats});
         MIL_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_apool_merge_value, dim3(B, AP_H), dim3(1024), 0, st, pacc, pml, bag_tile_off, E, pooled, lse, Wv, bv, C,
+    hipLaunchKernelGGL(k_apool_merge_value<true>, dim3(B, AP_H), dim3(1024), 0, st, pacc, pml, bag_tile_off, E, pooled, lse, Wv, bv, C,
                        o_attn);
     MIL_CHECK_LAUNCH();
     return MIL_OK;

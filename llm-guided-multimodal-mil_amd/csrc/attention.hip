@@ -312,7 +312,7 @@ __global__ __launch_bounds__(512) void k_attn_pool_fwd_lds(const float* __restri
     for (int pr = tid; pr < 64 * H; pr += I) {
         const int n = pr & 63, h = pr >> 6;
         f32x4 kr[C / 4];
-        const float* krow = k + (size_t)(key0 + min(n, nkeys - 1)) * I + h * C;
+        const float* krow = k + (size_t)(key0 + max(min(n, nkeys - 1), 0)) * I + h * C;     // nkeys == 0 (a padding tile): row key0, unused
 #pragma unroll
         for (int c = 0; c < C / 4; ++c) kr[c] = *reinterpret_cast<const f32x4*>(krow + 4 * c);
         for (int t = 0; t < T; ++t) {
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(512) void k_attn_pool_bwd_lds(const float* __restri
     for (int pr = tid; pr < 64 * H; pr += I) {
         const int n = pr & 63, h = pr >> 6;
         f32x4 kr[C / 4], vr[C / 4];
-        const size_t rowoff = (size_t)(key0 + min(n, nkeys - 1)) * I + h * C;
+        const size_t rowoff = (size_t)(key0 + max(min(n, nkeys - 1), 0)) * I + h * C;       // nkeys == 0: row key0, weight 0
 #pragma unroll
         for (int c = 0; c < C / 4; ++c) {
             kr[c] = *reinterpret_cast<const f32x4*>(k + rowoff + 4 * c);
