@@ -188,6 +188,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_ppeg_bwd": (c_int, [_P, _P, c_int] + [_P] * 6 + [_P]),
     "mil_tm_cls_attn": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
 }
+# entries that return a value, not a status: checked() leaves them without an errcheck
+VALUE_RETURNING = frozenset(n for n, (res, _) in SIGNATURES.items() if res is c_size_t) | frozenset((
+    "mil_abi_version", "mil_gemm_nt2_ok", "mil_gemm_tn2_ok", "mil_gemm_tn2_splits", "mil_layernorm_bwd_blocks",
+    "mil_layernorm_bagrow_rows_per_block"))
 
 STAGE_DROPBITS, STAGE_GATE_FWD, STAGE_POOL, STAGE_TAIL, STAGE_GATE_BWD, STAGE_REDUCE, STAGE_ADAM = 1, 2, 4, 8, 16, 32, 64
 STAGE_TILEMAP = 0x80
@@ -243,6 +247,7 @@ class ImageOnlyStep(ctypes.Structure):
 
 
 _lib = None
+_checked = _checked_of = None      # checked(): the errcheck handle and the raw one it mirrors
 
 
 class MilHipError(RuntimeError):
@@ -278,6 +283,30 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+def _raise_on_status(result, func, args):
+    if result != 0:             # check() tests it too; not calling it keeps a successful launch at one Python frame
+        check(result, func.__name__)
+    return result
+
+
+def checked() -> ctypes.CDLL:
+    """A second handle on the library lib() holds, whose status-returning entries raise MilHipError themselves (ctypes
+    errcheck): a call site is one line and cannot forget the check.  ctypes keeps its function objects per CDLL instance, so
+    lib() still returns raw codes.  It follows `_lib`: the kernel benchmarks under tools/ swap that for a variant build."""
+    global _checked, _checked_of
+    if _checked_of is not _lib or _lib is None:
+        raw = lib()                                   # first: it validates the path and the ABI
+        handle = ctypes.CDLL(raw._name, mode=ctypes.RTLD_GLOBAL)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+            if name not in VALUE_RETURNING:
+                fn.errcheck = _raise_on_status
+        _checked, _checked_of = handle, raw
+    return _checked
+
+
 SHIM_DIR = os.path.join(_HERE, "csrc", "shim_build")
 SHIM_SRC = os.path.join(_HERE, "csrc", "torch_shim.cpp")
 _shim = False
@@ -294,8 +323,8 @@ def build_shim(verbose: bool = False):
 
 def shim():
     """The torch cpp_extension binding of the token-side entries (csrc/torch_shim.cpp) when MIL_TORCH_SHIM=1 and it has been
-    built, else None: ops.py then reaches the same C functions through ctypes.  Opt-in because it measured no faster: the
-    eager fusion step (32 bags x 1024 x 768) takes 3.01 ms through it and 2.91 ms through ctypes - what the host spends per
+    built, else None: the ops package then reaches the same C functions through ctypes.  Opt-in because it measured no faster:
+    the eager fusion step (32 bags x 1024 x 768) takes 3.01 ms through it and 2.91 ms through ctypes - what the host spends per
     launch is autograd-node bookkeeping, not argument marshalling."""
     global _shim
     if _shim is False:

@@ -182,9 +182,8 @@ def upload_lengths(dst: torch.Tensor, lengths) -> None:
         import ctypes
         from . import _lib
         arr = (ctypes.c_int32 * n)(*lengths)
-        rc = _lib.lib().mil_set_i32(ctypes.c_void_p(dst.data_ptr()), arr, n,
-                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "mil_set_i32")
+        _lib.checked().mil_set_i32(ctypes.c_void_p(dst.data_ptr()), arr, n,
+                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     else:
         dst.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=True)
 

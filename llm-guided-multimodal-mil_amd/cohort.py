@@ -118,10 +118,9 @@ class DeviceCohort:
         if not augment or all(k == n for k, n in zip(self.k_train, self.n)):
             self.epoch = None
             return self
-        rc = _lib.lib().mil_patch_drop_select(_p(self.row_off_dev), _p(self.keep_dev), _p(self.sel_off_dev), self.nb, 0,
-                                              ctypes.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF), ctypes.c_uint64(int(epoch)),
-                                              _p(self.sel), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "mil_patch_drop_select")
+        _lib.checked().mil_patch_drop_select(_p(self.row_off_dev), _p(self.keep_dev), _p(self.sel_off_dev), self.nb, 0,
+                                             ctypes.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF), ctypes.c_uint64(int(epoch)),
+                                             _p(self.sel), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         self.epoch = int(epoch)
         return self
 
@@ -167,8 +166,7 @@ class DeviceCohort:
             for a, (tab, dst) in enumerate(aux):
                 d.aux_table[a], d.aux_dst[a] = tab.data_ptr(), dst.data_ptr()
                 d.aux_words[a] = tab[0].numel() * tab.element_size() // 4
-            rc = _lib.lib().mil_cohort_feed(_p(self.x), sel, ctypes.byref(d), _p(x_dst), _p(len_dev), stream)
-            _lib.check(rc, "mil_cohort_feed")
+            _lib.checked().mil_cohort_feed(_p(self.x), sel, ctypes.byref(d), _p(x_dst), _p(len_dev), stream)
             row0 += sum(kp)
         return ks
 
@@ -246,14 +244,13 @@ class HostFeed:
         sel = None
         if epoch is not None and k < n:
             vals = (ctypes.c_int32 * 2)(0, n)
-            _lib.check(_lib.lib().mil_set_i32(_p(tab["row_off"]), vals, 2, stream), "mil_set_i32")
+            _lib.checked().mil_set_i32(_p(tab["row_off"]), vals, 2, stream)
             vals = (ctypes.c_int32 * 1)(k)
-            _lib.check(_lib.lib().mil_set_i32(_p(tab["keep"]), vals, 1, stream), "mil_set_i32")
+            _lib.checked().mil_set_i32(_p(tab["keep"]), vals, 1, stream)
             # a one-bag table for cohort bag j (bag0 = j): the subset the resident cohort would draw for it
-            rc = _lib.lib().mil_patch_drop_select(_p(tab["row_off"]), _p(tab["keep"]), _p(tab["out_off"]), 1, j,
-                                                  ctypes.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF),
-                                                  ctypes.c_uint64(int(epoch)), _p(tab["sel"]), stream)
-            _lib.check(rc, "mil_patch_drop_select")
+            _lib.checked().mil_patch_drop_select(_p(tab["row_off"]), _p(tab["keep"]), _p(tab["out_off"]), 1, j,
+                                                 ctypes.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF),
+                                                 ctypes.c_uint64(int(epoch)), _p(tab["sel"]), stream)
             sel = _p(tab["sel"])
         d = _lib.CohortFeedDesc()
         d.struct_bytes = ctypes.sizeof(_lib.CohortFeedDesc)
@@ -265,8 +262,7 @@ class HostFeed:
         d.naux = len(aux)
         for a, (t_, dst) in enumerate(aux):
             d.aux_table[a], d.aux_dst[a], d.aux_words[a] = t_.data_ptr(), dst.data_ptr(), t_[0].numel() * t_.element_size() // 4
-        _lib.check(_lib.lib().mil_cohort_feed(_p(self.stage[s]), sel, ctypes.byref(d), _p(x_dst), _p(len_dev), stream),
-                   "mil_cohort_feed")
+        _lib.checked().mil_cohort_feed(_p(self.stage[s]), sel, ctypes.byref(d), _p(x_dst), _p(len_dev), stream)
         self.consumed[s].record(cur)
         self._used[s] = True
         return k

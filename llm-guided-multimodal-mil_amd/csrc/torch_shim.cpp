@@ -4,7 +4,7 @@
 // the token-side chain of the fusion step calls ~100 times per step, where a ctypes call (14 boxed arguments) costs more
 // host time than the launch: tensors come in as at::Tensor, the stream as the integer torch.cuda.current_stream().cuda_stream.
 // No kernels, no HIP headers, no torch types inside libmil_hip.so; built by __graft_entry__.build() into
-// csrc/shim_build/mil_torch_shim.so.  Without it ops.py uses ctypes - the same C functions either way.
+// csrc/shim_build/mil_torch_shim.so.  Without it the ops package uses ctypes - the same C functions either way.
 #include <torch/extension.h>
 #include <cstdint>
 

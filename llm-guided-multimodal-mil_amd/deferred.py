@@ -46,8 +46,7 @@ def flush_pending() -> None:
             d.dW, d.db = (dW.data_ptr() if dW is not None else None), (db.data_ptr() if db is not None else None)
             d.lddy, d.ldyv, d.ldx = dy.stride(0), (yv.stride(0) if yv is not None else 0), x.stride(0)
             d.lddw, d.act, d.M, d.N, d.K = x.shape[1], int(act), M, N, x.shape[1]
-        rc = _lib.lib().mil_linear_small_dw_grouped(arr, len(chunk), stream)
-        _lib.check(rc, "mil_linear_small_dw_grouped")
+        _lib.checked().mil_linear_small_dw_grouped(arr, len(chunk), stream)
     _queue.clear()
 
 

@@ -1,0 +1,279 @@
+"""TransMIL: Nystrom attention, PPEG and the sequence assembly (csrc/transmil.hip)."""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from .. import _lib
+from ._base import _f32c, _p, _stream
+
+
+# Nystrom attention of one bag (nystrom_attention: 8 heads x 64, 256 landmarks, 6 pseudo-inverse iterations, 33-tap residual
+# conv on v) on the [n_pad, 1536] to_qkv rows of its front-zero-padded LayerNorm output; PPEG; the row gather of the
+# sequence assembly.  Every product runs on mil_tm_bgemm, reading per-head operands in place out of the merged rows.
+TM_H, TM_DH, TM_D, TM_M, TM_CONV, TM_PINV_ITERS = 8, 64, 512, 256, 33, 6
+TM_QSCALE = TM_DH ** -0.5
+
+
+def _tm_splits(M: int, N: int, batch: int, K: int) -> int:
+    tiles = -(-M // 64) * -(-N // 64) * batch
+    if tiles >= 256 or K < 512:
+        return 1
+    return max(1, min(K // 256, 512 // tiles))
+
+
+def tm_bgemm(A, sA, B, sB, C, sC, batch: int, M: int, N: int, K: int, alpha: float = 1.0, beta: float = 0.0,
+             diag: float = 0.0, D=None, split: bool = True):
+    """C[b] = alpha A[b] B[b] + beta D[b] (D = C if None) + diag I over general strides (sA = (batch, row, k) etc., in floats);
+    A, B, C, D are tensors or views whose data_ptr is element (0, 0) of batch 0 (mil_tm_bgemm)."""
+    splits = _tm_splits(M, N, batch, K) if (split and D is None and diag == 0.0 and beta in (0.0, 1.0)) else 1
+    if splits > 1 and beta == 0.0:
+        C.zero_()
+        beta = 1.0
+    _lib.checked().mil_tm_bgemm(_p(A), *sA, _p(B), *sB, _p(C), *sC, _p(D), batch, M, N, K, float(alpha), float(beta),
+                                float(diag), splits, _stream())
+    return C
+
+
+def tm_softmax_rows(x):
+    _lib.checked().mil_tm_softmax_rows(_p(x), x.numel() // x.shape[-1], x.shape[-1], _stream())
+    return x
+
+
+def tm_softmax_rows_bwd(p, dp):
+    _lib.checked().mil_tm_softmax_rows_bwd(_p(p), _p(dp), p.numel() // p.shape[-1], p.shape[-1], _stream())
+    return dp
+
+
+class _TmRowGather(torch.autograd.Function):
+    """dst[r] = src[idx[r]] (idx >= 0) / extra (idx == -2) / 0 (idx == -1); repeated rows add their gradients."""
+
+    @staticmethod
+    def forward(ctx, src, extra, idx):
+        src = _f32c(src, "src")
+        E = src.shape[1]
+        dst = torch.empty((idx.numel(), E), device=src.device, dtype=torch.float32)
+        ex = _f32c(extra, "extra").reshape(-1) if extra is not None else None
+        _lib.checked().mil_tm_row_gather(_p(src), _p(ex), _p(idx), idx.numel(), E, _p(dst), _stream())
+        ctx.save_for_backward(idx)
+        ctx.src_rows, ctx.has_extra = src.shape[0], extra is not None
+        ctx.extra_shape = extra.shape if extra is not None else None
+        return dst
+
+    @staticmethod
+    def backward(ctx, ddst):
+        (idx,) = ctx.saved_tensors
+        ddst = _f32c(ddst, "ddst")
+        E = ddst.shape[1]
+        dsrc = torch.zeros((ctx.src_rows, E), device=ddst.device, dtype=torch.float32)
+        dex = torch.zeros(E, device=ddst.device, dtype=torch.float32) if ctx.has_extra else None
+        _lib.checked().mil_tm_row_gather_bwd(_p(ddst), _p(idx), idx.numel(), E, _p(dsrc), _p(dex), _stream())
+        return dsrc, (dex.reshape(ctx.extra_shape) if dex is not None else None), None
+
+
+def tm_row_gather(src, extra, idx):
+    """idx: device int32 [rows] (model/dim1/TransMIL.py builds it per bag on the host)."""
+    return _TmRowGather.apply(src, extra, idx)
+
+
+def tm_seq_index(len_dev, sides, idx_out, rows_dev=None, flag=None, x_tail=None):
+    """idx_out (device int32, at least sum(1 + s^2) entries) <- tm_row_gather's index of the sequence assembly, from the bag
+    lengths on the device (len_dev int32 [B]) and the bags' grid sides (host ints: the launch shape); rows_dev [1] <- the
+    sum of the lengths; flag [1] <- 1 if a length lies outside its side's bucket (it is clamped, nothing is written out of
+    range); x_tail [rows >= sum(s^2), L]: its rows behind the bags are zeroed.  One launch (two with x_tail), no host sync."""
+    sides = [int(s) for s in sides]
+    arr = (ctypes.c_int32 * len(sides))(*sides)
+    if x_tail is not None and (x_tail.dtype != torch.float32 or not x_tail.is_contiguous()):
+        raise _lib.MilHipError("tm_seq_index: x_tail must be a contiguous float32 tensor")
+    _lib.checked().mil_tm_seq_index(_p(len_dev), len(sides), arr, _p(idx_out), idx_out.numel(), _p(rows_dev), _p(flag),
+                                    _p(x_tail), x_tail.shape[0] if x_tail is not None else 0,
+                                    x_tail.shape[1] if x_tail is not None else 0, _stream())
+    return idx_out
+
+
+class _TmPPEG(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, s: int, W7, b7, W5, b5, W3, b3):
+        x = _f32c(x, "x")
+        W7, W5, W3 = _f32c(W7, "W7"), _f32c(W5, "W5"), _f32c(W3, "W3")
+        y = torch.empty_like(x)
+        _lib.checked().mil_tm_ppeg_fwd(_p(x), s, _p(W7), _p(_f32c(b7, "b7")), _p(W5), _p(_f32c(b5, "b5")), _p(W3),
+                                       _p(_f32c(b3, "b3")), _p(y), _stream())
+        ctx.save_for_backward(x, W7, W5, W3)
+        ctx.s = s
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W7, W5, W3 = ctx.saved_tensors
+        dy = _f32c(dy, "dy")
+        dx = torch.empty_like(x)
+        dWf = torch.zeros((TM_D, 1, 7, 7), device=x.device, dtype=torch.float32)
+        db = torch.zeros(TM_D, device=x.device, dtype=torch.float32)
+        _lib.checked().mil_tm_ppeg_bwd(_p(dy), _p(x), ctx.s, _p(W7), _p(W5), _p(W3), _p(dx), _p(dWf), _p(db), _stream())
+        # one 7 x 7 correlation map: dW7 is all of it, dW5 / dW3 its central 5 x 5 / 3 x 3; the three biases share db
+        return (dx, None, dWf, db, dWf[:, :, 1:6, 1:6].contiguous(), db.clone(), dWf[:, :, 2:5, 2:5].contiguous(), db.clone())
+
+
+def tm_ppeg(x, s: int, W7, b7, W5, b5, W3, b3):
+    """PPEG (TransMIL.py:32-47) on one bag's [1 + s^2, 512] rows: cls passed through, the s x s grid through the folded
+    depthwise 7 x 7."""
+    return _TmPPEG.apply(x, s, W7, b7, W5, b5, W3, b3)
+
+
+def tm_cls_attention(A1, Z, A3, pad: int, s: int, n=None, len_dev=None, bag: int = 0):
+    """Per-patch attention of the cls token out of the Nystrom factors, without the [8, n_pad, n_pad] map (mil_tm_cls_attn):
+    A1 [8, n_pad, 256] and A3 [8, 256, n_pad] softmaxed, Z [8, 256, 256] as _tm_fwd holds them, pad = n_pad - s^2 - 1 the cls
+    row.  With P = A1 Z A3: out[h, i] = P[h, pad, pad + 1 + i] + (i < s^2 - N ? P[h, pad, pad + 1 + N + i] : 0) for i < N - a
+    patch the square padding repeats gets the sum of its two keys - and 0 for N <= i < s^2; not renormalised (the Nystrom
+    approximation can go negative).  N is the host int `n`, or len_dev[bag] read on the device (clamped into the side's
+    bucket) for a replayed step.  Returns [8, s^2] fp32; 8 x 256 floats of workspace, two launches, no host sync."""
+    if (n is None) == (len_dev is None):
+        raise ValueError("tm_cls_attention: give the bag length either as n or as len_dev (+ bag)")
+    A1, Z, A3 = _f32c(A1, "A1"), _f32c(Z, "Z"), _f32c(A3, "A3")
+    n_pad = A3.shape[-1]
+    if tuple(A1.shape) != (TM_H, n_pad, TM_M) or tuple(Z.shape) != (TM_H, TM_M, TM_M) or tuple(A3.shape) != (TM_H, TM_M, n_pad):
+        raise _lib.MilHipError(f"tm_cls_attention: A1 {tuple(A1.shape)} / Z {tuple(Z.shape)} / A3 {tuple(A3.shape)} outside the built shape")
+    if len_dev is not None and (len_dev.dtype != torch.int32 or not 0 <= int(bag) < len_dev.numel()):
+        raise _lib.MilHipError("tm_cls_attention: len_dev must be int32 and hold entry `bag`")
+    out = torch.empty((TM_H, int(s) * int(s)), device=A3.device, dtype=torch.float32)
+    t = torch.empty((TM_H, TM_M), device=A3.device, dtype=torch.float32)
+    _lib.checked().mil_tm_cls_attn(_p(A1), _p(Z), _p(A3), n_pad, int(pad), int(s), int(n) if n is not None else 0, _p(len_dev),
+                                   int(bag), _p(t), _p(out), _stream())
+    return out
+
+
+def _tm_fwd(qkv, w, need_attn, cls=None):
+    n = qkv.shape[0]
+    dev = qkv.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    H, M, DH, L3 = TM_H, TM_M, TM_DH, 3 * TM_D
+    q, k, v = qkv, qkv[:, TM_D:], qkv[:, 2 * TM_D:]
+    qL = torch.empty((H, M, DH), **f32)
+    kL = torch.empty((H, M, DH), **f32)
+    _lib.checked().mil_tm_landmarks(_p(qkv), n, TM_QSCALE, _p(qL), _p(kL), _stream())
+    A1 = torch.empty((H, n, M), **f32)
+    tm_bgemm(q, (DH, L3, 1), kL, (M * DH, 1, DH), A1, (n * M, M, 1), H, n, M, DH, alpha=TM_QSCALE)
+    A2 = torch.empty((H, M, M), **f32)
+    tm_bgemm(qL, (M * DH, DH, 1), kL, (M * DH, 1, DH), A2, (M * M, M, 1), H, M, M, DH)
+    A3 = torch.empty((H, M, n), **f32)
+    tm_bgemm(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
+    for A in (A1, A2, A3):
+        tm_softmax_rows(A)
+    W = torch.empty((H, M, DH), **f32)
+    tm_bgemm(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
+    # Newton-Schulz pseudo-inverse of A2: Z0 = A2^T / (max row sum x max column sum over the bag's 8 heads), then
+    # X = A2 Z, T2 = 15 I - X (7 I - X) = X X - 7 X + 15 I, T3 = 13 I - X T2, Z = Z T3 / 4
+    scale = torch.empty(3 + 2 * H, **f32)                       # (s, max row sum, max column sum), per-head maxima behind
+    arg = torch.empty(1 + H, device=dev, dtype=torch.int32)
+    Zs, Xs, T2s, T3s = [], [], [], []
+    Z = torch.empty((H, M, M), **f32)
+    _lib.checked().mil_tm_pinv_init(_p(A2), _p(scale), _p(arg), _p(Z), _stream())
+    sq = (M * M, M, 1)
+    for _ in range(TM_PINV_ITERS):
+        X = tm_bgemm(A2, sq, Z, sq, torch.empty_like(Z), sq, H, M, M, M)
+        T2 = tm_bgemm(X, sq, X, sq, torch.empty_like(Z), sq, H, M, M, M, beta=-7.0, diag=15.0, D=X)
+        T3 = tm_bgemm(X, sq, T2, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, diag=13.0)
+        Zn = tm_bgemm(Z, sq, T3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
+        Zs.append(Z); Xs.append(X); T2s.append(T2); T3s.append(T3)
+        Z = Zn
+    U = tm_bgemm(Z, sq, W, (M * DH, DH, 1), torch.empty((H, M, DH), **f32), (M * DH, DH, 1), H, M, DH, M)
+    O = torch.empty((n, TM_D), **f32)
+    tm_bgemm(A1, (n * M, M, 1), U, (M * DH, DH, 1), O, (DH, TM_D, 1), H, n, DH, M)
+    _lib.checked().mil_tm_resconv(_p(qkv), _p(w), n, _p(O), _stream())
+    attn = None
+    if need_attn == "cls":  # the cls row of that map folded onto the patches, [8, s^2]: no map is formed
+        attn = tm_cls_attention(A1, Z, A3, **cls)
+    elif need_attn:         # A1 Z A3 [8, n_pad, n_pad] (nystrom_attention return_attn), forward only
+        T = tm_bgemm(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
+        attn = tm_bgemm(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
+    saved = (qL, kL, A1, A2, A3, W, U, Z, scale, arg, Zs, Xs, T2s, T3s)
+    return O, attn, saved
+
+
+def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s):
+    """dA2 from dZ (the gradient of the last iterate) by the reverse sweep of the six iterations and of Z0."""
+    H, M = TM_H, TM_M
+    sq = (M * M, M, 1)
+    dA2 = torch.zeros_like(A2)
+    for t in reversed(range(TM_PINV_ITERS)):
+        Z, X, T2, T3 = Zs[t], Xs[t], T2s[t], T3s[t]
+        dZ = tm_bgemm(G, sq, T3, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)      # Zn = Z T3 / 4
+        dT3 = tm_bgemm(Z, (M * M, 1, M), G, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
+        dT2 = tm_bgemm(X, (M * M, 1, M), dT3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0)   # T3 = 13 I - X T2
+        dX = tm_bgemm(dT3, sq, T2, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, beta=-7.0, D=dT2)
+        tm_bgemm(dT2, sq, X, (M * M, 1, M), dX, sq, H, M, M, M, beta=1.0)                           # T2 = X X - 7 X + 15 I
+        tm_bgemm(X, (M * M, 1, M), dT2, sq, dX, sq, H, M, M, M, beta=1.0)
+        tm_bgemm(dX, sq, Z, (M * M, 1, M), dA2, sq, H, M, M, M, beta=1.0)                           # X = A2 Z
+        tm_bgemm(A2, (M * M, 1, M), dX, sq, dZ, sq, H, M, M, M, beta=1.0)
+        G = dZ
+    ws = torch.zeros(1, device=A2.device, dtype=torch.float32)
+    _lib.checked().mil_tm_pinv_init_bwd(_p(G), _p(Zs[0]), _p(scale), _p(arg), _p(dA2), _p(ws), _stream())
+    return dA2
+
+
+def _tm_bwd(dO, qkv, w, saved):
+    qL, kL, A1, A2, A3, W, U, Z, scale, arg, Zs, Xs, T2s, T3s = saved
+    n = qkv.shape[0]
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    H, M, DH, L3 = TM_H, TM_M, TM_DH, 3 * TM_D
+    q, k, v = qkv, qkv[:, TM_D:], qkv[:, 2 * TM_D:]
+    sq, sl = (M * M, M, 1), (M * DH, DH, 1)
+    dqkv = torch.empty((n, L3), **f32)
+    dw = torch.zeros(H * TM_CONV, **f32)
+    dA1 = tm_bgemm(dO, (DH, TM_D, 1), U, (M * DH, 1, DH), torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, DH)
+    dU = tm_bgemm(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
+    dZ = tm_bgemm(dU, sl, W, (M * DH, 1, DH), torch.empty((H, M, M), **f32), sq, H, M, M, DH)
+    dW = tm_bgemm(Z, (M * M, 1, M), dU, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
+    dA3 = tm_bgemm(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
+    tm_bgemm(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)                # dv = A3^T dW
+    _lib.checked().mil_tm_resconv_bwd(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw), _stream())
+    dS1 = tm_softmax_rows_bwd(A1, dA1)
+    dS3 = tm_softmax_rows_bwd(A3, dA3)
+    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, scale, arg, Zs, Xs, T2s, T3s))
+    tm_bgemm(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)            # dq
+    dkL = tm_bgemm(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
+    tm_bgemm(dS2, (M * M, 1, M), qL, sl, dkL, sl, H, M, DH, M, beta=1.0)
+    dqL = tm_bgemm(dS2, sq, kL, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
+    tm_bgemm(dS3, (M * n, n, 1), k, (DH, L3, 1), dqL, sl, H, M, DH, n, beta=1.0)
+    tm_bgemm(dS3, (M * n, 1, n), qL, sl, dqkv[:, TM_D:], (DH, L3, 1), H, n, DH, M)                  # dk
+    _lib.checked().mil_tm_landmarks_bwd(_p(dqL), _p(dkL), n, TM_QSCALE, _p(dqkv), _stream())
+    return dqkv, dw
+
+
+class _NystromCore(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, w, need_attn, cls=None):
+        qkv = _f32c(qkv, "qkv")
+        w = _f32c(w, "res_conv.weight")
+        if qkv.shape[1] != 3 * TM_D or qkv.shape[0] % TM_M or w.numel() != TM_H * TM_CONV:
+            raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
+        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls)
+        ctx.saved = saved
+        ctx.save_for_backward(qkv, w)
+        ctx.w_shape = w.shape
+        if attn is not None:
+            ctx.mark_non_differentiable(attn)
+        return O, attn
+
+    @staticmethod
+    def backward(ctx, dO, _dattn):
+        qkv, w = ctx.saved_tensors
+        dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved)
+        ctx.saved = None
+        return dqkv, dw.reshape(ctx.w_shape), None, None
+
+
+def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0):
+    """qkv [n_pad, 1536] (to_qkv of the front-zero-padded rows, n_pad % 256 == 0), w = res_conv.weight [8, 1, 33, 1] ->
+    (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
+    [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
+    as keywords: pad, s and the length as n or as len_dev (+ bag).  attn carries no gradient in any mode."""
+    if isinstance(need_attn, bool):
+        return _NystromCore.apply(qkv, w, need_attn, None)
+    if not (isinstance(need_attn, str) and need_attn == "cls"):
+        raise ValueError(f"nystrom_core: need_attn must be False, True or 'cls', got {need_attn!r}")
+    if pad is None or s is None or (n is None) == (len_dev is None):
+        raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
+    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)))

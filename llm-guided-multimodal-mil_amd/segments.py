@@ -75,7 +75,7 @@ class AttnSegs:
 
 
 class _SegView:
-    """One AttnSegs-shaped face of a FusionBucket (the attribute names the attention wrappers in ops.py read)."""
+    """One AttnSegs-shaped face of a FusionBucket (the attribute names the attention wrappers in ops/ read)."""
     device_lengths = True
 
     def __init__(self, **kw):
@@ -162,10 +162,9 @@ class FusionBucket:
     def refresh(self):
         """Rebuild every map from len_dev on the current stream (capture-safe: one launch, no host sync)."""
         p = lambda t: t.data_ptr()      # noqa: E731
-        rc = self._lib.lib().mil_build_fusion_segs_tail(p(self.len_dev), self.B, len(self.tail), self._tail_host, self.cap,
-                                                        p(self.k_off), p(self.k_bag), p(self.tile64), p(self.bag_tile64_off),
-                                                        self.T64, p(self.tile32), p(self.bag_tile32_off), self.T32,
-                                                        p(self.row_bag_dev), p(self.rows_dev), p(self.ds),
-                                                        torch.cuda.current_stream().cuda_stream)
-        self._lib.check(rc, "mil_build_fusion_segs_tail")
+        self._lib.checked().mil_build_fusion_segs_tail(p(self.len_dev), self.B, len(self.tail), self._tail_host, self.cap,
+                                                       p(self.k_off), p(self.k_bag), p(self.tile64), p(self.bag_tile64_off),
+                                                       self.T64, p(self.tile32), p(self.bag_tile32_off), self.T32,
+                                                       p(self.row_bag_dev), p(self.rows_dev), p(self.ds),
+                                                       torch.cuda.current_stream().cuda_stream)
         return lifetime.note(self)

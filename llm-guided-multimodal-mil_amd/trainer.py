@@ -154,8 +154,7 @@ class ImageOnlyTrainer:
         if self._wp is None:
             self._wp = torch.empty(3 * 2 * Wv.numel(), device=self.device, dtype=torch.int16)
         if self._wp_version != self._param_version and not torch.cuda.is_current_stream_capturing():
-            rc = _lib.lib().mil_gate_pieces(Wv.data_ptr(), Wu.data_ptr(), self._wp.data_ptr(), Wv.shape[1], ops._stream())
-            _lib.check(rc, "mil_gate_pieces")
+            _lib.checked().mil_gate_pieces(Wv.data_ptr(), Wu.data_ptr(), self._wp.data_ptr(), Wv.shape[1], ops._stream())
             self._wp_version = self._param_version
         return self._wp
 
@@ -273,8 +272,7 @@ class ImageOnlyTrainer:
         # dropout stream position: (micro-batch index of this optimizer step) << 32 | pass count; in counted mode the device
         # step counter is added on the device, so a replayed graph moves on by itself
         a.offset = (self._micro << 32) | (0 if self.step_counter is not None else (self.drop_pass & 0xFFFFFFFF))
-        rc = _lib.lib().mil_image_only_step_run(ctypes.byref(a), ops._stream())
-        _lib.check(rc, "mil_image_only_step_run")
+        _lib.checked().mil_image_only_step_run(ctypes.byref(a), ops._stream())
 
     # ------------------------------------------------------------------ pieces
     def forward(self, x: torch.Tensor, layout: BagLayout, y: Optional[torch.Tensor] = None,
@@ -399,8 +397,7 @@ class ImageOnlyTrainer:
         ms = ctypes.c_float(0.0)
         for name, stg in groups:
             a.accumulate = 0
-            rc = _lib.lib().mil_image_only_step_time(ctypes.byref(a), stg, warm, iters, ctypes.byref(ms), ops._stream())
-            _lib.check(rc, "mil_image_only_step_time")
+            _lib.checked().mil_image_only_step_time(ctypes.byref(a), stg, warm, iters, ctypes.byref(ms), ops._stream())
             out[name] = float(ms.value)
         # Adam on scratch copies of the parameters and moments, so timing it does not train
         fp = self.fp
@@ -411,8 +408,7 @@ class ImageOnlyTrainer:
             scratch.append(self._wp.clone())
             a2.Wp = scratch[-1].data_ptr()
         a2.adam_step_dev, a2.adam_step, a2.lr, a2.x_bf16 = None, 1, self.lr, 0
-        rc = _lib.lib().mil_image_only_step_time(ctypes.byref(a2), _lib.STAGE_ADAM, warm, iters, ctypes.byref(ms), ops._stream())
-        _lib.check(rc, "mil_image_only_step_time")
+        _lib.checked().mil_image_only_step_time(ctypes.byref(a2), _lib.STAGE_ADAM, warm, iters, ctypes.byref(ms), ops._stream())
         out["adam"] = float(ms.value)
         return out
 
@@ -471,10 +467,9 @@ class ImageOnlyTrainer:
         ys_arr = (ctypes.c_void_p * max(1, nrot))(*[t[1].data_ptr() for t in (rot or [])])
         for b in range(nb):
             out = (ctypes.c_float * (len(groups) + 1))()
-            rc = _lib.lib().mil_image_only_step_profile_rot(ctypes.byref(a2), xs_arr if nrot else None, ys_arr if nrot else None,
-                                                            nrot, masks, len(groups), warm if b == 0 else 1, per, out,
-                                                            ops._stream())
-            _lib.check(rc, "mil_image_only_step_profile_rot")
+            _lib.checked().mil_image_only_step_profile_rot(ctypes.byref(a2), xs_arr if nrot else None, ys_arr if nrot else None,
+                                                           nrot, masks, len(groups), warm if b == 0 else 1, per, out,
+                                                           ops._stream())
             runs.append([float(v) for v in out])
         med = [sorted(r[i] for r in runs)[nb // 2] for i in range(len(groups) + 1)]
         return {n: med[i] for i, (n, _) in enumerate(groups)}, med[len(groups)]
