@@ -507,7 +507,10 @@ int mil_sum4(const float* a, const float* b, const float* c, const float* d, flo
 /*   mil_linear_small_bwd_split  the dx of mil_linear_small_bwd as nsplit (2 | 4) partial sums over n, N / nsplit a multiple
  *                               of 512: dx_parts [nsplit][M][K] - a 2048-wide contraction (mlp.lin1) spread over 4 x the
  *                               workgroups; the next backward kernel sums the parts while it stages them:
- *   mil_linear_small_ln_bwd5    mil_linear_small_ln_bwd with up to five addends (g4, g5 [M, 512] contiguous, nullable). */
+ *   mil_linear_small_ln_bwd5    mil_linear_small_ln_bwd with up to five addends (g4, g5 [M, 512] contiguous, nullable).
+ *                               All three LayerNorm backward entries need ldg1 >= 512 (MIL_EINVAL otherwise).  A missing g2 / g3
+ *                               is read as g1 with weight 0, a missing one of g4 / g5 as the other of the two with weight 0:
+ *                               no entry reads outside the operands it is given. */
 int mil_linear_small_bwd_split(const float* dy, int lddy, const float* y_or_pre, int ldyv, int act, const float* W, int ldw,
                                float* dx_parts, int M, int N, int K, int nsplit, void* stream);
 int mil_linear_small_ln_bwd5(const float* g1, int ldg1, const float* g2, int ldg2, const float* g3, int ldg3, const float* g4,

@@ -423,11 +423,24 @@ __global__ __launch_bounds__(64 * NW) void k_small_fwd_ln(const float* __restric
         }
 #pragma unroll
         for (int m = 16; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-        const float mean = s / K;
-        float ss = 0.f;
+        float mean = s / K;
+        // The float32 sum of 512 values near m is off by a few ulp(512 m) / 512: for rows of mean 30 and std 1 that alone cost
+        // 1e-6 of xn (16 x what the float32 restatement loses).  u - mean is (nearly) exact, so the mean of the differences is
+        // what the sum lost: one more reduction puts the centred row and the stored mean right to the last bit or two.
+        float sc = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             v[j] = v[j] - mean;
+            sc += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
+        }
+#pragma unroll
+        for (int m = 16; m >= 1; m >>= 1) sc += __shfl_xor(sc, m);
+        const float corr = sc / K;
+        mean += corr;
+        float ss = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = v[j] - corr;
             const f32x4 q = v[j] * v[j];
             ss += (q[0] + q[1]) + (q[2] + q[3]);
         }
@@ -766,10 +779,12 @@ extern "C" int mil_linear_small_ln_bwd5(const float* g1, int ldg1, const float* 
     if (!g1 || !u || !stats || !gamma || M <= 0 || M > MIL_SMALL_ROWS) return MIL_EINVAL;
     if (g3 && ((ldg3 & 3) || !sl_aligned16(g3))) return MIL_EINVAL;
     if ((g4 && !sl_aligned16(g4)) || (g5 && !sl_aligned16(g5))) return MIL_EINVAL;
-    const SmallLnMore mo{g4 ? g4 : g1, g5 ? g5 : g1, g4 ? 1.f : 0.f, g5 ? 1.f : 0.f};
-    if ((!g4 || !g5) && ldg1 != SLN_E) {                       // the stand-in is read with the extras' stride
-        if (ldg1 < SLN_E) return MIL_EINVAL;
-    }
+    if (ldg1 < SLN_E) return MIL_EINVAL;
+    // the stand-in of a missing g4 / g5 is read with THEIR stride (512): the other of the two where there is one - g1 read
+    // that way with ldg1 > 512 lands in the gap columns of g1's parent buffer, and 0 x NaN there is NaN.  (Both missing:
+    // the kernel without them.)
+    const float* const g45 = g4 ? g4 : g5;
+    const SmallLnMore mo{g4 ? g4 : g45, g5 ? g5 : g45, g4 ? 1.f : 0.f, g5 ? 1.f : 0.f};
     if ((dx != nullptr) && (!W || K <= 0)) return MIL_EINVAL;
     if ((dgamma == nullptr) != (dbeta == nullptr)) return MIL_EINVAL;
     if ((ldg1 & 3) || (g2 && (ldg2 & 3)) || (ldu & 3) || !sl_aligned16(g1) || (g2 && !sl_aligned16(g2)) || !sl_aligned16(u) ||
@@ -780,7 +795,7 @@ extern "C" int mil_linear_small_ln_bwd5(const float* g1, int ldg1, const float* 
     auto kern = (g4 || g5) ? k_small_bwd_ln<SL_WAVES, true> : k_small_bwd_ln<SL_WAVES, false>;
     hipLaunchKernelGGL(kern, dim3(nX + (dgamma ? 4 : 0)), dim3(64 * SL_WAVES), 0, (hipStream_t)stream, g1, ldg1,
                        g2 ? g2 : g1, g2 ? ldg2 : ldg1, g3 ? g3 : g1, g3 ? ldg3 : ldg1, g2 ? 1.f : 0.f, g3 ? 1.f : 0.f, mo, u, ldu, stats, gamma,
-                       W, ldw, dx, lddx, du, dgamma, dbeta, M, dx ? K : 16, nX);      // a missing addend: g1 again, weight 0 (no branch)
+                       W, ldw, dx, lddx, du, dgamma, dbeta, M, dx ? K : 16, nX);      // a missing g2 / g3: g1 again, weight 0 (no branch)
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
