@@ -61,7 +61,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 9 */
+int mil_abi_version(void);   /* 10 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -261,6 +261,11 @@ int mil_rowdot(const float* a, const float* c, float* out, int B, int L, void* s
 int mil_attn_pool_bwd(const float* x, const float* scores, const float* lse, const float* dM,
                       const float* cdot, const int32_t* tile_map, int T, int L, float* ds,
                       float* dx, const uint32_t* xbits, float xscale, void* stream);
+
+/* The pool's softmax weights themselves (ABI 10): w[n] = exp(s_n - lse) over the rows [row_off[b], row_off[b + 1]) of bag b,
+ * row_off [B + 1]; scores and w cover row_off[B] rows.  len_dev [B] (nullable): the true length of bag b on the device - the
+ * rows behind it inside the bag's slot get 0.  One workgroup per bag, sums in a fixed order. */
+int mil_bag_softmax(const float* scores, const int32_t* row_off, const int32_t* len_dev, int B, float* w, void* stream);
 
 /* Gate parameter gradients from the saved gates and ds:
  * dWv = dPreV^T x, dWu = dPreU^T x, dbv, dbu, dw = sum_i ds_i V_i U_i, db = sum_i ds_i,
@@ -629,6 +634,14 @@ int mil_absorb_query_bwd(const float* qp, const float* Wk, const float* dQp, int
 int mil_absorbed_pool_fwd(const float* keys, const float* pe, const float* Qp, const int32_t* k_off,
                           const int32_t* tile_map, const int32_t* bag_tile_off, int ntiles, int B, int H, int C, int E,
                           float* pooled, float* lse, float* workspace, void* stream);
+/* The softmax weights of that pool, which the forward folds into its running sums and never writes (ABI 10):
+ * attn[n][h] = exp(Qp[b][h] . (keys_n + pe_{n - k_off[b]}) / sqrt(C) - lse[b][h]) for every key row n a tile of tile_map
+ * [ntiles][3] = {bag, key0, nkeys <= 64} covers, attn [n_keys, H] (16-byte aligned); lse [B, H] as mil_absorbed_pool_fwd wrote
+ * it.  A padding tile of a capacity bucket {0, row0, -count} (mil_build_fusion_segs) writes `count` zero rows; rows no tile
+ * covers are not written.  H = 8, E = 512, C = 32 or 64.  One pass over the keys, one launch, no workspace: with the tile
+ * map built on the device nothing is read from the host (capture-safe). */
+int mil_absorbed_pool_attn(const float* keys, const float* pe, const float* Qp, const float* lse, const int32_t* k_off,
+                           const int32_t* tile_map, int ntiles, int B, int H, int C, int E, float* attn, void* stream);
 /* pooled [B, H, E]: the forward's result; the softmax backward's row constant cdot_h = dpooled_h . pooled_h is formed inside
  * (round 2 took it as an input computed by a mil_rowdot launch). */
 int mil_absorbed_pool_bwd(const float* keys, const float* pe, const float* Qp, const float* lse, const float* dpooled,

@@ -100,6 +100,12 @@ def create_arg_parser(argv=None):
                    "DIR/<bag key or index>.npy per bag, float32 [2, 8, N] = layers x heads x patches, the cls token's attention "
                    "to each patch (a repeated patch's two keys summed; not renormalised), bags in the order test_ddp.py runs "
                    "them.  Works with and without --transmil_graph 1; the files are written when the run ends")
+    p.add_argument("--save_note_attn", type=str, default="", help="test_ddp.py, --variant fusion --modality \"['pathology']\": "
+                   "write DIR/<bag key or index>.npz per bag with float32 note [3, P, 8, N] = attention sites (block 0, block 1, "
+                   "final) x text tokens x heads x patches, the softmax weights of the note's token(s) over the patches, and bag "
+                   "[N + P], the final gated-attention aggregator's weights, patches first.  The flag switches --hip_graph off: "
+                   "with --hip_graph 1 the evaluation runs the eager forward, not the replayed one.  The files are written when "
+                   "the run ends")
     p.add_argument("--flat_adam", type=int, default=1, help="autograd path: parameters in one flat buffer, one gradient "
                    "all-reduce and one Adam launch per step (optim.FlatAdam); 0 = torch DDP + torch.optim.Adam")
     args = p.parse_args(argv)
@@ -107,4 +113,11 @@ def create_arg_parser(argv=None):
         # refused here, before an entry point touches the GPU
         raise ValueError("--save_patch_attn writes TransMIL's cls-token attention: it needs --variant image_only "
                          "--model_pathology TransMIL (ABMIL keeps its scores in extractor_pathology.last_scores)")
+    if args.save_note_attn and (args.variant != "fusion" or list(args.modality) != ["pathology"]):
+        raise ValueError("--save_note_attn writes the note's attention over the patches: it needs --variant fusion "
+                         "--modality \"['pathology']\"")
+    if args.save_note_attn and args.hip_graph:
+        # the weights come out of the eager forward (model.note_attn), not the replayed one: test_ddp.py then takes its
+        # op-by-op evaluation loop
+        args.hip_graph = 0
     return args

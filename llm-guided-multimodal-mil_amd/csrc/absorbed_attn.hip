@@ -317,6 +317,80 @@ __global__ __launch_bounds__(256, 2) void k_apool_partial(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------- absorbed pool, attention weights
+// attn[n][h] = exp(scale Qp[b][h] . (keys_n + pe_n) - lse[b][h]): the softmax weights k_apool_partial folds into its running
+// sums and never writes, rebuilt from what the forward holds (keys, the PE table, Qp, lse, the 64-key tile map) in ONE pass
+// over the keys - no workspace, no atomic.  One workgroup (256 threads) per tile; wave w owns rows 16 w .. 16 w + 15, all 32
+// 16-byte loads of a lane issued up front (nontemporal: the keys are streamed once) and the rows stay in registers; the
+// bag's eight scaled query vectors live in LDS (16 KB, 16-byte reads, conflict-free).  Per row a lane forms its partial sums
+// of the eight dot products and one transposing wave reduction (wave_reduce8) leaves head h on the lanes 8 h .. 8 h + 7;
+// lane l keeps the value of rows (l & 7) and 8 + (l & 7), so the wave's result - 16 rows x 8 heads, 512 contiguous bytes of
+// attn [n_keys, 8] - leaves in two stores of 256 contiguous bytes each.  Padding tiles of a capacity bucket (nkeys < 0)
+// write zero rows; rows no tile covers are not written.
+__global__ __launch_bounds__(256, 2) void k_apool_attn(const float* __restrict__ keys, const float* __restrict__ pe,
+                                                       const float* __restrict__ Qp, const float* __restrict__ lse,
+                                                       const int32_t* __restrict__ k_off, const int32_t* __restrict__ tile_map,
+                                                       float scale, float* __restrict__ attn) {
+    constexpr int E = 512, NQ = 2, RW = AP_TILE / 4;
+    __shared__ __attribute__((aligned(16))) float V[AP_H * E];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = blockIdx.x;
+    const int b = tile_map[3 * g], key0 = tile_map[3 * g + 1], nkeys = tile_map[3 * g + 2];
+    if (nkeys <= 0) {
+        for (int i = tid; i < -2 * nkeys; i += 256)
+            *reinterpret_cast<f32x4*>(attn + (size_t)key0 * AP_H + 4 * i) = f32x4{0, 0, 0, 0};
+        return;
+    }
+    const int pos0 = key0 - k_off[b];
+    f32x4 kv[RW][NQ];
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const int rr = min(RW * wave + i, nkeys - 1);                      // rows past the tile end: clamped, not stored
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            kv[i][q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(keys + (size_t)(key0 + rr) * E + 256 * q + 4 * lane));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = i * 256 + tid;                                     // 1024 pieces of 16 bytes
+        *reinterpret_cast<f32x4*>(V + 4 * idx) = scale * *reinterpret_cast<const f32x4*>(Qp + (size_t)b * AP_H * E + 4 * idx);
+    }
+    const float lse_l = lse[b * AP_H + (lane >> 3)];                       // wave_reduce8 leaves head l >> 3 on lane l
+    __syncthreads();
+    const float* Vl = V + 4 * lane;
+    float keep[2] = {0.f, 0.f};
+    // the positional rows (L2-resident table) in batches of four, as k_apool_partial reads them
+#pragma unroll
+    for (int i0 = 0; i0 < RW; i0 += 4) {
+        f32x4 pv[4][NQ];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int rr = min(RW * wave + i0 + u, nkeys - 1);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) pv[u][q] = *reinterpret_cast<const f32x4*>(pe + (size_t)(pos0 + rr) * E + 256 * q + 4 * lane);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = i0 + u;
+            const f32x4 k0 = kv[i][0] + pv[u][0], k1 = kv[i][1] + pv[u][1];
+            float d8[AP_H];
+#pragma unroll
+            for (int h = 0; h < AP_H; ++h) {
+                f32x4 t = k0 * *reinterpret_cast<const f32x4*>(Vl + h * E);
+                t += k1 * *reinterpret_cast<const f32x4*>(Vl + h * E + 256);
+                d8[h] = (t[0] + t[1]) + (t[2] + t[3]);
+            }
+            const float tot = wave_reduce8(d8, lane);
+            if ((lane & 7) == (i & 7)) keep[i >> 3] = tot;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int row = RW * wave + 8 * j + (lane & 7);
+        if (row < nkeys) attn[(size_t)(key0 + row) * AP_H + (lane >> 3)] = expf(keep[j] - lse_l);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- absorbed pool, backward
 // Per row n of a tile: a_h = exp(scale Qp_h . kin_n - lse_h);  da_h = dpooled_h . keys_n;  ds_h = a_h (da_h - cdot_h);
 //   dkeys_n = sum_h (a_h dpooled_h + scale ds_h Qp_h);   dQp_h += scale ds_h kin_n  (per-tile partial, merged per bag)
@@ -1565,6 +1639,20 @@ extern "C" int mil_absorbed_pool_fwd(const float* keys, const float* pe, const f
     }
     hipLaunchKernelGGL(k_apool_merge_value<false>, dim3(B, AP_H), dim3(1024), 0, st, pacc, pml, bag_tile_off, E, pooled, lse,
                        (const float*)nullptr, (const float*)nullptr, C, (float*)nullptr);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+// attn [n_keys, H]: the softmax weights of the forward's one-token pool, attn[n][h] = exp(Qp[b][h] . (keys_n + pe_n) / sqrt(C)
+// - lse[b][h]) for the rows the tile map covers (padding tiles: zero rows); one launch, no workspace.
+extern "C" int mil_absorbed_pool_attn(const float* keys, const float* pe, const float* Qp, const float* lse,
+                                      const int32_t* k_off, const int32_t* tile_map, int ntiles, int B, int H, int C, int E,
+                                      float* attn, void* stream) {
+    AP_CHECK(keys && pe && Qp && lse && k_off && tile_map && attn && ((uintptr_t)attn & 15) == 0);
+    AP_CHECK(H == AP_H && E == 512 && (C == 32 || C == 64) && B >= 0 && ntiles >= 0);
+    if (B == 0 || ntiles == 0) return MIL_OK;
+    hipLaunchKernelGGL(k_apool_attn, dim3(ntiles), dim3(256), 0, (hipStream_t)stream, keys, pe, Qp, lse, k_off, tile_map,
+                       1.0f / sqrtf((float)C), attn);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

@@ -389,3 +389,41 @@ extern "C" int mil_attn_pool_bwd(const float* x, const float* scores, const floa
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
+
+// ================================================================================ softmax weights of a bag
+// w[n] = exp(s_n - lse) over the rows [row_off[b], row_off[b + 1]) of bag b: the weights k_pool_partial folds into the pooled
+// sum and never writes.  One workgroup per bag, two passes over its scores (a few KB, L2-resident): per-thread online
+// (max, sum), merged over the wave and then over the four waves in wave order - a fixed order, the same bits every run -
+// then the weights.  len_dev (nullable): the bag's true length on the device; the rows behind it inside the slot get zero.
+__global__ __launch_bounds__(256) void k_bag_softmax(const float* __restrict__ scores, const int32_t* __restrict__ row_off,
+                                                     const int32_t* __restrict__ len_dev, float* __restrict__ w) {
+    __shared__ float m_lds[4], l_lds[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int r0 = row_off[b], cap = row_off[b + 1] - r0;
+    const int n = len_dev != nullptr ? max(min(len_dev[b], cap), 0) : cap;
+    float m = -INFINITY, l = 0.f;
+    for (int i = tid; i < n; i += 256) {
+        const float s = scores[r0 + i];
+        if (s > m) { l = l * expf(m - s) + 1.0f; m = s; }
+        else l += expf(s - m);
+    }
+    const float mw = wave_allmax(m);
+    l = wave_allsum(m == -INFINITY ? 0.f : l * expf(m - mw));
+    if ((tid & 63) == 0) { m_lds[tid >> 6] = mw; l_lds[tid >> 6] = l; }
+    __syncthreads();
+    const float mt = fmaxf(fmaxf(m_lds[0], m_lds[1]), fmaxf(m_lds[2], m_lds[3]));
+    float lt = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) lt += m_lds[k] == -INFINITY ? 0.f : l_lds[k] * expf(m_lds[k] - mt);
+    const float inv = 1.0f / lt;
+    for (int i = tid; i < cap; i += 256) w[r0 + i] = i < n ? expf(scores[r0 + i] - mt) * inv : 0.f;
+}
+
+extern "C" int mil_bag_softmax(const float* scores, const int32_t* row_off, const int32_t* len_dev, int B, float* w,
+                               void* stream) {
+    if (!scores || !row_off || !w || B < 0) return MIL_EINVAL;
+    if (B == 0) return MIL_OK;
+    hipLaunchKernelGGL(k_bag_softmax, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, row_off, len_dev, w);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}

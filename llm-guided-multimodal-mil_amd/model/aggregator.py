@@ -73,6 +73,81 @@ class aggregator(nn.Module):
         self.last_loss: Optional[torch.Tensor] = None
         self._labels: Optional[torch.Tensor] = None
         self._loss_scale: Optional[float] = None
+        # note_attn: an eval-mode, no-grad forward of the pathology (+ text) model also leaves, per bag,
+        #   last_note_attn[site][bag]  [8, N_b] (P = 1 text token per bag; [P, 8, N_b] for P = 2 .. 12): the softmax weights of
+        #       the note's token(s) over the bag's patches at the three token->image attention sites - block 0, block 1, the
+        #       final attention of TwoWayTransformer_Pth - every head summing to 1 over the patches;
+        #   last_bag_attn[bag]  [N_b + P]: the final gated-attention aggregator's weights over the multi-modal bag, PATCHES
+        #       FIRST, then the note's tokens - the order of the rows in memory (upstream concatenates the tokens first,
+        #       aggregator.py:192; pooling does not depend on the order).
+        # Off: the forward issues exactly the launches it always did and both stay None.  The returned tuple never changes.
+        self.note_attn = False
+        self.last_note_attn = None
+        self.last_bag_attn = None
+        self._note_dir, self._note_names, self._note_kept, self._note_done = None, None, [], 0
+
+    NOTE_KEEP_BYTES = 1 << 30
+
+    def save_note_attn_to(self, directory: str, names=None):
+        """--save_note_attn (train_ddp.build_model): every eval-mode, no-grad forward from here on keeps its bags' weights ON
+        THE DEVICE (note [3, P, 8, N] and bag [N + P] per bag), and flush_note_attn() - registered to run when the process
+        ends - copies them to the host and writes DIR/<names[i] or i>.npz, float32, bags numbered in the order they ran: an
+        entry point that times each forward has no host copy and no file inside its bracket.  Beyond NOTE_KEEP_BYTES kept, a
+        forward flushes first."""
+        import atexit
+        import os
+        os.makedirs(directory, exist_ok=True)
+        self._note_dir, self._note_names = directory, (list(names) if names is not None else None)
+        self.note_attn = True
+        atexit.register(self.flush_note_attn)
+
+    def flush_note_attn(self):
+        import os
+        import numpy as np
+        for note, bag in self._note_kept:
+            i = self._note_done
+            name = str(self._note_names[i]) if self._note_names is not None and i < len(self._note_names) else str(i)
+            np.savez(os.path.join(self._note_dir, name + ".npz"), note=note.float().cpu().numpy(), bag=bag.float().cpu().numpy())
+            self._note_done += 1
+        self._note_kept = []
+
+    def _keep_note_attn(self):
+        if self._note_dir is None or self.last_note_attn is None or self.last_bag_attn is None:
+            return
+        if sum(n.numel() + b.numel() for n, b in self._note_kept) * 4 > self.NOTE_KEEP_BYTES:
+            self.flush_note_attn()
+        for b, bag in enumerate(self.last_bag_attn):
+            note = torch.stack([site[b].reshape(-1, 8, site[b].shape[-1]) for site in self.last_note_attn])
+            self._note_kept.append((note, bag.clone()))
+
+    def _wants_note_attn(self) -> bool:
+        return bool(self.note_attn) and not self.training and not torch.is_grad_enabled()
+
+    def _note_attention(self, sites, n_len, P, layout):
+        """After the forward: the weights of the three token->image sites from what their kernels held (`sites`,
+        ops.note_sites), one launch per site, and the aggregator's weights from its scores."""
+        if len(sites) != 3:
+            raise NotImplementedError(f"note_attn: {len(sites)} of the 3 token->image attention sites ran on the absorbed "
+                                      "one-token / multi-token pool; the general attention_pool route keeps no weights")
+        off = [0]
+        for n in n_len:
+            off.append(off[-1] + int(n))
+        out = []
+        for rec in sites:
+            if "A" in rec:      # P = 2 .. 12: views of the softmaxed score matrix [rows, P 8 (+ padding)], column t 8 + h
+                A, TH = rec["A"], rec["TH"]
+                out.append([A[off[b]:off[b + 1], :TH].t().reshape(P, TH // P, -1) for b in range(len(n_len))])
+            else:
+                a = ops.absorbed_pool_attention(rec["keys"], rec["pe"], rec["Qp"], rec["lse"], rec["segs"], rec["C"])
+                out.append([a[off[b]:off[b + 1]].t() for b in range(len(n_len))])
+        self.last_note_attn = out
+        self._bag_attention(layout)
+        self._keep_note_attn()
+
+    def _bag_attention(self, layout):
+        agg = getattr(self, "aggregator", None)
+        if agg is not None and getattr(agg, "last_scores", None) is not None:
+            self.last_bag_attn = list(torch.split(ops.bag_softmax(agg.last_scores, layout), list(layout.lengths)))
 
     # ------------------------------------------------------------------ positional table (aggregator.py:99-106)
     def pe_rows(self, n: int, device) -> torch.Tensor:
@@ -105,7 +180,7 @@ class aggregator(nn.Module):
         y = self._labels
         C = self.args.num_classes
         if y is not None and hasattr(getattr(self, "aggregator", None), "flat_head_loss") and \
-                self.aggregator.can_fuse_head(x0, C):
+                self.aggregator.can_fuse_head(x0, C) and not self._wants_note_attn():      # note_attn reads last_scores
             ce = C > 2                                     # train_ddp.py:95-98: CrossEntropyLoss on the sigmoid outputs
             scale = self._loss_scale if self._loss_scale is not None else 1.0 / (layout.B * (1 if ce else C))
             loss, p, z = self.aggregator.flat_head_loss(x0, layout, self.fc[1].weight, self.fc[1].bias, y, scale,
@@ -237,6 +312,12 @@ class aggregator(nn.Module):
         # the return tuple is unchanged
         self._labels, self._loss_scale, self.last_loss = labels, loss_scale, None
         modality = self.args.modality
+        want = self._wants_note_attn()
+        if want:
+            self.last_note_attn = self.last_bag_attn = None
+            if "CT" in modality or bucket is not None:
+                raise NotImplementedError("note_attn is built for modality ['pathology'] (or ['CI']) on host-side bag lengths: "
+                                          "the CT branches and the capacity-bucket forward keep no attention weights")
         # text_features [B, P, 512] (optional): embeddings of the frozen text tower computed earlier by
         # `self.clinic_extractor(x_CI)`; lets a captured hipGraph replay the trainable part only
         t = text_features if text_features is not None else self.clinic_extractor(x_CI)   # :151  [B, P, 512]
@@ -260,16 +341,28 @@ class aggregator(nn.Module):
                 flat = torch.cat([x[b, :n] for b, n in enumerate(n_len)], 0)
             xi = self._lin_tanh(self.fc_pathology, flat)                                  # :149
             point = self._lin_tanh(self.fc_CI2Pth, t.reshape(B * P, EMBED))               # :190
-            q, k = self.TwoWayTransformer_Pth.flat(xi, point, self.pe_rows(max(n_len), xi.device), n_len, [P] * B,
-                                                   keys_tail_rows=B * P)
+            if want:
+                with ops.note_sites() as sites:
+                    q, k = self.TwoWayTransformer_Pth.flat(xi, point, self.pe_rows(max(n_len), xi.device), n_len, [P] * B,
+                                                           keys_tail_rows=B * P)
+            else:
+                q, k = self.TwoWayTransformer_Pth.flat(xi, point, self.pe_rows(max(n_len), xi.device), n_len, [P] * B,
+                                                       keys_tail_rows=B * P)
             # multi-modal bag per patient = its text tokens + its patch tokens (:192).  Rows are kept as
             # [all patches | all tokens] (the patch tokens stay where the last LayerNorm wrote them, only the few
             # token rows are appended) and the tile map tells the pool kernels which rows belong to which bag;
             # attention pooling does not depend on the order of a bag's rows.
             x0 = ops.append_rows(k, q, tail_reserved=True)     # k comes from the last block's norm4 with keys_tail_rows
             layout = BagLayout.two_segment(n_len, [P] * B, x0.device)
-            return self._pool_head(x0, layout), q.view(B, P, EMBED)                       # :198-200,207
+            prob = self._pool_head(x0, layout)
+            if want:
+                self._note_attention(sites, n_len, P, layout)
+            return prob, q.view(B, P, EMBED)                                              # :198-200,207
         if "CI" in modality:
             x0 = self._lin_tanh(self.fc_CI, t.reshape(B * P, EMBED))                      # :195
-            return self._pool_head(x0, BagLayout.uniform(B, P, x0.device))                # :198-200,209
+            layout = BagLayout.uniform(B, P, x0.device)
+            prob = self._pool_head(x0, layout)                                            # :198-200,209
+            if want:
+                self._bag_attention(layout)
+            return prob
         raise NotImplementedError(f"modality {modality}")

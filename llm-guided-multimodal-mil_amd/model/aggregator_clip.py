@@ -38,6 +38,10 @@ class aggregator(nn.Module):
         self.patch_attn = False
         self.last_patch_attn = None
         self._attn_dir, self._attn_names, self._attn_kept, self._attn_done = None, None, [], 0
+        # ABMIL only: an eval-mode, no-grad forward also leaves the pool's softmax weights in last_bag_attn, one [N_b] tensor
+        # per bag (ops.bag_softmax of extractor_pathology.last_scores); the returned tuple does not change
+        self.note_attn = False
+        self.last_bag_attn = None
 
     ATTN_KEEP_BYTES = 1 << 30
 
@@ -103,6 +107,14 @@ class aggregator(nn.Module):
             h = F.dropout(M, 0.25, True)
         p, z = ops.head_sigmoid(h, self.fc[1].weight, self.fc[1].bias)
         self.last_logits = z
+        if self.note_attn and not self.training and not torch.is_grad_enabled():
+            if not isinstance(self.extractor_pathology, ABMIL):
+                raise NotImplementedError("note_attn gives the gated-attention pool's weights (ABMIL); TransMIL has patch_attn")
+            from ..bags import BagLayout
+            xs = x0 if x0.dim() == 3 else x0.unsqueeze(0)
+            layout = BagLayout.make(lengths, x0.device) if lengths is not None else BagLayout.uniform(xs.shape[0], xs.shape[1], x0.device)
+            scores = self.extractor_pathology.last_scores
+            self.last_bag_attn = list(torch.split(ops.bag_softmax(scores, layout), list(layout.lengths)))
         if want and geom is None:
             self._keep_patch_attn()
         return M, p

@@ -18,7 +18,7 @@ from .gate import (dropout_keep_bits, dropout_keep_bits_pair, counter_add, dropo
                    adam_step_dev, adam_step_dev_segs, sgd_step, _GatedAttentionPool, gated_attention_pool,
                    gate_bwd_input_pool, _GatedPoolHeadLoss, gated_pool_head_loss, _HeadSigmoid, head_sigmoid, cast_bf16,
                    gate_scores_fwd_bf16, attn_pool_partial_bf16, attn_pool_partial_h_bf16, attn_pool_bwd_bf16,
-                   gate_bwd_params_x16, gate_bwd_params_bf16)
+                   gate_bwd_params_x16, gate_bwd_params_bf16, bag_softmax)
 from .linear import (gemm, gemm_aux, linear_bwd_params, colsum, act_bwd, SMALL_ROWS, _small_ok, MID_ROWS, MID_WORK, _mid_ok,
                      linear_mid_fwd, linear_mid_bwd, linear_small_fwd, linear_small_bwd, _GradBox, _sum_overflow, _ONES,
                      backward, sum_n, _ok_extra, _FanOut, fan_out, _LinearAct, _small_dw, _LinLnLin, lin_ln_lin_ok,
@@ -31,7 +31,8 @@ from .tokens import (_tail_view, _LayerNorm, _layer_norm_bwd, _LayerNormRes, lay
                      embed_tokens, gather_eot, _AddBagRow, add_bag_row)
 from .losses import (_ClipContrastive, clip_contrastive_loss, _CosineEmbedding, cosine_embedding_loss)
 from .absorbed import (_AbsorbQuery, _dkeys_buffer, _AbsorbedPool, _ValueProj, _value_proj_bwd, _AbsorbedPoolValue,
-                       _LnbrAbsorbedPoolValue, lnbr_one_token_ok, lnbr_one_token_attention, one_token_attention)
+                       _LnbrAbsorbedPoolValue, lnbr_one_token_ok, lnbr_one_token_attention, one_token_attention, note_sites,
+                       absorbed_pool_attention)
 from .grouped import (_gg, _gg_nt, _gg_nn, _gg_tn, _gcs_ws, _seg_colsum, _GroupedNT, _GroupedNN, _GroupedTN, _GrpColSoftmax,
                       _RowSoftmaxT, multi_token_ok, _MultiTokenPoolCore, _MultiTokenRowsCore, multi_token_pool_attention,
                       multi_token_rows_attention)

@@ -8,6 +8,48 @@ from ._base import _f32c, _p, _stream, _stream_int, grad_slot
 from .linear import SMALL_ROWS, colsum, linear_act
 
 
+# A list while a model collects what its token->image sites hold (model.note_attn; note_sites() below), None otherwise: the
+# forwards of the pool nodes append one record per site - tensors they have formed anyway, no launch is added or changed.
+_site_tap = None
+
+
+class note_sites:
+    """with note_sites() as sites: every absorbed one-token pool (and multi-token pool, ops/grouped.py) that runs inside
+    appends dict(keys, pe, Qp, lse, segs, C) (multi-token: dict(A, segs, TH), A the softmaxed score matrix) to `sites`, in the
+    order the sites run.  absorbed_pool_attention() turns a record into the softmax weights afterwards."""
+
+    def __enter__(self):
+        global _site_tap
+        self._outer, _site_tap = _site_tap, []
+        return _site_tap
+
+    def __exit__(self, *exc):
+        global _site_tap
+        _site_tap = self._outer
+        return False
+
+
+def _note_site(keys, pe, Qp, lse, segs, C):
+    if _site_tap is not None:
+        _site_tap.append(dict(keys=keys, pe=pe, Qp=Qp, lse=lse, segs=segs, C=C))
+
+
+def absorbed_pool_attention(keys, pe, Qp, lse, segs, C: int):
+    """The softmax weights of the one-token pool, attn [n_keys, 8] with attn[n][h] = exp(Qp[b][h] . (keys_n + pe_n) / sqrt(C) -
+    lse[b][h]) (mil_absorbed_pool_attn: one pass over the keys).  keys, pe, Qp, lse: what the forward read and wrote (for the
+    fused LayerNorm sites keys = the y it wrote).  Bag b's heads x patches view is attn[k_off[b]:k_off[b + 1]].t().  Rows of a
+    capacity bucket behind the bags read 0.  No gradient."""
+    keys, pe, Qp, lse = (_f32c(t.detach(), n) for t, n in ((keys, "keys"), (pe, "pe"), (Qp, "Qp"), (lse, "lse")))
+    B, H, E = Qp.shape
+    if keys.dim() != 2 or keys.shape[1] != E or lse.shape != (B, H):
+        raise ValueError("absorbed_pool_attention: keys [n_keys, E], Qp [B, H, E], lse [B, H]")
+    covered = not getattr(segs, "device_lengths", False) or getattr(segs, "pad_tiles", False)
+    attn = (torch.empty if covered else torch.zeros)((keys.shape[0], H), device=keys.device, dtype=torch.float32)
+    _lib.checked().mil_absorbed_pool_attn(_p(keys), _p(pe), _p(Qp), _p(lse), _p(segs.k_off), _p(segs.tile_map), segs.ntiles,
+                                          B, H, C, E, _p(attn), _stream())
+    return attn
+
+
 class _AbsorbQuery(torch.autograd.Function):
     """Qp[b][h] = scale * Wk_h^T qp[b][h]  (also the value projection's backward map).  T > 1: the B = bags x T rows are
     the T text tokens of each bag and the result is the grouped products' operand [bags, T H padded to a multiple of 32, E]
@@ -100,6 +142,7 @@ class _AbsorbedPool(torch.autograd.Function):
         ctx.segs, ctx.C = segs, C
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(keys, pe, Qp, pooled, lse)
+        _note_site(keys, pe, Qp, lse, segs, C)
         return pooled, keys_in.view_as(keys_in)
 
     @staticmethod
@@ -199,6 +242,7 @@ class _AbsorbedPoolValue(torch.autograd.Function):
         ctx.segs, ctx.C, ctx.bv_param = segs, C, bv
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(keys, pe, Qp, pooled, lse, Wv)
+        _note_site(keys, pe, Qp, lse, segs, C)
         return o, keys_in.view_as(keys_in)
 
     @staticmethod
@@ -248,6 +292,7 @@ class _LnbrAbsorbedPoolValue(torch.autograd.Function):
         ctx.segs, ctx.C, ctx.bv_param, ctx.beta_param = segs, C, bv, beta
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x, row, gamma, stats, y, pe, Qp, pooled, lse, Wv, beta)
+        _note_site(y, pe, Qp, lse, segs, C)             # the keys this site read are the y it wrote
         return o, y
 
     @staticmethod

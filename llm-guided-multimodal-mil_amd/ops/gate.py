@@ -341,6 +341,52 @@ def gated_attention_pool(x, Wv, bv, Wu, bu, w, b, layout: BagLayout, xbits=None)
     return _GatedAttentionPool.apply(x, Wv, bv, Wu, bu, w, b, layout, xbits)
 
 
+def _bag_order(layout):
+    """(lengths, perm): per-bag row counts and the int64 device index that gathers the rows of a layout bag by bag (None when
+    the bags are contiguous already).  Cached on the layout; needs its lengths on the host."""
+    lengths = getattr(layout, "lengths", None)
+    if lengths is None:
+        lengths = getattr(layout, "k_lengths", None)          # AttnSegs-shaped: the keys of each bag, contiguous
+        if lengths is None:
+            raise NotImplementedError("bag_softmax: the layout's bag lengths live on the device only (capacity bucket)")
+        return [int(v) for v in lengths], None
+    hit = getattr(layout, "_bag_order", None)
+    if hit is None:
+        rb = layout.row_bag().cpu()
+        perm = torch.argsort(rb, stable=True)
+        same = bool((perm == torch.arange(perm.numel())).all())
+        hit = layout._bag_order = ([int(v) for v in lengths], None if same else perm.to(layout.tile_map.device))
+    return hit
+
+
+def bag_softmax(scores, layout_or_segs, len_dev=None):
+    """The gated-attention pool's weights: w = softmax of `scores` [R] over the rows of each bag (mil_bag_softmax), returned bag
+    by bag - bag b at [off[b], off[b] + lengths[b]), off = cumsum of the layout's lengths, its rows in the order they have
+    in memory (a two-segment multi-modal bag: its patch rows, then its token rows).  len_dev (int32 [B], on the device): the
+    layout's lengths are slot capacities and bag b has len_dev[b] rows; the rows behind them get 0.  No gradient."""
+    scores = _f32c(scores.detach(), "scores").reshape(-1)
+    lengths, perm = _bag_order(layout_or_segs)
+    if scores.numel() != sum(lengths):
+        raise ValueError(f"bag_softmax: {scores.numel()} scores for bags of {sum(lengths)} rows")
+    if perm is not None:
+        scores = scores.index_select(0, perm)
+    off = [0]
+    for n in lengths:
+        off.append(off[-1] + n)
+    row_off = getattr(layout_or_segs, "_bag_row_off", None)
+    if row_off is None or row_off.device != scores.device:
+        row_off = torch.tensor(off, dtype=torch.int32).to(scores.device)
+        try:
+            layout_or_segs._bag_row_off = row_off
+        except AttributeError:
+            pass
+    if len_dev is not None and (not len_dev.is_cuda or len_dev.dtype != torch.int32 or len_dev.numel() != len(lengths)):
+        raise _lib.MilHipError("bag_softmax: len_dev must be int32 [B] on the GPU")
+    w = torch.empty_like(scores)
+    _lib.checked().mil_bag_softmax(_p(scores), _p(row_off), _p(len_dev), len(lengths), _p(w), _stream())
+    return w
+
+
 def gate_bwd_input_pool(gates, ds, w, Wv, Wu, dx, scores, lse, row_bag, dM, xbits=None, xscale: float = 1.0):
     """dx = a_row dM[bag(row)] + dPre [Wv; Wu] written in ONE pass (mil_gate_bwd_input_pool): the attention pool's own input
     gradient is formed in the epilogue of the gate's input-gradient product, dx is never read."""

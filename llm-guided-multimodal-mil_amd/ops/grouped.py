@@ -6,6 +6,7 @@ import torch
 from .. import _lib
 from ._base import _f32c, _p, _stream
 from .linear import colsum, linear_act
+from . import absorbed
 from .absorbed import _AbsorbQuery, _ValueProj
 
 
@@ -187,6 +188,8 @@ class _MultiTokenPoolCore(torch.autograd.Function):
         ctx.segs, ctx.TH = segs, TH
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(keys, kin, Qp, A)
+        if absorbed._site_tap is not None:             # model.note_attn: A holds the softmax weights, column t H + h
+            absorbed._site_tap.append(dict(A=A, segs=segs, TH=TH))
         return pooled, keys_in.view_as(keys_in)
 
     @staticmethod

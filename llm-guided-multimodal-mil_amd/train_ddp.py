@@ -51,6 +51,15 @@ def build_model(args):
             from .dataset import load_cohort
             names = list(load_cohort(args, "test", 1)[0].keys)
         model.save_patch_attn_to(save, names)
+    save = getattr(args, "save_note_attn", "") or ""
+    if save:
+        if args.variant != "fusion" or list(args.modality) != ["pathology"]:
+            raise ValueError("--save_note_attn needs --variant fusion --modality \"['pathology']\"")
+        names = None
+        if getattr(args, "path_data_pathology", ""):
+            from .dataset import load_cohort
+            names = list(load_cohort(args, "test", 1)[0].keys)
+        model.save_note_attn_to(save, names)
     return model
 
 

@@ -23,6 +23,9 @@ ap.add_argument("--op_tail", action="store_true", help="criterion outside the mo
 ap.add_argument("--tower_in_graph", action="store_true", help="frozen prompts: run the text tower inside the captured step "
                 "(fixed-shape form) instead of caching its output per note")
 ap.add_argument("--graph", action="store_true", help="capture fwd+bwd+Adam of the trainable part in one hipGraph")
+ap.add_argument("--note-attn", dest="note_attn", action="store_true",
+                help="eval forward (no grad, text features given) without model.note_attn, with it, without again: one process, "
+                     "per column the median of 7 timed regions of --steps forwards each, as bench_transmil.py --attn cls does")
 a = ap.parse_args()
 dev = torch.device("cuda")
 if a.coop:
@@ -48,6 +51,29 @@ else:
     from mil_amd.optim import FlatAdam
     opt = FlatAdam([p for p in model.parameters() if p.requires_grad], lr=1e-5, weight_decay=1e-7, counted=a.graph)
 crit = torch.nn.BCELoss()
+
+if a.note_attn:
+    import statistics
+    with torch.no_grad():
+        tfeat = model.clinic_extractor(ids)
+        cols = []
+        for tag, on in (("without", False), ("with", True), ("without again", False)):
+            model.note_attn = on
+            for _ in range(max(a.warmup, 1)):
+                model([x], None, text_features=tfeat)
+            regions = []
+            for _ in range(7):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    model([x], None, text_features=tfeat)
+                torch.cuda.synchronize()
+                regions.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            cols.append({"column": tag, "ms_median": round(statistics.median(regions), 4), "ms_min": round(min(regions), 4),
+                         "ms_max": round(max(regions), 4)})
+    print(json.dumps({"bench": "fusion eval forward, note_attn", "bags": a.bags, "patches": a.patches, "prompts": a.prompts,
+                      "forwards_per_region": a.steps, "columns": cols}))
+    sys.exit(0)
 
 def fwd_loss(**kw):
     if a.op_tail:
