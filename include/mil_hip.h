@@ -61,7 +61,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 10 */
+int mil_abi_version(void);   /* 11 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -937,6 +937,44 @@ typedef struct mil_gate_route {
  * ncu: compute units to plan for, <= 0: those of the current device. */
 int mil_gate_step_route(int R, int L, int C, int save_gates, int keep, int pieces, int fused_pool, int bucketed, int ncu,
                         mil_gate_route* out);
+
+/* Which kernel the generic fp32 linear launches for a shape: the plan mil_gemm / mil_gemm_rows / mil_gemm_aux and
+ * mil_linear_bwd_params(_rows) execute and their workspace queries size from, as a host-only query (no launch, no
+ * allocation; with ncu > 0 no device call at all and the MIL_G64N_SLOTS override is not read).
+ *   kernel           MIL_GEMM_KERNEL_*: NT2 k_gemm_nt2, G64 k_gemm64, G64N k_gemm64n, TAIL whole rounds without split-K then
+ *                    the rows of the last partial round on k_gemm<0, b_mode> with split-K, NT / NN / TN k_gemm<0,0> /
+ *                    <0,1> / <1,1>; for the parameter backward TN2 k_gemm_tn2 or TN_AX k_gemm<1,1,true>
+ *   S, kchunk        K splits (1: the epilogue runs in the product kernel, else in k_splitk_reduce) and the K of a split;
+ *                    TAIL: those of the last round's launch
+ *   rows_main        TAIL: rows of the whole rounds (a multiple of 128), which main_kernel (NT2, NT or NN) takes unsplit; else 0
+ *   rows_honoured    the kernel reads rows_dev itself (mil_gemm_rows otherwise clears the rows behind the bucket afterwards;
+ *                    k_gemm<1,1,true> walks every row and relies on the padding rows' zero gradients)
+ *   workspace_floats floats of workspace this route uses (0: none) */
+#define MIL_GEMM_KERNEL_NT2 0
+#define MIL_GEMM_KERNEL_G64 1
+#define MIL_GEMM_KERNEL_G64N 2
+#define MIL_GEMM_KERNEL_TAIL 3
+#define MIL_GEMM_KERNEL_NT 4
+#define MIL_GEMM_KERNEL_NN 5
+#define MIL_GEMM_KERNEL_TN 6
+#define MIL_GEMM_KERNEL_TN2 7
+#define MIL_GEMM_KERNEL_TN_AX 8
+typedef struct mil_gemm_plan {
+    int32_t kernel, S, kchunk;
+    int32_t rows_main, main_kernel;
+    int32_t rows_honoured;
+    uint64_t workspace_floats;
+} mil_gemm_plan;
+/* The arguments of mil_gemm_aux as far as the dispatch reads them.  has_residual / accumulate / aux_mode / act: as passed.
+ * has_workspace: a workspace of at least mil_gemm_workspace_floats() floats is given.  bucketed: rows_dev given
+ * (mil_gemm_rows).  aligned16: A and B are 16-byte aligned.  ncu: compute units to plan for, <= 0: those of the current
+ * device.  MIL_EINVAL for what mil_gemm refuses.  (The result type is mil_gemm_plan: C has one name space for both.) */
+int mil_gemm_route(int M, int N, int K, int a_mode, int b_mode, int lda, int ldb, int ldc, int act, int has_residual,
+                   int accumulate, int aux_mode, int has_workspace, int bucketed, int aligned16, int ncu, mil_gemm_plan* out);
+/* The same for mil_linear_bwd_params(_rows): dW [n_out, k_in] from `rows` rows.  ldy: 0 without a saved output.
+ * aligned16: dY, Y and X are 16-byte aligned. */
+int mil_linear_bwd_params_route(int rows, int n_out, int k_in, int lddy, int ldy, int ldx, int aligned16, int ncu,
+                                mil_gemm_plan* out);
 
 /* torch.nn.CosineEmbeddingLoss()(x1, x2, target = +1), mean over the B rows, forward + backward in one launch: the optional
  * 'textCosSim' term between the text-aligned tokens x_CT2CI and x_Pth2CI (reference train_ddp.py:102,266,325-329).

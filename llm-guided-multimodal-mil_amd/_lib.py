@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -62,6 +62,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_image_only_step_run": (c_int, [_P, _P]),
     "mil_image_only_step_time": (c_int, [_P, c_uint32, c_int, c_int, _P, _P]),
     "mil_gate_step_route": (c_int, [c_int] * 9 + [_P]),
+    "mil_gemm_route": (c_int, [c_int] * 16 + [_P]),
+    "mil_linear_bwd_params_route": (c_int, [c_int] * 8 + [_P]),
     "mil_image_only_step_profile": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "mil_image_only_step_profile_rot": (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "mil_patch_drop_select": (c_int, [_P, _P, _P, c_int, c_int, c_uint64, c_uint64, _P, _P]),
@@ -213,6 +215,16 @@ class GateRoute(ctypes.Structure):
     header by tests/test_abi.py."""
     _fields_ = [(n, c_int32) for n in ("main", "rt", "tail", "tail_rows", "tail_kernel", "tail_rt", "bits", "pool_fused",
                                        "dw", "S", "kc")]
+
+
+class GemmPlan(ctypes.Structure):
+    """Mirror of mil_gemm_plan (include/mil_hip.h, with the MIL_GEMM_KERNEL_* values of `kernel`); layout checked against
+    the header by tests/test_abi.py."""
+    _fields_ = [(n, c_int32) for n in ("kernel", "S", "kchunk", "rows_main", "main_kernel", "rows_honoured")] + \
+               [("workspace_floats", c_uint64)]
+
+
+GEMM_KERNELS = ("NT2", "G64", "G64N", "TAIL", "NT", "NN", "TN", "TN2", "TN_AX")       # MIL_GEMM_KERNEL_* by value
 
 
 SMALL_DW_MAX = 32

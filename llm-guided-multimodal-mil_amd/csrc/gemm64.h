@@ -334,16 +334,21 @@ void k_gemm64n(const float* __restrict__ A, int lda, const float* __restrict__ B
     }
 }
 
+// workgroups the k_gemm64n plan aims at on the current device: one per CU, or MIL_G64N_SLOTS (an A/B switch, read once)
+static int g64n_slots_of_device() {
+    static const int slots = getenv("MIL_G64N_SLOTS") ? atoi(getenv("MIL_G64N_SLOTS")) : MIL_NUM_CU;
+    return slots;
+}
+
 // plan for k_gemm64n: products of at most 2048 rows whose 64 x 128 tiles would not fill 1.5 rounds; S = K splits
-static bool small_tile_plan(int M, int N, int K, int a_mode, int* S_out, int* kchunk_out) {
+static bool small_tile_plan(int M, int N, int K, int a_mode, int ncu, int slots, int* S_out, int* kchunk_out) {
     if (a_mode != 0 || M > 2048 || K < 256 || (K % LG_BK) != 0 || (N & 3)) return false;
     const long t128 = (long)((M + 63) / 64) * ((N + 127) / 128);
-    if (t128 >= 3 * MIL_NUM_CU / 2) return false;                  // k_gemm64 takes it
+    if (t128 >= 3 * ncu / 2) return false;                         // k_gemm64 takes it
     const long t = (long)((M + 63) / 64) * ((N + 63) / 64);
     if (t < 16) return false;                                      // a handful of tiles: the split-K plan of the big tile
-    // target number of workgroups: one per CU (end to end, the learnable-prompt step of one ragged bag: 7.33 / 6.83 / 6.80 /
-    // 7.07 / 7.11 ms at 128 / 192 / 256 / 320 / 512 - a split costs its partial tiles and the fold launch)
-    static const int slots = getenv("MIL_G64N_SLOTS") ? atoi(getenv("MIL_G64N_SLOTS")) : MIL_NUM_CU;
+    // target number of workgroups (slots): one per CU (end to end, the learnable-prompt step of one ragged bag: 7.33 / 6.83 /
+    // 6.80 / 7.07 / 7.11 ms at 128 / 192 / 256 / 320 / 512 - a split costs its partial tiles and the fold launch)
     int S = (int)((slots + t / 2) / t);
     if (S > K / 256) S = K / 256;                                  // at least eight 32-deep slices per split
     if (S < 1) S = 1;

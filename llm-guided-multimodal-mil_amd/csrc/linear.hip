@@ -425,14 +425,14 @@ __global__ __launch_bounds__(256) void k_act_bwd(const float* __restrict__ dy, c
 // Split-K policy.  Weight gradients (a_mode 1: K = number of rows) always split to fill the chip.  The other forms
 // split only when the output is a handful of tiles (token-side projections: M = bags x text tokens <= a few dozen
 // rows), where a single 128 x 128 workgroup per tile would walk all of K alone: 30-60 us of latency for <0.1 GFLOP.
-static int splitk_plan(int M, int N, int K, int a_mode, int* kchunk_out) {
+static int splitk_plan(int M, int N, int K, int a_mode, int ncu, int* kchunk_out) {
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     int S;
     if (a_mode == 1) {
-        S = (2 * MIL_NUM_CU) / (tiles > 0 ? tiles : 1);
+        S = (2 * ncu) / (tiles > 0 ? tiles : 1);
     } else {
         if (K < 256) { *kchunk_out = K; return 1; }
-        const int slots = 2 * MIL_NUM_CU;
+        const int slots = 2 * ncu;
         if (tiles > 32) {
             // One partial round of the 512 resident workgroups (e.g. 10 K text-tower rows x N = 512 = 324 tiles): a round costs
             // its full K walk however empty it is, so splitting K into S makes it ceil(tiles S / slots) / S of that - if
@@ -465,9 +465,9 @@ static int splitk_plan(int M, int N, int K, int a_mode, int* kchunk_out) {
 // tiles, and a last round that is mostly empty still costs a whole round (M = 24 640 text-tower rows x N = 512:
 // 772 tiles = 1.5 rounds -> 2).  The rows of that last partial round are issued as a second launch with split-K
 // chosen to fill the round (772 -> 512 + 260 x 2), its partials folded by k_splitk_reduce with the epilogue.
-static bool tail_plan(int M, int N, int K, int a_mode, int* rows_main, int* S_out, int* kchunk_out) {
+static bool tail_plan(int M, int N, int K, int a_mode, int ncu, int* rows_main, int* S_out, int* kchunk_out) {
     if (a_mode != 0) return false;
-    const int slots = 2 * MIL_NUM_CU;
+    const int slots = 2 * ncu;
     const int ct = (N + 127) / 128, rt = (M + 127) / 128;
     if (ct > slots || (long)rt * ct <= slots) return false;
     const int per_round = slots / ct;
@@ -493,16 +493,115 @@ static bool tail_plan(int M, int N, int K, int a_mode, int* rows_main, int* S_ou
     return true;
 }
 
+// ---- the route plan: which kernel a product takes, decided here and nowhere else (mil_gemm_route, include/mil_hip.h).
+// Pure host arithmetic: no HIP call, the CU count and k_gemm64n's workgroup target come in as parameters.  gemm_impl launches
+// from it, mil_gemm_workspace_floats sizes from it.
+struct GemmPlanIn {
+    int M, N, K, a_mode, b_mode, lda, ldb, ldc, act, aux_mode;
+    bool residual, accumulate, bucketed, aligned16;
+    size_t ws_floats;       // floats of workspace given (0: none)
+};
+// tall NT product whose 256 x 256 tiles fill whole rounds of the chip (fc_pathology: 32 768 x 512 = 256 tiles): at least 3/4 of
+// one round, and 7/8 of the rounds it takes
+static bool nt2_fills(int M, int N, int ncu) {
+    const long tiles = (long)((M + 255) / 256) * (N / 256);
+    const long rounds = (tiles + ncu - 1) / ncu;
+    return tiles >= (3 * ncu) / 4 && 8 * tiles >= 7 * rounds * ncu;
+}
+static mil_gemm_plan gemm_plan(const GemmPlanIn& in, int ncu, int g64n_slots) {
+    const int M = in.M, N = in.N, K = in.K;
+    mil_gemm_plan p{};
+    p.S = 1;
+    p.kchunk = K;
+    if (in.a_mode == 0 && in.b_mode == 0 && !in.residual && !in.accumulate && in.aux_mode == AUX_NONE && in.act <= ACT_RELU &&
+        in.ldc >= N && mil_gemm_nt2_ok(in.lda, in.ldb, M, N, K) && in.aligned16 && !in.bucketed && nt2_fills(M, N, ncu)) {
+        p.kernel = MIL_GEMM_KERNEL_NT2;             // the low-VALU LDS-DMA kernel (linear_nt2.hip)
+        return p;
+    }
+    if (in.a_mode == 0) {
+        // Tall products take 64 x 128 tiles (gemm64.h: three workgroups per CU = 768 slots) as soon as those fill half
+        // of the chip: finer rounds and a third resident workgroup beat the 128-row tile on every shape measured
+        // (tools/kbench_gemm64.py, kbench_gemm_k.py: 10 300 x 2048 x 512 241 -> 199 us, x 512 x 512 85 -> 65, 32 768 x 512 x 384
+        // 137 -> 126, x 1536 equal), and no product of this kind needs split-K or the split last round any more.
+        const long ct = (N + 127) / 128, t64 = ((M + 63) / 64) * ct;
+        if ((t64 >= 3 * ncu / 2 || (in.bucketed && t64 >= ncu / 2 && (N & 3) == 0)) && K >= 256) {
+            p.kernel = MIL_GEMM_KERNEL_G64;
+            p.rows_honoured = 1;
+            return p;
+        }
+    }
+    {
+        // a few hundred rows: 64 x 64 tiles, K split over blockIdx.z when the tiles alone leave CUs idle (gemm64.h)
+        int S64, kc64;
+        if (small_tile_plan(M, N, K, in.a_mode, ncu, g64n_slots, &S64, &kc64) && (S64 == 1 || in.ws_floats >= (size_t)S64 * M * N)) {
+            p.kernel = MIL_GEMM_KERNEL_G64N;
+            p.S = S64;
+            p.kchunk = kc64;
+            p.workspace_floats = S64 > 1 ? (uint64_t)S64 * M * N : 0;
+            return p;
+        }
+    }
+    {
+        // whole rounds without split-K, then the rows of the last partial round with split-K
+        int rows_main, S_tail, kc_tail;
+        if (in.ws_floats > 0 && tail_plan(M, N, K, in.a_mode, ncu, &rows_main, &S_tail, &kc_tail) &&
+            in.ws_floats >= (size_t)S_tail * (M - rows_main) * N) {
+            GemmPlanIn main = in;
+            main.M = rows_main;
+            main.ws_floats = 0;
+            main.bucketed = false;
+            p.kernel = MIL_GEMM_KERNEL_TAIL;
+            p.S = S_tail;
+            p.kchunk = kc_tail;
+            p.rows_main = rows_main;
+            p.main_kernel = gemm_plan(main, ncu, g64n_slots).kernel;
+            p.workspace_floats = (uint64_t)S_tail * (M - rows_main) * N;
+            return p;
+        }
+    }
+    p.kernel = in.a_mode == 1 ? MIL_GEMM_KERNEL_TN : in.b_mode == 0 ? MIL_GEMM_KERNEL_NT : MIL_GEMM_KERNEL_NN;
+    if (in.ws_floats > 0) {
+        int kc;
+        const int want = splitk_plan(M, N, K, in.a_mode, ncu, &kc);
+        if (want > 1 && in.ws_floats >= (size_t)want * M * N) {
+            p.S = want;
+            p.kchunk = kc;
+            p.workspace_floats = (uint64_t)want * M * N;
+        }
+    }
+    return p;
+}
+
+// what mil_gemm / mil_gemm_rows / mil_gemm_aux refuse
+static int gemm_check(int M, int N, int K, int a_mode, int b_mode, int lda, int ldb, int act) {
+    if (M < 0 || N < 0 || K <= 0) return MIL_EINVAL;
+    if ((lda & 3) || (ldb & 3) || act < 0 || act > 3) return MIL_EINVAL;
+    if (a_mode == 0 && (K % LG_BK) != 0) return MIL_EINVAL;        // k-contiguous operands: whole slices only
+    if (b_mode == 0 && (K % LG_BK) != 0) return MIL_EINVAL;
+    if (a_mode == 1 && (M < 4 || (M & 3))) return MIL_EINVAL;      // k-major operands: 16-byte columns
+    if (b_mode == 1 && (N < 4 || (N & 3))) return MIL_EINVAL;
+    if (a_mode == 1 && b_mode == 0) return MIL_EINVAL;             // TT form is never needed
+    return MIL_OK;
+}
+
+// The largest need over every call of this shape: a residual rules the NT2 kernel out, and a bucket only widens k_gemm64's
+// range (neither of the two uses a workspace), so the plan of such a call with every workspace on offer is the bound.
 extern "C" size_t mil_gemm_workspace_floats(int M, int N, int K, int a_mode) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    int kchunk, rows_main, S_tail;
-    {
-        int S64;
-        if (small_tile_plan(M, N, K, a_mode, &S64, &kchunk)) return S64 > 1 ? (size_t)S64 * M * N : 0;
-    }
-    if (tail_plan(M, N, K, a_mode, &rows_main, &S_tail, &kchunk)) return (size_t)S_tail * (M - rows_main) * N;
-    const int S = splitk_plan(M, N, K, a_mode, &kchunk);
-    return S > 1 ? (size_t)S * M * N : 0;
+    const GemmPlanIn in{M, N, K, a_mode, 1, K, N, N, ACT_NONE, AUX_NONE, true, false, false, true, SIZE_MAX};
+    return (size_t)gemm_plan(in, MIL_NUM_CU, g64n_slots_of_device()).workspace_floats;
+}
+
+extern "C" int mil_gemm_route(int M, int N, int K, int a_mode, int b_mode, int lda, int ldb, int ldc, int act, int has_residual,
+                              int accumulate, int aux_mode, int has_workspace, int bucketed, int aligned16, int ncu,
+                              mil_gemm_plan* out) {
+    if (!out || M <= 0 || N <= 0 || (a_mode != 0 && a_mode != 1) || (b_mode != 0 && b_mode != 1)) return MIL_EINVAL;
+    if (gemm_check(M, N, K, a_mode, b_mode, lda, ldb, act) != MIL_OK) return MIL_EINVAL;
+    if (aux_mode < 0 || aux_mode > 2 || (a_mode != 0 && (aux_mode != AUX_NONE || bucketed))) return MIL_EINVAL;
+    const GemmPlanIn in{M, N, K, a_mode, b_mode, lda, ldb, ldc, act, aux_mode, has_residual != 0, accumulate != 0, bucketed != 0,
+                        aligned16 != 0, has_workspace ? SIZE_MAX : 0};
+    *out = ncu > 0 ? gemm_plan(in, ncu, ncu) : gemm_plan(in, MIL_NUM_CU, g64n_slots_of_device());
+    return MIL_OK;
 }
 
 static int gemm_impl(const float* A, int lda, int a_mode, const float* B, int ldb, int b_mode, float* C, int ldc, int M,
@@ -511,103 +610,83 @@ static int gemm_impl(const float* A, int lda, int a_mode, const float* B, int ld
                      const int32_t* rows_dev = nullptr, int* rows_honoured = nullptr) {
     if (!A || !B || !C || M < 0 || N < 0 || K <= 0) return MIL_EINVAL;
     if (M == 0 || N == 0) return MIL_OK;
-    if ((lda & 3) || (ldb & 3) || act < 0 || act > 3) return MIL_EINVAL;
-    if (a_mode == 0 && (K % LG_BK) != 0) return MIL_EINVAL;        // k-contiguous operands: whole slices only
-    if (b_mode == 0 && (K % LG_BK) != 0) return MIL_EINVAL;
-    if (a_mode == 1 && (M < 4 || (M & 3))) return MIL_EINVAL;      // k-major operands: 16-byte columns
-    if (b_mode == 1 && (N < 4 || (N & 3))) return MIL_EINVAL;
-    if (a_mode == 1 && b_mode == 0) return MIL_EINVAL;             // TT form is never needed
+    {
+        const int rc = gemm_check(M, N, K, a_mode, b_mode, lda, ldb, act);
+        if (rc != MIL_OK) return rc;
+    }
     hipStream_t st = (hipStream_t)stream;
-    if (a_mode == 0 && b_mode == 0 && residual == nullptr && !accumulate && aux_mode == AUX_NONE && act <= ACT_RELU &&
-        ldc >= N && mil_gemm_nt2_ok(lda, ldb, M, N, K) && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0) {
-        // tall NT product whose 256 x 256 tiles fill whole rounds of the chip (fc_pathology: 32 768 x 512 = 256 tiles): the
-        // low-VALU LDS-DMA kernel (linear_nt2.hip)
-        const long tiles = (long)((M + 255) / 256) * (N / 256);
-        const long rounds = (tiles + MIL_NUM_CU - 1) / MIL_NUM_CU;
-        if (rows_dev == nullptr && tiles >= (3 * MIL_NUM_CU) / 4 && 8 * tiles >= 7 * rounds * MIL_NUM_CU)
-            return mil_gemm_nt2(A, lda, B, ldb, C, ldc, M, N, K, bias, act, stream);
+    const GemmPlanIn in{M, N, K, a_mode, b_mode, lda, ldb, ldc, act, aux_mode, residual != nullptr, accumulate != 0,
+                        rows_dev != nullptr, ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0,
+                        workspace != nullptr ? workspace_floats : 0};
+    const mil_gemm_plan p = gemm_plan(in, MIL_NUM_CU, g64n_slots_of_device());
+    const GemmGroups nogroups{nullptr, 0, 0, 0, GRP_NONE, 1};
+    switch (p.kernel) {
+    case MIL_GEMM_KERNEL_NT2:
+        return mil_gemm_nt2(A, lda, B, ldb, C, ldc, M, N, K, bias, act, stream);
+    case MIL_GEMM_KERNEL_G64: {
+        const dim3 grid((unsigned)((N + 127) / 128), (M + 63) / 64);
+        if (b_mode == 0)
+            hipLaunchKernelGGL(k_gemm64<0>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode, rows_dev);
+        else
+            hipLaunchKernelGGL(k_gemm64<1>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode, rows_dev);
+        MIL_CHECK_LAUNCH();
+        if (rows_honoured != nullptr) *rows_honoured = 1;
+        return MIL_OK;
     }
-    if (a_mode == 0) {
-        // Tall products take 64 x 128 tiles (gemm64.h: three workgroups per CU = 768 slots) as soon as those fill half
-        // of the chip: finer rounds and a third resident workgroup beat the 128-row tile on every shape measured
-        // (tools/kbench_gemm64.py, kbench_gemm_k.py: 10 300 x 2048 x 512 241 -> 199 us, x 512 x 512 85 -> 65, 32 768 x 512 x 384
-        // 137 -> 126, x 1536 equal), and no product of this kind needs split-K or the split last round any more.
-        const long ct = (N + 127) / 128, t64 = ((M + 63) / 64) * ct;
-        if ((t64 >= 3 * MIL_NUM_CU / 2 || (rows_dev != nullptr && t64 >= MIL_NUM_CU / 2 && (N & 3) == 0)) && K >= 256) {
-            const dim3 grid((unsigned)ct, (M + 63) / 64);
-            if (b_mode == 0)
-                hipLaunchKernelGGL(k_gemm64<0>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode, rows_dev);
-            else
-                hipLaunchKernelGGL(k_gemm64<1>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode, rows_dev);
+    case MIL_GEMM_KERNEL_G64N: {
+        const dim3 grid((N + 63) / 64, (M + 63) / 64, p.S);
+        float* part = p.S > 1 ? workspace : nullptr;
+        if (b_mode == 0)
+            hipLaunchKernelGGL(k_gemm64n<0>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.kchunk, part, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode);
+        else
+            hipLaunchKernelGGL(k_gemm64n<1>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.kchunk, part, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode);
+        MIL_CHECK_LAUNCH();
+        if (p.S > 1) {
+            const size_t n = (size_t)M * N;
+            hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, p.S, C, ldc, M, N, bias,
+                               act, residual, ldr, accumulate, aux, ldaux, aux_mode);
             MIL_CHECK_LAUNCH();
-            if (rows_honoured != nullptr) *rows_honoured = 1;
-            return MIL_OK;
         }
+        return MIL_OK;
     }
-    {
-        // a few hundred rows: 64 x 64 tiles, K split over blockIdx.z when the tiles alone leave CUs idle (gemm64.h)
-        int S64, kc64;
-        if (small_tile_plan(M, N, K, a_mode, &S64, &kc64) && (S64 == 1 || (workspace != nullptr && workspace_floats >= (size_t)S64 * M * N))) {
-            const dim3 grid((N + 63) / 64, (M + 63) / 64, S64);
-            float* part = S64 > 1 ? workspace : nullptr;
-            if (b_mode == 0)
-                hipLaunchKernelGGL(k_gemm64n<0>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, kc64, part, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode);
-            else
-                hipLaunchKernelGGL(k_gemm64n<1>, grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, kc64, part, bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode);
-            MIL_CHECK_LAUNCH();
-            if (S64 > 1) {
-                const size_t n = (size_t)M * N;
-                hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, S64, C, ldc, M, N, bias,
-                                   act, residual, ldr, accumulate, aux, ldaux, aux_mode);
-                MIL_CHECK_LAUNCH();
-            }
-            return MIL_OK;
-        }
+    case MIL_GEMM_KERNEL_TAIL: {
+        // whole rounds without split-K (the plan's main_kernel: the same plan function on rows_main rows and no workspace)
+        const int rows_main = p.rows_main;
+        int rc = gemm_impl(A, lda, a_mode, B, ldb, b_mode, C, ldc, rows_main, N, K, bias, act, residual, ldr, accumulate,
+                           nullptr, 0, aux, ldaux, aux_mode, stream);
+        if (rc != MIL_OK) return rc;
+        const int Mt = M - rows_main;
+        const float* At = A + (size_t)rows_main * lda;
+        float* Ct = C + (size_t)rows_main * ldc;
+        const float* Rt = residual ? residual + (size_t)rows_main * ldr : nullptr;
+        float* Xt = aux ? aux + (size_t)rows_main * ldaux : nullptr;
+        const dim3 gridt((N + 127) / 128, (Mt + 127) / 128, p.S);
+        if (b_mode == 0)
+            hipLaunchKernelGGL((k_gemm<0, 0>), gridt, dim3(256), 0, st, At, lda, B, ldb, Ct, ldc, Mt, N, K, p.kchunk, bias, act, Rt, ldr, accumulate, workspace, Xt, ldaux, aux_mode, nogroups);
+        else
+            hipLaunchKernelGGL((k_gemm<0, 1>), gridt, dim3(256), 0, st, At, lda, B, ldb, Ct, ldc, Mt, N, K, p.kchunk, bias, act, Rt, ldr, accumulate, workspace, Xt, ldaux, aux_mode, nogroups);
+        MIL_CHECK_LAUNCH();
+        const size_t n = (size_t)Mt * N;
+        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, p.S, Ct, ldc,
+                           Mt, N, bias, act, Rt, ldr, accumulate, Xt, ldaux, aux_mode);
+        MIL_CHECK_LAUNCH();
+        return MIL_OK;
     }
-    {
-        int rows_main, S_tail, kc_tail;
-        if (workspace != nullptr && tail_plan(M, N, K, a_mode, &rows_main, &S_tail, &kc_tail) &&
-            workspace_floats >= (size_t)S_tail * (M - rows_main) * N) {
-            // whole rounds without split-K, then the rows of the last partial round with split-K
-            int rc = gemm_impl(A, lda, a_mode, B, ldb, b_mode, C, ldc, rows_main, N, K, bias, act, residual, ldr, accumulate,
-                               nullptr, 0, aux, ldaux, aux_mode, stream);
-            if (rc != MIL_OK) return rc;
-            const int Mt = M - rows_main;
-            const float* At = A + (size_t)rows_main * lda;
-            float* Ct = C + (size_t)rows_main * ldc;
-            const float* Rt = residual ? residual + (size_t)rows_main * ldr : nullptr;
-            float* Xt = aux ? aux + (size_t)rows_main * ldaux : nullptr;
-            const dim3 gridt((N + 127) / 128, (Mt + 127) / 128, S_tail);
-            if (b_mode == 0)
-                hipLaunchKernelGGL((k_gemm<0, 0>), gridt, dim3(256), 0, st, At, lda, B, ldb, Ct, ldc, Mt, N, K, kc_tail, bias, act, Rt, ldr, accumulate, workspace, Xt, ldaux, aux_mode, GemmGroups{nullptr, 0, 0, 0, GRP_NONE, 1});
-            else
-                hipLaunchKernelGGL((k_gemm<0, 1>), gridt, dim3(256), 0, st, At, lda, B, ldb, Ct, ldc, Mt, N, K, kc_tail, bias, act, Rt, ldr, accumulate, workspace, Xt, ldaux, aux_mode, GemmGroups{nullptr, 0, 0, 0, GRP_NONE, 1});
-            MIL_CHECK_LAUNCH();
-            const size_t n = (size_t)Mt * N;
-            hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, workspace, S_tail, Ct, ldc,
-                               Mt, N, bias, act, Rt, ldr, accumulate, Xt, ldaux, aux_mode);
-            MIL_CHECK_LAUNCH();
-            return MIL_OK;
-        }
+    default:
+        break;
     }
-    int S = 1, kchunk = K;
-    float* partial = nullptr;
-    if (workspace != nullptr) {
-        int kc;
-        const int want = splitk_plan(M, N, K, a_mode, &kc);
-        if (want > 1 && workspace_floats >= (size_t)want * M * N) { S = want; kchunk = kc; partial = workspace; }
-    }
-    dim3 grid((N + 127) / 128, (M + 127) / 128, S);
-    if (a_mode == 0 && b_mode == 0)
-        hipLaunchKernelGGL((k_gemm<0, 0>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, kchunk, bias, act, residual, ldr, accumulate, partial, aux, ldaux, aux_mode, GemmGroups{nullptr, 0, 0, 0, GRP_NONE, 1});
-    else if (a_mode == 0 && b_mode == 1)
-        hipLaunchKernelGGL((k_gemm<0, 1>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, kchunk, bias, act, residual, ldr, accumulate, partial, aux, ldaux, aux_mode, GemmGroups{nullptr, 0, 0, 0, GRP_NONE, 1});
+    float* partial = p.S > 1 ? workspace : nullptr;
+    dim3 grid((N + 127) / 128, (M + 127) / 128, p.S);
+    if (p.kernel == MIL_GEMM_KERNEL_NT)
+        hipLaunchKernelGGL((k_gemm<0, 0>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.kchunk, bias, act, residual, ldr, accumulate, partial, aux, ldaux, aux_mode, nogroups);
+    else if (p.kernel == MIL_GEMM_KERNEL_NN)
+        hipLaunchKernelGGL((k_gemm<0, 1>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.kchunk, bias, act, residual, ldr, accumulate, partial, aux, ldaux, aux_mode, nogroups);
     else
-        hipLaunchKernelGGL((k_gemm<1, 1>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, kchunk, bias, act, residual, ldr, accumulate, partial, aux, ldaux, aux_mode, GemmGroups{nullptr, 0, 0, 0, GRP_NONE, 1});
+        hipLaunchKernelGGL((k_gemm<1, 1>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.kchunk, bias, act, residual, ldr, accumulate, partial, aux, ldaux, aux_mode, nogroups);
     MIL_CHECK_LAUNCH();
     if (partial != nullptr) {
         const size_t n = (size_t)M * N;
-        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, partial, S, C, ldc, M, N,
+        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, partial, p.S, C, ldc, M, N,
                            bias, act, residual, ldr, accumulate, aux, ldaux, aux_mode);
         MIL_CHECK_LAUNCH();
     }
@@ -668,15 +747,41 @@ extern "C" int mil_gemm_aux(const float* A, int lda, int a_mode, const float* B,
 }
 
 // dW[N_out, K_in] (+)= (dY (.) act'(Y))^T . X,   db[N_out] (+)= column sums of dY (.) act'(Y):  the parameter half of a
-// Linear layer's backward in one product launch + its split-K fold.
+// Linear layer's backward in one product launch + its split-K fold.  The plan (mil_linear_bwd_params_route): tall
+// activations with whole 128 x 128 output tiles take the low-VALU split-rows kernel (linear_nt2.hip), everything else
+// k_gemm<1,1,true>; both leave partial [S][n_out][k_in] and column-sum partials [S][n_out] in the workspace.
+static mil_gemm_plan bwd_params_plan(int rows, int n_out, int k_in, int lddy, int ldy, int ldx, bool aligned16, int ncu) {
+    mil_gemm_plan p{};
+    int kc;
+    if (aligned16 && gemm_tn2_ok(lddy, ldy ? ldy : lddy, ldx, rows, n_out, k_in, ncu)) {
+        p.kernel = MIL_GEMM_KERNEL_TN2;
+        p.S = gemm_tn2_plan(rows, n_out, k_in, ncu, &kc);
+        p.rows_honoured = 1;
+    } else {
+        p.kernel = MIL_GEMM_KERNEL_TN_AX;
+        p.S = splitk_plan(n_out, k_in, rows, 1, ncu, &kc);
+        if (p.S < 1) { p.S = 1; kc = rows; }
+    }
+    p.kchunk = kc;
+    p.workspace_floats = (uint64_t)p.S * n_out * k_in + (uint64_t)p.S * n_out;
+    return p;
+}
+
+// the larger of the two kernels' needs: which one runs depends on the leading dimensions and the alignment of the call
 extern "C" size_t mil_linear_bwd_params_workspace_floats(int rows, int n_out, int k_in) {
     if (rows <= 0 || n_out <= 0 || k_in <= 0) return 0;
-    int kc;
-    int S = splitk_plan(n_out, k_in, rows, 1, &kc);
-    if (S < 1) S = 1;
-    const int S2 = mil_gemm_tn2_splits(rows, n_out, k_in);         // the low-VALU kernel's own row split (linear_nt2.hip)
-    if (S2 > S) S = S2;
-    return (size_t)S * n_out * k_in + (size_t)S * n_out;
+    const int ncu = MIL_NUM_CU;
+    const uint64_t a = bwd_params_plan(rows, n_out, k_in, n_out, 0, k_in, true, ncu).workspace_floats;
+    const uint64_t b = bwd_params_plan(rows, n_out, k_in, n_out, 0, k_in, false, ncu).workspace_floats;
+    return (size_t)(a > b ? a : b);
+}
+
+extern "C" int mil_linear_bwd_params_route(int rows, int n_out, int k_in, int lddy, int ldy, int ldx, int aligned16, int ncu,
+                                           mil_gemm_plan* out) {
+    if (!out || rows <= 0 || n_out < 4 || (n_out & 3) || k_in < 4 || (k_in & 3)) return MIL_EINVAL;
+    if ((lddy & 3) || (ldx & 3) || (ldy & 3)) return MIL_EINVAL;
+    *out = bwd_params_plan(rows, n_out, k_in, lddy, ldy, ldx, aligned16 != 0, ncu > 0 ? ncu : MIL_NUM_CU);
+    return MIL_OK;
 }
 
 // rows_dev (nullable): device int32 with the true number of rows (<= rows: the capacity of a bucket) - the rows behind it
@@ -690,34 +795,25 @@ extern "C" int mil_linear_bwd_params_rows(const float* dY, int lddy, const float
     if (act != ACT_NONE && Y == nullptr) return MIL_EINVAL;
     if (workspace_floats < mil_linear_bwd_params_workspace_floats(rows, n_out, k_in)) return MIL_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
-    if (mil_gemm_tn2_ok(lddy, Y ? ldy : lddy, ldx, rows, n_out, k_in) &&
-        ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0) {
+    const bool aligned16 = ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0;
+    const mil_gemm_plan p = bwd_params_plan(rows, n_out, k_in, lddy, Y ? ldy : 0, ldx, aligned16, MIL_NUM_CU);
+    float* partial = workspace;
+    float* cs_part = db != nullptr ? workspace + (size_t)p.S * n_out * k_in : nullptr;
+    if (p.kernel == MIL_GEMM_KERNEL_TN2) {
         // tall activation, whole 128 x 128 output tiles: the low-VALU split-rows kernel (linear_nt2.hip), same partial layout
-        const int S2 = mil_gemm_tn2_splits(rows, n_out, k_in);
-        float* cs2 = db != nullptr ? workspace + (size_t)S2 * n_out * k_in : nullptr;
-        int rc = mil_gemm_tn2_rows(dY, lddy, act != ACT_NONE ? Y : nullptr, ldy, act, X, ldx, rows, n_out, k_in, workspace, cs2,
+        int rc = mil_gemm_tn2_rows(dY, lddy, act != ACT_NONE ? Y : nullptr, ldy, act, X, ldx, rows, n_out, k_in, partial, cs_part,
                                    rows_dev, stream);
         if (rc != MIL_OK) return rc;
-        const size_t n2 = (size_t)n_out * k_in;
-        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, workspace, S2, dW, lddw, n_out,
-                           k_in, (const float*)nullptr, 0, (const float*)nullptr, 0, accumulate, (float*)nullptr, 0, 0,
-                           (const float*)cs2, db, accumulate);
+    } else {
+        const GemmExtra ex{act != ACT_NONE ? Y : nullptr, cs_part, ldy, act};
+        const dim3 grid((k_in + 127) / 128, (n_out + 127) / 128, p.S);
+        hipLaunchKernelGGL((k_gemm<1, 1, true>), grid, dim3(256), 0, st, dY, lddy, X, ldx, dW, lddw, n_out, k_in, rows, p.kchunk,
+                           (const float*)nullptr, 0, (const float*)nullptr, 0, accumulate, partial, (float*)nullptr, 0, 0,
+                           GemmGroups{nullptr, 0, 0, 0, GRP_NONE, 1}, ex);
         MIL_CHECK_LAUNCH();
-        return MIL_OK;
     }
-    int kchunk;
-    int S = splitk_plan(n_out, k_in, rows, 1, &kchunk);
-    if (S < 1) { S = 1; kchunk = rows; }
-    float* partial = workspace;
-    float* cs_part = db != nullptr ? workspace + (size_t)S * n_out * k_in : nullptr;
-    const GemmExtra ex{act != ACT_NONE ? Y : nullptr, cs_part, ldy, act};
-    const dim3 grid((k_in + 127) / 128, (n_out + 127) / 128, S);
-    hipLaunchKernelGGL((k_gemm<1, 1, true>), grid, dim3(256), 0, st, dY, lddy, X, ldx, dW, lddw, n_out, k_in, rows, kchunk,
-                       (const float*)nullptr, 0, (const float*)nullptr, 0, accumulate, partial, (float*)nullptr, 0, 0,
-                       GemmGroups{nullptr, 0, 0, 0, GRP_NONE, 1}, ex);
-    MIL_CHECK_LAUNCH();
     const size_t n = (size_t)n_out * k_in;
-    hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, partial, S, dW, lddw, n_out, k_in,
+    hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, partial, p.S, dW, lddw, n_out, k_in,
                        (const float*)nullptr, 0, (const float*)nullptr, 0, accumulate, (float*)nullptr, 0, 0,
                        (const float*)cs_part, db, accumulate);
     MIL_CHECK_LAUNCH();

@@ -371,10 +371,10 @@ __global__ __launch_bounds__(512) void k_gemm_tn2(const float* __restrict__ dY, 
     }
 }
 
-static inline int tn2_plan(int rows, int N, int K, int* KC_out) {
+int gemm_tn2_plan(int rows, int N, int K, int ncu, int* KC_out) {
     const int tiles = (N / 128) * (K / 128);
     if (tiles <= 0 || rows <= 0) { *KC_out = 2 * TN2_BKR; return 0; }   // not a shape of this kernel
-    int smax = MIL_NUM_CU / tiles;                 // one 512-thread workgroup per CU
+    int smax = ncu / tiles;                        // one 512-thread workgroup per CU
     if (smax < 1) smax = 1;
     int kc = ((rows + smax - 1) / smax + 2 * TN2_BKR - 1) / (2 * TN2_BKR) * (2 * TN2_BKR);
     if (kc < 2 * TN2_BKR) kc = 2 * TN2_BKR;
@@ -384,18 +384,21 @@ static inline int tn2_plan(int rows, int N, int K, int* KC_out) {
 
 // 1 when mil_linear_bwd_params should take this kernel: whole 128-tiles, a row chunk deep enough for the two K groups, offsets
 // inside 31 bits, and at least 3/4 of the chip busy.
-extern "C" int mil_gemm_tn2_ok(int lddy, int ldy, int ldx, int rows, int N, int K) {
+int gemm_tn2_ok(int lddy, int ldy, int ldx, int rows, int N, int K, int ncu) {
     if (rows < 4096 || N <= 0 || K <= 0 || (N % 128) != 0 || (K % 128) != 0 || (lddy & 3) || (ldy & 3) || (ldx & 3)) return 0;
     int kc;
-    const int S = tn2_plan(rows, N, K, &kc);
+    const int S = gemm_tn2_plan(rows, N, K, ncu, &kc);
     if ((long long)kc * (lddy > ldx ? lddy : ldx) * 4 >= 0x7fff0000ll || (long long)kc * ldy * 4 >= 0x7fff0000ll) return 0;
-    if ((long)S * (N / 128) * (K / 128) * 4 < 3 * MIL_NUM_CU || kc < 512) return 0;
+    if ((long)S * (N / 128) * (K / 128) * 4 < 3 * ncu || kc < 512) return 0;
     return 1;
+}
+extern "C" int mil_gemm_tn2_ok(int lddy, int ldy, int ldx, int rows, int N, int K) {
+    return gemm_tn2_ok(lddy, ldy, ldx, rows, N, K, MIL_NUM_CU);
 }
 extern "C" int mil_gemm_tn2_splits(int rows, int N, int K) {
     if (rows <= 0 || N < 128 || K < 128 || (N % 128) != 0 || (K % 128) != 0) return 0;
     int kc;
-    return tn2_plan(rows, N, K, &kc);
+    return gemm_tn2_plan(rows, N, K, MIL_NUM_CU, &kc);
 }
 
 int mil_gemm_tn2_rows(const float* dY, int lddy, const float* Y, int ldy, int act, const float* X, int ldx, int rows, int N, int K,
@@ -405,7 +408,7 @@ int mil_gemm_tn2_rows(const float* dY, int lddy, const float* Y, int ldy, int ac
     if (act != NT2_ACT_NONE && !Y) return MIL_EINVAL;
     if ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) return MIL_EINVAL;
     int kc;
-    const int S = tn2_plan(rows, N, K, &kc);
+    const int S = gemm_tn2_plan(rows, N, K, MIL_NUM_CU, &kc);
     const int NM = N / 128, NJ = K / 128;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(S * NM * NJ);

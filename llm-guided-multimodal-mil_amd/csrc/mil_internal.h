@@ -65,5 +65,8 @@ int dropout_keep_bits_pair_tilemap(uint32_t* xbits, int R, uint32_t* mbits, int 
                                    uint64_t offset, const int32_t* offset_dev, const TileMapJob& tm, void* stream);
 
 // ---- linear_nt2.hip (called from linear.hip)
+// k_gemm_tn2's row split on ncu compute units (-> splits, *KC_out rows per split) and whether mil_linear_bwd_params takes it
+MIL_HIDDEN int gemm_tn2_plan(int rows, int N, int K, int ncu, int* KC_out);
+MIL_HIDDEN int gemm_tn2_ok(int lddy, int ldy, int ldx, int rows, int N, int K, int ncu);
 int mil_gemm_tn2_rows(const float* dY, int lddy, const float* Y, int ldy, int act, const float* X, int ldx, int rows, int N, int K,
                       float* partial, float* cs_partial, const int32_t* rows_dev, void* stream);

@@ -53,9 +53,10 @@ def test_tile_map_ragged():
 
 
 @pytest.mark.parametrize("cname,pyname", [("mil_image_only_step", "ImageOnlyStep"), ("mil_small_dw_desc", "SmallDwDesc"),
-                                          ("mil_cohort_feed_desc", "CohortFeedDesc"), ("mil_gate_route", "GateRoute")])
+                                          ("mil_cohort_feed_desc", "CohortFeedDesc"), ("mil_gate_route", "GateRoute"),
+                                          ("mil_gemm_plan", "GemmPlan")])
 def test_struct_layouts_match_the_header(tmp_path, cname, pyname):
-    """The ctypes mirrors of the C structs (the one-call step, the grouped weight-gradient descriptor, the gate step's route)
+    """The ctypes mirrors of the C structs (the one-call step, the grouped weight-gradient descriptor, the gate step's route, the tiled linear's route)
     against the C compiler's view of include/mil_hip.h."""
     import ctypes
     import subprocess

@@ -3,10 +3,20 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import linear_ref
 from conftest import rel_err
 from mil_amd import ops
 
 pytestmark = pytest.mark.gpu
+
+# what each epilogue flavour of the tests below passes to the dispatch (mil_gemm_route's arguments)
+EXTRAS_ROUTE = {"bias_tanh": dict(act=1), "residual": dict(residual=True), "accumulate": dict(accumulate=True),
+                "aux": dict(act=3, aux_mode=1), "plain": {}}
+
+
+def _route(M, N, K, b_mode=0, **kw):
+    """The kernel mil_gemm takes for this call on the current device (mil_gemm_route with ncu = 0: the plan the launch executes)."""
+    return linear_ref.lib_gemm_route(M, N, K, 0, b_mode, ncu=0, **kw)
 
 
 @pytest.mark.parametrize("M,K,N,act", [(1, 512, 512, "tanh"), (10, 512, 256, "none"), (77, 512, 2048, "quickgelu"),
@@ -49,13 +59,7 @@ def test_linear_residual_and_accumulate():
     assert rel_err(out.cpu(), x @ W.t() + 1) <= 2e-6
 
 
-@pytest.mark.parametrize("b_mode", [0, 1])
-def test_tall_gemm_with_a_split_last_round(b_mode):
-    """M x N tiles = 592 = one round of 512 + 80: the last 20 row tiles run as a second launch with split-K and the
-    epilogue in the reduce kernel; the result must not depend on that plan."""
-    from mil_amd import ops, _lib
-    M, N, K = 128 * 148 - 37, 512, 256
-    assert _lib.lib().mil_gemm_workspace_floats(M, N, K, 0) > 0
+def _tall_gemm_bias_residual(M, N, K, b_mode):
     g = torch.Generator().manual_seed(b_mode)
     A = torch.randn((M, K), generator=g)
     B = torch.randn((N, K) if b_mode == 0 else (K, N), generator=g) / K ** 0.5
@@ -66,6 +70,31 @@ def test_tall_gemm_with_a_split_last_round(b_mode):
     assert rel_err(out.cpu(), ref) <= 2e-6
     plain = ops.gemm(A.cuda(), 0, B.cuda(), b_mode, M, N, K, bias=bias.cuda(), act=0, residual=res.cuda(), split_k=False)
     assert rel_err(out.cpu(), plain.cpu()) <= 2e-6
+
+
+@pytest.mark.parametrize("b_mode", [0, 1])
+def test_tall_gemm_with_a_split_last_round(b_mode):
+    """M x N tiles of 128 x 128 = 592 = one round of 512 + 80 - the shape the split last round was written for.  At K = 256
+    k_gemm64 takes it (from K = 256 on it takes every product of more than a round) and no workspace is needed; the result
+    must not depend on whether one is offered.  test_split_last_round_below_k_256 is the case that reaches the route."""
+    from mil_amd import _lib
+    M, N, K = 128 * 148 - 37, 512, 256
+    route = _route(M, N, K, b_mode, residual=True)
+    assert route["kernel"] == "G64" and route["need"] == 0 and _lib.lib().mil_gemm_workspace_floats(M, N, K, 0) == 0
+    _tall_gemm_bias_residual(M, N, K, b_mode)
+
+
+@pytest.mark.parametrize("b_mode", [0, 1])
+def test_split_last_round_below_k_256(b_mode):
+    """The smallest product whose last partial round runs as a second launch with split-K and the epilogue in the reduce
+    kernel: 34 x 16 tiles = one round of 512 + 32, K = 128; the result must not depend on that plan."""
+    from mil_amd import _lib
+    M, N, K = 128 * 34 - 126, 2048, 128
+    route = _route(M, N, K, b_mode, residual=True)
+    assert route["kernel"] == "TAIL" and route["rows_main"] == 4096 and route["S"] == 2, route
+    assert _lib.lib().mil_gemm_workspace_floats(M, N, K, 0) >= route["need"] > 0
+    assert _route(M, N, K, b_mode, residual=True, workspace=False)["kernel"] == ("NT", "NN")[b_mode]
+    _tall_gemm_bias_residual(M, N, K, b_mode)
 
 
 def test_fused_quickgelu_mlp_matches_torch():
@@ -125,8 +154,11 @@ def test_parameter_backward_with_fused_activation_and_bias_gradient(M, K, N, act
                                                  (33000, 512, 128, 1, "accumulate"), (70000, 520, 32, 1, "plain"),
                                                  (66000, 2048, 64, 0, "aux")])
 def test_tall_gemm_over_several_rounds(M, N, K, b_mode, extras):
-    """Several rounds of the chip (more than 512 tiles, no split-K): ragged last row tile, a clamped last column tile,
-    one-slice and multi-slice contractions, every epilogue flavour."""
+    """Several rounds of the chip on k_gemm<0, b_mode> (more than 512 tiles of 128 x 128, K < 256): ragged last row tile, a
+    clamped last column tile, one-slice and multi-slice contractions, every epilogue flavour.  No split-K, except that the
+    K = 128 case runs the 2 row tiles beyond its whole round as the split last round."""
+    route = _route(M, N, K, b_mode, **EXTRAS_ROUTE[extras])
+    assert (route["kernel"], route["S"]) == (("TAIL", 2) if K == 128 else (("NT", "NN")[b_mode], 1)), route
     g = torch.Generator().manual_seed(M + N + K)
     dev = torch.device("cuda")
     A = torch.randn(M, K, generator=g)
@@ -201,6 +233,7 @@ def test_mid_size_layers_one_launch_per_product(M, K, N, act, mode):
 def test_64_row_tiles_for_partial_rounds(M, N, K, b_mode, extras):
     """Tall products (from half a round of the chip upwards) take k_gemm64: 64 x 128 tiles in an unpadded, XOR-swizzled
     LDS image, three workgroups per CU, no split-K."""
+    assert _route(M, N, K, b_mode, **EXTRAS_ROUTE[extras])["kernel"] == "G64"
     g = torch.Generator().manual_seed(M + N + K)
     dev = torch.device("cuda")
     A = torch.randn(M, K, generator=g)
@@ -232,11 +265,14 @@ def test_64_row_tiles_for_partial_rounds(M, N, K, b_mode, extras):
     assert rel_err(out.cpu(), ref.float()) <= 2e-6
 
 
-@pytest.mark.parametrize("M,N,K,act", [(32768, 512, 768, "tanh"), (49152 + 77, 256, 512, "none"), (65536, 512, 64, "relu")])
+@pytest.mark.parametrize("M,N,K,act", [(32768, 512, 768, "tanh"), (49152 + 77, 256, 512, "none"), (65536, 512, 64, "relu"),
+                                       (7000, 2048, 64, "relu")])
 def test_tall_nt_product_on_the_low_valu_kernel(M, N, K, act):
-    """mil_gemm_nt2 (256 x 256 tiles, LDS-DMA, csrc/linear_nt2.hip) directly and through mil_gemm's dispatch (fc_pathology's
-    shape is the first case) against torch in float64; a ragged last row tile in the second case."""
+    """mil_gemm_nt2 (256 x 256 tiles, LDS-DMA, csrc/linear_nt2.hip) directly and through mil_gemm (fc_pathology's shape is the
+    first case) against torch in float64; a ragged last row tile in the second and the last case.  mil_gemm's dispatch takes
+    the kernel for every case but the second, whose 193 tiles fill less than 7/8 of a round: that one goes to k_gemm64."""
     from mil_amd import _lib
+    assert _route(M, N, K, act=ops.ACT[act])["kernel"] == ("G64" if M == 49152 + 77 else "NT2")
     g = torch.Generator().manual_seed(3)
     A = torch.randn(M, K, generator=g).to("cuda")
     W = (torch.randn(N, K, generator=g) / K ** 0.5).to("cuda")
@@ -257,6 +293,7 @@ def test_tall_nt_product_on_the_low_valu_kernel(M, N, K, act):
 def test_weight_gradient_of_a_tall_activation_on_the_low_valu_kernel(rows, N, K, act):
     """ops.linear_bwd_params at fc_pathology's size (and two more): dispatched to k_gemm_tn2 (csrc/linear_nt2.hip), checked
     against float64 - dW = (dY (.) act'(Y))^T X and db = the column sums."""
+    assert linear_ref.lib_bwd_params_route(rows, N, K, ldy=N if act != "none" else 0, ncu=0)["kernel"] == "TN2"
     g = torch.Generator().manual_seed(5)
     dy = (torch.randn(rows, N, generator=g) * 1e-2).to("cuda")
     x = torch.randn(rows, K, generator=g).to("cuda")
@@ -282,7 +319,10 @@ def test_weight_gradient_of_a_tall_activation_on_the_low_valu_kernel(rows, N, K,
 def test_64_x_64_tiles_for_a_few_hundred_rows(M, N, K, b_mode, extras):
     """Products of at most 2048 rows whose 64 x 128 tiles would leave CUs idle (the text tower at one bag x 10 prompts x 77 tokens)
     take k_gemm64n: 64 x 64 tiles, K split over blockIdx.z (raw partial tiles + k_splitk_reduce's epilogue) when the tiles alone
-    do not fill the chip."""
+    do not fill the chip (S > 1 in six of the cases)."""
+    route = _route(M, N, K, b_mode, **EXTRAS_ROUTE[extras])
+    assert route["kernel"] == "G64N" and (route["S"] > 1) == ((M, N, K) in ((770, 512, 2048), (770, 512, 1536), (770, 516, 2048),
+                                                                        (513, 520, 1024), (77, 1536, 512), (77, 512, 2048))), route
     g = torch.Generator().manual_seed(M + N + K)
     dev = torch.device("cuda")
     A = torch.randn(M, K, generator=g)
