@@ -1047,6 +1047,16 @@ int mil_tm_row_gather_bwd(const float* ddst, const int32_t* idx, int rows, int E
  * lengths on are zeroed (what an earlier step left behind the bags of this one). */
 int mil_tm_seq_index(const int32_t* len_dev, int B, const int32_t* s_of_bag, int32_t* idx_out, int idx_rows, int32_t* rows_dev_out,
                      int32_t* flag_dev, float* x_tail, int x_rows, int L, void* stream);
+/* The same index for bags whose rows do not lie back to back (the fusion model's multi-modal bag).  table_dev [B, 9] int32 ON
+ * THE DEVICE, per bag: grid side s, then 4 segments (first row in the source, length) in sequence order, unused segments of
+ * length 0; any B up to 65536.  With L_b the sum of a bag's lengths, bag b gets 1 + s_b^2 entries: -2 (cls), the segments'
+ * rows in order, then the first s_b^2 - L_b of those again.  total = sum of 1 + s_b^2 (the launch shape; <= idx_rows, the
+ * extent of idx_out); x_rows = rows of the source (<= 2^29).  The position within a bag is clamped into [0, L_b - 1], a bag
+ * with L_b == 0 and any row outside [0, x_rows) give -1 (a zero row): no entry leaves the source whatever the table holds.
+ * flag_dev [1] (nullable) is set to 1 (never cleared here) when an L_b lies outside ((s_b - 1)^2, s_b^2] or a row was
+ * dropped. */
+int mil_tm_seq_index_segs(const int32_t* table_dev, int B, int total, int x_rows, int32_t* idx_out, int idx_rows, int32_t* flag_dev,
+                          void* stream);
 /* Landmarks: qL, kL [8, 256, 64] = means of l = n_pad / 256 consecutive rows of q (times qscale) and k, zero pad rows
  * counted.  Backward: dqkv's q and k columns += the spread-out landmark gradients. */
 int mil_tm_landmarks(const float* qkv, int n_pad, float qscale, float* qL, float* kL, void* stream);

@@ -182,6 +182,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_row_gather": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     "mil_tm_row_gather_bwd": (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
     "mil_tm_seq_index": (c_int, [_P, c_int, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_seq_index_segs": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "mil_tm_landmarks": (c_int, [_P, c_int, c_float, _P, _P, _P]),
     "mil_tm_landmarks_bwd": (c_int, [_P, _P, c_int, c_float, _P, _P]),
     "mil_tm_pinv_init": (c_int, [_P] * 4 + [_P]),

@@ -103,12 +103,22 @@ def create_arg_parser(argv=None):
     p.add_argument("--save_note_attn", type=str, default="", help="test_ddp.py, --variant fusion --modality \"['pathology']\": "
                    "write DIR/<bag key or index>.npz per bag with float32 note [3, P, 8, N] = attention sites (block 0, block 1, "
                    "final) x text tokens x heads x patches, the softmax weights of the note's token(s) over the patches, and bag "
-                   "[N + P], the final gated-attention aggregator's weights, patches first.  The flag switches --hip_graph off: "
+                   "[N + P], the final gated-attention aggregator's weights, patches first (with --aggregator TransMIL "
+                   "--fusion_transmil 1: bag [2, 8, N + P] = layers x heads x rows, the cls token's attention to each row of the "
+                   "multi-modal bag, a repeated row's two keys summed, patches first).  The flag switches --hip_graph off: "
                    "with --hip_graph 1 the evaluation runs the eager forward, not the replayed one.  The files are written when "
                    "the run ends")
     p.add_argument("--flat_adam", type=int, default=1, help="autograd path: parameters in one flat buffer, one gradient "
                    "all-reduce and one Adam launch per step (optim.FlatAdam); 0 = torch DDP + torch.optim.Adam")
+    p.add_argument("--fusion_transmil", type=int, default=0, help="--variant fusion: 1 = build --aggregator TransMIL (and "
+                   "--model_pathology TransMIL's unused extractor) over the multi-modal bag, rows in upstream's sequence "
+                   "order, bags one after another; eager autograd path only (refused with --hip_graph 1).  0: both "
+                   "values raise NotImplementedError as before")
     args = p.parse_args(argv)
+    if args.fusion_transmil and args.hip_graph:
+        # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,
+        # TransMIL's shapes follow the grid side of each bag
+        raise ValueError("--fusion_transmil 1 runs on the eager autograd path only: drop --hip_graph 1")
     if args.save_patch_attn and (args.variant != "image_only" or args.model_pathology != "TransMIL"):
         # refused here, before an entry point touches the GPU
         raise ValueError("--save_patch_attn writes TransMIL's cls-token attention: it needs --variant image_only "

@@ -218,6 +218,68 @@ __global__ __launch_bounds__(256) void k_tm_zero_tail(const int32_t* __restrict_
     for (int c = threadIdx.x; c < L / 4; c += 256) p[c] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// The sequence index of bags whose rows do NOT lie back to back (the fusion model's multi-modal bag: [all patches | small
+// blocks] in memory, [tokens | patches] per bag in upstream's sequence order).  tab [B, TM_SEG_STRIDE] int32 on the device: per
+// bag its grid side s, then TM_SEG_MAX segments (first row in the source, length) in sequence order, unused ones of length 0.
+// Thread per entry, bag b owns 1 + s_b^2 entries: -2, the segments walked in order (L_b rows), the first s_b^2 - L_b of
+// those again.  The position within the bag is clamped into [0, L_b - 1] and a resolved row outside [0, x_rows) becomes -1
+// (a zero row), so no entry leaves the source whatever the table holds.  `flag` is raised (sticky) when L_b is outside
+// ((s_b - 1)^2, s_b^2] or a row had to be dropped.  Any number of bags: the table is read, not passed by value.
+constexpr int TM_SEG_MAX = 4, TM_SEG_STRIDE = 1 + 2 * TM_SEG_MAX;
+
+__device__ __forceinline__ int tm_seg_side(const int32_t* __restrict__ tab, int b) {
+    return min(max(tab[b * TM_SEG_STRIDE], 1), 4096);
+}
+
+__global__ __launch_bounds__(256) void k_tm_seq_index_segs(const int32_t* __restrict__ tab, int B, int total, int x_rows,
+                                                           int32_t* __restrict__ idx, int32_t* __restrict__ flag) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= total) return;
+    int b = 0, first = 0;
+    for (; b < B - 1; ++b) {
+        const int s = tm_seg_side(tab, b), seq = 1 + s * s;
+        if (r < first + seq) break;
+        first += seq;
+    }
+    const int32_t* t = tab + b * TM_SEG_STRIDE;
+    const int s = tm_seg_side(tab, b), j = r - first;
+    int len[TM_SEG_MAX], L = 0;
+#pragma unroll
+    for (int k = 0; k < TM_SEG_MAX; ++k) {
+        len[k] = min(max(t[2 + 2 * k], 0), x_rows);          // x_rows < 2^31 / 4: the sum cannot wrap
+        L += len[k];
+    }
+    if (j == 0) {
+        if ((L > s * s || L <= (s - 1) * (s - 1)) && flag) flag[0] = 1;
+        idx[r] = -2;
+        return;
+    }
+    if (L == 0) {
+        idx[r] = -1;
+        return;
+    }
+    int pos = j - 1;
+    if (pos >= L) pos -= L;                                  // the repeat of the first s^2 - L rows
+    pos = min(max(pos, 0), L - 1);
+    long row = -1;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < TM_SEG_MAX; ++k) {
+        if (found) continue;
+        if (pos < len[k]) {
+            row = (long)t[1 + 2 * k] + pos;
+            found = true;
+        } else {
+            pos -= len[k];
+        }
+    }
+    if (row < 0 || row >= x_rows) {
+        if (flag) flag[0] = 1;
+        row = -1;
+    }
+    idx[r] = (int32_t)row;
+}
+
 // qL [8, 256, 64] = qscale * mean of l consecutive q rows, kL the same of k (no scale); thread per (landmark, q|k column)
 __global__ __launch_bounds__(256) void k_tm_landmarks(const float* __restrict__ qkv, int l, float qscale, float* qL, float* kL) {
     const int j = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;        // c < 1024
@@ -582,6 +644,15 @@ int mil_tm_seq_index(const int32_t* len_dev, int B, const int32_t* s_of_bag, int
     if (tail > 0)
         hipLaunchKernelGGL(k_tm_zero_tail, dim3((unsigned)(tail < x_rows ? tail : x_rows)), dim3(256), 0, (hipStream_t)stream, len_dev,
                            B, sd, x_tail, x_rows, L);
+    return launch_rc();
+}
+
+int mil_tm_seq_index_segs(const int32_t* table_dev, int B, int total, int x_rows, int32_t* idx_out, int idx_rows, int32_t* flag_dev,
+                          void* stream) {
+    if (!table_dev || !idx_out || B <= 0 || B > 65536 || total <= 0 || total > idx_rows || x_rows <= 0 || x_rows > (1 << 29))
+        return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_seq_index_segs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table_dev, B,
+                       total, x_rows, idx_out, flag_dev);
     return launch_rc();
 }
 

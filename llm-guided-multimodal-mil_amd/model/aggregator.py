@@ -11,7 +11,16 @@ tensor op on the path runs through the HIP library:
 Differences, all deliberate: a batch is B independent bags (the reference's B>1 ABMIL
 degenerates to a sum); CT encoders / TransMIL / tabular-CI MLPs are out of scope and raise; the positional
 table lives on the device (the reference re-uploads `pe[:, :N]` every forward, aggregator.py:160-190);
-`last_logits` exposes the pre-sigmoid scores for the parity checks."""
+`last_logits` exposes the pre-sigmoid scores for the parity checks.
+
+`args.fusion_transmil` (opt-in, default off; without it `aggregator="TransMIL"` and `model_pathology="TransMIL"` raise as
+they always did): the multi-modal bag is aggregated by TransMIL (dim1/TransMIL.py, csrc/transmil.hip) - upstream's default
+`--aggregator` and the authors' own run.  TransMIL depends on the order of a bag's rows, so each branch hands `_pool_head`
+the bag's pieces in upstream's sequence order (aggregator.py:173,184,192,195) while the rows stay where they lie in memory;
+the sequence is assembled through an index written on the device (ops.tm_seq_index_segs).  Upstream feeds TransMIL's
+returned TUPLE `(h, attn)` into `self.fc` (aggregator.py:199-200), which cannot run; the dataflow built here is element 0,
+`h [B, 512]`, into `fc`.  Bags run one after another, eager autograd path only (no `bucket=`, no hipGraph replay).
+`model_pathology="TransMIL"` builds `extractor_pathology` for the state_dict alone (aggregator.py:54-56): never called."""
 import math
 from typing import List, Optional
 
@@ -30,6 +39,14 @@ def _arg(args, name, default):
     return getattr(args, name, default)
 
 
+def _offsets(lengths):
+    """First row of each bag when the bags lie back to back."""
+    off = [0]
+    for n in lengths:
+        off.append(off[-1] + int(n))
+    return off
+
+
 class aggregator(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -46,8 +63,12 @@ class aggregator(nn.Module):
             if _arg(args, "model_pathology", "ABMIL") == "ABMIL":
                 from .dim1 import ABMIL
                 self.extractor_pathology = ABMIL(args, L=EMBED)                           # :50 (built, never called)
+            elif args.model_pathology == "TransMIL" and _arg(args, "fusion_transmil", 0):
+                from .dim1 import TransMIL
+                self.extractor_pathology = TransMIL(n_classes=args.num_classes, L=EMBED)  # :54-56 (built, never called)
             elif args.model_pathology not in ("-", None):
-                raise NotImplementedError(f"model_pathology={args.model_pathology}: only ABMIL is on the built path")
+                raise NotImplementedError(f"model_pathology={args.model_pathology}: only ABMIL is on the built path by default; "
+                                          "TransMIL is built with fusion_transmil=1 (--fusion_transmil 1)")
             self.TwoWayTransformer_Pth = mk_twoway()                                      # :58
         if "CT" in modality:
             self.TwoWayTransformer_CT = mk_twoway()                                       # :36
@@ -58,9 +79,12 @@ class aggregator(nn.Module):
         if agg == "ABMIL":
             from .dim1 import ABMIL
             self.aggregator = ABMIL(args, L=EMBED)                                        # :81
+        elif agg == "TransMIL" and _arg(args, "fusion_transmil", 0):
+            from .dim1 import TransMIL
+            self.aggregator = TransMIL(n_classes=args.num_classes, L=EMBED)               # :85-87
         elif agg != "-":
-            raise NotImplementedError(f"aggregator={agg}: TransMIL needs the absent nystrom_attention package "
-                                      "(parity unpinned, SURVEY.md section 8f); ABMIL_v2 is not on the built path")
+            raise NotImplementedError(f"aggregator={agg}: TransMIL over the multi-modal bag is opt-in, set fusion_transmil=1 "
+                                      "(--fusion_transmil 1; eager autograd path only); ABMIL_v2 is not on the built path")
         if _arg(args, "model_CI", "CLIP") == "CLIP":
             from .dim1 import CLIP
             self.clinic_extractor = CLIP(args)                                            # :122
@@ -71,6 +95,7 @@ class aggregator(nn.Module):
         self._pe: Optional[torch.Tensor] = None
         self.last_logits: Optional[torch.Tensor] = None
         self.last_loss: Optional[torch.Tensor] = None
+        self.last_pooled: Optional[torch.Tensor] = None    # op-by-op tail only (the fused pool + head + loss node keeps no M)
         self._labels: Optional[torch.Tensor] = None
         self._loss_scale: Optional[float] = None
         # note_attn: an eval-mode, no-grad forward of the pathology (+ text) model also leaves, per bag,
@@ -79,18 +104,21 @@ class aggregator(nn.Module):
         #       final attention of TwoWayTransformer_Pth - every head summing to 1 over the patches;
         #   last_bag_attn[bag]  [N_b + P]: the final gated-attention aggregator's weights over the multi-modal bag, PATCHES
         #       FIRST, then the note's tokens - the order of the rows in memory (upstream concatenates the tokens first,
-        #       aggregator.py:192; pooling does not depend on the order).
+        #       aggregator.py:192; pooling does not depend on the order).  With a TransMIL aggregator [2, 8, N_b + P] = layers
+        #       x heads x rows: the cls token's attention to each row of the bag (a repeated row's two keys summed, not
+        #       renormalised; ops.tm_cls_attention), in the same patches-first order.
         # Off: the forward issues exactly the launches it always did and both stay None.  The returned tuple never changes.
         self.note_attn = False
         self.last_note_attn = None
         self.last_bag_attn = None
+        self._tm_bag_attn = None
         self._note_dir, self._note_names, self._note_kept, self._note_done = None, None, [], 0
 
     NOTE_KEEP_BYTES = 1 << 30
 
     def save_note_attn_to(self, directory: str, names=None):
         """--save_note_attn (train_ddp.build_model): every eval-mode, no-grad forward from here on keeps its bags' weights ON
-        THE DEVICE (note [3, P, 8, N] and bag [N + P] per bag), and flush_note_attn() - registered to run when the process
+        THE DEVICE (note [3, P, 8, N] and bag [N + P] - [2, 8, N + P] with a TransMIL aggregator - per bag), and flush_note_attn() - registered to run when the process
         ends - copies them to the host and writes DIR/<names[i] or i>.npz, float32, bags numbered in the order they ran: an
         entry point that times each forward has no host copy and no file inside its bracket.  Beyond NOTE_KEEP_BYTES kept, a
         forward flushes first."""
@@ -146,7 +174,9 @@ class aggregator(nn.Module):
 
     def _bag_attention(self, layout):
         agg = getattr(self, "aggregator", None)
-        if agg is not None and getattr(agg, "last_scores", None) is not None:
+        if self._is_transmil():
+            self.last_bag_attn = self._tm_bag_attn
+        elif agg is not None and getattr(agg, "last_scores", None) is not None:
             self.last_bag_attn = list(torch.split(ops.bag_softmax(agg.last_scores, layout), list(layout.lengths)))
 
     # ------------------------------------------------------------------ positional table (aggregator.py:99-106)
@@ -173,8 +203,13 @@ class aggregator(nn.Module):
         self.last_logits = z
         return p
 
-    def _pool_head(self, x0, layout):
-        """Multi-modal bag rows -> prob.  With labels handed to forward() (the training loop's `criterion(prob, y)` of
+    def _is_transmil(self) -> bool:
+        return hasattr(getattr(self, "aggregator", None), "flat_segments")
+
+    def _pool_head(self, x0, layout, segs):
+        """Multi-modal bag rows -> prob.  segs[b]: the pieces (first row, length) of bag b in x0 in UPSTREAM'S SEQUENCE ORDER
+        (aggregator.py:173,184,192,195), which a TransMIL aggregator needs (square padding repeats the first rows, PPEG is
+        positional) and the attention pool does not (None then).  With labels handed to forward() (the training loop's `criterion(prob, y)` of
         train_ddp.py:323-324 moved inside) and an ABMIL aggregator, pool + Dropout(.25) + fc + sigmoid + BCE / CE run as one
         fused node (ops.gated_pool_head_loss) and the loss is left in `self.last_loss`; otherwise op by op."""
         y = self._labels
@@ -187,7 +222,24 @@ class aggregator(nn.Module):
                                                         1 if ce else 0, head_train=self.training)
             self.last_logits, self.last_loss = z, loss
             return p
-        M = self.aggregator.flat(x0, layout) if hasattr(self, "aggregator") else x0
+        if self._is_transmil():
+            # TransMIL returns (h, attn); element 0 feeds fc.  need_attn="cls" only under note_attn (eval, no grad)
+            want = self._wants_note_attn()
+            M, attn = self.aggregator.flat_segments(x0, segs, need_attn="cls" if want else False)
+            self._tm_bag_attn = None
+            if want:
+                # [2, 8, L_b] = layers x heads x rows in sequence order -> the rows' order in memory (patches first)
+                self._tm_bag_attn = []
+                for b, bag in enumerate(segs):
+                    a = torch.stack([attn[0][b], attn[1][b]])
+                    start, cuts = 0, []
+                    for first, n in bag:
+                        cuts.append((first, start, n))
+                        start += n
+                    self._tm_bag_attn.append(torch.cat([a[..., st:st + n] for _, st, n in sorted(cuts)], -1))
+        else:
+            M = self.aggregator.flat(x0, layout) if hasattr(self, "aggregator") else x0
+        self.last_pooled = M                               # [B, 512]: what the head saw (parity checks, like last_logits)
         p = self._head(M)
         if y is not None:
             crit = torch.nn.CrossEntropyLoss() if C > 2 else torch.nn.BCELoss()
@@ -214,7 +266,8 @@ class aggregator(nn.Module):
                                                   keys_tail_rows=B * P)                       # :179
             x0 = ops.append_rows(k, q, tail_reserved=True)                                    # :184
             layout = BagLayout.two_segment([D] * B, [P] * B, dev)
-            return self._pool_head(x0, layout), q.view(B, P, EMBED)                           # :204-205
+            segs = [[(B * D + b * P, P), (b * D, D)] for b in range(B)] if self._is_transmil() else None   # :184
+            return self._pool_head(x0, layout, segs), q.view(B, P, EMBED)                     # :204-205
         x = x_list[1]
         if x.dim() == 2:
             x = x.unsqueeze(0)
@@ -236,7 +289,12 @@ class aggregator(nn.Module):
         # the last LayerNorm wrote it, the small blocks are appended, the tile map says which rows form a bag.
         x0 = ops.append_rows(k_p, torch.cat([q_ct, k_ct, q_p], 0), tail_reserved=True)
         layout = BagLayout.multi_segment([n_len, [P] * B, [D] * B, [P] * B], dev)
-        return self._pool_head(x0, layout), q_ct.view(B, P, EMBED), q_p.view(B, P, EMBED)     # :198-200,202-203
+        segs = None
+        if self._is_transmil():
+            R, off = sum(n_len), _offsets(n_len)
+            segs = [[(R + b * P, P), (R + B * P + b * D, D), (R + B * (P + D) + b * P, P), (off[b], n_len[b])]
+                    for b in range(B)]                                                    # :173
+        return self._pool_head(x0, layout, segs), q_ct.view(B, P, EMBED), q_p.view(B, P, EMBED)   # :198-200,202-203
 
     # ------------------------------------------------------------------ capacity-bucket form of the pathology branch
     def _forward_bucket(self, x, t, bucket):
@@ -254,7 +312,7 @@ class aggregator(nn.Module):
         q, k = self.TwoWayTransformer_Pth.flat(xi, point, self.pe_rows(bucket.cap, xi.device), None, None,
                                                keys_tail_rows=B * P, segs=(bucket.s_tt, bucket.s_ti, bucket.s_it))
         x0 = ops.append_rows(k, q, tail_reserved=True)                                     # :192 (no concat copy)
-        return self._pool_head(x0, bucket.layout), q.view(B, P, EMBED)                     # :198-200,207
+        return self._pool_head(x0, bucket.layout, None), q.view(B, P, EMBED)               # :198-200,207
 
     def _forward_ct_bucket(self, x_list, t, bucket):
         """The CT + pathology branch (aggregator.py:155-173,202-203) on a segments.FusionBucket whose tail is [P, D, P]:
@@ -281,7 +339,7 @@ class aggregator(nn.Module):
         q_p, k_p = tw.flat(xi, self._lin_tanh(self.fc_CI2Pth, tflat), self.pe_rows(bucket.cap, dev), None, None,
                            keys_tail_rows=bucket.tail_rows, segs=(bucket.s_tt, bucket.s_ti, bucket.s_it))
         x0 = ops.append_rows(k_p, torch.cat([q_ct, k_ct, q_p], 0), tail_reserved=True)        # :173 (no concat of the patches)
-        return self._pool_head(x0, bucket.layout), q_ct.view(B, P, EMBED), q_p.view(B, P, EMBED)
+        return self._pool_head(x0, bucket.layout, None), q_ct.view(B, P, EMBED), q_p.view(B, P, EMBED)
 
     # ------------------------------------------------------------------ forward (aggregator.py:134-209)
     def forward(self, x_list: List[torch.Tensor], x_CI: torch.Tensor, lengths: Optional[List[int]] = None,
@@ -310,8 +368,11 @@ class aggregator(nn.Module):
         # labels [B, C] float one-hot (optional, an extension of the reference signature): the criterion of
         # train_ddp.py:323-324 evaluated inside, result in `self.last_loss` (mean loss unless loss_scale is given);
         # the return tuple is unchanged
-        self._labels, self._loss_scale, self.last_loss = labels, loss_scale, None
+        self._labels, self._loss_scale, self.last_loss, self.last_pooled = labels, loss_scale, None, None
         modality = self.args.modality
+        if bucket is not None and self._is_transmil():
+            raise NotImplementedError("bucket=: the capacity-bucket forward is built for the ABMIL aggregator; TransMIL's "
+                                      "shapes follow the grid side ceil(sqrt(rows)) of each bag (eager path only)")
         want = self._wants_note_attn()
         if want:
             self.last_note_attn = self.last_bag_attn = None
@@ -354,14 +415,18 @@ class aggregator(nn.Module):
             # attention pooling does not depend on the order of a bag's rows.
             x0 = ops.append_rows(k, q, tail_reserved=True)     # k comes from the last block's norm4 with keys_tail_rows
             layout = BagLayout.two_segment(n_len, [P] * B, x0.device)
-            prob = self._pool_head(x0, layout)
+            segs = None
+            if self._is_transmil():
+                R, off = sum(n_len), _offsets(n_len)
+                segs = [[(R + b * P, P), (off[b], n_len[b])] for b in range(B)]           # :192 [x_Pth2CI | x_CI2Pth]
+            prob = self._pool_head(x0, layout, segs)
             if want:
                 self._note_attention(sites, n_len, P, layout)
             return prob, q.view(B, P, EMBED)                                              # :198-200,207
         if "CI" in modality:
             x0 = self._lin_tanh(self.fc_CI, t.reshape(B * P, EMBED))                      # :195
             layout = BagLayout.uniform(B, P, x0.device)
-            prob = self._pool_head(x0, layout)                                            # :198-200,209
+            prob = self._pool_head(x0, layout, [[(b * P, P)] for b in range(B)] if self._is_transmil() else None)   # :198-200,209
             if want:
                 self._bag_attention(layout)
             return prob

@@ -61,6 +61,57 @@ def seq_index(lengths: Sequence[int]) -> List[int]:
     return idx
 
 
+def seg_index_entry(j: int, s: int, bag_segs: Sequence[Tuple[int, int]], x_rows: Optional[int] = None) -> int:
+    """Entry j (0 <= j <= s^2) of one bag whose rows lie in the pieces bag_segs = [(first row, length), ..] of the source, in
+    sequence order: -2 = the cls row, the pieces' rows one after another (L of them), then the first s^2 - L again.  The
+    position is clamped into [0, L - 1]; no rows at all, or a row outside [0, x_rows), give -1 (a zero row).
+    csrc/transmil.hip: k_tm_seq_index_segs evaluates exactly this per entry from the table on the device."""
+    if j == 0:
+        return -2
+    lens = [max(int(n), 0) for _, n in bag_segs]
+    L = sum(lens)
+    if L == 0:
+        return -1
+    pos = j - 1
+    if pos >= L:
+        pos -= L
+    pos = min(max(pos, 0), L - 1)
+    for (first, _), n in zip(bag_segs, lens):
+        if pos < n:
+            row = int(first) + pos
+            return row if row >= 0 and (x_rows is None or row < x_rows) else -1
+        pos -= n
+    return -1
+
+
+def seq_index_segments(segs: Sequence[Sequence[Tuple[int, int]]], sides: Optional[Sequence[int]] = None,
+                       x_rows: Optional[int] = None) -> List[int]:
+    """The index of the sequence assembly for bags whose rows are NOT packed back to back (the fusion model's multi-modal
+    bag): segs[b] = the bag's (first row, length) pieces in sequence order, sides[b] its grid side (default: the side of its
+    row count).  The host mirror of ops.tm_seq_index_segs, entry by entry."""
+    idx: List[int] = []
+    for b, bag in enumerate(segs):
+        s = int(sides[b]) if sides is not None else bucket_side(sum(max(int(n), 0) for _, n in bag))
+        idx += [seg_index_entry(j, s, bag, x_rows) for j in range(1 + s * s)]
+    return idx
+
+
+def segment_table(segs: Sequence[Sequence[Tuple[int, int]]], sides: Optional[Sequence[int]] = None) -> Tuple[List[List[int]], int]:
+    """(rows of the int32 table ops.tm_seq_index_segs reads - per bag [s, first0, len0, .. first3, len3] -, the number of
+    index entries sum(1 + s^2))."""
+    rows, total = [], 0
+    for b, bag in enumerate(segs):
+        if len(bag) > ops.TM_SEG_MAX:
+            raise ValueError(f"TransMIL: a bag of {len(bag)} segments (at most {ops.TM_SEG_MAX})")
+        s = int(sides[b]) if sides is not None else bucket_side(sum(max(int(n), 0) for _, n in bag))
+        row = [s]
+        for first, n in bag:
+            row += [int(first), int(n)]
+        rows.append(row + [0] * (ops.TM_SEG_STRIDE - len(row)))
+        total += 1 + s * s
+    return rows, total
+
+
 def pad_index(g: dict) -> List[int]:
     """Front zero pad of one bag's rows to n_pad: -1 = a zero row.  Depends on the side only."""
     return [-1] * g["pad"] + list(range(g["seq"]))
@@ -182,7 +233,6 @@ class TransMIL(nn.Module):
         the static [8, s_b^2] tensor, zeros behind the bag's length on the device."""
         if not (isinstance(need_attn, bool) or (isinstance(need_attn, str) and need_attn == "cls")):
             raise ValueError(f"TransMIL: need_attn must be False, True or 'cls', got {need_attn!r}")
-        want_cls = not isinstance(need_attn, bool)
         dev = x.device
         if geom is not None:
             if x.dim() != 2 or x.shape[0] != geom.cap:
@@ -211,6 +261,35 @@ class TransMIL(nn.Module):
             # [cls | tokens | first `add` tokens again] per bag, one gather for all bags; index -2 = the cls row
             idx_dev = torch.tensor(seq_index(lengths), dtype=torch.int32).to(dev, non_blocking=True)
         seqs = ops.tm_row_gather(h, self.cls_token, idx_dev)
+        return self._run_bags(seqs, geo, need_attn, geom)
+
+    def flat_segments(self, x0: torch.Tensor, segs: Sequence[Sequence[Tuple[int, int]]], need_attn=False):
+        """forward() over rows that are not contiguous per bag: x0 [R, L], segs[b] = the bag's (first row, length) pieces in
+        SEQUENCE order (at most ops.TM_SEG_MAX).  _fc1 + ReLU runs over all R rows in whatever order they lie, the sequences
+        [cls | the bag's rows | its first s^2 - L_b rows again] are assembled through an index written on the device from the
+        [B, 9] table of the pieces (ops.tm_seq_index_segs: no list of 1 + s^2 ints per bag is built or uploaded), then the
+        bags run as in forward().  Same returns; with need_attn="cls" bag b's entries are [8, L_b] in sequence order.  Rows of
+        x0 that no bag names get a zero gradient."""
+        if not (isinstance(need_attn, bool) or (isinstance(need_attn, str) and need_attn == "cls")):
+            raise ValueError(f"TransMIL: need_attn must be False, True or 'cls', got {need_attn!r}")
+        if x0.dim() != 2 or x0.shape[1] != self.L:
+            raise ValueError(f"TransMIL: flat_segments wants rows [R, {self.L}], got {tuple(x0.shape)}")
+        R = x0.shape[0]
+        segs = [[(int(f), int(n)) for f, n in bag] for bag in segs]
+        for b, bag in enumerate(segs):                                      # the kernel clamps and flags; eager mode refuses
+            if sum(n for _, n in bag) < 1 or any(n < 0 or f < 0 or f + n > R for f, n in bag):
+                raise ValueError(f"TransMIL: segments {bag} of bag {b} do not lie in the {R} rows (or hold none)")
+        rows, total = segment_table(segs)
+        table = torch.tensor(rows, dtype=torch.int32).to(x0.device, non_blocking=True)
+        h = ops.linear_act(x0, self._fc1[0].weight, self._fc1[0].bias, "relu")        # [R, 512]
+        idx_dev = ops.tm_seq_index_segs(table, total, R)
+        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev)
+        return self._run_bags(seqs, [geometry(sum(n for _, n in bag)) for bag in segs], need_attn, None)
+
+    def _run_bags(self, seqs: torch.Tensor, geo: List[dict], need_attn, geom: Optional[DeviceGeometry]):
+        """The assembled sequences [sum(1 + s_b^2), 512], one bag after another: layer1 -> PPEG -> layer2 -> norm of the cls rows."""
+        want_cls = not isinstance(need_attn, bool)
+        dev = seqs.device
         train = self.training
         if train:
             self._drop_state(dev)

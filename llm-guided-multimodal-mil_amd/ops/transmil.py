@@ -92,6 +92,31 @@ def tm_seq_index(len_dev, sides, idx_out, rows_dev=None, flag=None, x_tail=None)
     return idx_out
 
 
+TM_SEG_MAX = 4                      # segments per bag of a tm_seq_index_segs table (csrc/transmil.hip)
+TM_SEG_STRIDE = 1 + 2 * TM_SEG_MAX  # int32 per bag: s, then (first row, length) per segment
+
+
+def tm_seq_index_segs(table, total: int, x_rows: int, idx_out=None, flag=None):
+    """tm_row_gather's index for bags whose rows lie in up to four pieces of the source (mil_tm_seq_index_segs): table, device
+    int32 [B, TM_SEG_STRIDE] = per bag (s, first0, len0, .. first3, len3) with the segments in sequence order
+    (model/dim1/TransMIL.py: segment_table builds it), total = sum(1 + s^2) (host int: the launch shape), x_rows = rows of the
+    source.  Per bag [-2 | the segments' rows | the first s^2 - L of them again]; nothing leaves [0, x_rows); flag [1]
+    (optional) <- 1 if a bag's rows do not fit its side.  One launch, no host sync.  Returns idx_out[:total]."""
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != TM_SEG_STRIDE or not table.is_contiguous():
+        raise _lib.MilHipError(f"tm_seq_index_segs: table must be contiguous int32 [B, {TM_SEG_STRIDE}], got "
+                               f"{table.dtype} {tuple(table.shape)}")
+    total = int(total)
+    if idx_out is None:
+        idx_out = torch.empty(total, device=table.device, dtype=torch.int32)
+    if idx_out.dtype != torch.int32 or not idx_out.is_contiguous() or idx_out.device != table.device:
+        raise _lib.MilHipError("tm_seq_index_segs: idx_out must be a contiguous int32 tensor on the table's device")
+    if flag is not None and (flag.dtype != torch.int32 or flag.numel() < 1):
+        raise _lib.MilHipError("tm_seq_index_segs: flag must be int32 [1]")
+    _lib.checked().mil_tm_seq_index_segs(_p(table), table.shape[0], total, int(x_rows), _p(idx_out), idx_out.numel(), _p(flag),
+                                         _stream())
+    return idx_out[:total]
+
+
 class _TmPPEG(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, s: int, W7, b7, W5, b5, W3, b3):
