@@ -3,6 +3,10 @@
 // Reference arithmetic: model/dim1/ABMIL.py:47-56.  The gate GEMM x[R,L] . [Wv;Wu]^T -> [R,384] is a dense fp32
 // contraction: v_mfma_f32_32x32x2_f32 (exact f32, 157 TFLOP/s roof), or the split-bf16 loop of
 // k_gate_fwd2<.., PW>.  The other stages of K1: attn_pool.hip (pool, ds), gate_bwd_dw.hip, gate_bwd_dx.hip.
+//
+// The 128-row kernels are built from parts: GateFwdCoord (who am I), GateKeepWords (dropout keep bits), one K loop
+// (k_gate_fwd's own, gate_kloop_f32 or gate_kloop_pw: each owns its staging, its LDS image and its barriers),
+// gate_fwd_scores_epilogue, and the fused pool pass (gate_pool_request_rows / gate_fwd_pool_pass).
 #include "mil_internal.h"
 #include "philox.h"
 #include <type_traits>
@@ -26,10 +30,99 @@
 #define GF_BK 32
 
 typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
+typedef __attribute__((address_space(3))) f32x4 lds_f4;
+typedef __attribute__((address_space(3))) float lds_f32;      // the parts take smem as an LDS pointer, not a generic one
+
+// Lane and workgroup coordinates of the 128-row kernels, built once at the top of the kernel and handed to the parts by
+// value.  UNIFORM_WAVE = false (k_gate_fwd, whose DMA sources are per-lane pointers anyway) leaves the wave index a VGPR.
+struct GateFwdCoord {
+    int tid, lane, wave;        // wave is wave-uniform (an SGPR, through readfirstlane)
+    int wr, wc;                 // wave (wr, wc): rows 32 wr .. + 31 of the tile, d-chunks 3 wc .. 3 wc + 2
+    int r, h;                   // lane (r, h) of the 32 x 32 MFMA operand layout
+    int row0, rows_here;        // first row of the workgroup's tile, and how many of its 128 rows exist
+    unsigned lds0;              // LDS byte address of smem
+};
+template <bool UNIFORM_WAVE = true>
+__device__ __forceinline__ GateFwdCoord gate_fwd_coord(const float* smem, int R) {
+    GateFwdCoord co;
+    co.tid = threadIdx.x;
+    co.lane = co.tid & 63;
+    co.wave = UNIFORM_WAVE ? __builtin_amdgcn_readfirstlane(co.tid >> 6) : co.tid >> 6;
+    co.wr = co.wave >> 1;
+    co.wc = co.wave & 1;
+    co.r = co.lane & 31;
+    co.h = co.lane >> 5;
+    co.row0 = blockIdx.x * GF_TM;
+    co.rows_here = min(GF_TM, R - co.row0);
+    co.lds0 = (unsigned)(uintptr_t)(lds_void*)smem;
+    return co;
+}
+
+__device__ __forceinline__ void gate_acc_clear(f32x16 (&acc)[3][2]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[c][u][i] = 0.f;
+}
+
+// LDS regions of the epilogue and of the fused pool pass (float offsets into smem: the K loop's buffers are dead by then)
+#define GF_SRED_OFF 0                          /* [2 wc][128] the two halves of every row's score */
+#define GF_SC_OFF (2 * GF_TM)                  /* [128] final scores, for the fused pool pass */
+#define GF_PRED_OFF 1024                       /* [4 tiles][2 virtual waves][NQ][256] pool sums of the wc = 1 waves */
+#define GF_PRED_FLOATS(NQ) (4 * 2 * (NQ) * 256)
+static_assert(GF_SRED_OFF + 2 * GF_TM <= GF_SC_OFF && GF_SC_OFF + GF_TM <= GF_PRED_OFF, "epilogue LDS regions overlap");
+
+// Activations, the gates store, the score of every row: acc = x . [Wv; Wu]^T of this wave's 32 rows x 3 d-chunks.  In
+// train mode the survivors' scale 1/(1-p) is applied here.  copy_scores: the final scores also go to smem + GF_SC_OFF
+// (-inf for rows beyond R); the caller puts a barrier in front of reading them.
+template <bool DROP>
+__device__ __forceinline__ void gate_fwd_scores_epilogue(const GateFwdCoord co, const f32x16 (&acc)[3][2], const float* bv,
+                                                         const float* bu, const float* wvec, const float* battn,
+                                                         float* scores, float* gates, int R, float xscale, lds_f32* smem,
+                                                         bool copy_scores) {
+    float part[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) part[i] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int d = 32 * (3 * co.wc + c) + co.r;
+        const float bvd = bv[d], bud = bu[d], wd = wvec[d];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float v = fast_tanh(DROP ? fmaf(acc[c][0][i], xscale, bvd) : acc[c][0][i] + bvd);
+            const float u = fast_sigmoid(DROP ? fmaf(acc[c][1][i], xscale, bud) : acc[c][1][i] + bud);
+            part[i] += wd * v * u;
+            if (gates != nullptr) {
+                const int gr = co.row0 + 32 * co.wr + mfma32_row(i, co.h);
+                if (gr < R) {
+                    gates[(size_t)gr * GF_NG + d] = v;
+                    gates[(size_t)gr * GF_NG + 192 + d] = u;
+                }
+            }
+        }
+    }
+    lds_f32* sred = smem + GF_SRED_OFF;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float v = half_sum_lane31(part[i]);
+        if (co.r == 31) sred[co.wc * GF_TM + 32 * co.wr + mfma32_row(i, co.h)] = v;
+    }
+    __syncthreads();
+    if (co.tid < GF_TM) {
+        const int gr = co.row0 + co.tid;
+        const float sc = sred[co.tid] + sred[GF_TM + co.tid] + battn[0];
+        if (gr < R) scores[gr] = sc;
+        if (copy_scores) smem[GF_SC_OFF + co.tid] = gr < R ? sc : -INFINITY;
+    }
+}
+
+// L > 4096 (gate_route_plan: MIL_ROUTE_MAIN_LEGACY): the K loop with 64-bit source pointers, in the kernel body.
 // DROP: train mode (ABMIL.py:49).  xbits [R][L/32] keep bits (csrc/dropout.hip); a K-slice is 32 columns = ONE word per
 // row, loaded one slice ahead next to the DMA pieces; the A fragment of lane (r, h) holds k = 8t + 4h + j, so the word is
-// shifted by 4h once and element (t, j) is kept by bit 8t + j (two VALU per element, under the MFMAs).  The survivors'
-// scale 1/(1-p) is applied to the accumulators in the epilogue.
+// shifted by 4h once and element (t, j) is kept by bit 8t + j (two VALU per element, under the MFMAs).
 template <bool DROP>
 __global__ __launch_bounds__(512) void k_gate_fwd(const float* __restrict__ x, const float* __restrict__ Wv,
                                                        const float* __restrict__ bv, const float* __restrict__ Wu,
@@ -40,10 +133,8 @@ __global__ __launch_bounds__(512) void k_gate_fwd(const float* __restrict__ x, c
     __shared__ __attribute__((aligned(16))) float smem[2 * (GF_TM + GF_NG) * 32];
     float* xs = smem;                      // [2][128][32]
     float* ws = smem + 2 * GF_TM * 32;     // [2][384][32]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int r = lane & 31, h = lane >> 5;
-    const int row0 = blockIdx.x * GF_TM;
+    const GateFwdCoord co = gate_fwd_coord<false>(smem, R);
+    const int lane = co.lane, wave = co.wave, wr = co.wr, wc = co.wc, r = co.r, h = co.h, row0 = co.row0;
     // DMA pieces of this wave: 2 x-pieces (8 rows each) and 6 W-pieces; lane -> (row in piece, physical chunk)
     const int prow = lane >> 3, pch = lane & 7;
     const float* gsrc[8];
@@ -66,12 +157,7 @@ __global__ __launch_bounds__(512) void k_gate_fwd(const float* __restrict__ x, c
         __builtin_amdgcn_global_load_lds(gsrc[i] + k0, (lds_void*)dst, 16, 0, 0);
     };
     f32x16 acc[3][2];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[c][u][i] = 0.f;
+    gate_acc_clear(acc);
 
     const int nslice = L / GF_BK;
     // (starting each workgroup's K loop at a different slice, to de-correlate the L2 requests for the shared gate
@@ -130,54 +216,23 @@ __global__ __launch_bounds__(512) void k_gate_fwd(const float* __restrict__ x, c
         }
         __syncthreads();
     }
-
-    float part[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) part[i] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int d = 32 * (3 * wc + c) + r;
-        const float bvd = bv[d], bud = bu[d], wd = wvec[d];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float v = fast_tanh(DROP ? fmaf(acc[c][0][i], xscale, bvd) : acc[c][0][i] + bvd);
-            const float u = fast_sigmoid(DROP ? fmaf(acc[c][1][i], xscale, bud) : acc[c][1][i] + bud);
-            part[i] += wd * v * u;
-            if (gates != nullptr) {
-                const int gr = row0 + 32 * wr + mfma32_row(i, h);
-                if (gr < R) {
-                    gates[(size_t)gr * GF_NG + d] = v;
-                    gates[(size_t)gr * GF_NG + 192 + d] = u;
-                }
-            }
-        }
-    }
-    float* sred = smem;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float v = half_sum_lane31(part[i]);
-        if (r == 31) sred[wc * GF_TM + 32 * wr + mfma32_row(i, h)] = v;
-    }
-    __syncthreads();
-    if (tid < GF_TM) {
-        const int gr = row0 + tid;
-        if (gr < R) scores[gr] = sred[tid] + sred[GF_TM + tid] + battn[0];
-    }
+    gate_fwd_scores_epilogue<DROP>(co, acc, bv, bu, wvec, battn, scores, gates, R, xscale, (lds_f32*)smem, false);
 }
 
-// ================================================================================ K1a gate forward, "VALU diet" form
-// Same tiling, k order and results (bit for bit) as k_gate_fwd; the main loop sheds the vector-ALU instructions that the
-// f32 MFMA cannot hide (see k_gate_bwd_dw2 / tools/mfma_valu_mix.hip):
-//   * LDS-DMA through buffer resources (buffer_load_dwordx4 ... lds): the per-lane source offset is a loop invariant, the
-//     K offset an SGPR, the LDS destination goes to M0 by scalar ALU (no 64-bit pointer adds, no v_readfirstlane);
-//     rows of the last tile beyond R read as zeros by the hardware range check;
-//   * fragment reads are ds_read_b128 with immediate offsets from twelve precomputed per-lane LDS addresses (the buffer
-//     index is a compile-time constant: the slice loop is unrolled by two);
-//   * in train mode the keep-mask word of the next slice comes through a buffer resource as well.
-// Left in the loop per 32-column slice and wave: the mask itself (2 VALU per A element, train mode only).
-typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
-#define GF2_XS_BYTES (GF_TM * 32 * 4)          /* one x buffer  (16 KB) */
-#define GF2_WS_BYTES (GF_NG * 32 * 4)          /* one W buffer  (48 KB) */
+// ================================================================================ K1a gate forward, L <= 4096
+// k_gate_fwd2<DROP, GEN, PQ, PW>: the same tiling, k order and epilogue as k_gate_fwd, with 32-bit buffer offsets.
+//   PW   which K loop: gate_kloop_f32 (same results as k_gate_fwd, bit for bit; MIL_GATE_PIECES=0) or gate_kloop_pw
+//        (split-bf16, the default of the fp32 one-call step)
+//   GEN  the workgroup draws its keep words itself (GateFwdGen, GateKeepWords)
+//   PQ   > 0 (= L / 256): the pool partial pass runs behind the epilogue (GateFwdPool, gate_fwd_pool_pass)
+#define GF2_XS_BYTES (GF_TM * 32 * 4)          /* gate_kloop_f32: one x buffer  (16 KB) */
+#define GF2_WS_BYTES (GF_NG * 32 * 4)          /* gate_kloop_f32: one W buffer  (48 KB) */
+#define GP_XS_BYTES (GF_TM * 16 * 4)           /* gate_kloop_pw: one x buffer            (8 KiB) */
+#define GP_WS_BYTES (GP_SLICE_ELEMS * 2)       /* gate_kloop_pw: one W piece block      (36 KiB) */
+constexpr int gate_fwd2_smem_floats(bool pw) { return pw ? 2 * (GP_XS_BYTES + GP_WS_BYTES) / 4 : 2 * (GF2_XS_BYTES + GF2_WS_BYTES) / 4; }
+static_assert(GF_PRED_OFF + GF_PRED_FLOATS(2) <= gate_fwd2_smem_floats(false) &&
+                  GF_PRED_OFF + GF_PRED_FLOATS(2) <= gate_fwd2_smem_floats(true),
+              "the epilogue / pool regions must fit the LDS image of either K loop");
 
 // GEN (train mode, L <= 1024): the workgroup DRAWS the keep words of its 128 rows itself - the same Philox blocks
 // k_dropout_keep_bits would produce (philox.h) - keeps them in LDS for its own A fragments and writes them to xbits for
@@ -192,64 +247,80 @@ struct GateFwdGen {
     const int32_t* offset_dev;
 };
 
-// PQ > 0 (= L / 256): the attention-pool PARTIAL PASS of the workgroup's four 32-row tiles runs in the epilogue, once the
-// 128 scores are final - k_pool_partial's arithmetic, operation for operation (tile weights by the same wave reductions,
-// virtual wave v = rows v, v + 4, ..., the four virtual waves of a tile folded in the same order, the head-projection
-// by-product through the same 16-value reduction), so partials / hrow equal the stand-alone kernel's.  The rows come back
-// from L2 / Infinity Cache (the DMA stream of the main loop read them moments ago): one launch and one cold start less
-// per step - the stand-alone pass costs 14 us at 32 x 1024 x 512 although its bytes take 7.  Only for batches whose
-// tiles are all full and aligned (T * 32 == R, i.e. tile t = rows 32 t ..), which the host checks.
-struct GateFwdPool {
-    const int32_t* tile_map;    // [T][4] = {bag, row0, nrows, 0}
-    float* partials;            // [T][L] then [T][2]
-    int T;
-    const float* Wf;            // [2][L] head rows (C == 2)
-    float* hrow;                // [R][2]
-    const uint32_t* mbits;      // [B][L/32] keep words of the head's dropout (train mode without GEN), else NULL
-    float mscale;
+// Keep words of this lane's fragment row (row 32 wr + r of the tile), one word per 32 columns: from xbits through a
+// buffer resource, or (GEN) drawn by init() into mlds [128][L/32].  Both K loops walk them the same way:
+//   unsigned mnext = kw.first();  per 32 columns s: { use mnext; mnext = kw.word(min(s + 1, nslice - 1)); }
+template <bool DROP, bool GEN>
+struct GateKeepWords {
+    uint32_t* mlds;
+    __amdgpu_buffer_rsrc_t srd_m;
+    int vmask;                  // GEN: word index of the row in mlds; else byte offset of the row in srd_m
+    unsigned w0;                // !GEN: the word of slice 0, requested by init()
+    uint64_t off;               // GEN: the Philox offset of this step
+
+    // in front of the K loop's first load; the GEN words are visible after the barrier behind that load
+    __device__ __forceinline__ void init(const GateFwdCoord co, const uint32_t* xbits, const GateFwdGen& gen, uint32_t* lds,
+                                         int L) {
+        const int nslice = L / GF_BK;
+        mlds = lds;
+        vmask = 0;
+        w0 = 0;
+        off = 0;
+        if (DROP && !GEN) {
+            srd_m = __builtin_amdgcn_make_buffer_rsrc((void*)(xbits + (size_t)co.row0 * nslice), 0, co.rows_here * nslice * 4,
+                                                      MIL_SRD_FLAGS);
+            vmask = (32 * co.wr + co.r) * nslice * 4;
+            w0 = __builtin_amdgcn_raw_buffer_load_b32(srd_m, vmask, 0, 0);
+        }
+        if (GEN) {
+            off = gen.offset;
+            if (gen.offset_dev != nullptr) off += (uint64_t)(uint32_t)gen.offset_dev[0];
+            const size_t blk0 = (size_t)co.row0 * nslice / 4;               // 128 nslice words per workgroup: a multiple of 4
+            const int nblk = co.rows_here * nslice / 4;                     // nslice % 4 == 0 (host)
+            for (int q = co.tid; q < nblk; q += 512) {
+                const uint4 wds = philox_keep_words_half(blk0 + q, off, gen.seed_lo, gen.seed_hi);
+                *reinterpret_cast<uint4*>(gen.xbits_out + 4 * (blk0 + q)) = wds;
+                *reinterpret_cast<uint4*>(mlds + 4 * q) = wds;
+            }
+            if (blockIdx.x == 0 && gen.mbits_out != nullptr) {
+                const int nw = gen.B * (L >> 5);                            // even (L % 64 == 0)
+                for (int q = co.tid; 2 * q < nw; q += 512) {
+                    const uint2 wds = philox_keep_words_quarter((uint64_t)q, off, gen.mseed_lo, gen.mseed_hi);
+                    gen.mbits_out[2 * q] = wds.x;
+                    gen.mbits_out[2 * q + 1] = wds.y;
+                }
+            }
+            vmask = (32 * co.wr + co.r) * nslice;
+        }
+    }
+    __device__ __forceinline__ unsigned first() const { return GEN ? mlds[vmask] : w0; }
+    __device__ __forceinline__ unsigned word(int s1) const {
+        if (GEN) return mlds[vmask + s1];
+        return __builtin_amdgcn_raw_buffer_load_b32(srd_m, vmask, s1 * 4, 0);
+    }
 };
 
-// PW (split-bf16 main loop, the default of the fp32 one-call step; MIL_GATE_PIECES=0 keeps the f32-MFMA loop above): the
-// contraction runs on v_mfma_f32_32x32x16_bf16 over three-piece bf16 operands, x = x0 + x1 + x2 and W = w0 + w1 + w2 (each
-// split exact, gp_split3), keeping the six cross terms (p, q) with p + q <= 2: per 16 k and output tile six bf16 MFMAs of 32
-// cycles (192) where the f32 MFMA takes 512.  The dropped terms x1w2, x2w1, x2w2 are below 2^-24 relative.  Same
-// workgroup shape, epilogue, keep draw and pool pass as the f32 loop; only the K loop differs.
-//   * K slices are 16 deep (one bf16 MFMA), double-buffered: per buffer an x image [128][16] fp32 (64-byte rows, 16-byte
-//     chunk c of row `row` at c ^ ((row >> 2) & 3): conflict-free for the ds_read_b128 lane groups) and the W piece block
-//     [3][2][384][8] bf16 of the slice (36 KiB, gp_index: copied as it lies in Wp).  2 x 44 KiB; 32-deep slices would need
-//     2 x 88 KiB, over the 160 KiB of a CU.
-//   * W pieces are precomputed (Wp, refreshed by the optimizer, gate_reduce.h); x is split after the fragment read, in
-//     registers, by both waves that share a row tile (the VALU work hides under the bf16 MFMAs).
-//   * dropped elements are zeroed before the split (all three pieces 0); 1/(1-p) stays in the epilogue.
-//   * non-finite x: x0 = x, x1 = x2 = 0 (gp_split3).  A product term x0 * w_q with w_q == 0 still makes an infinite x a
-//     NaN in that gate column, where the f32 loop gives +-inf (tanh/sigmoid then +-1 / 0 / 1): rows with an infinite
-//     feature are not carried through this path with the f32 loop's values.
-#define GP_XS_BYTES (GF_TM * 16 * 4)             /* one x buffer            (8 KiB) */
-#define GP_WS_BYTES (GP_SLICE_ELEMS * 2)         /* one W piece block      (36 KiB) */
-template <bool DROP, bool GEN, int PQ, bool PW = false>
-__global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, const float* __restrict__ Wv,
-                                                   const float* __restrict__ bv, const float* __restrict__ Wu,
-                                                   const float* __restrict__ bu, const float* __restrict__ wvec,
-                                                   const float* __restrict__ battn, float* __restrict__ scores,
-                                                   float* __restrict__ gates, int R, int L,
-                                                   const uint32_t* __restrict__ xbits, float xscale, GateFwdGen gen,
-                                                   GateFwdPool pool, const unsigned short* __restrict__ Wp = nullptr) {
-    constexpr int SMEM_FLOATS = PW ? (2 * (GP_XS_BYTES + GP_WS_BYTES)) / 4 : 2 * (GF_TM + GF_NG) * 32;
-    __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];                  // [2] x buffers, then [2] W buffers
-    __shared__ __attribute__((aligned(16))) uint32_t mlds[GEN ? GF_TM * 32 : 4];       // keep words [128][nslice <= 32]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;
-    const int r = lane & 31, h = lane >> 5;
-    const int row0 = blockIdx.x * GF_TM;
+// ---- K loop on the f32 MFMA, "VALU diet" form: k_gate_fwd's loop without the vector-ALU instructions that the f32 MFMA
+// cannot hide (see k_gate_bwd_dw2 / tools/mfma_valu_mix.hip).  LDS image as k_gate_fwd's: [2] x buffers [128][32], then
+// [2] W buffers [384][32], chunk c of a row at c ^ ((row >> 1) & 7).
+//   * LDS-DMA through buffer resources (buffer_load_dwordx4 ... lds): the per-lane source offset is a loop invariant, the
+//     K offset an SGPR, the LDS destination goes to M0 by scalar ALU (no 64-bit pointer adds, no v_readfirstlane);
+//     rows of the last tile beyond R read as zeros by the hardware range check;
+//   * fragment reads are ds_read_b128 with immediate offsets from twelve precomputed per-lane LDS addresses (the buffer
+//     index is a compile-time constant: the slice loop is unrolled by two);
+//   * in train mode the keep-mask word of the next slice comes through a buffer resource as well (or from LDS, GEN).
+// Left in the loop per 32-column slice and wave: the mask itself (2 VALU per A element, train mode only).
+// Owns everything from the slice-0 load to the barrier behind the last slice.
+template <bool DROP, bool GEN>
+__device__ __forceinline__ void gate_kloop_f32(const GateFwdCoord co, const GateKeepWords<DROP, GEN>& kw, const float* x,
+                                               const float* Wv, const float* Wu, int L, f32x16 (&acc)[3][2]) {
+    const int lane = co.lane, wave = co.wave, wr = co.wr, wc = co.wc, r = co.r, h = co.h;
+    const unsigned lds0 = co.lds0;
     const int nslice = L / GF_BK;
-    const unsigned lds0 = (unsigned)(uintptr_t)(lds_void*)smem;
-
     // ---- DMA pieces of this wave: 2 x pieces (8 rows each), 6 W pieces; lane -> (row in piece, physical 16-byte chunk)
     const int prow = lane >> 3, pch = lane & 7;
-    const int rows_here = min(GF_TM, R - row0);
     const __amdgpu_buffer_rsrc_t srd_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)row0 * L), 0, rows_here * L * 4, MIL_SRD_FLAGS);
+        __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)co.row0 * L), 0, co.rows_here * L * 4, MIL_SRD_FLAGS);
     const __amdgpu_buffer_rsrc_t srd_v = __builtin_amdgcn_make_buffer_rsrc((void*)Wv, 0, MIL_GATE_D * L * 4, MIL_SRD_FLAGS);
     const __amdgpu_buffer_rsrc_t srd_u = __builtin_amdgcn_make_buffer_rsrc((void*)Wu, 0, MIL_GATE_D * L * 4, MIL_SRD_FLAGS);
     int vsrc[8];                 // per-lane byte offset of the piece's source (slice 0)
@@ -285,64 +356,10 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
         for (int b = 0; b < 2; ++b)
             fb_addr[b][t] = lds0 + (unsigned)(2 * GF2_XS_BYTES + b * GF2_WS_BYTES + (96 * wc + r) * 128) + ch;
     }
-    // ---- keep bits of this lane's fragment row (train mode)
-    __amdgpu_buffer_rsrc_t srd_m = srd_x;
-    int vmask = 0;
-    unsigned mnext = 0;
-    if (DROP && !GEN) {
-        srd_m = __builtin_amdgcn_make_buffer_rsrc((void*)(xbits + (size_t)row0 * nslice), 0, rows_here * nslice * 4, MIL_SRD_FLAGS);
-        vmask = (32 * wr + r) * nslice * 4;
-        mnext = __builtin_amdgcn_raw_buffer_load_b32(srd_m, vmask, 0, 0);
-    }
-    uint64_t off = 0;
-    if (GEN) {
-        off = gen.offset;
-        if (gen.offset_dev != nullptr) off += (uint64_t)(uint32_t)gen.offset_dev[0];
-        const size_t blk0 = (size_t)row0 * nslice / 4;                  // 128 nslice words per workgroup: a multiple of 4
-        const int nblk = rows_here * nslice / 4;                        // nslice % 4 == 0 (host)
-        for (int q = tid; q < nblk; q += 512) {
-            const uint4 wds = philox_keep_words_half(blk0 + q, off, gen.seed_lo, gen.seed_hi);
-            *reinterpret_cast<uint4*>(gen.xbits_out + 4 * (blk0 + q)) = wds;
-            *reinterpret_cast<uint4*>(mlds + 4 * q) = wds;
-        }
-        if (blockIdx.x == 0 && gen.mbits_out != nullptr) {
-            const int nw = gen.B * (L >> 5);                            // even (L % 64 == 0)
-            for (int q = tid; 2 * q < nw; q += 512) {
-                const uint2 wds = philox_keep_words_quarter((uint64_t)q, off, gen.mseed_lo, gen.mseed_hi);
-                gen.mbits_out[2 * q] = wds.x;
-                gen.mbits_out[2 * q + 1] = wds.y;
-            }
-        }
-        vmask = (32 * wr + r) * nslice;                                 // word index into mlds
-    }
-
-    f32x16 acc[3][2];
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[c][u][i] = 0.f;
-
-    if constexpr (PW) {
-        // slice 0 of the split-bf16 loop: x rows 16w .. 16w + 15 and W piece blocks w, w + 8, .. (same map as its dma16)
-        const int xrow = 16 * wave + (lane >> 2);
-        const __amdgpu_buffer_rsrc_t srd_p = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, GP_WS_BYTES, MIL_SRD_FLAGS);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_x, (lds_void*)(uintptr_t)(lds0 + (unsigned)(wave * 1024)), 16,
-                                                 (xrow * L + 4 * ((lane & 3) ^ ((xrow >> 2) & 3))) * 4, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int p = wave + 8 * i;
-            if (i < 4 || p < 36)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p, (lds_void*)(uintptr_t)(lds0 + (unsigned)(2 * GP_XS_BYTES + p * 1024)),
-                                                         16, lane * 16, p * 1024, 0, 0);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dma_piece(i, 0, 0);
-    }
+    for (int i = 0; i < 8; ++i) dma_piece(i, 0, 0);
     __syncthreads();                                   // hipcc drains the DMA (vmcnt(0)) in front of the barrier
-    if (GEN) mnext = mlds[vmask];
+    unsigned mnext = kw.first();
 
     auto slice = [&](int s, auto buf_c) {
         constexpr int buf = decltype(buf_c)::value;
@@ -351,8 +368,7 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
         unsigned mcur = 0;
         if (DROP) {
             mcur = mnext >> (4 * h);
-            if (GEN) mnext = mlds[vmask + s1];
-            else mnext = __builtin_amdgcn_raw_buffer_load_b32(srd_m, vmask, s1 * 4, 0);
+            mnext = kw.word(s1);
         }
         f32x4 a[2], b[2][3][2];
         auto frag_piece = [&](int t, int q, int p) {
@@ -386,7 +402,6 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
             }
         }
     };
-    if constexpr (!PW) {
     int s = 0;
     for (; s + 1 < nslice; s += 2) {
         slice(s, std::integral_constant<int, 0>{});
@@ -398,246 +413,284 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
         slice(s, std::integral_constant<int, 0>{});
         __syncthreads();
     }
-    } else {
-        // ---- split-bf16 K loop (see the comment above the kernel): 16-deep slices, buffer = slice parity
-        const int n16 = L / 16;
-        const int xrow = 16 * wave + (lane >> 2);                         // x DMA: wave w fills rows 16w .. 16w + 15
-        const int xsrc = (xrow * L + 4 * ((lane & 3) ^ ((xrow >> 2) & 3))) * 4;
-        const __amdgpu_buffer_rsrc_t srd_p = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, n16 * GP_WS_BYTES, MIL_SRD_FLAGS);
-        auto dma16 = [&](int buf, int s16) {
-            const unsigned xdst = lds0 + (unsigned)(buf * GP_XS_BYTES + wave * 1024);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_x, (lds_void*)(uintptr_t)xdst, 16, xsrc, s16 * 64, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {                                 // 36 W pieces of 1 KiB: 4 or 5 per wave
-                const int p = wave + 8 * i;
-                if (i < 4 || p < 36) {
-                    const unsigned wdst = lds0 + (unsigned)(2 * GP_XS_BYTES + buf * GP_WS_BYTES + p * 1024);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p, (lds_void*)(uintptr_t)wdst, 16, lane * 16,
-                                                             s16 * GP_WS_BYTES + p * 1024, 0, 0);
-                }
-            }
-        };
-        const unsigned xr = lds0 + (unsigned)((32 * wr + r) * 64);
-        const unsigned pa0 = xr + 16u * (unsigned)((2 * h) ^ ((r >> 2) & 3));
-        const unsigned pa1 = xr + 16u * (unsigned)((2 * h + 1) ^ ((r >> 2) & 3));
-        const unsigned pb = lds0 + (unsigned)(2 * GP_XS_BYTES + (h * GF_NG + 96 * wc + r) * 16);
-        // one 16-deep slice from buffer `buf`; mw = keep bits of this lane's 8 k in bits 0..7
-        auto slice16 = [&](int s16, unsigned mw, auto buf_c) {
-            constexpr int buf = decltype(buf_c)::value;
-            const f32x4 xa0 = *(lds_cf4*)(uintptr_t)(pa0 + (unsigned)(buf * GP_XS_BYTES));
-            const f32x4 xa1 = *(lds_cf4*)(uintptr_t)(pa1 + (unsigned)(buf * GP_XS_BYTES));
-            f32x4 bq[3][3][2];                                            // [piece][c][u], smallest piece first
-#pragma unroll
-            for (int q = 2; q >= 0; --q)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-                        bq[q][c][u] = *(lds_cf4*)(uintptr_t)(pb + (unsigned)(buf * GP_WS_BYTES + (q * 2 * GF_NG + u * 192 + 32 * c) * 16));
-            // the next slice goes to the other buffer (after this slice's reads in program order: no LDS wait in between)
-            dma16(buf ^ 1, min(s16 + 1, n16 - 1));
-            gp_bf16x8 ap[3];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float v = j < 4 ? xa0[j] : xa1[j - 4];
-                if (DROP) v = keep_if(v, mw, j);
-                unsigned short p0, p1, p2;
-                gp_split3(v, p0, p1, p2);
-                ap[0][j] = __builtin_bit_cast(__bf16, p0);
-                ap[1][j] = __builtin_bit_cast(__bf16, p1);
-                ap[2][j] = __builtin_bit_cast(__bf16, p2);
-            }
-            // cross terms (p, q), p + q <= 2, smallest first; the B piece q of every tile is read before its first use
-            constexpr int TP[6] = {0, 1, 2, 0, 1, 0}, TQ[6] = {2, 1, 0, 1, 0, 0};
-#pragma unroll
-            for (int t = 0; t < 6; ++t)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-                        acc[c][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[TP[t]], __builtin_bit_cast(gp_bf16x8, bq[TQ[t]][c][u]),
-                                                                            acc[c][u], 0, 0, 0);
-            // keep the MFMAs in front of the barrier (and its DMA drain): the next slice's DMA lands under them
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        for (int s = 0; s < nslice; ++s) {                                // 32-deep steps: one keep word, two slices
-            unsigned mw = 0;
-            if (DROP) {
-                mw = mnext;
-                const int s1 = min(s + 1, nslice - 1);
-                if (GEN) mnext = mlds[vmask + s1];
-                else mnext = __builtin_amdgcn_raw_buffer_load_b32(srd_m, vmask, s1 * 4, 0);
-            }
-            slice16(2 * s, mw >> (8 * h), std::integral_constant<int, 0>{});
-            __syncthreads();
-            slice16(2 * s + 1, mw >> (16 + 8 * h), std::integral_constant<int, 1>{});
-            __syncthreads();
-        }
-    }
+}
 
-    // fused pool pass: the x rows of this wave's tile are requested NOW (they depend on nothing the epilogue computes), so
-    // that their trip from L2 / Infinity Cache runs under the activation epilogue
-    constexpr int PNQ = PQ > 0 ? PQ : 1;
-    f32x4 pv[PQ > 0 ? 2 : 1][PQ > 0 ? MIL_POOL_TILE / 4 : 1][PNQ];
-    if (PQ > 0) {
-        const int trow0 = row0 + 32 * wr;
-        if (trow0 < R) {
+// ---- split-bf16 K loop (PW): the contraction runs on v_mfma_f32_32x32x16_bf16 over three-piece bf16 operands,
+// x = x0 + x1 + x2 and W = w0 + w1 + w2 (each split exact, gp_split3), keeping the six cross terms (p, q) with p + q <= 2:
+// per 16 k and output tile six bf16 MFMAs of 32 cycles (192) where the f32 MFMA takes 512.  The dropped terms x1w2, x2w1,
+// x2w2 are below 2^-24 relative.
+//   * K slices are 16 deep (one bf16 MFMA), double-buffered, buffer = slice parity.  LDS image: [2] x buffers [128][16]
+//     fp32 (64-byte rows, 16-byte chunk c of row `row` at c ^ ((row >> 2) & 3): conflict-free for the ds_read_b128 lane
+//     groups), then [2] W piece blocks [3][2][384][8] bf16 of the slice (36 KiB, gp_index: copied as it lies in Wp).
+//     2 x 44 KiB; 32-deep slices would need 2 x 88 KiB, over the 160 KiB of a CU.
+//   * W pieces are precomputed (Wp, refreshed by the optimizer, gate_reduce.h); x is split after the fragment read, in
+//     registers, by both waves that share a row tile (the VALU work hides under the bf16 MFMAs).
+//   * dropped elements are zeroed before the split (all three pieces 0); 1/(1-p) stays in the epilogue.
+//   * non-finite x: x0 = x, x1 = x2 = 0 (gp_split3).  A product term x0 * w_q with w_q == 0 still makes an infinite x a
+//     NaN in that gate column, where the f32 loop gives +-inf (tanh/sigmoid then +-1 / 0 / 1): rows with an infinite
+//     feature are not carried through this path with the f32 loop's values.
+// Owns everything from the slice-0 load to the barrier behind the last slice.
+template <bool DROP, bool GEN>
+__device__ __forceinline__ void gate_kloop_pw(const GateFwdCoord co, const GateKeepWords<DROP, GEN>& kw, const float* x,
+                                              const unsigned short* Wp, int L, f32x16 (&acc)[3][2]) {
+    const int lane = co.lane, wave = co.wave, wr = co.wr, wc = co.wc, r = co.r, h = co.h;
+    const unsigned lds0 = co.lds0;
+    const int nslice = L / GF_BK, n16 = L / 16;
+    const __amdgpu_buffer_rsrc_t srd_x =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)co.row0 * L), 0, co.rows_here * L * 4, MIL_SRD_FLAGS);
+    const __amdgpu_buffer_rsrc_t srd_p = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, n16 * GP_WS_BYTES, MIL_SRD_FLAGS);
+    const int xrow = 16 * wave + (lane >> 2);                         // x DMA: wave w fills rows 16w .. 16w + 15
+    const int xsrc = (xrow * L + 4 * ((lane & 3) ^ ((xrow >> 2) & 3))) * 4;
+    auto dma16 = [&](int buf, int s16) {
+        const unsigned xdst = lds0 + (unsigned)(buf * GP_XS_BYTES + wave * 1024);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_x, (lds_void*)(uintptr_t)xdst, 16, xsrc, s16 * 64, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {                                 // 36 W pieces of 1 KiB: 4 or 5 per wave
+            const int p = wave + 8 * i;
+            if (i < 4 || p < 36) {
+                const unsigned wdst = lds0 + (unsigned)(2 * GP_XS_BYTES + buf * GP_WS_BYTES + p * 1024);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p, (lds_void*)(uintptr_t)wdst, 16, lane * 16,
+                                                         s16 * GP_WS_BYTES + p * 1024, 0, 0);
+            }
+        }
+    };
+    // fragment reads: byte offsets into smem of row (32 wr + r) of the x image (its two swizzled chunks) and of row
+    // (h, 96 wc + r) of the W block; lds0 is added at the read
+    const unsigned xr = (unsigned)((32 * wr + r) * 64);
+    const unsigned pa0 = xr + 16u * (unsigned)((2 * h) ^ ((r >> 2) & 3));
+    const unsigned pa1 = xr + 16u * (unsigned)((2 * h + 1) ^ ((r >> 2) & 3));
+    const unsigned pb = (unsigned)(2 * GP_XS_BYTES + (h * GF_NG + 96 * wc + r) * 16);
+    // one 16-deep slice from buffer `buf`; mw = keep bits of this lane's 8 k in bits 0..7
+    auto slice16 = [&](int s16, unsigned mw, auto buf_c) {
+        constexpr int buf = decltype(buf_c)::value;
+        const f32x4 xa0 = *(lds_cf4*)(uintptr_t)(lds0 + pa0 + (unsigned)(buf * GP_XS_BYTES));
+        const f32x4 xa1 = *(lds_cf4*)(uintptr_t)(lds0 + pa1 + (unsigned)(buf * GP_XS_BYTES));
+        f32x4 bq[3][3][2];                                            // [piece][c][u], smallest piece first
+#pragma unroll
+        for (int q = 2; q >= 0; --q)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    bq[q][c][u] = *(lds_cf4*)(uintptr_t)(lds0 + pb + (unsigned)(buf * GP_WS_BYTES + (q * 2 * GF_NG + u * 192 + 32 * c) * 16));
+        // the next slice goes to the other buffer (after this slice's reads in program order: no LDS wait in between)
+        dma16(buf ^ 1, min(s16 + 1, n16 - 1));
+        gp_bf16x8 ap[3];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float v = j < 4 ? xa0[j] : xa1[j - 4];
+            if (DROP) v = keep_if(v, mw, j);
+            unsigned short p0, p1, p2;
+            gp_split3(v, p0, p1, p2);
+            ap[0][j] = __builtin_bit_cast(__bf16, p0);
+            ap[1][j] = __builtin_bit_cast(__bf16, p1);
+            ap[2][j] = __builtin_bit_cast(__bf16, p2);
+        }
+        // cross terms (p, q), p + q <= 2, smallest first; the B piece q of every tile is read before its first use
+        constexpr int TP[6] = {0, 1, 2, 0, 1, 0}, TQ[6] = {2, 1, 0, 1, 0, 0};
+#pragma unroll
+        for (int t = 0; t < 6; ++t)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    acc[c][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[TP[t]], __builtin_bit_cast(gp_bf16x8, bq[TQ[t]][c][u]),
+                                                                        acc[c][u], 0, 0, 0);
+        // keep the MFMAs in front of the barrier (and its DMA drain): the next slice's DMA lands under them
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    dma16(0, 0);
+    __syncthreads();                                   // hipcc drains the DMA (vmcnt(0)) in front of the barrier
+    unsigned mnext = kw.first();
+    for (int s = 0; s < nslice; ++s) {                                // 32-deep steps: one keep word, two slices
+        unsigned mw = 0;
+        if (DROP) {
+            mw = mnext;
+            mnext = kw.word(min(s + 1, nslice - 1));
+        }
+        slice16(2 * s, mw >> (8 * h), std::integral_constant<int, 0>{});
+        __syncthreads();
+        slice16(2 * s + 1, mw >> (16 + 8 * h), std::integral_constant<int, 1>{});
+        __syncthreads();
+    }
+}
+
+// ---- fused pool pass (PQ > 0, = L / 256): the attention-pool PARTIAL PASS of the workgroup's four 32-row tiles runs
+// behind the epilogue, once the 128 scores are final - k_pool_partial's arithmetic, operation for operation (tile weights
+// by the same wave reductions, virtual wave v = rows v, v + 4, ..., the four virtual waves of a tile folded in the same
+// order, the head-projection by-product through the same 16-value reduction), so partials / hrow equal the stand-alone
+// kernel's.  The rows come back from L2 / Infinity Cache (the DMA stream of the main loop read them moments ago): one
+// launch and one cold start less per step - the stand-alone pass costs 14 us at 32 x 1024 x 512 although its bytes take 7.
+// Only for batches whose tiles are all full and aligned (T * 32 == R, i.e. tile t = rows 32 t ..), which the host checks.
+struct GateFwdPool {
+    const int32_t* tile_map;    // [T][4] = {bag, row0, nrows, 0}
+    float* partials;            // [T][L] then [T][2]
+    int T;
+    const float* Wf;            // [2][L] head rows (C == 2)
+    float* hrow;                // [R][2]
+    const uint32_t* mbits;      // [B][L/32] keep words of the head's dropout (train mode without GEN), else NULL
+    float mscale;
+};
+// rows 2 wc + j + 4 i (j < 2, i < 8) of this wave's 32-row tile: lane l holds columns 256 q + 4 l .. + 3
+template <int NQ>
+struct GatePoolRows {
+    f32x4 v[2][MIL_POOL_TILE / 4][NQ];
+};
+// The x rows are requested in FRONT of the activation epilogue (they depend on nothing it computes), so that their trip
+// from L2 / Infinity Cache runs under it.
+template <int NQ>
+__device__ __forceinline__ void gate_pool_request_rows(const GateFwdCoord co, const float* x, int R, int L, GatePoolRows<NQ>& pv) {
+    const int trow0 = co.row0 + 32 * co.wr;
+    if (trow0 < R) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < MIL_POOL_TILE / 4; ++i) {
+                const float* xr = x + (size_t)(trow0 + 2 * co.wc + j + 4 * i) * L + 4 * co.lane;
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) pv.v[j][i][q] = *reinterpret_cast<const f32x4*>(xr + 256 * q);
+            }
+    }
+}
+// Behind gate_fwd_scores_epilogue<DROP>(.., copy_scores = true); pv from gate_pool_request_rows.
+template <bool DROP, bool GEN, int NQ>
+__device__ __forceinline__ void gate_fwd_pool_pass(const GateFwdCoord co, const GateKeepWords<DROP, GEN>& kw, GatePoolRows<NQ>& pv,
+                                                   const uint32_t* xbits, int R, int L, float xscale, const GateFwdGen& gen,
+                                                   const GateFwdPool& pool, lds_f32* smem) {
+    const int lane = co.lane, wr = co.wr, wc = co.wc;
+    const int nslice = L / GF_BK;
+    const lds_f32* sc_lds = smem + GF_SC_OFF;
+    lds_f32* pred = smem + GF_PRED_OFF;
+    __syncthreads();
+    const int trow0 = co.row0 + 32 * wr;           // this wave's tile: rows trow0 .. trow0 + 31 (wave-uniform)
+    const bool live = trow0 < R;                   // R % 32 == 0 (host): a tile is whole or absent
+    const int t = trow0 >> 5;
+    // tile weights, as wave 0 of k_pool_partial forms them
+    const float s_ = lane < 32 ? sc_lds[32 * wr + lane] : -INFINITY;
+    const float m_ = wave_allmax(s_);
+    const float p_ = lane < 32 ? expf(s_ - m_) : 0.f;
+    const float l_ = wave_allsum(p_);
+    const float xs = DROP ? xscale : 1.0f;
+    f32x4 pacc[2][NQ];
+    if (live) {
+        auto& v = pv.v;
+        const int sh = 4 * (lane & 7);
+        if (DROP) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int i = 0; i < MIL_POOL_TILE / 4; ++i) {
-                    const float* xr = x + (size_t)(trow0 + 2 * wc + j + 4 * i) * L + 4 * lane;
-#pragma unroll
-                    for (int q = 0; q < PNQ; ++q) pv[j][i][q] = *reinterpret_cast<const f32x4*>(xr + 256 * q);
-                }
-        }
-    }
-    float part[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) part[i] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int d = 32 * (3 * wc + c) + r;
-        const float bvd = bv[d], bud = bu[d], wd = wvec[d];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float v = fast_tanh(DROP ? fmaf(acc[c][0][i], xscale, bvd) : acc[c][0][i] + bvd);
-            const float u = fast_sigmoid(DROP ? fmaf(acc[c][1][i], xscale, bud) : acc[c][1][i] + bud);
-            part[i] += wd * v * u;
-            if (gates != nullptr) {
-                const int gr = row0 + 32 * wr + mfma32_row(i, h);
-                if (gr < R) {
-                    gates[(size_t)gr * GF_NG + d] = v;
-                    gates[(size_t)gr * GF_NG + 192 + d] = u;
-                }
-            }
-        }
-    }
-    float* sred = smem;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float v = half_sum_lane31(part[i]);
-        if (r == 31) sred[wc * GF_TM + 32 * wr + mfma32_row(i, h)] = v;
-    }
-    __syncthreads();
-    float* sc_lds = smem + 2 * GF_TM;                  // [128] final scores (fused pool pass)
-    if (tid < GF_TM) {
-        const int gr = row0 + tid;
-        const float sc = sred[tid] + sred[GF_TM + tid] + battn[0];
-        if (gr < R) scores[gr] = sc;
-        if (PQ > 0) sc_lds[tid] = gr < R ? sc : -INFINITY;
-    }
-    if (PQ > 0) {
-        constexpr int NQ = PQ > 0 ? PQ : 1;
-        float* pred = smem + 1024;                     // [4 tiles][2 virtual waves][NQ][256]
-        __syncthreads();
-        const int trow0 = row0 + 32 * wr;              // this wave's tile: rows trow0 .. trow0 + 31 (wave-uniform)
-        const bool live = trow0 < R;                   // R % 32 == 0 (host): a tile is whole or absent
-        const int t = trow0 >> 5;
-        // tile weights, as wave 0 of k_pool_partial forms them
-        const float s_ = lane < 32 ? sc_lds[32 * wr + lane] : -INFINITY;
-        const float m_ = wave_allmax(s_);
-        const float p_ = lane < 32 ? expf(s_ - m_) : 0.f;
-        const float l_ = wave_allsum(p_);
-        const float xs = DROP ? xscale : 1.0f;
-        f32x4 pacc[2][NQ];
-        if (live) {
-            auto& v = pv;
-            const int sh = 4 * (lane & 7);
-            if (DROP) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < MIL_POOL_TILE / 4; ++i) {
-                        const int rr = 2 * wc + j + 4 * i;
-#pragma unroll
-                        for (int q = 0; q < NQ; ++q) {
-                            const unsigned wd = GEN ? mlds[(32 * wr + rr) * nslice + 8 * q + (lane >> 3)]
-                                                    : xbits[(size_t)(trow0 + rr) * (L >> 5) + 8 * q + (lane >> 3)];
-                            const unsigned mm = wd >> sh;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[j][i][q][e] = keep_if(v[j][i][q][e], mm, e);
-                        }
-                    }
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) pacc[j][q] = f32x4{0, 0, 0, 0};
-#pragma unroll
-                for (int i = 0; i < MIL_POOL_TILE / 4; ++i) {
                     const int rr = 2 * wc + j + 4 * i;
-                    const float pw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_), rr)) * xs;
 #pragma unroll
-                    for (int q = 0; q < NQ; ++q) pacc[j][q] += pw * v[j][i][q];
+                    for (int q = 0; q < NQ; ++q) {
+                        const unsigned wd = GEN ? kw.mlds[(32 * wr + rr) * nslice + 8 * q + (lane >> 3)]
+                                                : xbits[(size_t)(trow0 + rr) * (L >> 5) + 8 * q + (lane >> 3)];
+                        const unsigned mm = wd >> sh;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[j][i][q][e] = keep_if(v[j][i][q][e], mm, e);
+                    }
                 }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) pacc[j][q] = f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < MIL_POOL_TILE / 4; ++i) {
+                const int rr = 2 * wc + j + 4 * i;
+                const float pw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_), rr)) * xs;
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) pacc[j][q] += pw * v[j][i][q];
             }
-            // head rows as this tile's bag sees them (k_pool_partial's head_row), then the by-product h[row][c]
-            const int bag_ = pool.tile_map[4 * t];
-            f32x4 wf[2][NQ];
+        }
+        // head rows as this tile's bag sees them (k_pool_partial's head_row), then the by-product h[row][c]
+        const int bag_ = pool.tile_map[4 * t];
+        f32x4 wf[2][NQ];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                f32x4 w = *reinterpret_cast<const f32x4*>(pool.Wf + (size_t)c * L + 256 * q + 4 * lane) * xs;
+                if (DROP) {
+                    const int widx = bag_ * (L >> 5) + 8 * q + (lane >> 3);
+                    unsigned wd;
+                    if (GEN) {      // the word workgroup 0 writes to mbits_out in this same launch: drawn again here
+                        const uint2 pr = philox_keep_words_quarter((uint64_t)(widx >> 1), kw.off, gen.mseed_lo, gen.mseed_hi);
+                        wd = (widx & 1) ? pr.y : pr.x;
+                    } else {
+                        wd = pool.mbits[widx];
+                    }
+                    const unsigned mm = wd >> sh;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w[e] = keep_if(w[e], mm, e) * pool.mscale;
+                }
+                wf[c][q] = w;
+            }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float d16[16];
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    f32x4 w = *reinterpret_cast<const f32x4*>(pool.Wf + (size_t)c * L + 256 * q + 4 * lane) * xs;
-                    if (DROP) {
-                        const int widx = bag_ * (L >> 5) + 8 * q + (lane >> 3);
-                        unsigned wd;
-                        if (GEN) {      // the word workgroup 0 writes to mbits_out in this same launch: drawn again here
-                            const uint2 pr = philox_keep_words_quarter((uint64_t)(widx >> 1), off, gen.mseed_lo, gen.mseed_hi);
-                            wd = (widx & 1) ? pr.y : pr.x;
-                        } else {
-                            wd = pool.mbits[widx];
-                        }
-                        const unsigned mm = wd >> sh;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) w[e] = keep_if(w[e], mm, e) * pool.mscale;
-                    }
-                    wf[c][q] = w;
-                }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float d16[16];
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int i = 0; i < MIL_POOL_TILE / 4; ++i) {
-                        float d = 0.f;
-#pragma unroll
-                        for (int q = 0; q < NQ; ++q)
-                            d += v[j][i][q][0] * wf[c][q][0] + v[j][i][q][1] * wf[c][q][1] + v[j][i][q][2] * wf[c][q][2] + v[j][i][q][3] * wf[c][q][3];
-                        d16[2 * i + c] = d;
-                    }
-                const float tot = wave_reduce16(d16, lane);
-                const int k = wave_reduce16_index(lane), rr = 2 * wc + j + 4 * (k >> 1);
-                if ((lane & 3) == 0) pool.hrow[(size_t)(trow0 + rr) * 2 + (k & 1)] = tot;
-            }
-            if (wc == 1) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
+                for (int i = 0; i < MIL_POOL_TILE / 4; ++i) {
+                    float d = 0.f;
 #pragma unroll
                     for (int q = 0; q < NQ; ++q)
-                        *reinterpret_cast<f32x4*>(pred + ((wr * 2 + j) * NQ + q) * 256 + 4 * lane) = pacc[j][q];
-            }
+                        d += v[j][i][q][0] * wf[c][q][0] + v[j][i][q][1] * wf[c][q][1] + v[j][i][q][2] * wf[c][q][2] + v[j][i][q][3] * wf[c][q][3];
+                    d16[2 * i + c] = d;
+                }
+            const float tot = wave_reduce16(d16, lane);
+            const int k = wave_reduce16_index(lane), rr = 2 * wc + j + 4 * (k >> 1);
+            if ((lane & 3) == 0) pool.hrow[(size_t)(trow0 + rr) * 2 + (k & 1)] = tot;
         }
-        __syncthreads();
-        if (live && wc == 0) {
-            float* out = pool.partials + (size_t)t * L;
+        if (wc == 1) {
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                f32x4 vv = pacc[0][q];
-                vv += pacc[1][q];
-                vv += *reinterpret_cast<const f32x4*>(pred + ((wr * 2 + 0) * NQ + q) * 256 + 4 * lane);
-                vv += *reinterpret_cast<const f32x4*>(pred + ((wr * 2 + 1) * NQ + q) * 256 + 4 * lane);
-                *reinterpret_cast<f32x4*>(out + 256 * q + 4 * lane) = vv;
-            }
-            if (lane == 0) {
-                float* ml = pool.partials + (size_t)pool.T * L + 2 * t;
-                ml[0] = m_;
-                ml[1] = l_;
-            }
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q)
+                    *(lds_f4*)(pred + ((wr * 2 + j) * NQ + q) * 256 + 4 * lane) = pacc[j][q];
         }
     }
+    __syncthreads();
+    if (live && wc == 0) {
+        float* out = pool.partials + (size_t)t * L;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            f32x4 vv = pacc[0][q];
+            vv += pacc[1][q];
+            vv += *(lds_cf4*)(pred + ((wr * 2 + 0) * NQ + q) * 256 + 4 * lane);
+            vv += *(lds_cf4*)(pred + ((wr * 2 + 1) * NQ + q) * 256 + 4 * lane);
+            *reinterpret_cast<f32x4*>(out + 256 * q + 4 * lane) = vv;
+        }
+        if (lane == 0) {
+            float* ml = pool.partials + (size_t)pool.T * L + 2 * t;
+            ml[0] = m_;
+            ml[1] = l_;
+        }
+    }
+}
+
+template <bool DROP, bool GEN, int PQ, bool PW = false>
+__global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, const float* __restrict__ Wv,
+                                                   const float* __restrict__ bv, const float* __restrict__ Wu,
+                                                   const float* __restrict__ bu, const float* __restrict__ wvec,
+                                                   const float* __restrict__ battn, float* __restrict__ scores,
+                                                   float* __restrict__ gates, int R, int L,
+                                                   const uint32_t* __restrict__ xbits, float xscale, GateFwdGen gen,
+                                                   GateFwdPool pool, const unsigned short* __restrict__ Wp = nullptr) {
+    __shared__ __attribute__((aligned(16))) float smem[gate_fwd2_smem_floats(PW)];     // the K loop's image, then the epilogue's
+    __shared__ __attribute__((aligned(16))) uint32_t mlds[GEN ? GF_TM * 32 : 4];       // keep words [128][nslice <= 32]
+    const GateFwdCoord co = gate_fwd_coord(smem, R);
+    GateKeepWords<DROP, GEN> kw;
+    kw.init(co, xbits, gen, mlds, L);
+    f32x16 acc[3][2];
+    gate_acc_clear(acc);
+    if constexpr (PW) gate_kloop_pw<DROP, GEN>(co, kw, x, Wp, L, acc);
+    else gate_kloop_f32<DROP, GEN>(co, kw, x, Wv, Wu, L, acc);
+    GatePoolRows<(PQ > 0 ? PQ : 1)> pv;
+    if constexpr (PQ > 0) gate_pool_request_rows(co, x, R, L, pv);
+    gate_fwd_scores_epilogue<DROP>(co, acc, bv, bu, wvec, battn, scores, gates, R, xscale, (lds_f32*)smem, PQ > 0);
+    if constexpr (PQ > 0) gate_fwd_pool_pass<DROP, GEN, PQ>(co, kw, pv, xbits, R, L, xscale, gen, pool, (lds_f32*)smem);
 }
 
 // ================================================================================ K1a gate forward, 32-row tiles
@@ -880,17 +933,34 @@ extern "C" int mil_gate_step_route(int R, int L, int C, int save_gates, int keep
     return MIL_OK;
 }
 
+// ---- the launch tables: every instantiation of the forward kernels is named here and nowhere else
+using GateFwdR32Kernel = decltype(&k_gate_fwd_r32<false, 1>);
+static const GateFwdR32Kernel GATE_FWD_R32_KERNELS[2][3] = {                    // [keep bits][RT - 1]
+    {k_gate_fwd_r32<false, 1>, k_gate_fwd_r32<false, 2>, k_gate_fwd_r32<false, 3>},
+    {k_gate_fwd_r32<true, 1>, k_gate_fwd_r32<true, 2>, k_gate_fwd_r32<true, 3>}};
+using GateFwd2Kernel = decltype(&k_gate_fwd2<false, false, 0, false>);
+static const GateFwd2Kernel GATE_FWD2_KERNELS[3][2][2] = {                      // [none / bits given / drawn (GEN)][pool fused][PW]
+    {{k_gate_fwd2<false, false, 0, false>, k_gate_fwd2<false, false, 0, true>}, {k_gate_fwd2<false, false, 2, false>, k_gate_fwd2<false, false, 2, true>}},
+    {{k_gate_fwd2<true, false, 0, false>, k_gate_fwd2<true, false, 0, true>}, {k_gate_fwd2<true, false, 2, false>, k_gate_fwd2<true, false, 2, true>}},
+    {{k_gate_fwd2<true, true, 0, false>, k_gate_fwd2<true, true, 0, true>}, {k_gate_fwd2<true, true, 2, false>, k_gate_fwd2<true, true, 2, true>}}};
+
 static int launch_gate_fwd_r32(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
                                const float* w, const float* b, float* scores, float* gates, int R, int L,
                                const uint32_t* xbits, float xscale, int rt, hipStream_t st, const int32_t* rows_dev = nullptr) {
     const dim3 grid((R + GS_TM * rt - 1) / (GS_TM * rt));
     const float xs = xbits ? xscale : 1.0f;
-#define R32_LAUNCH(D_, RT_) hipLaunchKernelGGL((k_gate_fwd_r32<D_, RT_>), grid, dim3(GS_THREADS), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, xbits, xs, rows_dev)
-    if (xbits) { if (rt == 1) R32_LAUNCH(true, 1); else if (rt == 2) R32_LAUNCH(true, 2); else R32_LAUNCH(true, 3); }
-    else { if (rt == 1) R32_LAUNCH(false, 1); else if (rt == 2) R32_LAUNCH(false, 2); else R32_LAUNCH(false, 3); }
-#undef R32_LAUNCH
+    hipLaunchKernelGGL(GATE_FWD_R32_KERNELS[xbits != nullptr][rt <= 1 ? 0 : rt == 2 ? 1 : 2], grid, dim3(GS_THREADS), 0, st, x, Wv, bv, Wu, bu, w, b, scores,
+                       gates, R, L, xbits, xs, rows_dev);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
+}
+// the 128-row tiles of k_gate_fwd2; Wp only with pw
+static void launch_gate_fwd2(bool draw, bool pool_fused, bool pw, dim3 grid, hipStream_t st, const float* x, const float* Wv,
+                             const float* bv, const float* Wu, const float* bu, const float* w, const float* b, float* scores,
+                             float* gates, int R, int L, const uint32_t* xbits, float xs, const GateFwdGen& gen,
+                             const GateFwdPool& pool, const uint16_t* Wp) {
+    hipLaunchKernelGGL(GATE_FWD2_KERNELS[draw ? 2 : xbits ? 1 : 0][pool_fused][pw], grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b,
+                       scores, gates, R, L, xbits, xs, gen, pool, pw ? (const unsigned short*)Wp : nullptr);
 }
 
 // gen: the keep bits are drawn by this call (in the forward kernel or by a generator launch in front of it: the plan
@@ -943,24 +1013,13 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
     const dim3 grid((Rm + GF_TM - 1) / GF_TM);
     const float xs = xbits ? xscale : 1.0f;
     if (p.main == MIL_ROUTE_MAIN_LEGACY) {
-        if (xbits) hipLaunchKernelGGL(k_gate_fwd<true>, grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L, xbits, xs);
-        else hipLaunchKernelGGL(k_gate_fwd<false>, grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L, xbits, xs);
+        hipLaunchKernelGGL(xbits ? k_gate_fwd<true> : k_gate_fwd<false>, grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates,
+                           Rm, L, xbits, xs);
     } else {
         const GateFwdGen fgen = draw ? *gen : GateFwdGen{};
         const GateFwdPool fpool = p.pool_fused ? *pool : GateFwdPool{};
-#define GF2_LAUNCH(D_, G_, PQ_)                                                                                                \
-    do {                                                                                                                       \
-        if (p.main == MIL_ROUTE_MAIN_FWD2_PW)                                                                                  \
-            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_, true>), grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, \
-                               Rm, L, xbits, xs, fgen, fpool, (const unsigned short*)Wp);                                      \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((k_gate_fwd2<D_, G_, PQ_>), grid, dim3(512), 0, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, \
-                               L, xbits, xs, fgen, fpool);                                                                     \
-    } while (0)
-        if (draw) { if (p.pool_fused) GF2_LAUNCH(true, true, 2); else GF2_LAUNCH(true, true, 0); }
-        else if (xbits) { if (p.pool_fused) GF2_LAUNCH(true, false, 2); else GF2_LAUNCH(true, false, 0); }
-        else { if (p.pool_fused) GF2_LAUNCH(false, false, 2); else GF2_LAUNCH(false, false, 0); }
-#undef GF2_LAUNCH
+        launch_gate_fwd2(draw, p.pool_fused, p.main == MIL_ROUTE_MAIN_FWD2_PW, grid, st, x, Wv, bv, Wu, bu, w, b, scores, gates, Rm, L,
+                         xbits, xs, fgen, fpool, Wp);
     }
     if (p.pool_fused) *fused = 1;
     MIL_CHECK_LAUNCH();

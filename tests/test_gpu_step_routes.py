@@ -9,10 +9,11 @@ on the same input (floor 1e-7)."""
 import pytest
 import torch
 
-from mil_amd import synthetic as syn
+from mil_amd import ops, synthetic as syn
 from mil_amd.bags import BagLayout, bucket_rows
 from mil_amd.trainer import PARAM_ORDER, ImageOnlyTrainer, RaggedImageOnlyStepper
-from step_ref import WB, WW, gates_ref, keep_from_bits, lib_route, max_err, step_ref, step_route
+from step_ref import (BU, BV, GF_TM, WB, WU, WV, WW, gates_ref, keep_from_bits, lib_route, max_err, num_cu, step_ref,
+                      step_route)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -150,6 +151,34 @@ def test_dw_kg2_route_against_float64():
     """k_gate_bwd_dw<.., KG = 2>: R * L >= 2^29, where k_gate_bwd_dw2 (32-bit offsets) hands over.  512 bags x 1024 rows
     x 1024 columns, 2 GiB of x, eval mode."""
     _route_case("dw_kg2 eval", [1024] * 512, 1024, 2, dict(PW, dw="dw<2>", bits=None), False)
+
+
+# ------------------------------------------------------------------------------------------ k_gate_fwd (L > 4096)
+@pytest.mark.parametrize("keep", [False, True], ids=["eval", "keep_bits"])
+def test_legacy_gate_forward_against_float64(keep):
+    """k_gate_fwd, the 128-row kernel with 64-bit source pointers that takes over beyond L = 4096 (ops.gate_scores_fwd with
+    saved gates), at L = 4128: 48 rows more than the smallest row count that leaves the 32-row kernel, so 191 full tiles
+    and one of 49 rows.  Once without keep bits, once with bits from ops.dropout_keep_bits and xscale = 2.  Scores and
+    gates against float64, max|got - ref| <= 1e-5 max|ref| (TOL_FWD) - measured before the kernel's epilogue became the
+    shared gate_fwd_scores_epilogue: scores 1.03e-6, gates 4.67e-6 without keep bits; 5.6e-7, 4.23e-6 with them."""
+    L = 4128
+    rmin = ((3 * num_cu()) // 4 - 1) * GF_TM + 1          # gate_route_plan: fewer 128-row tiles than 3/4 of the CUs go to r32
+    R = rmin + 48
+    for route in (step_route, lib_route):
+        assert route(rmin - 1, L, 2, False, given_bits=keep)["main"] == "r32"
+        assert route(rmin, L, 2, False, given_bits=keep)["main"] == "legacy"
+        have = route(R, L, 2, False, given_bits=keep)
+        assert have["main"] == "legacy" and have["tail"] is None, have
+    p = syn.image_only_params(300 + L, L=L)
+    x = _randn(R, L, R + L)
+    bits = ops.dropout_keep_bits(R, L, 0.5, 29, 0, DEV) if keep else None
+    gp = [p[k].to(DEV) for k in (WV, BV, WU, BU)] + [p[WW].reshape(-1).to(DEV), p[WB].to(DEV)]
+    scores, gates = ops.gate_scores_fwd(x, *gp, save_gates=True, xbits=bits, xscale=2.0 if keep else 1.0)
+    torch.cuda.synchronize()
+    rs, rg = gates_ref(x, p, keep_from_bits(bits, L) if keep else None)
+    es, eg = max_err(scores, rs), max_err(gates, rg)
+    print(f"legacy {R} x {L} {'keep bits' if keep else 'eval'}: scores {es:.2e} gates {eg:.2e}")
+    assert es <= TOL_FWD and eg <= TOL_FWD, (es, eg)
 
 
 # ------------------------------------------------------------------------------------------ bucketed (device lengths)

@@ -23,7 +23,9 @@ L = a.dim or (1024 if a.bf16 else 512)
 
 
 def load(path):
-    h = ctypes.CDLL(path)
+    # RTLD_DEEPBIND: the variant's kernel handles and its calls between its own files bind to ITSELF.  Without it they bind
+    # to the main library (loaded RTLD_GLOBAL, same symbol names) and every "variant" runs the main build's kernels.
+    h = ctypes.CDLL(path, mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)
     for name, (res, args) in _lib.SIGNATURES.items():
         try:
             fn = getattr(h, name)
