@@ -61,7 +61,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 11 */
+int mil_abi_version(void);   /* 12 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1091,6 +1091,21 @@ int mil_tm_ppeg_bwd(const float* dy, const float* x, int s, const float* W7, con
  * `stream`, no host sync. */
 int mil_tm_cls_attn(const float* A1, const float* Z, const float* A3, int n_pad, int pad, int s, int n, const int32_t* len_dev,
                     int bag, float* t_ws, float* out, void* stream);
+/* The landmark-query pass without its [8, 256, n_pad] softmax map (csrc/landmark_attn.hip).  Per head h: Q = qL[h] [256, 64]
+ * (mil_tm_landmarks has applied the scale; none is applied here), K / V = columns 512 + 64 h .. / 1024 + 64 h .. of the
+ * [n_pad, 1536] rows of qkv, every row a key (the zero front pad rows score 0 and take part).
+ *   fwd: W [8, 256, 64] = softmax(Q K^T) V, lse [8, 256] = logsumexp(Q K^T).
+ *   bwd, from dW [8, 256, 64] and the forward's W and lse: columns 512 .. 1535 of every row of dqkv <- dK | dV (overwritten;
+ *        columns 0 .. 511 are not touched), dqL [8, 256, 64] <- dS K (overwritten).
+ * The keys are split across workgroups with a running maximum and sum; partial results meet in `ws` and are combined in a
+ * fixed order: no atomics, two runs give the same bits.  ws: mil_tm_lmk_attn_ws_floats(n_pad, backward) floats from the caller,
+ * less than one map (8 x 256 x n_pad) for n_pad >= 512; 0 for an n_pad that is not a positive multiple of 256, which the two
+ * status entries refuse with MIL_EINVAL before any launch, as they do a null pointer or an operand that is not 16-byte
+ * aligned.  fp32 MFMA throughout.  Two / three launches on `stream`, no host sync. */
+size_t mil_tm_lmk_attn_ws_floats(int n_pad, int backward);
+int mil_tm_lmk_attn_fwd(const float* qkv, const float* qL, int n_pad, float* W, float* lse, float* ws, void* stream);
+int mil_tm_lmk_attn_bwd(const float* qkv, const float* qL, const float* W, const float* lse, const float* dW, int n_pad,
+                        float* dqkv, float* dqL, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

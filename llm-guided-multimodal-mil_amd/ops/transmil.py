@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 
@@ -169,7 +170,55 @@ def tm_cls_attention(A1, Z, A3, pad: int, s: int, n=None, len_dev=None, bag: int
     return out
 
 
-def _tm_fwd(qkv, w, need_attn, cls=None):
+def _lmk_check(qkv, qL):
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] <= 0 or qkv.shape[0] % TM_M or tuple(qL.shape) != (TM_H, TM_M, TM_DH):
+        raise _lib.MilHipError(f"tm_lmk_attn: qkv {tuple(qkv.shape)} / qL {tuple(qL.shape)} outside the built shape")
+
+
+def tm_lmk_attn(qkv, qL):
+    """The landmark-query pass without its map (mil_tm_lmk_attn_fwd, csrc/landmark_attn.hip): qkv [n_pad, 1536], qL [8, 256, 64]
+    (scaled, as mil_tm_landmarks leaves it) -> (W [8, 256, 64] = softmax(qL k^T) v, lse [8, 256]) over all n_pad keys.  The
+    workspace is one torch.empty below the size of one map; two launches, no host sync, bit-reproducible."""
+    qkv, qL = _f32c(qkv, "qkv"), _f32c(qL, "qL")
+    _lmk_check(qkv, qL)
+    n = qkv.shape[0]
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    W = torch.empty((TM_H, TM_M, TM_DH), **f32)
+    lse = torch.empty((TM_H, TM_M), **f32)
+    ws = torch.empty(_lib.lib().mil_tm_lmk_attn_ws_floats(n, 0), **f32)
+    _lib.checked().mil_tm_lmk_attn_fwd(_p(qkv), _p(qL), n, _p(W), _p(lse), _p(ws), _stream())
+    return W, lse
+
+
+def tm_lmk_attn_bwd(qkv, qL, W, lse, dW, dqkv=None):
+    """Backward of tm_lmk_attn (mil_tm_lmk_attn_bwd): -> (dqkv, dqL).  Columns 512 .. 1535 of dqkv [n_pad, 1536] (a fresh
+    torch.empty when None) are overwritten with dk | dv, columns 0 .. 511 are left as they are; dqL [8, 256, 64] is overwritten.
+    Three launches, no atomics, no host sync."""
+    qkv, qL, W, lse, dW = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (qL, "qL"), (W, "W"), (lse, "lse"), (dW, "dW")))
+    _lmk_check(qkv, qL)
+    n = qkv.shape[0]
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    if tuple(W.shape) != (TM_H, TM_M, TM_DH) or tuple(dW.shape) != (TM_H, TM_M, TM_DH) or lse.numel() != TM_H * TM_M:
+        raise _lib.MilHipError(f"tm_lmk_attn_bwd: W {tuple(W.shape)} / dW {tuple(dW.shape)} / lse {tuple(lse.shape)} outside the built shape")
+    if dqkv is None:
+        dqkv = torch.empty((n, 3 * TM_D), **f32)
+    elif dqkv.dtype != torch.float32 or not dqkv.is_contiguous() or tuple(dqkv.shape) != (n, 3 * TM_D) or dqkv.device != qkv.device:
+        raise _lib.MilHipError("tm_lmk_attn_bwd: dqkv must be a contiguous float32 [n_pad, 1536] tensor on qkv's device")
+    dqL = torch.empty((TM_H, TM_M, TM_DH), **f32)
+    ws = torch.empty(_lib.lib().mil_tm_lmk_attn_ws_floats(n, 1), **f32)
+    _lib.checked().mil_tm_lmk_attn_bwd(_p(qkv), _p(qL), _p(W), _p(lse), _p(dW), n, _p(dqkv), _p(dqL), _p(ws), _stream())
+    return dqkv, dqL
+
+
+def _tm_fused_a3(fused_a3, need_attn) -> bool:
+    """The switch of the fused landmark-query pass: the keyword, else MIL_TM_FUSED_A3 (default 0), read per call.  The
+    attention outputs (need_attn True / "cls") are formed from the map, so they keep the materialised route."""
+    if fused_a3 is None:
+        fused_a3 = os.environ.get("MIL_TM_FUSED_A3", "0") not in ("", "0")
+    return bool(fused_a3) and need_attn is False
+
+
+def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False):
     n = qkv.shape[0]
     dev = qkv.device
     f32 = dict(device=dev, dtype=torch.float32)
@@ -182,12 +231,17 @@ def _tm_fwd(qkv, w, need_attn, cls=None):
     tm_bgemm(q, (DH, L3, 1), kL, (M * DH, 1, DH), A1, (n * M, M, 1), H, n, M, DH, alpha=TM_QSCALE)
     A2 = torch.empty((H, M, M), **f32)
     tm_bgemm(qL, (M * DH, DH, 1), kL, (M * DH, 1, DH), A2, (M * M, M, 1), H, M, M, DH)
-    A3 = torch.empty((H, M, n), **f32)
-    tm_bgemm(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
-    for A in (A1, A2, A3):
-        tm_softmax_rows(A)
-    W = torch.empty((H, M, DH), **f32)
-    tm_bgemm(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
+    if fused_a3:        # no A3: W and the rows' logsumexp straight from qL and the k | v columns (saved where A3 was)
+        for A in (A1, A2):
+            tm_softmax_rows(A)
+        W, A3 = tm_lmk_attn(qkv, qL)
+    else:
+        A3 = torch.empty((H, M, n), **f32)
+        tm_bgemm(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
+        for A in (A1, A2, A3):
+            tm_softmax_rows(A)
+        W = torch.empty((H, M, DH), **f32)
+        tm_bgemm(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
     # Newton-Schulz pseudo-inverse of A2: Z0 = A2^T / (max row sum x max column sum over the bag's 8 heads), then
     # X = A2 Z, T2 = 15 I - X (7 I - X) = X X - 7 X + 15 I, T3 = 13 I - X T2, Z = Z T3 / 4
     scale = torch.empty(3 + 2 * H, **f32)                       # (s, max row sum, max column sum), per-head maxima behind
@@ -238,7 +292,8 @@ def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s):
     return dA2
 
 
-def _tm_bwd(dO, qkv, w, saved):
+def _tm_bwd(dO, qkv, w, saved, fused_a3=False):
+    """fused_a3: `saved` carries lse3 [8, 256] where A3 was (what _tm_fwd left with the same switch)."""
     qL, kL, A1, A2, A3, W, U, Z, scale, arg, Zs, Xs, T2s, T3s = saved
     n = qkv.shape[0]
     f32 = dict(device=qkv.device, dtype=torch.float32)
@@ -251,31 +306,39 @@ def _tm_bwd(dO, qkv, w, saved):
     dU = tm_bgemm(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
     dZ = tm_bgemm(dU, sl, W, (M * DH, 1, DH), torch.empty((H, M, M), **f32), sq, H, M, M, DH)
     dW = tm_bgemm(Z, (M * M, 1, M), dU, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
-    dA3 = tm_bgemm(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
-    tm_bgemm(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)                # dv = A3^T dW
+    if fused_a3:        # dk | dv into dqkv and the pass's share of dqL, before the stages that add onto them
+        _, dqL = tm_lmk_attn_bwd(qkv, qL, W, A3, dW, dqkv)
+    else:
+        dA3 = tm_bgemm(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
+        tm_bgemm(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)            # dv = A3^T dW
     _lib.checked().mil_tm_resconv_bwd(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw), _stream())
     dS1 = tm_softmax_rows_bwd(A1, dA1)
-    dS3 = tm_softmax_rows_bwd(A3, dA3)
+    if not fused_a3:
+        dS3 = tm_softmax_rows_bwd(A3, dA3)
     dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, scale, arg, Zs, Xs, T2s, T3s))
     tm_bgemm(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)            # dq
     dkL = tm_bgemm(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
     tm_bgemm(dS2, (M * M, 1, M), qL, sl, dkL, sl, H, M, DH, M, beta=1.0)
-    dqL = tm_bgemm(dS2, sq, kL, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
-    tm_bgemm(dS3, (M * n, n, 1), k, (DH, L3, 1), dqL, sl, H, M, DH, n, beta=1.0)
-    tm_bgemm(dS3, (M * n, 1, n), qL, sl, dqkv[:, TM_D:], (DH, L3, 1), H, n, DH, M)                  # dk
+    if fused_a3:
+        tm_bgemm(dS2, sq, kL, sl, dqL, sl, H, M, DH, M, beta=1.0)
+    else:
+        dqL = tm_bgemm(dS2, sq, kL, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
+        tm_bgemm(dS3, (M * n, n, 1), k, (DH, L3, 1), dqL, sl, H, M, DH, n, beta=1.0)
+        tm_bgemm(dS3, (M * n, 1, n), qL, sl, dqkv[:, TM_D:], (DH, L3, 1), H, n, DH, M)              # dk
     _lib.checked().mil_tm_landmarks_bwd(_p(dqL), _p(dkL), n, TM_QSCALE, _p(dqkv), _stream())
     return dqkv, dw
 
 
 class _NystromCore(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, w, need_attn, cls=None):
+    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False):
         qkv = _f32c(qkv, "qkv")
         w = _f32c(w, "res_conv.weight")
         if qkv.shape[1] != 3 * TM_D or qkv.shape[0] % TM_M or w.numel() != TM_H * TM_CONV:
             raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
-        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls)
+        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3)
         ctx.saved = saved
+        ctx.fused_a3 = fused_a3
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
         if attn is not None:
@@ -285,20 +348,23 @@ class _NystromCore(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dO, _dattn):
         qkv, w = ctx.saved_tensors
-        dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved)
+        dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved, ctx.fused_a3)
         ctx.saved = None
-        return dqkv, dw.reshape(ctx.w_shape), None, None
+        return dqkv, dw.reshape(ctx.w_shape), None, None, None
 
 
-def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0):
+def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0, fused_a3=None):
     """qkv [n_pad, 1536] (to_qkv of the front-zero-padded rows, n_pad % 256 == 0), w = res_conv.weight [8, 1, 33, 1] ->
     (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
     [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
-    as keywords: pad, s and the length as n or as len_dev (+ bag).  attn carries no gradient in any mode."""
+    as keywords: pad, s and the length as n or as len_dev (+ bag).  attn carries no gradient in any mode.
+    fused_a3: the landmark-query pass (softmax(qL k^T) v and its backward) as one kernel family that never forms the
+    [8, 256, n_pad] map (tm_lmk_attn); None reads the environment switch MIL_TM_FUSED_A3 (default 0) at every call.  It applies
+    with need_attn False only: True and "cls" read the map and keep the materialised route whatever the switch says."""
     if isinstance(need_attn, bool):
-        return _NystromCore.apply(qkv, w, need_attn, None)
+        return _NystromCore.apply(qkv, w, need_attn, None, _tm_fused_a3(fused_a3, need_attn))
     if not (isinstance(need_attn, str) and need_attn == "cls"):
         raise ValueError(f"nystrom_core: need_attn must be False, True or 'cls', got {need_attn!r}")
     if pad is None or s is None or (n is None) == (len_dev is None):
         raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
-    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)))
+    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False)

@@ -10,7 +10,11 @@ memory of the graph's pool are reported with it.
 --ragged K: K bags drawn from U[2000, 15592] in turn through the stepper: ms/step, replay / eager counts, eager steps after a
 key's second visit (must be 0), graphs, the memory of their shared pool and the free memory the whole run took.
 --attn cls: per N, the eval forward without attention and with the per-patch cls attention (need_attn="cls"), and the peak
-allocated bytes of both, in one process."""
+allocated bytes of both, in one process.
+--fused-a3: per N, the eager TRAINING step (model.train(), BCE, backward, counted FlatAdam) with the landmark-query pass
+materialised (MIL_TM_FUSED_A3=0: the A3 map, its softmax and their products), fused (=1: csrc/landmark_attn.hip), and
+materialised again - same model, same bag, same process, the switch read per call; median (min - max) of --reps regions each
+and the peak allocated bytes of one step per route."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -163,6 +167,45 @@ def attn_rows(a, dev, args):
         torch.cuda.empty_cache()
 
 
+def fused_a3_rows(a, dev, args):
+    from mil_amd import ops
+    from mil_amd.optim import FlatAdam
+    bce = torch.nn.BCELoss()
+    y = syn.make_labels(3, 1).to(dev)
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    for N in a.N:
+        torch.manual_seed(1234)
+        model = get_model(args).to(dev).train()
+        opt = FlatAdam(list(model.parameters()), lr=1e-5, counted=True)
+        x = syn.make_bags(N, 1, N, 768)[0].to(dev)
+
+        def step():
+            opt.zero_grad()
+            _, prob = model([x], [N])
+            ops.backward(bce(prob, y))
+            opt.step()
+
+        res = dict(N=N, n_pad=geometry(N)["n_pad"])
+        for switch, tag in (("0", "materialised"), ("1", "fused"), ("0", "materialised_again")):
+            os.environ["MIL_TM_FUSED_A3"] = switch
+            ts = region_times(step, a.reps, a.warmup)
+            res.update({tag + "_ms": round(med(ts), 3), tag + "_min_ms": round(min(ts), 3), tag + "_max_ms": round(max(ts), 3)})
+        for switch, tag in (("0", "materialised"), ("1", "fused")):
+            os.environ["MIL_TM_FUSED_A3"] = switch
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step()
+            torch.cuda.synchronize()
+            res[tag + "_peak_mib"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+        os.environ.pop("MIL_TM_FUSED_A3", None)
+        res["a3_map_mib"] = round(8 * 256 * res["n_pad"] * 4 / 2 ** 20, 1)
+        res["fused_over_materialised"] = round(res["fused_ms"] / min(res["materialised_ms"], res["materialised_again_ms"]), 4)
+        print(json.dumps(res), flush=True)
+        del model, opt, x
+        torch.cuda.empty_cache()
+
+
 def region_times(fn, reps, warm):
     for _ in range(warm):
         fn()
@@ -189,12 +232,17 @@ def main():
     ap.add_argument("--max_graphs", type=int, default=0, help="--ragged: the stepper's graph cap (0 = its default)")
     ap.add_argument("--attn", choices=["cls"], default=None, help="eval forward per N with and without the per-patch cls "
                     "attention (need_attn='cls'): ms and peak allocated bytes of both")
+    ap.add_argument("--fused-a3", dest="fused_a3", action="store_true", help="eager training step per N with the landmark-query "
+                    "pass materialised, fused (MIL_TM_FUSED_A3=1), materialised again: ms and peak allocated bytes")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
     args = SimpleNamespace(modality=["pathology"], model_pathology="TransMIL", num_classes=2, patch_dim=768, variant="image_only")
     if a.attn:
         attn_rows(a, dev, args)
+        return
+    if a.fused_a3:
+        fused_a3_rows(a, dev, args)
         return
     if a.graph or a.ragged:
         if a.graph:
