@@ -38,6 +38,8 @@
  *    `_time`, `_profile[_rot]`     measurement helpers of the one-call step
  *  The image-only TransMIL extractor (`--model_pathology TransMIL`) has a family of its own, `mil_tm_*` (csrc/transmil.hip):
  *    one batched product (`mil_tm_bgemm`) and the row-wise / conv stages around it, forward and backward each.
+ *    Variants of that product with its softmax, for a pass whose map is never formed: `mil_tm_lmk_attn_*` (landmark queries,
+ *    csrc/landmark_attn.hip) and `mil_tm_tok_attn_*` (token queries, csrc/token_attn.hip), each a `_ws_floats` / `_fwd` / `_bwd` triple.
  */
 #ifndef MIL_HIP_H
 #define MIL_HIP_H
@@ -61,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 12 */
+int mil_abi_version(void);   /* 13 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1106,6 +1108,26 @@ size_t mil_tm_lmk_attn_ws_floats(int n_pad, int backward);
 int mil_tm_lmk_attn_fwd(const float* qkv, const float* qL, int n_pad, float* W, float* lse, float* ws, void* stream);
 int mil_tm_lmk_attn_bwd(const float* qkv, const float* qL, const float* W, const float* lse, const float* dW, int n_pad,
                         float* dqkv, float* dqL, float* ws, void* stream);
+/* The token-query pass without its [8, n_pad, 256] softmax map (csrc/token_attn.hip).  Per head h: Q = columns 64 h .. 64 h + 63
+ * of the [n_pad, 1536] rows of qkv, every row a query (a zero front pad row gets uniform weights), K = kL[h] [256, 64] (not
+ * scaled), V = U[h] [256, 64]; the scale 64^-0.5 is applied to the scores here.
+ *   fwd: columns 64 h .. of every row of O [n_pad, 512] <- softmax(S) U[h] with S = 64^-0.5 Q kL[h]^T (overwritten),
+ *        lse [8, n_pad] = logsumexp(S).
+ *   bwd, from the whole dO [n_pad, 512] and the forward's lse: columns 0 .. 511 of every row of dqkv <- 64^-0.5 dS kL
+ *        (overwritten; columns 512 .. 1535 are not touched), dU [8, 256, 64] <- sum over the rows of P^T dO_h and dkL [8, 256, 64]
+ *        <- 64^-0.5 sum over the rows of dS^T Q (both overwritten), with P = exp(S - lse), dS = P o (dP - rowsum(P o dP)),
+ *        dP = dO_h U[h]^T.
+ * All 256 keys of a row meet in one wave, so the forward has no partials; the backward's two sums over the rows leave one
+ * partial per (256-row chunk, head) in `ws` and are added chunk 0, 1, 2 .. in that order: no atomics, two runs give the same
+ * bits.  ws: mil_tm_tok_attn_ws_floats(n_pad, backward) floats from the caller - 0 forward (ws may then be null), 1024 x n_pad
+ * backward, half of one map (8 x 256 x n_pad); 0 for an n_pad that is not a positive multiple of 256, which the two status
+ * entries refuse with MIL_EINVAL before any launch, as they do a null pointer or an operand that is not 16-byte aligned.
+ * fp32 MFMA throughout.  One / two launches on `stream`, no host sync. */
+size_t mil_tm_tok_attn_ws_floats(int n_pad, int backward);
+int mil_tm_tok_attn_fwd(const float* qkv, const float* kL, const float* U, int n_pad, float* O, float* lse, float* ws,
+                        void* stream);
+int mil_tm_tok_attn_bwd(const float* qkv, const float* kL, const float* U, const float* lse, const float* dO, int n_pad,
+                        float* dqkv, float* dU, float* dkL, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -210,6 +210,51 @@ def tm_lmk_attn_bwd(qkv, qL, W, lse, dW, dqkv=None):
     return dqkv, dqL
 
 
+def _tok_check(qkv, kL, U):
+    if (qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] <= 0 or qkv.shape[0] % TM_M
+            or tuple(kL.shape) != (TM_H, TM_M, TM_DH) or tuple(U.shape) != (TM_H, TM_M, TM_DH)):
+        raise _lib.MilHipError(f"tm_tok_attn: qkv {tuple(qkv.shape)} / kL {tuple(kL.shape)} / U {tuple(U.shape)} outside the built shape")
+    if kL.device != qkv.device or U.device != qkv.device:
+        raise _lib.MilHipError("tm_tok_attn: qkv, kL and U must be on one device")
+
+
+def tm_tok_attn(qkv, kL, U):
+    """The token-query pass without its map (mil_tm_tok_attn_fwd, csrc/token_attn.hip): qkv [n_pad, 1536], kL [8, 256, 64] (not
+    scaled), U [8, 256, 64] -> (O [n_pad, 512] = softmax(64^-0.5 q kL^T) U with the heads merged, lse [8, n_pad]); every row is a
+    query.  One launch, no workspace, no host sync, bit-reproducible."""
+    qkv, kL, U = _f32c(qkv, "qkv"), _f32c(kL, "kL"), _f32c(U, "U")
+    _tok_check(qkv, kL, U)
+    n = qkv.shape[0]
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    O = torch.empty((n, TM_D), **f32)
+    lse = torch.empty((TM_H, n), **f32)
+    nws = _lib.lib().mil_tm_tok_attn_ws_floats(n, 0)            # 0 as built: every row's 256 landmarks meet in one wave
+    ws = torch.empty(nws, **f32) if nws else None
+    _lib.checked().mil_tm_tok_attn_fwd(_p(qkv), _p(kL), _p(U), n, _p(O), _p(lse), _p(ws), _stream())
+    return O, lse
+
+
+def tm_tok_attn_bwd(qkv, kL, U, lse, dO, dqkv=None):
+    """Backward of tm_tok_attn (mil_tm_tok_attn_bwd): -> (dqkv, dU, dkL).  Columns 0 .. 511 of dqkv [n_pad, 1536] (a fresh
+    torch.empty when None) are overwritten with dq, columns 512 .. 1535 are left as they are; dU and dkL [8, 256, 64] are
+    overwritten.  The workspace is one torch.empty of half a map; two launches, no atomics, no host sync."""
+    qkv, kL, U, lse, dO = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (kL, "kL"), (U, "U"), (lse, "lse"), (dO, "dO")))
+    _tok_check(qkv, kL, U)
+    n = qkv.shape[0]
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    if tuple(lse.shape) != (TM_H, n) or tuple(dO.shape) != (n, TM_D) or lse.device != qkv.device or dO.device != qkv.device:
+        raise _lib.MilHipError(f"tm_tok_attn_bwd: lse {tuple(lse.shape)} / dO {tuple(dO.shape)} outside the built shape or on another device")
+    if dqkv is None:
+        dqkv = torch.empty((n, 3 * TM_D), **f32)
+    elif dqkv.dtype != torch.float32 or not dqkv.is_contiguous() or tuple(dqkv.shape) != (n, 3 * TM_D) or dqkv.device != qkv.device:
+        raise _lib.MilHipError("tm_tok_attn_bwd: dqkv must be a contiguous float32 [n_pad, 1536] tensor on qkv's device")
+    dU = torch.empty((TM_H, TM_M, TM_DH), **f32)
+    dkL = torch.empty((TM_H, TM_M, TM_DH), **f32)
+    ws = torch.empty(_lib.lib().mil_tm_tok_attn_ws_floats(n, 1), **f32)
+    _lib.checked().mil_tm_tok_attn_bwd(_p(qkv), _p(kL), _p(U), _p(lse), _p(dO), n, _p(dqkv), _p(dU), _p(dkL), _p(ws), _stream())
+    return dqkv, dU, dkL
+
+
 def _tm_fused_a3(fused_a3, need_attn) -> bool:
     """The switch of the fused landmark-query pass: the keyword, else MIL_TM_FUSED_A3 (default 0), read per call.  The
     attention outputs (need_attn True / "cls") are formed from the map, so they keep the materialised route."""
@@ -218,7 +263,15 @@ def _tm_fused_a3(fused_a3, need_attn) -> bool:
     return bool(fused_a3) and need_attn is False
 
 
-def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False):
+def _tm_fused_a1(fused_a1, need_attn) -> bool:
+    """The switch of the fused token-query pass: the keyword, else MIL_TM_FUSED_A1 (default 0), read per call.  The attention
+    outputs (need_attn True / "cls") are formed from the map (tm_cls_attention takes A1), so they keep the materialised route."""
+    if fused_a1 is None:
+        fused_a1 = os.environ.get("MIL_TM_FUSED_A1", "0") not in ("", "0")
+    return bool(fused_a1) and need_attn is False
+
+
+def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
     n = qkv.shape[0]
     dev = qkv.device
     f32 = dict(device=dev, dtype=torch.float32)
@@ -227,18 +280,21 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False):
     qL = torch.empty((H, M, DH), **f32)
     kL = torch.empty((H, M, DH), **f32)
     _lib.checked().mil_tm_landmarks(_p(qkv), n, TM_QSCALE, _p(qL), _p(kL), _stream())
-    A1 = torch.empty((H, n, M), **f32)
-    tm_bgemm(q, (DH, L3, 1), kL, (M * DH, 1, DH), A1, (n * M, M, 1), H, n, M, DH, alpha=TM_QSCALE)
+    maps = []                                                   # the bag-sized maps this call forms, softmaxed below
+    if not fused_a1:
+        A1 = torch.empty((H, n, M), **f32)
+        tm_bgemm(q, (DH, L3, 1), kL, (M * DH, 1, DH), A1, (n * M, M, 1), H, n, M, DH, alpha=TM_QSCALE)
+        maps.append(A1)
     A2 = torch.empty((H, M, M), **f32)
     tm_bgemm(qL, (M * DH, DH, 1), kL, (M * DH, 1, DH), A2, (M * M, M, 1), H, M, M, DH)
     if fused_a3:        # no A3: W and the rows' logsumexp straight from qL and the k | v columns (saved where A3 was)
-        for A in (A1, A2):
+        for A in maps + [A2]:
             tm_softmax_rows(A)
         W, A3 = tm_lmk_attn(qkv, qL)
     else:
         A3 = torch.empty((H, M, n), **f32)
         tm_bgemm(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
-        for A in (A1, A2, A3):
+        for A in maps + [A2, A3]:
             tm_softmax_rows(A)
         W = torch.empty((H, M, DH), **f32)
         tm_bgemm(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
@@ -258,8 +314,11 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False):
         Zs.append(Z); Xs.append(X); T2s.append(T2); T3s.append(T3)
         Z = Zn
     U = tm_bgemm(Z, sq, W, (M * DH, DH, 1), torch.empty((H, M, DH), **f32), (M * DH, DH, 1), H, M, DH, M)
-    O = torch.empty((n, TM_D), **f32)
-    tm_bgemm(A1, (n * M, M, 1), U, (M * DH, DH, 1), O, (DH, TM_D, 1), H, n, DH, M)
+    if fused_a1:        # no A1: O and the rows' logsumexp straight from the q columns, kL and U (saved where A1 was)
+        O, A1 = tm_tok_attn(qkv, kL, U)
+    else:
+        O = torch.empty((n, TM_D), **f32)
+        tm_bgemm(A1, (n * M, M, 1), U, (M * DH, DH, 1), O, (DH, TM_D, 1), H, n, DH, M)
     _lib.checked().mil_tm_resconv(_p(qkv), _p(w), n, _p(O), _stream())
     attn = None
     if need_attn == "cls":  # the cls row of that map folded onto the patches, [8, s^2]: no map is formed
@@ -292,8 +351,9 @@ def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s):
     return dA2
 
 
-def _tm_bwd(dO, qkv, w, saved, fused_a3=False):
-    """fused_a3: `saved` carries lse3 [8, 256] where A3 was (what _tm_fwd left with the same switch)."""
+def _tm_bwd(dO, qkv, w, saved, fused_a3=False, fused_a1=False):
+    """fused_a3: `saved` carries lse3 [8, 256] where A3 was (what _tm_fwd left with the same switch); fused_a1: lse1 [8, n_pad]
+    where A1 was."""
     qL, kL, A1, A2, A3, W, U, Z, scale, arg, Zs, Xs, T2s, T3s = saved
     n = qkv.shape[0]
     f32 = dict(device=qkv.device, dtype=torch.float32)
@@ -302,8 +362,11 @@ def _tm_bwd(dO, qkv, w, saved, fused_a3=False):
     sq, sl = (M * M, M, 1), (M * DH, DH, 1)
     dqkv = torch.empty((n, L3), **f32)
     dw = torch.zeros(H * TM_CONV, **f32)
-    dA1 = tm_bgemm(dO, (DH, TM_D, 1), U, (M * DH, 1, DH), torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, DH)
-    dU = tm_bgemm(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
+    if fused_a1:        # dq into columns 0 .. 511 of dqkv before anything adds onto them, dU, and the pass's share of dkL
+        _, dU, dkL = tm_tok_attn_bwd(qkv, kL, U, A1, dO, dqkv)
+    else:
+        dA1 = tm_bgemm(dO, (DH, TM_D, 1), U, (M * DH, 1, DH), torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, DH)
+        dU = tm_bgemm(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
     dZ = tm_bgemm(dU, sl, W, (M * DH, 1, DH), torch.empty((H, M, M), **f32), sq, H, M, M, DH)
     dW = tm_bgemm(Z, (M * M, 1, M), dU, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
     if fused_a3:        # dk | dv into dqkv and the pass's share of dqL, before the stages that add onto them
@@ -312,12 +375,14 @@ def _tm_bwd(dO, qkv, w, saved, fused_a3=False):
         dA3 = tm_bgemm(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
         tm_bgemm(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)            # dv = A3^T dW
     _lib.checked().mil_tm_resconv_bwd(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw), _stream())
-    dS1 = tm_softmax_rows_bwd(A1, dA1)
+    if not fused_a1:
+        dS1 = tm_softmax_rows_bwd(A1, dA1)
     if not fused_a3:
         dS3 = tm_softmax_rows_bwd(A3, dA3)
     dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, scale, arg, Zs, Xs, T2s, T3s))
-    tm_bgemm(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)            # dq
-    dkL = tm_bgemm(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
+    if not fused_a1:
+        tm_bgemm(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)        # dq
+        dkL = tm_bgemm(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
     tm_bgemm(dS2, (M * M, 1, M), qL, sl, dkL, sl, H, M, DH, M, beta=1.0)
     if fused_a3:
         tm_bgemm(dS2, sq, kL, sl, dqL, sl, H, M, DH, M, beta=1.0)
@@ -331,14 +396,15 @@ def _tm_bwd(dO, qkv, w, saved, fused_a3=False):
 
 class _NystromCore(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False):
+    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
         qkv = _f32c(qkv, "qkv")
         w = _f32c(w, "res_conv.weight")
         if qkv.shape[1] != 3 * TM_D or qkv.shape[0] % TM_M or w.numel() != TM_H * TM_CONV:
             raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
-        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3)
+        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1)
         ctx.saved = saved
         ctx.fused_a3 = fused_a3
+        ctx.fused_a1 = fused_a1
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
         if attn is not None:
@@ -348,23 +414,26 @@ class _NystromCore(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dO, _dattn):
         qkv, w = ctx.saved_tensors
-        dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved, ctx.fused_a3)
+        dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved, ctx.fused_a3, ctx.fused_a1)
         ctx.saved = None
-        return dqkv, dw.reshape(ctx.w_shape), None, None, None
+        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None
 
 
-def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0, fused_a3=None):
+def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0, fused_a3=None,
+                 fused_a1=None):
     """qkv [n_pad, 1536] (to_qkv of the front-zero-padded rows, n_pad % 256 == 0), w = res_conv.weight [8, 1, 33, 1] ->
     (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
     [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
     as keywords: pad, s and the length as n or as len_dev (+ bag).  attn carries no gradient in any mode.
     fused_a3: the landmark-query pass (softmax(qL k^T) v and its backward) as one kernel family that never forms the
     [8, 256, n_pad] map (tm_lmk_attn); None reads the environment switch MIL_TM_FUSED_A3 (default 0) at every call.  It applies
-    with need_attn False only: True and "cls" read the map and keep the materialised route whatever the switch says."""
+    with need_attn False only: True and "cls" read the map and keep the materialised route whatever the switch says.
+    fused_a1: the same for the token-query pass (softmax(q kL^T) U and its backward, tm_tok_attn), which never forms the
+    [8, n_pad, 256] map; None reads MIL_TM_FUSED_A1 (default 0).  The two switches are independent of each other."""
     if isinstance(need_attn, bool):
-        return _NystromCore.apply(qkv, w, need_attn, None, _tm_fused_a3(fused_a3, need_attn))
+        return _NystromCore.apply(qkv, w, need_attn, None, _tm_fused_a3(fused_a3, need_attn), _tm_fused_a1(fused_a1, need_attn))
     if not (isinstance(need_attn, str) and need_attn == "cls"):
         raise ValueError(f"nystrom_core: need_attn must be False, True or 'cls', got {need_attn!r}")
     if pad is None or s is None or (n is None) == (len_dev is None):
         raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
-    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False)
+    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False, False)

@@ -14,7 +14,9 @@ allocated bytes of both, in one process.
 --fused-a3: per N, the eager TRAINING step (model.train(), BCE, backward, counted FlatAdam) with the landmark-query pass
 materialised (MIL_TM_FUSED_A3=0: the A3 map, its softmax and their products), fused (=1: csrc/landmark_attn.hip), and
 materialised again - same model, same bag, same process, the switch read per call; median (min - max) of --reps regions each
-and the peak allocated bytes of one step per route."""
+and the peak allocated bytes of one step per route.
+--fused-a1: the same three columns for the token-query pass (MIL_TM_FUSED_A1=0: the A1 map, its softmax and their products;
+=1: csrc/token_attn.hip).  MIL_TM_FUSED_A3 is left as the environment has it and reported: run it once with 0 and once with 1."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -167,7 +169,8 @@ def attn_rows(a, dev, args):
         torch.cuda.empty_cache()
 
 
-def fused_a3_rows(a, dev, args):
+def fused_rows(a, dev, args, env="MIL_TM_FUSED_A3", name="a3"):
+    """The three columns of --fused-a3 / --fused-a1: `env` is the switch that moves, `name` tags the map's size in the result."""
     from mil_amd import ops
     from mil_amd.optim import FlatAdam
     bce = torch.nn.BCELoss()
@@ -185,21 +188,26 @@ def fused_a3_rows(a, dev, args):
             ops.backward(bce(prob, y))
             opt.step()
 
-        res = dict(N=N, n_pad=geometry(N)["n_pad"])
+        res = dict(N=N, n_pad=geometry(N)["n_pad"], switch=env)
+        if name == "a1":
+            res["fused_a3"] = os.environ.get("MIL_TM_FUSED_A3", "0")
+        before = os.environ.get(env)
         for switch, tag in (("0", "materialised"), ("1", "fused"), ("0", "materialised_again")):
-            os.environ["MIL_TM_FUSED_A3"] = switch
+            os.environ[env] = switch
             ts = region_times(step, a.reps, a.warmup)
             res.update({tag + "_ms": round(med(ts), 3), tag + "_min_ms": round(min(ts), 3), tag + "_max_ms": round(max(ts), 3)})
         for switch, tag in (("0", "materialised"), ("1", "fused")):
-            os.environ["MIL_TM_FUSED_A3"] = switch
+            os.environ[env] = switch
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
             step()
             torch.cuda.synchronize()
             res[tag + "_peak_mib"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
-        os.environ.pop("MIL_TM_FUSED_A3", None)
-        res["a3_map_mib"] = round(8 * 256 * res["n_pad"] * 4 / 2 ** 20, 1)
+        os.environ.pop(env, None)
+        if before is not None:
+            os.environ[env] = before
+        res[name + "_map_mib"] = round(8 * 256 * res["n_pad"] * 4 / 2 ** 20, 1)
         res["fused_over_materialised"] = round(res["fused_ms"] / min(res["materialised_ms"], res["materialised_again_ms"]), 4)
         print(json.dumps(res), flush=True)
         del model, opt, x
@@ -234,6 +242,8 @@ def main():
                     "attention (need_attn='cls'): ms and peak allocated bytes of both")
     ap.add_argument("--fused-a3", dest="fused_a3", action="store_true", help="eager training step per N with the landmark-query "
                     "pass materialised, fused (MIL_TM_FUSED_A3=1), materialised again: ms and peak allocated bytes")
+    ap.add_argument("--fused-a1", dest="fused_a1", action="store_true", help="the same for the token-query pass "
+                    "(MIL_TM_FUSED_A1); MIL_TM_FUSED_A3 stays as the environment has it")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
@@ -242,7 +252,10 @@ def main():
         attn_rows(a, dev, args)
         return
     if a.fused_a3:
-        fused_a3_rows(a, dev, args)
+        fused_rows(a, dev, args)
+        return
+    if a.fused_a1:
+        fused_rows(a, dev, args, "MIL_TM_FUSED_A1", "a1")
         return
     if a.graph or a.ragged:
         if a.graph:
