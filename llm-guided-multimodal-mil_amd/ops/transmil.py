@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -170,9 +171,25 @@ def tm_cls_attention(A1, Z, A3, pad: int, s: int, n=None, len_dev=None, bag: int
     return out
 
 
-def _lmk_check(qkv, qL):
-    if qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] <= 0 or qkv.shape[0] % TM_M or tuple(qL.shape) != (TM_H, TM_M, TM_DH):
-        raise _lib.MilHipError(f"tm_lmk_attn: qkv {tuple(qkv.shape)} / qL {tuple(qL.shape)} outside the built shape")
+def _fused_operands(op, qkv, **small):
+    """The operands of a fused pass: qkv [n_pad, 1536] with n_pad a positive multiple of 256, every keyword an [8, 256, 64] tensor
+    on qkv's device; `op` is the caller the message names.  Returns n_pad and the keywords of the outputs' torch.empty."""
+    if (qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] <= 0 or qkv.shape[0] % TM_M
+            or any(tuple(t.shape) != (TM_H, TM_M, TM_DH) for t in small.values())):
+        shapes = " / ".join(f"{k} {tuple(t.shape)}" for k, t in [("qkv", qkv), *small.items()])
+        raise _lib.MilHipError(f"{op}: {shapes} outside the built shape")
+    if any(t.device != qkv.device for t in small.values()):
+        raise _lib.MilHipError(f"{op}: qkv, {' and '.join(small)} must be on one device")
+    return qkv.shape[0], dict(device=qkv.device, dtype=torch.float32)
+
+
+def _fused_dqkv(op, dqkv, qkv):
+    """The [n_pad, 1536] rows a fused backward writes its columns of: the caller's, or a fresh torch.empty when None."""
+    if dqkv is None:
+        return torch.empty((qkv.shape[0], 3 * TM_D), device=qkv.device, dtype=torch.float32)
+    if dqkv.dtype != torch.float32 or not dqkv.is_contiguous() or tuple(dqkv.shape) != (qkv.shape[0], 3 * TM_D) or dqkv.device != qkv.device:
+        raise _lib.MilHipError(f"{op}: dqkv must be a contiguous float32 [n_pad, 1536] tensor on qkv's device")
+    return dqkv
 
 
 def tm_lmk_attn(qkv, qL):
@@ -180,9 +197,7 @@ def tm_lmk_attn(qkv, qL):
     (scaled, as mil_tm_landmarks leaves it) -> (W [8, 256, 64] = softmax(qL k^T) v, lse [8, 256]) over all n_pad keys.  The
     workspace is one torch.empty below the size of one map; two launches, no host sync, bit-reproducible."""
     qkv, qL = _f32c(qkv, "qkv"), _f32c(qL, "qL")
-    _lmk_check(qkv, qL)
-    n = qkv.shape[0]
-    f32 = dict(device=qkv.device, dtype=torch.float32)
+    n, f32 = _fused_operands("tm_lmk_attn", qkv, qL=qL)
     W = torch.empty((TM_H, TM_M, TM_DH), **f32)
     lse = torch.empty((TM_H, TM_M), **f32)
     ws = torch.empty(_lib.lib().mil_tm_lmk_attn_ws_floats(n, 0), **f32)
@@ -195,27 +210,14 @@ def tm_lmk_attn_bwd(qkv, qL, W, lse, dW, dqkv=None):
     torch.empty when None) are overwritten with dk | dv, columns 0 .. 511 are left as they are; dqL [8, 256, 64] is overwritten.
     Three launches, no atomics, no host sync."""
     qkv, qL, W, lse, dW = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (qL, "qL"), (W, "W"), (lse, "lse"), (dW, "dW")))
-    _lmk_check(qkv, qL)
-    n = qkv.shape[0]
-    f32 = dict(device=qkv.device, dtype=torch.float32)
+    n, f32 = _fused_operands("tm_lmk_attn_bwd", qkv, qL=qL)
     if tuple(W.shape) != (TM_H, TM_M, TM_DH) or tuple(dW.shape) != (TM_H, TM_M, TM_DH) or lse.numel() != TM_H * TM_M:
         raise _lib.MilHipError(f"tm_lmk_attn_bwd: W {tuple(W.shape)} / dW {tuple(dW.shape)} / lse {tuple(lse.shape)} outside the built shape")
-    if dqkv is None:
-        dqkv = torch.empty((n, 3 * TM_D), **f32)
-    elif dqkv.dtype != torch.float32 or not dqkv.is_contiguous() or tuple(dqkv.shape) != (n, 3 * TM_D) or dqkv.device != qkv.device:
-        raise _lib.MilHipError("tm_lmk_attn_bwd: dqkv must be a contiguous float32 [n_pad, 1536] tensor on qkv's device")
+    dqkv = _fused_dqkv("tm_lmk_attn_bwd", dqkv, qkv)
     dqL = torch.empty((TM_H, TM_M, TM_DH), **f32)
     ws = torch.empty(_lib.lib().mil_tm_lmk_attn_ws_floats(n, 1), **f32)
     _lib.checked().mil_tm_lmk_attn_bwd(_p(qkv), _p(qL), _p(W), _p(lse), _p(dW), n, _p(dqkv), _p(dqL), _p(ws), _stream())
     return dqkv, dqL
-
-
-def _tok_check(qkv, kL, U):
-    if (qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] <= 0 or qkv.shape[0] % TM_M
-            or tuple(kL.shape) != (TM_H, TM_M, TM_DH) or tuple(U.shape) != (TM_H, TM_M, TM_DH)):
-        raise _lib.MilHipError(f"tm_tok_attn: qkv {tuple(qkv.shape)} / kL {tuple(kL.shape)} / U {tuple(U.shape)} outside the built shape")
-    if kL.device != qkv.device or U.device != qkv.device:
-        raise _lib.MilHipError("tm_tok_attn: qkv, kL and U must be on one device")
 
 
 def tm_tok_attn(qkv, kL, U):
@@ -223,9 +225,7 @@ def tm_tok_attn(qkv, kL, U):
     scaled), U [8, 256, 64] -> (O [n_pad, 512] = softmax(64^-0.5 q kL^T) U with the heads merged, lse [8, n_pad]); every row is a
     query.  One launch, no workspace, no host sync, bit-reproducible."""
     qkv, kL, U = _f32c(qkv, "qkv"), _f32c(kL, "kL"), _f32c(U, "U")
-    _tok_check(qkv, kL, U)
-    n = qkv.shape[0]
-    f32 = dict(device=qkv.device, dtype=torch.float32)
+    n, f32 = _fused_operands("tm_tok_attn", qkv, kL=kL, U=U)
     O = torch.empty((n, TM_D), **f32)
     lse = torch.empty((TM_H, n), **f32)
     nws = _lib.lib().mil_tm_tok_attn_ws_floats(n, 0)            # 0 as built: every row's 256 landmarks meet in one wave
@@ -239,15 +239,10 @@ def tm_tok_attn_bwd(qkv, kL, U, lse, dO, dqkv=None):
     torch.empty when None) are overwritten with dq, columns 512 .. 1535 are left as they are; dU and dkL [8, 256, 64] are
     overwritten.  The workspace is one torch.empty of half a map; two launches, no atomics, no host sync."""
     qkv, kL, U, lse, dO = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (kL, "kL"), (U, "U"), (lse, "lse"), (dO, "dO")))
-    _tok_check(qkv, kL, U)
-    n = qkv.shape[0]
-    f32 = dict(device=qkv.device, dtype=torch.float32)
+    n, f32 = _fused_operands("tm_tok_attn_bwd", qkv, kL=kL, U=U)
     if tuple(lse.shape) != (TM_H, n) or tuple(dO.shape) != (n, TM_D) or lse.device != qkv.device or dO.device != qkv.device:
         raise _lib.MilHipError(f"tm_tok_attn_bwd: lse {tuple(lse.shape)} / dO {tuple(dO.shape)} outside the built shape or on another device")
-    if dqkv is None:
-        dqkv = torch.empty((n, 3 * TM_D), **f32)
-    elif dqkv.dtype != torch.float32 or not dqkv.is_contiguous() or tuple(dqkv.shape) != (n, 3 * TM_D) or dqkv.device != qkv.device:
-        raise _lib.MilHipError("tm_tok_attn_bwd: dqkv must be a contiguous float32 [n_pad, 1536] tensor on qkv's device")
+    dqkv = _fused_dqkv("tm_tok_attn_bwd", dqkv, qkv)
     dU = torch.empty((TM_H, TM_M, TM_DH), **f32)
     dkL = torch.empty((TM_H, TM_M, TM_DH), **f32)
     ws = torch.empty(_lib.lib().mil_tm_tok_attn_ws_floats(n, 1), **f32)
@@ -255,20 +250,20 @@ def tm_tok_attn_bwd(qkv, kL, U, lse, dO, dqkv=None):
     return dqkv, dU, dkL
 
 
-def _tm_fused_a3(fused_a3, need_attn) -> bool:
-    """The switch of the fused landmark-query pass: the keyword, else MIL_TM_FUSED_A3 (default 0), read per call.  The
-    attention outputs (need_attn True / "cls") are formed from the map, so they keep the materialised route."""
-    if fused_a3 is None:
-        fused_a3 = os.environ.get("MIL_TM_FUSED_A3", "0") not in ("", "0")
-    return bool(fused_a3) and need_attn is False
+def _tm_switch(value, env_name, need_attn) -> bool:
+    """The switch of a fused pass: the keyword, else the environment variable (default 0), read per call.  The attention outputs
+    (need_attn True / "cls") are formed from the maps (tm_cls_attention takes A1 and A3), so they keep the materialised route."""
+    if value is None:
+        value = os.environ.get(env_name, "0") not in ("", "0")
+    return bool(value) and need_attn is False
 
 
-def _tm_fused_a1(fused_a1, need_attn) -> bool:
-    """The switch of the fused token-query pass: the keyword, else MIL_TM_FUSED_A1 (default 0), read per call.  The attention
-    outputs (need_attn True / "cls") are formed from the map (tm_cls_attention takes A1), so they keep the materialised route."""
-    if fused_a1 is None:
-        fused_a1 = os.environ.get("MIL_TM_FUSED_A1", "0") not in ("", "0")
-    return bool(fused_a1) and need_attn is False
+def _tm_fused_a3(fused_a3, need_attn) -> bool:      # the landmark-query pass
+    return _tm_switch(fused_a3, "MIL_TM_FUSED_A3", need_attn)
+
+
+def _tm_fused_a1(fused_a1, need_attn) -> bool:      # the token-query pass
+    return _tm_switch(fused_a1, "MIL_TM_FUSED_A1", need_attn)
 
 
 def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
@@ -280,6 +275,7 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
     qL = torch.empty((H, M, DH), **f32)
     kL = torch.empty((H, M, DH), **f32)
     _lib.checked().mil_tm_landmarks(_p(qkv), n, TM_QSCALE, _p(qL), _p(kL), _stream())
+    A1 = A3 = lse1 = lse3 = None                                # per pass its softmaxed map, or (fused) its rows' logsumexp
     maps = []                                                   # the bag-sized maps this call forms, softmaxed below
     if not fused_a1:
         A1 = torch.empty((H, n, M), **f32)
@@ -287,10 +283,10 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
         maps.append(A1)
     A2 = torch.empty((H, M, M), **f32)
     tm_bgemm(qL, (M * DH, DH, 1), kL, (M * DH, 1, DH), A2, (M * M, M, 1), H, M, M, DH)
-    if fused_a3:        # no A3: W and the rows' logsumexp straight from qL and the k | v columns (saved where A3 was)
+    if fused_a3:        # no A3: W and the rows' logsumexp straight from qL and the k | v columns
         for A in maps + [A2]:
             tm_softmax_rows(A)
-        W, A3 = tm_lmk_attn(qkv, qL)
+        W, lse3 = tm_lmk_attn(qkv, qL)
     else:
         A3 = torch.empty((H, M, n), **f32)
         tm_bgemm(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
@@ -314,8 +310,8 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
         Zs.append(Z); Xs.append(X); T2s.append(T2); T3s.append(T3)
         Z = Zn
     U = tm_bgemm(Z, sq, W, (M * DH, DH, 1), torch.empty((H, M, DH), **f32), (M * DH, DH, 1), H, M, DH, M)
-    if fused_a1:        # no A1: O and the rows' logsumexp straight from the q columns, kL and U (saved where A1 was)
-        O, A1 = tm_tok_attn(qkv, kL, U)
+    if fused_a1:        # no A1: O and the rows' logsumexp straight from the q columns, kL and U
+        O, lse1 = tm_tok_attn(qkv, kL, U)
     else:
         O = torch.empty((n, TM_D), **f32)
         tm_bgemm(A1, (n * M, M, 1), U, (M * DH, DH, 1), O, (DH, TM_D, 1), H, n, DH, M)
@@ -326,7 +322,8 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
     elif need_attn:         # A1 Z A3 [8, n_pad, n_pad] (nystrom_attention return_attn), forward only
         T = tm_bgemm(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
         attn = tm_bgemm(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
-    saved = (qL, kL, A1, A2, A3, W, U, Z, scale, arg, Zs, Xs, T2s, T3s)
+    saved = SimpleNamespace(qL=qL, kL=kL, A1=A1, lse1=lse1, A2=A2, A3=A3, lse3=lse3, W=W, U=U, Z=Z,
+                            pinv=(scale, arg, Zs, Xs, T2s, T3s))
     return O, attn, saved
 
 
@@ -351,10 +348,12 @@ def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s):
     return dA2
 
 
-def _tm_bwd(dO, qkv, w, saved, fused_a3=False, fused_a1=False):
-    """fused_a3: `saved` carries lse3 [8, 256] where A3 was (what _tm_fwd left with the same switch); fused_a1: lse1 [8, n_pad]
-    where A1 was."""
-    qL, kL, A1, A2, A3, W, U, Z, scale, arg, Zs, Xs, T2s, T3s = saved
+def _tm_bwd(dO, qkv, w, saved):
+    """`saved` as _tm_fwd left it: a pass that ran fused has its lse (lse1 [8, n_pad], lse3 [8, 256]) and no map, and its
+    backward takes the fused entry too."""
+    s = saved
+    qL, kL, A1, A2, A3, W, U, Z = s.qL, s.kL, s.A1, s.A2, s.A3, s.W, s.U, s.Z
+    fused_a1, fused_a3 = s.lse1 is not None, s.lse3 is not None
     n = qkv.shape[0]
     f32 = dict(device=qkv.device, dtype=torch.float32)
     H, M, DH, L3 = TM_H, TM_M, TM_DH, 3 * TM_D
@@ -363,14 +362,14 @@ def _tm_bwd(dO, qkv, w, saved, fused_a3=False, fused_a1=False):
     dqkv = torch.empty((n, L3), **f32)
     dw = torch.zeros(H * TM_CONV, **f32)
     if fused_a1:        # dq into columns 0 .. 511 of dqkv before anything adds onto them, dU, and the pass's share of dkL
-        _, dU, dkL = tm_tok_attn_bwd(qkv, kL, U, A1, dO, dqkv)
+        _, dU, dkL = tm_tok_attn_bwd(qkv, kL, U, s.lse1, dO, dqkv)
     else:
         dA1 = tm_bgemm(dO, (DH, TM_D, 1), U, (M * DH, 1, DH), torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, DH)
         dU = tm_bgemm(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
     dZ = tm_bgemm(dU, sl, W, (M * DH, 1, DH), torch.empty((H, M, M), **f32), sq, H, M, M, DH)
     dW = tm_bgemm(Z, (M * M, 1, M), dU, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
     if fused_a3:        # dk | dv into dqkv and the pass's share of dqL, before the stages that add onto them
-        _, dqL = tm_lmk_attn_bwd(qkv, qL, W, A3, dW, dqkv)
+        _, dqL = tm_lmk_attn_bwd(qkv, qL, W, s.lse3, dW, dqkv)
     else:
         dA3 = tm_bgemm(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
         tm_bgemm(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)            # dv = A3^T dW
@@ -379,7 +378,7 @@ def _tm_bwd(dO, qkv, w, saved, fused_a3=False, fused_a1=False):
         dS1 = tm_softmax_rows_bwd(A1, dA1)
     if not fused_a3:
         dS3 = tm_softmax_rows_bwd(A3, dA3)
-    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, scale, arg, Zs, Xs, T2s, T3s))
+    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv))
     if not fused_a1:
         tm_bgemm(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)        # dq
         dkL = tm_bgemm(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
@@ -403,8 +402,6 @@ class _NystromCore(torch.autograd.Function):
             raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
         O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1)
         ctx.saved = saved
-        ctx.fused_a3 = fused_a3
-        ctx.fused_a1 = fused_a1
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
         if attn is not None:
@@ -414,7 +411,7 @@ class _NystromCore(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dO, _dattn):
         qkv, w = ctx.saved_tensors
-        dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved, ctx.fused_a3, ctx.fused_a1)
+        dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved)
         ctx.saved = None
         return dqkv, dw.reshape(ctx.w_shape), None, None, None, None
 

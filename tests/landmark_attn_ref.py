@@ -3,13 +3,15 @@ in the style of transmil_ref.py: per head Q = qL [256, 64] (already scaled), K /
 every row a key - W = softmax(Q K^T) V, lse = logsumexp(Q K^T), and from dW the gradients dkv [n_pad, 1024] (dk | dv, merged
 heads) and dqL.  Written for any float dtype: float64 is the reference, float32 on the CPU gives e32, and a block of a GPU
 result is held to transmil_ref.bound(e32, k).  mutate= plants one error (tests/test_landmark_attn_sensitivity_host.py)."""
+import functools
 import math
 
 import torch
 
+import fused_attn_common as C
 import transmil_ref as R
+from fused_attn_common import H, DH, M, D, heads, merged, pad_rows, ratios  # noqa: F401  (the tests reach them through here)
 
-H, DH, M, D = R.H, R.DH, R.M, R.H * R.DH
 CHUNK = 256                      # keys per chunk of the chunked forms below
 SIZES = (256, 512, 768, 1280)    # one chunk (the merge of a single partial), two, three, an odd number above
 CASES = ("randn", "ramp_up", "ramp_down", "hot")
@@ -21,20 +23,7 @@ HOT = 110.0
 # largest ratio 4.20 (n_pad 256, peak 3, dqkv.k_pad; the materialised route reads 2.76 there) -> 16.  Why the stage reads
 # above the 1.5 of the chunked float32 restatement: the lab notes.
 K_LMK = {"stage": 16, "core": 16}
-
-
-def pad_rows(n_pad):
-    return 37 if n_pad > 256 else 3          # as transmil_ref.core_case has them
-
-
-def heads(cols):
-    """[n, 512] merged-head columns -> [8, n, 64]."""
-    return cols.reshape(cols.shape[0], H, DH).transpose(0, 1)
-
-
-def merged(t):
-    """[8, n, 64] -> [n, 512]."""
-    return t.transpose(0, 1).reshape(t.shape[1], D)
+hold = functools.partial(C.hold, "lmk", K_LMK)      # hold(stage, tag, got, ref, r32, blks, k=None): `RATIO | lmk_<stage> | ..`
 
 
 def scores(qkv, qL):
@@ -154,33 +143,8 @@ def run_formulas(qkv, qL, dW, dtype=torch.float64, pad=0, mutate=None, chunked=F
 def blocks(n_pad, pad):
     """W, lse, dqL: all and each head.  dkv: the k and v column groups, each over all rows, the pad rows, the first and last
     16 rows and every 256-row chunk - a lost or doubled chunk shows in a block of its own."""
-    per_head = {"all": (Ellipsis,)}
-    per_head.update({f"h{h}": (h,) for h in range(H)})
     dkv = {}
     for i, c in enumerate("kv"):
-        cols = slice(D * i, D * (i + 1))
-        dkv[c] = (slice(None), cols)
-        dkv[c + "_pad"] = (slice(0, pad), cols)
-        dkv[c + "_first16"] = (slice(0, 16), cols)
-        dkv[c + "_last16"] = (slice(n_pad - 16, n_pad), cols)
-        for j in range(n_pad // CHUNK):
-            dkv[f"{c}_chunk{j}"] = (slice(CHUNK * j, CHUNK * (j + 1)), cols)
-    return {"W": dict(per_head), "lse": dict(per_head), "dkv": dkv, "dqL": dict(per_head)}
-
-
-def ratios(got, ref, r32, blks):
-    """{tensor.block: (error of got, e32, error / max(e32, FLOOR))}."""
-    e32, eg = R.flat_err(r32, ref, blks), R.flat_err(got, ref, blks)
-    return {b: (e, e32[b], e / max(e32[b], R.FLOOR)) for b, e in eg.items()}
-
-
-def hold(stage, tag, got, ref, r32, blks, k=None):
-    """Every block of every tensor of `got` within bound(e32, k) of `ref` (k = K_LMK[stage] unless given); prints each ratio
-    first."""
-    k = K_LMK[stage] if k is None else k
-    bad = []
-    for b, (e, e32, ratio) in ratios(got, ref, r32, blks).items():
-        print(f"RATIO | lmk_{stage} | {tag} | {b} | gpu {e:.2e} | e32 {e32:.2e} | {ratio:.2f}")
-        if not e <= R.bound(e32, k):
-            bad.append((b, e, e32))
-    assert not bad, (stage, tag, bad)
+        for name, ix in C.row_blocks(n_pad, pad, CHUNK, (slice(D * i, D * (i + 1)),)).items():
+            dkv[c if name == "all" else f"{c}_{name}"] = ix
+    return {"W": C.per_head(), "lse": C.per_head(), "dkv": dkv, "dqL": C.per_head()}

@@ -5,53 +5,15 @@ against transmil_ref.core_run; the switch off and the attention outputs on the l
 replayed step against the reference's goldens; and the peak memory the route gives back.  Bounds: k x max(e32, 1e-7) per block
 with k = token_attn_ref.K_TOK (the measured ratios: docs/lab_notes.md), the module's standing 1e-4 / 2e-3 where the goldens are
 the reference."""
-import argparse
-import ctypes
-
 import pytest
 import torch
 
 import token_attn_ref as TR
 import transmil_ref as R
+from fused_attn_common import DEV, MAP_BYTES, SENT, _bits, _check_grads, _core, _guarded, _guards_intact, _lib, _model, _p, _st, rel
 from test_transmil_host import golden_bags
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda:0")
-SENT = -12345.678                    # the sentinel; the bit pattern is what is compared
-GUARD = 64                           # floats of sentinel on either side of a buffer (a multiple of 4: operands stay 16-byte aligned)
-MAP_BYTES = 8 * 256 * 4              # x n_pad: one A1 map
-
-
-def _lib():
-    from mil_amd import _lib as L
-    return L.lib()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def _guarded(numel, fill=None):
-    """A device buffer of GUARD + numel + GUARD floats, all sentinel (or `fill` [numel] inside); returns (whole, inside view)."""
-    buf = torch.full((numel + 2 * GUARD,), SENT, device=DEV, dtype=torch.float32)
-    if fill is not None:
-        buf[GUARD:GUARD + numel].copy_(fill.reshape(-1).to(torch.float32))
-    return buf, buf[GUARD:GUARD + numel]
-
-
-def _guards_intact(tag, buf):
-    want = torch.full((GUARD,), SENT, dtype=torch.float32).view(torch.int32)
-    b = _bits(buf)
-    assert torch.equal(b[:GUARD], want) and torch.equal(b[-GUARD:], want), f"{tag}: wrote outside its extent"
 
 
 _refs = {}
@@ -121,16 +83,6 @@ def test_two_runs_give_the_same_bits():
     assert set(a) == {"O", "lse", "dq", "dU", "dkL"}
     for k in a:
         assert torch.equal(_bits(a[k]), _bits(b[k])), k
-
-
-def _core(qkv, w, dO, **kw):
-    from mil_amd import ops
-    qd = qkv.float().to(DEV).requires_grad_(True)
-    wd = w.float().to(DEV).requires_grad_(True)
-    o, attn = ops.nystrom_core(qd, wd, **kw)
-    o.backward(dO.float().to(DEV))
-    torch.cuda.synchronize()
-    return {"out": o.detach(), "dqkv": qd.grad, "dw": wd.grad.reshape(R.H, R.CONV)}, attn
 
 
 def _count_fused_calls(monkeypatch):
@@ -203,36 +155,6 @@ def test_attention_outputs_keep_the_materialised_route(monkeypatch):
     for o, m in ((o_env, m_env), (o_on, m_on)):
         assert torch.equal(_bits(m), _bits(m_off)) and torch.equal(_bits(o), _bits(o_off))
     assert len(calls) == 0
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
-def _model(seed):
-    from mil_amd import synthetic as syn
-    from mil_amd.model.utils_clip import get_model
-    args = argparse.Namespace(modality=["pathology"], model_pathology="TransMIL", num_classes=2, patch_dim=768, variant="image_only")
-    model = get_model(args)
-    sd = {"extractor_pathology." + k: v for k, v in syn.transmil_params(seed, 768, 2).items()}
-    sd.update(syn.head_params(seed + 1, 512, 2))
-    model.load_state_dict(sd)
-    return model.to(DEV).eval()
-
-
-def _check_grads(model, g, extra=None):
-    grads = {"g." + k: v.grad for k, v in model.named_parameters()}
-    grads.update(extra or {})
-    worst = 0.0
-    for k, v in grads.items():
-        if k.startswith("g.extractor_pathology._fc2"):
-            assert v is None
-            continue
-        e = max(abs(float(v.norm()) - float(g[k + ".norm"])) / float(g[k + ".norm"]), rel(v.flatten()[::97], g[k + ".sample"]))
-        assert e <= 2e-3, (k, e)
-        worst = max(worst, e)
-    return worst
 
 
 @pytest.mark.parametrize("a3", ["0", "1"])

@@ -4,11 +4,14 @@ the style of landmark_attn_ref.py: per head Q = the q columns of the [n_pad, 153
 [8, n_pad], and from dO [n_pad, 512] the gradients dq [n_pad, 512], dU and dkL [8, 256, 64].  Written for any float dtype:
 float64 is the reference, float32 on the CPU gives e32, and a block of a GPU result is held to transmil_ref.bound(e32, k).
 mutate= plants one error (tests/test_token_attn_sensitivity_host.py)."""
+import functools
+
 import torch
 
+import fused_attn_common as C
 import transmil_ref as R
+from fused_attn_common import H, DH, M, D, heads, merged, pad_rows, ratios  # noqa: F401  (the tests reach them through here)
 
-H, DH, M, D = R.H, R.DH, R.M, R.H * R.DH
 QSCALE = DH ** -0.5
 CHUNK = 256                      # rows per chunk of the backward's two sums over the rows
 SIZES = (256, 512, 768, 1280)    # one row chunk (the reduce of a single partial), two, three, an odd number above
@@ -21,20 +24,7 @@ HOT = 110.0
 # combinations over transmil_ref.core_blocks, largest ratio 4.20 (n_pad 256, peak 3, dqkv.k_pad, with fused_a1 off and fused_a3
 # on, as landmark_attn_ref has it; 3.27 on the same block with both on, 3.24 on dqkv.q_pad with fused_a1 alone) -> 16.
 K_TOK = {"stage": 8, "core": 16}
-
-
-def pad_rows(n_pad):
-    return 37 if n_pad > 256 else 3          # as transmil_ref.core_case has them
-
-
-def heads(cols):
-    """[n, 512] merged-head columns -> [8, n, 64]."""
-    return cols.reshape(cols.shape[0], H, DH).transpose(0, 1)
-
-
-def merged(t):
-    """[8, n, 64] -> [n, 512]."""
-    return t.transpose(0, 1).reshape(t.shape[1], D)
+hold = functools.partial(C.hold, "tok", K_TOK)      # hold(stage, tag, got, ref, r32, blks, k=None): `RATIO | tok_<stage> | ..`
 
 
 def scores(qkv, kL):
@@ -116,27 +106,5 @@ def run_formulas(qkv, kL, U, dO, dtype=torch.float64, pad=0, mutate=None, chunke
 def blocks(n_pad, pad):
     """O and dq: all rows, the pad rows, the first and last 16 rows and every 256-row chunk - a lost or doubled chunk shows in a
     block of its own.  lse, dU, dkL: all heads and each head."""
-    per_head = {"all": (Ellipsis,)}
-    per_head.update({f"h{h}": (h,) for h in range(H)})
-    rows = {"all": (Ellipsis,), "pad": (slice(0, pad),), "first16": (slice(0, 16),), "last16": (slice(n_pad - 16, n_pad),)}
-    for j in range(n_pad // CHUNK):
-        rows[f"chunk{j}"] = (slice(CHUNK * j, CHUNK * (j + 1)),)
-    return {"O": dict(rows), "lse": dict(per_head), "dq": dict(rows), "dU": dict(per_head), "dkL": dict(per_head)}
-
-
-def ratios(got, ref, r32, blks):
-    """{tensor.block: (error of got, e32, error / max(e32, FLOOR))}."""
-    e32, eg = R.flat_err(r32, ref, blks), R.flat_err(got, ref, blks)
-    return {b: (e, e32[b], e / max(e32[b], R.FLOOR)) for b, e in eg.items()}
-
-
-def hold(stage, tag, got, ref, r32, blks, k=None):
-    """Every block of every tensor of `got` within bound(e32, k) of `ref` (k = K_TOK[stage] unless given); prints each ratio
-    first."""
-    k = K_TOK[stage] if k is None else k
-    bad = []
-    for b, (e, e32, ratio) in ratios(got, ref, r32, blks).items():
-        print(f"RATIO | tok_{stage} | {tag} | {b} | gpu {e:.2e} | e32 {e32:.2e} | {ratio:.2f}")
-        if not e <= R.bound(e32, k):
-            bad.append((b, e, e32))
-    assert not bad, (stage, tag, bad)
+    rows = C.row_blocks(n_pad, pad, CHUNK)
+    return {"O": dict(rows), "lse": C.per_head(), "dq": dict(rows), "dU": C.per_head(), "dkL": C.per_head()}
