@@ -688,9 +688,10 @@ int mil_value_proj_bwd(const float* dO, const float* Wv, const float* pooled, in
  * [rows, ld] with column c = t H + h, columns >= T H are padding and come out as zeros):
  *   mil_grp_col_softmax      in place, over the ROWS of each group (bag) per column     (token -> image)
  *   mil_row_softmax_t        in place, over the T tokens of each (row, head)           (image -> token)
- * and their backwards dS = A (dA - sum A dA) over the same axis.  max_group_rows = rows of the longest group (0 = not
- * known): selects the workgroup shape that holds a whole group in registers (up to 32 768 rows forward, 16 384 backward;
- * longer groups re-read their columns). */
+ * and their backwards dS = A (dA - sum A dA) over the same axis (the sum is accumulated in double: behind a probability
+ * near 1 the difference cancels, and a float32 sum left 1e-5 of that row's dS).  max_group_rows = rows of the longest
+ * group (0 = not known): selects the workgroup shape that holds a whole group in registers (up to 32 768 rows forward,
+ * 16 384 backward; longer groups re-read their columns). */
 int mil_grp_col_softmax(float* S, int ld, const int32_t* grp_off, int G, int max_group_rows, int TH, void* stream);
 int mil_grp_col_softmax_bwd(const float* A, const float* dA, int ld, const int32_t* grp_off, int G, int max_group_rows,
                             int TH, float* dS, void* stream);

@@ -1335,6 +1335,26 @@ __device__ __forceinline__ float cs_reduce(float v, float (*red)[33], int cl) {
     return r;
 }
 
+// The backward's sum_rows A dA in double.  Behind a peaked column (A ~ 1 in one row) dS = A (dA - sum A dA) of that row is a
+// difference of nearly equal terms: a float32 sum, one rounding at the size of the large term per row added behind it, left
+// 1e-5 .. 5e-5 of the column's largest dS (docs/lab_notes.md, fusion norm and softmax stages, finding 1).  The products of
+// two floats are exact in double, and the kernels stay bound by their loads.
+template <int CW>
+__device__ __forceinline__ double cs_reduce_sum_d(double v, double (*red)[33], int cl) {
+    if (CW < 64) {
+#pragma unroll
+        for (int o = CW; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    }
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();                    // the previous use of red is over
+    if ((threadIdx.x & 63) < CW) red[wave][cl] = v;
+    __syncthreads();
+    double r = red[0][cl];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) r += red[i][cl];
+    return r;
+}
+
 template <int CW>
 __global__ __launch_bounds__(1024) void k_grp_col_softmax(float* __restrict__ S, int ld, const int32_t* __restrict__ grp_off,
                                                           int TH) {
@@ -1391,38 +1411,44 @@ __global__ __launch_bounds__(1024) void k_grp_col_softmax_bwd(const float* __res
                                                               const int32_t* __restrict__ grp_off, int TH,
                                                               float* __restrict__ dS) {
     constexpr int RL = 1024 / CW;
-    __shared__ float red[16][33];
+    __shared__ double red[16][33];
     const int g = blockIdx.x, cl = threadIdx.x % CW, c = blockIdx.y * CW + cl, rl = threadIdx.x / CW;
     const int r0 = grp_off[g], r1 = grp_off[g + 1], n = r1 - r0;
     const bool live = c < TH && c < ld;
     const bool fits = n <= RL * (CS_KEEP / 2);
     float a[CS_KEEP / 2], d[CS_KEEP / 2];
-    float cd = 0.f;
+    double cd = 0.0, cd1 = 0.0;         // two chains: the double adds wait on each other, not on the loads
     if (live) {
         if (fits) {
 #pragma unroll
-            for (int i = 0; i < CS_KEEP / 2; ++i) {
-                const int row = r0 + rl + RL * i;
-                a[i] = row < r1 ? A[(size_t)row * ld + c] : 0.f;
-                d[i] = row < r1 ? dA[(size_t)row * ld + c] : 0.f;
-                cd += a[i] * d[i];
+            for (int i = 0; i < CS_KEEP / 2; i += 2) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int row = r0 + rl + RL * (i + u);
+                    a[i + u] = row < r1 ? A[(size_t)row * ld + c] : 0.f;
+                    d[i + u] = row < r1 ? dA[(size_t)row * ld + c] : 0.f;
+                }
+                cd += (double)a[i] * (double)d[i];
+                cd1 += (double)a[i + 1] * (double)d[i + 1];
             }
         } else {
-            for (int row = r0 + rl; row < r1; row += RL) cd += A[(size_t)row * ld + c] * dA[(size_t)row * ld + c];
+            for (int row = r0 + rl; row < r1; row += RL) cd += (double)A[(size_t)row * ld + c] * (double)dA[(size_t)row * ld + c];
         }
     }
-    cd = cs_reduce<CW, false>(cd, red, cl);
+    cd = cs_reduce_sum_d<CW>(cd + cd1, red, cl);
     if (c >= ld) return;
+    // the sum as two floats: d - hi is exact where the two nearly cancel, and the rest is float32 work on small numbers
+    const float hi = (float)cd, lo = (float)(cd - (double)hi);
     if (live && fits) {
 #pragma unroll
         for (int i = 0; i < CS_KEEP / 2; ++i) {
             const int row = r0 + rl + RL * i;
-            if (row < r1) dS[(size_t)row * ld + c] = a[i] * (d[i] - cd);
+            if (row < r1) dS[(size_t)row * ld + c] = a[i] * ((d[i] - hi) - lo);
         }
     } else {
         for (int row = r0 + rl; row < r1; row += RL) {
             const size_t o = (size_t)row * ld + c;
-            dS[o] = live ? A[o] * (dA[o] - cd) : 0.f;
+            dS[o] = live ? A[o] * ((dA[o] - hi) - lo) : 0.f;
         }
     }
 }
@@ -1431,7 +1457,8 @@ __global__ __launch_bounds__(1024) void k_grp_col_softmax_bwd(const float* __res
 // workgroup, two columns wide for such a group - 48 workgroups reading 8 bytes of every 384-byte row (36 us forward, 51 us
 // backward for 3.5 MB).  Row-parallel form in two launches, every row read as a whole by consecutive lanes:
 //   k_gcs_stats  grid (G, NCH): workgroup (g, ch) = rows [ch RCH, (ch + 1) RCH) of group g, thread (row lane, column):
-//                online column maximum / sum (forward) or sum of A dA (backward) -> ws[g][ch][.][ld]
+//                online column maximum / sum (forward) or sum of A dA (backward) -> ws[g][ch][.][ld]; the backward's sum
+//                is kept in double and stored as two floats (leading part in the maximum's slot, remainder in the sum's)
 //   k_gcs_apply  grid (G, NCH): folds the NCH partials of its group (same order everywhere), then rewrites its rows.
 // ld <= 128.
 #define GCS_NCH_MAX 64
@@ -1447,7 +1474,10 @@ __global__ __launch_bounds__(1024) void k_gcs_stats(const float* __restrict__ S,
     float m = -INFINITY, l = 0.f;
     if (rl < RL && c < TH) {
         if (BWD) {
-            for (int row = a0 + rl; row < a1; row += RL) l += S[(size_t)row * ld + c] * dA[(size_t)row * ld + c];
+            double s = 0.0;
+            for (int row = a0 + rl; row < a1; row += RL) s += (double)S[(size_t)row * ld + c] * (double)dA[(size_t)row * ld + c];
+            m = (float)s;
+            l = (float)(s - (double)m);
         } else {
             for (int row = a0 + rl; row < a1; row += RL) {
                 const float v = S[(size_t)row * ld + c];
@@ -1456,12 +1486,16 @@ __global__ __launch_bounds__(1024) void k_gcs_stats(const float* __restrict__ S,
             }
         }
     }
+    if (BWD && !(rl < RL && c < TH)) m = 0.f;               // no rows, or a padding column: the sum is zero
     if (rl < RL) { red[0][rl][c] = m; red[1][rl][c] = l; }
     __syncthreads();
     if (rl == 0 && c < ld) {
         float M = -INFINITY, L = 0.f;
         if (BWD) {
-            for (int i = 0; i < RL; ++i) L += red[1][i][c];
+            double s = 0.0;
+            for (int i = 0; i < RL; ++i) s += (double)red[0][i][c] + (double)red[1][i][c];
+            M = (float)s;
+            L = (float)(s - (double)M);
         } else {
             for (int i = 0; i < RL; ++i) M = fmaxf(M, red[0][i][c]);
             for (int i = 0; i < RL; ++i) L += red[0][i][c] > -INFINITY ? red[1][i][c] * expf(red[0][i][c] - M) : 0.f;
@@ -1488,15 +1522,17 @@ __global__ __launch_bounds__(1024) void k_gcs_apply(float* __restrict__ S, const
     if (rl < RL) {
         const float* w = ws + (size_t)g * NCH * 2 * ld;
         float M = -INFINITY, L = 0.f;
+        double s = 0.0;
         for (int i = rl; i < NCH; i += RL) {
             const float mi = w[(size_t)i * 2 * ld + c], li = w[(size_t)i * 2 * ld + ld + c];
             if (BWD) {
-                L += li;
+                s += (double)mi + (double)li;
             } else if (mi > -INFINITY) {
                 if (mi > M) { L = L * expf(M - mi) + li; M = mi; }
                 else L += li * expf(mi - M);
             }
         }
+        if (BWD) { M = (float)s; L = (float)(s - (double)M); }
         red[0][rl][c] = M;
         red[1][rl][c] = L;
     }
@@ -1504,12 +1540,15 @@ __global__ __launch_bounds__(1024) void k_gcs_apply(float* __restrict__ S, const
     if (rl == 0) {
         float M = -INFINITY, L = 0.f;
         if (BWD) {
-            for (int i = 0; i < RL; ++i) L += red[1][i][c];
+            double s = 0.0;
+            for (int i = 0; i < RL; ++i) s += (double)red[0][i][c] + (double)red[1][i][c];
+            M = (float)s;
+            L = (float)(s - (double)M);
         } else {
             for (int i = 0; i < RL; ++i) M = fmaxf(M, red[0][i][c]);
             for (int i = 0; i < RL; ++i) L += red[0][i][c] > -INFINITY ? red[1][i][c] * expf(red[0][i][c] - M) : 0.f;
         }
-        cm[c] = M;
+        cm[c] = M;                                          // backward: the two parts of the sum
         cl_[c] = BWD ? L : (L > 0.f ? 1.0f / L : 0.f);
     }
     __syncthreads();
@@ -1518,7 +1557,7 @@ __global__ __launch_bounds__(1024) void k_gcs_apply(float* __restrict__ S, const
     const float M = cm[c], L = cl_[c];
     for (int row = a0 + rl; row < a1; row += RL) {
         const size_t o = (size_t)row * ld + c;
-        if (BWD) S[o] = live ? A[o] * (dA[o] - L) : 0.f;
+        if (BWD) S[o] = live ? A[o] * ((dA[o] - M) - L) : 0.f;          // (M, L) = the sum's two parts: d - M is exact where they cancel
         else S[o] = live ? expf(S[o] - M) * L : 0.f;
     }
 }
@@ -1560,15 +1599,23 @@ __global__ __launch_bounds__(256) void k_row_softmax_t_bwd(const float* __restri
     if (idx >= R * H) return;
     const int row = idx / H, h = idx % H;
     const size_t base = (size_t)row * ld + h;
-    float a[16], d[16], cd = 0.f;
+    float a[16], d[16];
+    double cd = 0.0, cd1 = 0.0;         // in double, as the column softmax's (cs_reduce_sum_d): behind a peaked row the float32 sum
+                                        // left up to 1e-3 of the head's largest dS.  Two chains; the tail in float32 on (hi, lo).
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
         a[t] = t < T ? A[base + t * H] : 0.f;
         d[t] = t < T ? dA[base + t * H] : 0.f;
-        cd += a[t] * d[t];
     }
 #pragma unroll
-    for (int t = 0; t < 16; ++t) if (t < T) dS[base + t * H] = a[t] * (d[t] - cd);
+    for (int t = 0; t < 16; t += 2) {
+        cd += (double)a[t] * (double)d[t];
+        cd1 += (double)a[t + 1] * (double)d[t + 1];
+    }
+    cd += cd1;
+    const float hi = (float)cd, lo = (float)(cd - (double)hi);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) if (t < T) dS[base + t * H] = a[t] * ((d[t] - hi) - lo);
     for (int c = T * H + h; c < ld; c += H) dS[(size_t)row * ld + c] = 0.f;
 }
 
