@@ -3,6 +3,10 @@
 // Reference arithmetic: torch autograd of model/dim1/ABMIL.py:47-56.  The transpose-product dPre^T . x is a dense
 // contraction over the rows: v_mfma_f32_32x32x2_f32 (k_gate_bwd_dw, k_gate_bwd_dw2) or the split-bf16 loop
 // (k_gate_bwd_dw2_pieces); the split-K fold is k_gate_bwd_reduce (gate_reduce.h).  Forward and route plan: gate_fwd.hip.
+// The three kernels are built from one set of parts (below): workgroup coordinates and K-group rows (dw_coord, dw_rows),
+// the keep mask of a staged x chunk (dw_keep4), the dPre formula and the bias / w / b sums (DwPre, DwSums), the buffer-resource
+// loaders of the dw2 kernels (DwSrdSource), the pinned f32 k-steps of a slice (dw_slice_f32) and the epilogue (dw_store_tile,
+// dw_publish_sums).  The host side names every instantiation in two tables (DW_KERNELS, DW2_KERNELS; gate_dw_launch picks).
 #include "mil_internal.h"
 #include "gate_reduce.h"
 #include <type_traits>
@@ -17,45 +21,281 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 // Both operands are "k-major" in LDS ([row][i] and [row][j]): lane (i = l & 31, k = l >> 5) reads
 // word row*128 + i: consecutive lanes -> consecutive banks, no conflicts, no padding.
 #define GB_BKR 32
+#define DW_GRP_FLOATS (2 * 2 * GB_BKR * 128)      /* the f32 stages of one K group: [2][32][128] dPre, [2][32][128] x (64 KiB) */
 typedef unsigned short gb_u16x8 __attribute__((ext_vector_type(8)));
 
+// ---------------------------------------------------------------- parts
+// Output tile of the workgroup: column tile jt (j0 = 128 jt), gate block m, row chunk s.  The 3*NJ workgroups of one row
+// chunk re-read the same x / gate rows, so they take consecutive slots of ONE XCD (xcd_order).  Handed to the parts by value.
+struct DwCoord {
+    int jt, m, s, j0;
+};
+__device__ __forceinline__ DwCoord dw_coord(int NJ) {
+    const int bid = xcd_order(blockIdx.x, gridDim.x);
+    const int jt = bid % NJ;
+    return {jt, (bid / NJ) % 3, bid / (3 * NJ), jt * 128};
+}
+
+// Bucketed batches: R is the bucket the launch is sized for, the true row count lives on the device (rows_dev, or NULL)
+__device__ __forceinline__ int dw_true_rows(int R, const int32_t* __restrict__ rows_dev) {
+    return rows_dev != nullptr ? min(R, __builtin_amdgcn_readfirstlane(rows_dev[0])) : R;
+}
+
+// Row chunk s of the workgroup, then K group grp's part of it (whole slices to group 0 first).  The slice loop runs nloop times
+// for every group (common barriers); nslice counts the group's own slices (the clamped loaders of k_gate_bwd_dw need it).
+struct DwRows {
+    int rbeg, rend, nloop, nslice;
+};
+template <int KG>
+__device__ __forceinline__ DwRows dw_rows(int s, int KC, int R, int grp) {
+    const int cbeg = min(s * KC, R), cend = min(R, cbeg + KC);
+    const int half = KG == 1 ? cend - cbeg : ((cend - cbeg + 2 * GB_BKR - 1) / (2 * GB_BKR)) * GB_BKR;
+    const int rbeg = min(cend, cbeg + grp * half), rend = KG == 1 ? cend : min(cend, rbeg + half);
+    return {rbeg, rend, (min(half, cend - cbeg) + GB_BKR - 1) / GB_BKR, (rend - rbeg + GB_BKR - 1) / GB_BKR};
+}
+
+// Train mode: the keep bits (the forward's mask, csrc/dropout.hip) of four staged x columns.  word = the 32 keep bits the
+// columns lie in, chunk = their 16-byte chunk index within the row.
+__device__ __forceinline__ f32x4 dw_keep4(f32x4 v, unsigned word, int chunk) {
+    const unsigned mm = word >> (4 * (chunk & 7));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = keep_if(v[e], mm, e);
+    return v;
+}
+
+// dPreV = ds w U (1 - V^2) = a - (a V) V and dPreU = ds w V U (1 - U) = t - t U with a = ds w U, t = a V: four VALU per
+// (V, U) pair instead of seven.  ds_w = ds w as the kernel formed it (the clamped kernel masks ds first).
+struct DwPre {
+    static __device__ __forceinline__ f32x4 v(const f32x4 ds_w, const f32x4 V, const f32x4 U, f32x4& t) {
+        const f32x4 a = ds_w * U;
+        t = a * V;
+        return a - t * V;
+    }
+    static __device__ __forceinline__ f32x4 u(const f32x4 t, const f32x4 U) { return t - t * U; }
+};
+
+// The bias / w / b sums of a thread's rows: dbv, dbu (float4 column ad4 of block m), dw and, in the ad4 == 0 threads, db.
+struct DwSums {
+    f32x4 bv = {0, 0, 0, 0}, bu = {0, 0, 0, 0}, w = {0, 0, 0, 0};
+    float ds = 0.f;
+    // k_gate_bwd_dw sums every slice: dPreV as it was staged, and with dPreU the w and b terms (dsv = the masked ds)
+    __device__ __forceinline__ void add_v(const f32x4 pv) { bv += pv; }
+    __device__ __forceinline__ void add_u(const f32x4 pu, float dsv, const f32x4 V, const f32x4 U, int ad4) {
+        bu += pu;
+        w += (dsv * V) * U;
+        if (ad4 == 0) ds += dsv;
+    }
+    // the dw2 kernels sum every NJ-th slice only, behind a scalar branch in the dPreU part: dPreV is formed again there
+    // (3 VALU per element), NOT carried over from the dPreV part
+    __device__ __forceinline__ void add_pub(float dsv, const f32x4 w4, const f32x4 V, const f32x4 U, const f32x4 t, const f32x4 pu,
+                                            int ad4) {
+        bv += (dsv * w4) * U - t * V;
+        add_u(pu, dsv, V, U, ad4);
+    }
+};
+
+// The global operands of the dw2 kernels, through buffer resources whose base / size live in SGPRs and advance by scalar ALU:
+// the per-lane byte offsets are loop invariants, and a row at or beyond `rend` is out of range, so the hardware range check
+// returns ZERO for it (no clamps, no validity masks: a zero ds row contributes nothing).  Thread t stages NX chunks of x
+// (rows (t >> 5) + (32 / NX) i, 16-byte chunk t & 31 of the 128-column tile) and NA float4 pairs of gates (rows (t >> 4) +
+// (32 / NA) i, d = 64m + 4 (t & 15)) per 32-row slice: 4 and 2 with 256 threads per K group, 2 and 1 with 512.
+template <bool DROP, int NX, int NA>
+struct DwSrdSource {
+    const float *x, *gates, *ds;
+    const uint32_t* xbits;
+    int L, LW, rend;
+    int vx[NX], vm[NX], vg[NA], vd[NA];
+    u32x4_t rx[NX], rv[NA], ru[NA];       // the staged slice: x chunks, V and U, ds and (train mode) the keep words
+    unsigned rm[NX];
+    float rds[NA];
+    __device__ __forceinline__ DwSrdSource(const float* x_, const float* gates_, const float* ds_, const uint32_t* xbits_, int L_,
+                                           int rend_, int t, const DwCoord c)
+        : x(x_), gates(gates_), ds(ds_), xbits(xbits_), L(L_), LW(L_ >> 5), rend(rend_) {
+        const int xrow = t >> 5, xc4 = t & 31, arow = t >> 4, ad4 = t & 15;
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            vx[i] = ((xrow + (32 / NX) * i) * L + c.j0 + 4 * xc4) * 4;
+            vm[i] = ((xrow + (32 / NX) * i) * LW + ((c.j0 + 4 * xc4) >> 5)) * 4;
+            rm[i] = 0;
+        }
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            vg[i] = ((arow + (32 / NA) * i) * GF_NG + 64 * c.m + 4 * ad4) * 4;
+            vd[i] = (arow + (32 / NA) * i) * 4;
+        }
+    }
+    // scalar: the resource of `left` rows from row0 of an operand with `stride` 4-byte words per row.  left = the rows up to
+    // rend, formed once per xload / aload and not in here: with the max() inside, the scalar instructions of the pieces kernel's
+    // K loop come out in another order (docs/lab_notes.md)
+    template <class T>
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t srd(const T* base, int row0, int left, int stride) const {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (size_t)row0 * stride), 0, left * stride * 4, MIL_SRD_FLAGS);
+    }
+    __device__ __forceinline__ void xload(int i, int row0) {
+        const int left = max(rend - row0, 0);
+        rx[i] = __builtin_amdgcn_raw_buffer_load_b128(srd(x, row0, left, L), vx[i], 0, 0);
+        if (DROP) rm[i] = __builtin_amdgcn_raw_buffer_load_b32(srd(xbits, row0, left, LW), vm[i], 0, 0);
+    }
+    __device__ __forceinline__ void aload(int i, int row0) {
+        const int left = max(rend - row0, 0);
+        const __amdgpu_buffer_rsrc_t g = srd(gates, row0, left, GF_NG);
+        rv[i] = __builtin_amdgcn_raw_buffer_load_b128(g, vg[i], 0, 0);
+        ru[i] = __builtin_amdgcn_raw_buffer_load_b128(g, vg[i] + 192 * 4, 0, 0);
+        rds[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srd(ds, row0, left, 1), vd[i], 0, 0));
+    }
+    __device__ __forceinline__ f32x4 xval(int i) const { return __builtin_bit_cast(f32x4, rx[i]); }
+    __device__ __forceinline__ f32x4 V(int i) const { return __builtin_bit_cast(f32x4, rv[i]); }
+    __device__ __forceinline__ f32x4 U(int i) const { return __builtin_bit_cast(f32x4, ru[i]); }
+};
+
+__device__ __forceinline__ void dw_zero(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+}
+
+// The 16 k-steps of one 32-row slice on v_mfma_f32_32x32x2_f32, with the staging of the slices behind it in their shadow.
+// Issue order inside a k-step.  The two waves of a SIMD (w and w + 4) share its matrix pipe and the older one wins every
+// arbitration: measured with in-kernel cycle stamps (docs/lab_notes.md), waves 0-3 spent 29 % of the loop parked at the
+// slice barrier while waves 4-7, starved until then, finished the slice ALONE.  A wave on its own only keeps the pipe
+// busy if its non-matrix instructions sit in the shadow of its own MFMAs, so the k-step is laid out as
+//     MFMA . fragment reads . MFMA . staging part a . MFMA . staging part b . MFMA
+// (one v_mfma_f32_32x32x2_f32 occupies the pipe for 64 cycles; a part is a handful of VALU / one LDS write / one or
+// two global loads), each boundary pinned with sched_barrier: hipcc otherwise gathers the staging in front of a
+// block of four MFMAs, behind which the wave sits blocked for 3 x 64 cycles with nothing else to issue.
+// Timetable: part a writes the LDS image of slice sl + 1 from the registers (x chunk ks - 1 at ks 1..4, dPreV / dPreU of gate
+// row i at ks 5 + 2i / 6 + 2i), part b reloads the registers with slice sl + 2 (x chunk ks - 1 at ks 1..4, gate row i at
+// ks 6 + 2i).  stage(what, i) is the kernel's staging; ap / bp: the lane's operand words of k-step 0, the second 32-wide
+// block STRIDE words on (32: blocks in order, 64: blocks stored {0, 2, 1, 3}, one ds_read2st64_b32 per operand).
+enum DwStage { DW_XWRITE, DW_XLOAD, DW_AWRITE_V, DW_AWRITE_U, DW_ALOAD };
+template <int STRIDE, class Stage>
+__device__ __forceinline__ void dw_slice_f32(const float* ap, const float* bp, f32x16 (&acc)[2][2], Stage&& stage) {
+    float fa[2][2], fb[2][2];
+    fa[0][0] = ap[0]; fa[0][1] = ap[STRIDE]; fb[0][0] = bp[0]; fb[0][1] = bp[STRIDE];
+#pragma unroll
+    for (int ks = 0; ks < GB_BKR / 2; ++ks) {
+        const int q = ks & 1;
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][0], fb[q][0], acc[0][0], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks + 1 < GB_BKR / 2) {
+            fa[q ^ 1][0] = ap[(ks + 1) * 256]; fa[q ^ 1][1] = ap[(ks + 1) * 256 + STRIDE];
+            fb[q ^ 1][0] = bp[(ks + 1) * 256]; fb[q ^ 1][1] = bp[(ks + 1) * 256 + STRIDE];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][0], fb[q][1], acc[0][1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks >= 1 && ks <= 4) stage(DW_XWRITE, ks - 1);
+        if (ks == 5 || ks == 7) stage(DW_AWRITE_V, (ks - 5) >> 1);
+        if (ks == 6 || ks == 8) stage(DW_AWRITE_U, (ks - 6) >> 1);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][1], fb[q][0], acc[1][0], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks >= 1 && ks <= 4) stage(DW_XLOAD, ks - 1);
+        if (ks == 6 || ks == 8) stage(DW_ALOAD, (ks - 6) >> 1);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][1], fb[q][1], acc[1][1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// Epilogue, first half: partial tile -> part[s][128m + 64wi + row][j0 + 64wj + col].  The accumulators hold a column per lane
+// (16 rows each); going through LDS turns 64 four-byte stores per lane into sixteen-byte ones: every wave writes its 64 x 64
+// tile row-major into its own 16 KB of its group's (now dead) staging area (stride 64 is conflict-free both ways).
+// KG = 2: both K groups do that, then the two waves that own the same tile (one per group) each fold and store HALF of its
+// rows - one LDS round trip and all eight waves storing, instead of fold -> transpose -> store by four.
+// KG = 1: no barrier, the same wave writes and reads (ordered by lgkmcnt).
+// LANE_FIRST: two spellings of the same 64 store addresses, each kernel keeping the code it had.  With the lane's part
+// (row 4h, column r) in the base pointer the stores are one base + immediates, paired into ds_write2 at KG = 2
+// (k_gate_bwd_dw); with it in the index the dw2 kernels get their 64 single stores and 16 v_or.
+template <int KG, bool LANE_FIRST>
+__device__ __forceinline__ void dw_store_tile(float* smem_all, const f32x16 (&acc)[2][2], float* __restrict__ part, const DwCoord c,
+                                              int L, int grp, int wave, int lane) {
+    const int wi = wave >> 1, wj = wave & 1, r = lane & 31, h = lane >> 5;
+    float* tw = smem_all + grp * DW_GRP_FLOATS + wave * (64 * 64) + (LANE_FIRST ? mfma32_row(0, h) * 64 + r : 0);
+    const int hi = LANE_FIRST ? 0 : h, ri = LANE_FIRST ? 0 : r;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) tw[(32 * a + mfma32_row(i, hi)) * 64 + 32 * b + ri] = acc[a][b][i];
+    if (KG == 2) __syncthreads();
+    float* pt = part + ((size_t)c.s * GF_NG + 128 * c.m + 64 * wi) * L + c.j0 + 64 * wj;
+    const int c4 = lane & 15, rr = lane >> 4;         // 16 float4 columns x 4 rows per pass
+    const float* t0 = smem_all + wave * (64 * 64);
+    const float* t1 = smem_all + DW_GRP_FLOATS + wave * (64 * 64);
+    constexpr int NP = 16 / KG;
+#pragma unroll
+    for (int pass = 0; pass < NP; ++pass) {
+        const int row = 4 * (pass + NP * grp) + rr;
+        f32x4 v = *reinterpret_cast<const f32x4*>(t0 + row * 64 + 4 * c4);
+        if (KG == 2) v += *reinterpret_cast<const f32x4*>(t1 + row * 64 + 4 * c4);
+        *reinterpret_cast<f32x4*>(pt + (size_t)row * L + 4 * c4) = v;
+    }
+}
+// Epilogue, second half: the workgroup's bias / w / b sums -> pb[4][192] (block m's 64 columns of dbv, dbu, dw; db from the
+// m == 0 workgroup), folded over the 16 KG row groups of the dPre staging map.  arow_all (0 .. 16 KG - 1), ad4: the thread's
+// row group and float4 column in that map.
+template <int KG>
+__device__ __forceinline__ void dw_publish_sums(float* smem_all, float* __restrict__ pb, int m, int arow_all, int ad4,
+                                                const DwSums sums) {
+    float* redf = smem_all;   // [16 KG row groups][3][64]
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        redf[(arow_all * 3 + 0) * 64 + 4 * ad4 + e] = sums.bv[e];
+        redf[(arow_all * 3 + 1) * 64 + 4 * ad4 + e] = sums.bu[e];
+        redf[(arow_all * 3 + 2) * 64 + 4 * ad4 + e] = sums.w[e];
+    }
+    __syncthreads();
+    if (threadIdx.x < 192) {
+        const int which = threadIdx.x / 64, d = threadIdx.x % 64;
+        float v = 0.f;
+#pragma unroll
+        for (int g = 0; g < 16 * KG; ++g) v += redf[(g * 3 + which) * 64 + d];
+        pb[which * 192 + 64 * m + d] = v;
+    }
+    if (m == 0) {
+        __syncthreads();
+        redf[threadIdx.x] = sums.ds;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float v = 0.f;
+            for (int g = 0; g < 256 * KG; g += 16) v += redf[g];
+            pb[3 * 192] = v;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- k_gate_bwd_dw: clamped loaders, bf16 or fp32 x, KG = 1 or 2
 // XB16: x is stored as bf16 and widened to fp32 while it is staged (config-5 path; the product stays fp32 MFMA).
 // KG: K groups per workgroup.  KG = 2 (tall inputs): 512 threads, the two halves of the workgroup run the same pipeline
 // on the two halves of the row chunk (own LDS stages, common barriers) and fold their accumulators through LDS before the
 // store, so a launch needs half as many row chunks for the same number of resident waves - half the partial tiles to
 // write here and to read in k_gate_bwd_reduce.
+// Only the j-tile-0 workgroups publish the bias / w / b sums: pbias[s][4][192].
 template <bool XB16, int KG, bool DROP>
 __global__ __launch_bounds__(256 * KG) void k_gate_bwd_dw(const void* __restrict__ xv, const float* __restrict__ gates,
                                                      const float* __restrict__ ds, const float* __restrict__ wvec,
                                                      float* __restrict__ part, float* __restrict__ pbias, int R, int L,
                                                      int KC, int NJ, const uint32_t* __restrict__ xbits,
                                                      const int32_t* __restrict__ rows_dev) {
-    __shared__ __attribute__((aligned(16))) float smem_all[KG * 2 * 2 * GB_BKR * 128];
-    if (rows_dev != nullptr) R = min(R, rows_dev[0]);      // bucketed batches: the true row count lives on the device
+    __shared__ __attribute__((aligned(16))) float smem_all[KG * DW_GRP_FLOATS];
+    R = dw_true_rows(R, rows_dev);
     const int grp = KG == 1 ? 0 : (int)(threadIdx.x >> 8);
-    float* smem = smem_all + grp * (2 * 2 * GB_BKR * 128);      // this K group's stages
+    float* smem = smem_all + grp * DW_GRP_FLOATS;      // this K group's stages
     float* ab = smem;                         // [2][32][128] dPre
     float* xb = smem + 2 * GB_BKR * 128;      // [2][32][128] x
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1;
     const int r = lane & 31, h = lane >> 5;
-    // XCD-aware order: hardware deals workgroup ids round-robin over the 8 XCDs (id % 8 shares an L2).
-    // The 3*NJ workgroups of one row chunk re-read the same x / gate rows, so give them consecutive
-    // slots of ONE XCD: logical = (id % 8) * ceil-share + id / 8 (bijective form for any grid size).
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
-    }
-    const int jt = bid % NJ, m = (bid / NJ) % 3, s = bid / (3 * NJ);
-    const int j0 = jt * 128;
-    // row chunk of the workgroup, then this K group's part of it (whole slices to group 0 first); the slice loop runs
-    // nloop times for everybody (common barriers): iterations past a group's own slices multiply dead copies (ds = 0)
-    const int cbeg = min(s * KC, R), cend = min(R, cbeg + KC);
-    const int half = KG == 1 ? cend - cbeg : ((cend - cbeg + 2 * GB_BKR - 1) / (2 * GB_BKR)) * GB_BKR;
-    const int rbeg = min(cend, cbeg + grp * half), rend = KG == 1 ? cend : min(cend, rbeg + half);
-    const int nslice = (rend - rbeg + GB_BKR - 1) / GB_BKR;
-    const int nloop = (min(half, cend - cbeg) + GB_BKR - 1) / GB_BKR;
+    const DwCoord c = dw_coord(NJ);
+    // iterations past a group's own slices multiply dead copies (ds = 0)
+    const DwRows rw = dw_rows<KG>(c.s, KC, R, grp);
+    const int rbeg = rw.rbeg, rend = rw.rend, nslice = rw.nslice;
 
     const float* x = static_cast<const float*>(xv);
     const unsigned short* xh = static_cast<const unsigned short*>(xv);
@@ -64,12 +304,11 @@ __global__ __launch_bounds__(256 * KG) void k_gate_bwd_dw(const void* __restrict
     const int hrow = tid >> 4, hc8 = tid & 15;    // bf16 x: rows hrow + 16i (i < 2), 16-byte chunk (8 columns) hc8
     gb_u16x8 rh[2];
     const int arow = tid >> 4, ad4 = tid & 15;    // gates: rows arow + 16i (i < 2), d = 64m + 4*ad4
-    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wvec + 64 * m + 4 * ad4);
+    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wvec + 64 * c.m + 4 * ad4);
     f32x4 rx[4], rv[2], ru[2];
-    unsigned rm[4] = {0, 0, 0, 0};   // train mode: keep bits of the staged x chunks (the forward's mask, csrc/dropout.hip)
+    unsigned rm[4] = {0, 0, 0, 0};   // train mode: keep bits of the staged x chunks
     float rds[2], rmask[2];      // raw ds value and its validity mask (applied at use, never at load)
-    f32x4 acc_bv = {0, 0, 0, 0}, acc_bu = {0, 0, 0, 0}, acc_w = {0, 0, 0, 0};
-    float acc_ds = 0.f;
+    DwSums sums;
 
     // Branch-free staging pieces (rows past the chunk end are clamped to its last row and get ds = 0, so they
     // add nothing): the loop body is one basic block and every piece sits between two MFMA groups.
@@ -78,17 +317,17 @@ __global__ __launch_bounds__(256 * KG) void k_gate_bwd_dw(const void* __restrict
         if (XB16) {
             if (i < 2) {
                 const int gr = max(min(rs + hrow + 16 * i, rend - 1), 0);
-                rh[i] = *reinterpret_cast<const gb_u16x8*>(xh + (size_t)gr * L + j0 + 8 * hc8);
-                if (DROP) rm[i] = xbits[(size_t)gr * LW + ((j0 + 8 * hc8) >> 5)];
+                rh[i] = *reinterpret_cast<const gb_u16x8*>(xh + (size_t)gr * L + c.j0 + 8 * hc8);
+                if (DROP) rm[i] = xbits[(size_t)gr * LW + ((c.j0 + 8 * hc8) >> 5)];
             }
         } else {
             const int gr = max(min(rs + xrow + 8 * i, rend - 1), 0);
-            rx[i] = *reinterpret_cast<const f32x4*>(x + (size_t)gr * L + j0 + 4 * xc4);
-            if (DROP) rm[i] = xbits[(size_t)gr * LW + ((j0 + 4 * xc4) >> 5)];
+            rx[i] = *reinterpret_cast<const f32x4*>(x + (size_t)gr * L + c.j0 + 4 * xc4);
+            if (DROP) rm[i] = xbits[(size_t)gr * LW + ((c.j0 + 4 * xc4) >> 5)];
         }
     };
     auto xwrite = [&](int i, int buf) {
-        if (XB16) {
+        if (XB16) {                               // eight columns per chunk: the 8-wide form of dw_keep4
             if (i < 2) {
                 float* dst = xb + (buf * GB_BKR + hrow + 16 * i) * 128 + 8 * hc8;
                 f32x4 lo, hi;
@@ -106,56 +345,35 @@ __global__ __launch_bounds__(256 * KG) void k_gate_bwd_dw(const void* __restrict
                 *reinterpret_cast<f32x4*>(dst + 4) = hi;
             }
         } else {
-            f32x4 v = rx[i];
-            if (DROP) {
-                const unsigned mm = rm[i] >> (4 * (xc4 & 7));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = keep_if(v[e], mm, e);
-            }
-            *reinterpret_cast<f32x4*>(xb + (buf * GB_BKR + xrow + 8 * i) * 128 + 4 * xc4) = v;
+            *reinterpret_cast<f32x4*>(xb + (buf * GB_BKR + xrow + 8 * i) * 128 + 4 * xc4) = DROP ? dw_keep4(rx[i], rm[i], xc4) : rx[i];
         }
     };
     auto aload = [&](int i, int rs, bool live) {
         const int gr = rs + arow + 16 * i;
         const int gc = max(min(gr, rend - 1), 0);
-        const float* gp = gates + (size_t)gc * GF_NG + 64 * m + 4 * ad4;
+        const float* gp = gates + (size_t)gc * GF_NG + 64 * c.m + 4 * ad4;
         rv[i] = *reinterpret_cast<const f32x4*>(gp);
         ru[i] = *reinterpret_cast<const f32x4*>(gp + 192);
         rds[i] = ds[gc];                                  // unconditional load: keeps the body branch-free
         rmask[i] = (live && gr < rend) ? 1.f : 0.f;
     };
-    // dPreV = ds w U (1 - V^2) = a - (a V) V and dPreU = ds w V U (1 - U) = t - t U with a = ds w U, t = a V: four VALU
-    // per (V, U) pair instead of seven.  (The bias / w / b sums stay unconditional: a wave-uniform `jt == 0` branch around
-    // them splits the k-step into basic blocks and costs more than the six VALU it saves.)
+    // (The bias / w / b sums stay unconditional: a wave-uniform `jt == 0` branch around them splits the k-step into basic
+    // blocks and costs more than the six VALU it saves.)
     f32x4 rt[2];
     auto awrite_v = [&](int i, int buf) {
-        const f32x4 v = rv[i];
-        const f32x4 a = ((rds[i] * rmask[i]) * w4) * ru[i];
-        const f32x4 t = a * v;
-        const f32x4 pv = a - t * v;
-        rt[i] = t;
+        const f32x4 pv = DwPre::v((rds[i] * rmask[i]) * w4, rv[i], ru[i], rt[i]);
         *reinterpret_cast<f32x4*>(ab + (buf * GB_BKR + arow + 16 * i) * 128 + 4 * ad4) = pv;
-        acc_bv += pv;
+        sums.add_v(pv);
     };
     auto awrite_u = [&](int i, int buf) {
-        const f32x4 t = rt[i], u = ru[i];
-        const f32x4 pu = t - t * u;
+        const f32x4 pu = DwPre::u(rt[i], ru[i]);
         *reinterpret_cast<f32x4*>(ab + (buf * GB_BKR + arow + 16 * i) * 128 + 64 + 4 * ad4) = pu;
-        const float dsv = rds[i] * rmask[i];
-        acc_bu += pu;
-        acc_w += (dsv * rv[i]) * u;
-        if (ad4 == 0) acc_ds += dsv;
+        sums.add_u(pu, rds[i] * rmask[i], rv[i], ru[i], ad4);
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-
-    {
+    dw_zero(acc);
+    {   // prologue: slice 0 -> LDS buffer 0, slice 1 -> registers
 #pragma unroll
         for (int i = 0; i < 4; ++i) xload(i, rbeg);
 #pragma unroll
@@ -171,187 +389,25 @@ __global__ __launch_bounds__(256 * KG) void k_gate_bwd_dw(const void* __restrict
         for (int i = 0; i < 2; ++i) aload(i, rs1, nslice > 1);   // a single-slice chunk must not count slice 0 twice
     }
     __syncthreads();
-    // Issue order inside a k-step.  The two waves of a SIMD (w and w + 4) share its matrix pipe and the older one wins every
-    // arbitration: measured with in-kernel cycle stamps (docs/lab_notes.md), waves 0-3 spent 29 % of the loop parked at the
-    // slice barrier while waves 4-7, starved until then, finished the slice ALONE.  A wave on its own only keeps the pipe
-    // busy if its non-matrix instructions sit in the shadow of its own MFMAs, so the k-step is laid out as
-    //     MFMA . fragment reads . MFMA . staging part a . MFMA . staging part b . MFMA . staging part c
-    // (one v_mfma_f32_32x32x2_f32 occupies the pipe for 64 cycles; a part is a handful of VALU / one LDS write / one or
-    // two global loads), each boundary pinned with sched_barrier: hipcc otherwise gathers the staging in front of a
-    // block of four MFMAs, behind which the wave sits blocked for 3 x 64 cycles with nothing else to issue.
-    auto slice_body = [&](int sl) {
+    for (int sl = 0; sl < rw.nloop; ++sl) {
         const int buf = sl & 1;
         // registers hold slice sl+1 (or, past this group's last slice, a dead copy with ds forced to 0)
         const bool live2 = sl + 2 < nslice;
         const int rs2 = rbeg + max(min(sl + 2, nslice - 1), 0) * GB_BKR;
-        const float* ap = ab + buf * GB_BKR * 128 + h * 128 + 64 * wi + r;
-        const float* bp = xb + buf * GB_BKR * 128 + h * 128 + 64 * wj + r;
-        float fa[2][2], fb[2][2];
-        fa[0][0] = ap[0]; fa[0][1] = ap[32]; fb[0][0] = bp[0]; fb[0][1] = bp[32];
-        // staging parts of k-step ks (p = 0, 1, 2): LDS image of slice sl+1 from the registers, registers reloaded with sl+2
-        auto part = [&](int ks, int p) {
-            if (ks >= 1 && ks <= 4) {
-                if (p == 0) xwrite(ks - 1, buf ^ 1);
-                if (p == 1) xload(ks - 1, rs2);
-            }
-            if (ks == 5 && p == 0) awrite_v(0, buf ^ 1);
-            if (ks == 6 && p == 0) awrite_u(0, buf ^ 1);
-            if (ks == 6 && p == 1) aload(0, rs2, live2);
-            if (ks == 7 && p == 0) awrite_v(1, buf ^ 1);
-            if (ks == 8 && p == 0) awrite_u(1, buf ^ 1);
-            if (ks == 8 && p == 1) aload(1, rs2, live2);
-        };
-#pragma unroll
-        for (int ks = 0; ks < GB_BKR / 2; ++ks) {
-            const int q = ks & 1;
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][0], fb[q][0], acc[0][0], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + 1 < GB_BKR / 2) {
-                fa[q ^ 1][0] = ap[(ks + 1) * 256]; fa[q ^ 1][1] = ap[(ks + 1) * 256 + 32];
-                fb[q ^ 1][0] = bp[(ks + 1) * 256]; fb[q ^ 1][1] = bp[(ks + 1) * 256 + 32];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][0], fb[q][1], acc[0][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            part(ks, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][1], fb[q][0], acc[1][0], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            part(ks, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][1], fb[q][1], acc[1][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            part(ks, 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    for (int sl = 0; sl < nloop; ++sl) {
-        slice_body(sl);
+        dw_slice_f32<32>(ab + buf * GB_BKR * 128 + h * 128 + 64 * wi + r, xb + buf * GB_BKR * 128 + h * 128 + 64 * wj + r, acc,
+                         [&](DwStage what, int i) {
+                             if (what == DW_XWRITE) xwrite(i, buf ^ 1);
+                             if (what == DW_XLOAD) xload(i, rs2);
+                             if (what == DW_AWRITE_V) awrite_v(i, buf ^ 1);
+                             if (what == DW_AWRITE_U) awrite_u(i, buf ^ 1);
+                             if (what == DW_ALOAD) aload(i, rs2, live2);
+                         });
         __syncthreads();
     }
 
-    // partial tile -> part[s][128m + 64wi + row][j0 + 64wj + col].  The accumulators hold a column per lane (16 rows
-    // each); going through LDS turns 64 four-byte stores per lane into sixteen-byte ones: every wave writes its 64 x 64
-    // tile row-major into its own 16 KB of its group's (now dead) staging area (stride 64 is conflict-free both ways).
-    // KG = 2: both K groups do that, then the two waves that own the same tile (one per group) each fold and store HALF
-    // of its rows - one LDS round trip and all eight waves storing, instead of fold -> transpose -> store by four.
-    {
-        __syncthreads();                                  // the staging buffers are dead from here on
-        float* tw = smem + wave * (64 * 64);
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) tw[(32 * a + mfma32_row(i, h)) * 64 + 32 * b + r] = acc[a][b][i];
-        if (KG == 2) __syncthreads();                     // KG = 1: same-wave write -> read, ordered by lgkmcnt
-        float* pt = part + ((size_t)s * GF_NG + 128 * m + 64 * wi) * L + j0 + 64 * wj;
-        const int c4 = lane & 15, rr = lane >> 4;         // 16 float4 columns x 4 rows per pass
-        const float* t0 = smem_all + wave * (64 * 64);
-        const float* t1 = smem_all + (2 * 2 * GB_BKR * 128) + wave * (64 * 64);
-        constexpr int NP = 16 / KG;
-#pragma unroll
-        for (int pass = 0; pass < NP; ++pass) {
-            const int row = 4 * (pass + NP * grp) + rr;
-            f32x4 v = *reinterpret_cast<const f32x4*>(t0 + row * 64 + 4 * c4);
-            if (KG == 2) v += *reinterpret_cast<const f32x4*>(t1 + row * 64 + 4 * c4);
-            *reinterpret_cast<f32x4*>(pt + (size_t)row * L + 4 * c4) = v;
-        }
-    }
-
-    // bias / w partials (only the j-tile-0 workgroups publish them); both K groups contribute their row groups
-    if (jt == 0) {
-        float* redf = smem_all;   // [16 KG row groups][3][64]
-        const int arow_all = arow + 16 * grp;
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            redf[(arow_all * 3 + 0) * 64 + 4 * ad4 + e] = acc_bv[e];
-            redf[(arow_all * 3 + 1) * 64 + 4 * ad4 + e] = acc_bu[e];
-            redf[(arow_all * 3 + 2) * 64 + 4 * ad4 + e] = acc_w[e];
-        }
-        __syncthreads();
-        if (grp == 0 && tid < 192) {
-            const int which = tid / 64, d = tid % 64;
-            float v = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16 * KG; ++g) v += redf[(g * 3 + which) * 64 + d];
-            pbias[((size_t)s * 4 + which) * 192 + 64 * m + d] = v;
-        }
-        if (m == 0) {
-            __syncthreads();
-            redf[threadIdx.x] = acc_ds;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                float v = 0.f;
-                for (int g = 0; g < 256 * KG; g += 16) v += redf[g];
-                pbias[((size_t)s * 4 + 3) * 192] = v;
-            }
-        }
-    }
-}
-
-
-// The epilogue shared by k_gate_bwd_dw2 and k_gate_bwd_dw2_pieces (512 threads: two K groups x four waves, wave (wi, wj) of
-// either group holding a partial 64 x 64 tile of the same output; smem_all = the 128 KiB staging area, dead by now).
-// partial tile -> part[s][128m + 64wi + row][j0 + 64wj + col]: every wave writes its 64 x 64 tile row-major into its own
-// 16 KB of its group's half; the two waves that own the same tile (one per K group) each fold and store half of its rows
-// with 16-byte stores.
-__device__ __forceinline__ void dw2_store_tile(float* smem_all, const f32x16 (&acc)[2][2], float* __restrict__ part, int s, int m,
-                                               int L, int j0, int grp, int wave, int lane) {
-    const int wi = wave >> 1, wj = wave & 1, r = lane & 31, h = lane >> 5;
-    float* tw = smem_all + grp * (2 * 2 * GB_BKR * 128) + wave * (64 * 64);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) tw[(32 * a + mfma32_row(i, h)) * 64 + 32 * b + r] = acc[a][b][i];
-    __syncthreads();
-    float* pt = part + ((size_t)s * GF_NG + 128 * m + 64 * wi) * L + j0 + 64 * wj;
-    const int c4 = lane & 15, rr = lane >> 4;
-    const float* t0 = smem_all + wave * (64 * 64);
-    const float* t1 = smem_all + (2 * 2 * GB_BKR * 128) + wave * (64 * 64);
-#pragma unroll
-    for (int pass = 0; pass < 8; ++pass) {
-        const int row = 4 * (pass + 8 * grp) + rr;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(t0 + row * 64 + 4 * c4) +
-                        *reinterpret_cast<const f32x4*>(t1 + row * 64 + 4 * c4);
-        *reinterpret_cast<f32x4*>(pt + (size_t)row * L + 4 * c4) = v;
-    }
-}
-// bias / w / b partials: every (s, jt) workgroup publishes the sums of its share of the slices -> pbias[s][jt][4][192].
-// arow_all (0..31), ad4: the thread's row group and float4 column of the dPre staging map.
-__device__ __forceinline__ void dw2_publish_sums(float* smem_all, float* __restrict__ pbias, int s, int NJ, int jt, int m,
-                                                 int arow_all, int ad4, const f32x4 acc_bv, const f32x4 acc_bu,
-                                                 const f32x4 acc_w, float acc_ds) {
-    float* redf = smem_all;   // [32 row groups][3][64]
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        redf[(arow_all * 3 + 0) * 64 + 4 * ad4 + e] = acc_bv[e];
-        redf[(arow_all * 3 + 1) * 64 + 4 * ad4 + e] = acc_bu[e];
-        redf[(arow_all * 3 + 2) * 64 + 4 * ad4 + e] = acc_w[e];
-    }
-    __syncthreads();
-    float* pb = pbias + ((size_t)s * NJ + jt) * 4 * 192;
-    if (threadIdx.x < 192) {
-        const int which = threadIdx.x / 64, d = threadIdx.x % 64;
-        float v = 0.f;
-#pragma unroll
-        for (int g = 0; g < 32; ++g) v += redf[(g * 3 + which) * 64 + d];
-        pb[which * 192 + 64 * m + d] = v;
-    }
-    if (m == 0) {
-        __syncthreads();
-        redf[threadIdx.x] = acc_ds;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float v = 0.f;
-            for (int g = 0; g < 512; g += 16) v += redf[g];
-            pb[3 * 192] = v;
-        }
-    }
+    __syncthreads();                                  // the staging buffers are dead from here on
+    dw_store_tile<KG, true>(smem_all, acc, part, c, L, grp, wave, lane);
+    if (c.jt == 0) dw_publish_sums<KG>(smem_all, pbias + (size_t)c.s * 4 * 192, c.m, arow + 16 * grp, ad4, sums);
 }
 
 // ================================================================================ K1 backward: gate dW, "VALU diet" form
@@ -362,14 +418,13 @@ __device__ __forceinline__ void dw2_publish_sums(float* smem_all, float* __restr
 // MFMA: 64 -> 84 cycles; LDS reads, scalar ALU and s_nop fillers are free).  The first kernel spent ~230 VALU
 // instructions per wave and 32-row slice (64 MFMAs) on 64-bit address arithmetic, row clamps, LDS addresses, masks:
 // 27 % of the loop.  Here
-//   * global operands come through buffer resources whose base / size live in SGPRs and advance by scalar ALU: the
-//     per-lane offset is a loop invariant, rows beyond the K group's end read as ZERO by the hardware range check (no
-//     clamps, no validity masks - a zero ds row contributes nothing);
+//   * global operands come through buffer resources (DwSrdSource): no clamps, no validity masks, no address VALU;
 //   * both LDS images store their four 32-column blocks in the order {0, 2, 1, 3}, so the two operand values a lane
 //     needs per k-step are 64 dwords apart and ONE ds_read2st64_b32 with immediate offsets fetches them (no address
 //     VALU; the buffer index is a compile-time constant: the slice loop is unrolled by two);
 //   * the bias / w / b sums are spread over the NJ column-tile workgroups of a row chunk (slice sl is summed by the
-//     workgroup with jt == sl % NJ, scalar branch) instead of being summed by all of them and published by one.
+//     workgroup with jt == sl % NJ, scalar branch) instead of being summed by all of them and published by one: every
+//     (s, jt) workgroup publishes into pbias[s][jt][4][192].
 // What is left is the arithmetic itself: dPre (20 VALU per (V, U) float4 pair) and, in train mode, the keep mask of x.
 
 template <bool DROP>
@@ -378,43 +433,22 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2(const float* __restrict__ 
                                                       float* __restrict__ part, float* __restrict__ pbias, int R, int L,
                                                       int KC, int NJ, const uint32_t* __restrict__ xbits,
                                                       const int32_t* __restrict__ rows_dev) {
-    __shared__ __attribute__((aligned(16))) float smem_all[2 * 2 * 2 * GB_BKR * 128];
-    if (rows_dev != nullptr) R = min(R, __builtin_amdgcn_readfirstlane(rows_dev[0]));      // bucketed batches: true row count on the device
+    __shared__ __attribute__((aligned(16))) float smem_all[2 * DW_GRP_FLOATS];
+    R = dw_true_rows(R, rows_dev);
     const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-    float* smem = smem_all + grp * (2 * 2 * GB_BKR * 128);      // this K group's stages: [2][32][128] dPre, [2][32][128] x
+    float* smem = smem_all + grp * DW_GRP_FLOATS;      // this K group's stages: [2][32][128] dPre, [2][32][128] x
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1;
     const int r = lane & 31, h = lane >> 5;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
-    }
-    const int jt = bid % NJ, m = (bid / NJ) % 3, s = bid / (3 * NJ);
-    const int j0 = jt * 128;
-    const int cbeg = min(s * KC, R), cend = min(R, cbeg + KC);
-    const int half = ((cend - cbeg + 2 * GB_BKR - 1) / (2 * GB_BKR)) * GB_BKR;
-    const int rbeg = min(cend, cbeg + grp * half), rend = min(cend, rbeg + half);
-    const int nloop = (min(half, cend - cbeg) + GB_BKR - 1) / GB_BKR;      // common to both groups (shared barriers)
+    const DwCoord c = dw_coord(NJ);
+    const DwRows rw = dw_rows<2>(c.s, KC, R, grp);
+    const int rbeg = rw.rbeg;
 
-    // per-lane byte offsets inside a slice (loop invariants)
-    const int xrow = tid >> 5, xc4 = tid & 31;    // x: rows xrow + 8i (i < 4), 16-byte chunk xc4 of the 128-column tile
-    const int arow = tid >> 4, ad4 = tid & 15;    // gates: rows arow + 16i (i < 2), d = 64m + 4 ad4
-    const int LW = L >> 5;
-    int vx[4], vm[4], vg[2], vd[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        vx[i] = ((xrow + 8 * i) * L + j0 + 4 * xc4) * 4;
-        vm[i] = ((xrow + 8 * i) * LW + ((j0 + 4 * xc4) >> 5)) * 4;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        vg[i] = ((arow + 16 * i) * GF_NG + 64 * m + 4 * ad4) * 4;
-        vd[i] = (arow + 16 * i) * 4;
-    }
-    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wvec + 64 * m + 4 * ad4);
+    DwSrdSource<DROP, 4, 2> src(x, gates, ds, xbits, L, rw.rend, tid, c);
+    const int xrow = tid >> 5, xc4 = tid & 31, arow = tid >> 4, ad4 = tid & 15;      // the source's staging map
+    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wvec + 64 * c.m + 4 * ad4);
     // LDS positions: 32-column blocks stored in the order {0, 2, 1, 3}
-    auto blkpos = [](int c) { return (c & 31) | ((c & 32) << 1) | ((c & 64) >> 1); };
+    auto blkpos = [](int col) { return (col & 31) | ((col & 32) << 1) | ((col & 64) >> 1); };
     float* const ab = smem;                       // [2][32][128]
     float* const xb = smem + 2 * GB_BKR * 128;    // [2][32][128]
     float* const xw = xb + xrow * 128 + blkpos(4 * xc4);              // + (buf * 32 + 8 i) * 128
@@ -422,141 +456,64 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2(const float* __restrict__ 
     const float* const ap = ab + h * 128 + 32 * wi + r;               // + buf * 4096 + ks * 256 (+ 64)
     const float* const bp = xb + h * 128 + 32 * wj + r;
 
-    u32x4_t rx[4], rv[2], ru[2];
-    unsigned rm[4] = {0, 0, 0, 0};
-    float rds[2];
     f32x4 rt[2];
-    f32x4 acc_bv = {0, 0, 0, 0}, acc_bu = {0, 0, 0, 0}, acc_w = {0, 0, 0, 0};
-    float acc_ds = 0.f;
-
-    // scalar: resources of slice `row0`.  Rows >= rend are out of range -> the loads return zeros.
-    auto x_srd = [&](int row0) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)row0 * L), 0, max(rend - row0, 0) * L * 4, MIL_SRD_FLAGS);
-    };
-    auto g_srd = [&](int row0) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(gates + (size_t)row0 * GF_NG), 0, max(rend - row0, 0) * GF_NG * 4,
-                                                 MIL_SRD_FLAGS);
-    };
-    auto d_srd = [&](int row0) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(ds + row0), 0, max(rend - row0, 0) * 4, MIL_SRD_FLAGS);
-    };
-    auto m_srd = [&](int row0) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(xbits + (size_t)row0 * LW), 0, max(rend - row0, 0) * LW * 4,
-                                                 MIL_SRD_FLAGS);
-    };
-    auto xload = [&](int i, int row0) {
-        rx[i] = __builtin_amdgcn_raw_buffer_load_b128(x_srd(row0), vx[i], 0, 0);
-        if (DROP) rm[i] = __builtin_amdgcn_raw_buffer_load_b32(m_srd(row0), vm[i], 0, 0);
-    };
-    auto aload = [&](int i, int row0) {
-        const __amdgpu_buffer_rsrc_t g = g_srd(row0);
-        rv[i] = __builtin_amdgcn_raw_buffer_load_b128(g, vg[i], 0, 0);
-        ru[i] = __builtin_amdgcn_raw_buffer_load_b128(g, vg[i] + 192 * 4, 0, 0);
-        rds[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(d_srd(row0), vd[i], 0, 0));
-    };
+    DwSums sums;
     auto xwrite = [&](int i, int buf) {
-        f32x4 v = __builtin_bit_cast(f32x4, rx[i]);
-        if (DROP) {
-            const unsigned mm = rm[i] >> (4 * (xc4 & 7));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = keep_if(v[e], mm, e);
-        }
-        *reinterpret_cast<f32x4*>(xw + (buf * GB_BKR + 8 * i) * 128) = v;
+        *reinterpret_cast<f32x4*>(xw + (buf * GB_BKR + 8 * i) * 128) = DROP ? dw_keep4(src.xval(i), src.rm[i], xc4) : src.xval(i);
     };
-    auto awrite_v = [&](int i, int buf) {           // dPreV = a - (a V) V,  a = ds w U
-        const f32x4 v = __builtin_bit_cast(f32x4, rv[i]);
-        const f32x4 a = (rds[i] * w4) * __builtin_bit_cast(f32x4, ru[i]);
-        const f32x4 t = a * v;
-        rt[i] = t;
-        *reinterpret_cast<f32x4*>(aw + (buf * GB_BKR + 16 * i) * 128) = a - t * v;
+    auto awrite_v = [&](int i, int buf) {
+        *reinterpret_cast<f32x4*>(aw + (buf * GB_BKR + 16 * i) * 128) = DwPre::v(src.rds[i] * w4, src.V(i), src.U(i), rt[i]);
     };
-    auto awrite_u = [&](int i, int buf, bool pub) { // dPreU = t - t U,  t = ds w U V
-        const f32x4 t = rt[i], u = __builtin_bit_cast(f32x4, ru[i]);
-        const f32x4 pu = t - t * u;
+    auto awrite_u = [&](int i, int buf, bool pub) {
+        const f32x4 pu = DwPre::u(rt[i], src.U(i));
         *reinterpret_cast<f32x4*>(aw + (buf * GB_BKR + 16 * i) * 128 + 32) = pu;
-        if (pub) {                                    // scalar branch: this slice's sums belong to this workgroup
-            const f32x4 v = __builtin_bit_cast(f32x4, rv[i]);
-            acc_bv += (rds[i] * w4) * u - t * v;      // = dPreV again (3 VALU per element, only every NJ-th slice)
-            acc_bu += pu;
-            acc_w += (rds[i] * v) * u;
-            if (ad4 == 0) acc_ds += rds[i];
-        }
+        if (pub) sums.add_pub(src.rds[i], w4, src.V(i), src.U(i), rt[i], pu, ad4);      // scalar branch: this slice's sums belong to this workgroup
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-
+    dw_zero(acc);
     // prologue: slice 0 -> LDS buffer 0, slice 1 -> registers
 #pragma unroll
-    for (int i = 0; i < 4; ++i) xload(i, rbeg);
+    for (int i = 0; i < 4; ++i) src.xload(i, rbeg);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) aload(i, rbeg);
+    for (int i = 0; i < 2; ++i) src.aload(i, rbeg);
 #pragma unroll
     for (int i = 0; i < 4; ++i) xwrite(i, 0);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) { awrite_v(i, 0); awrite_u(i, 0, jt == 0); }
+    for (int i = 0; i < 2; ++i) { awrite_v(i, 0); awrite_u(i, 0, c.jt == 0); }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) xload(i, rbeg + GB_BKR);
+    for (int i = 0; i < 4; ++i) src.xload(i, rbeg + GB_BKR);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) aload(i, rbeg + GB_BKR);
+    for (int i = 0; i < 2; ++i) src.aload(i, rbeg + GB_BKR);
     __syncthreads();
 
-    // one slice: 16 k-steps x 4 MFMAs; between the MFMAs the parts that stage slice sl + 1 and reload slice sl + 2
+    // one slice: between its MFMAs the parts that stage slice sl + 1 and reload slice sl + 2
     auto slice = [&](int sl, auto buf_c) {
         constexpr int buf = decltype(buf_c)::value;
         const int row2 = rbeg + (sl + 2) * GB_BKR;
-        const bool pub = ((sl + 1) % NJ) == jt;                     // the slice being written now is sl + 1
-        const float* apb = ap + buf * GB_BKR * 128;
-        const float* bpb = bp + buf * GB_BKR * 128;
-        float fa[2][2], fb[2][2];
-        fa[0][0] = apb[0]; fa[0][1] = apb[64]; fb[0][0] = bpb[0]; fb[0][1] = bpb[64];
-#pragma unroll
-        for (int ks = 0; ks < GB_BKR / 2; ++ks) {
-            const int q = ks & 1;
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][0], fb[q][0], acc[0][0], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + 1 < GB_BKR / 2) {
-                fa[q ^ 1][0] = apb[(ks + 1) * 256]; fa[q ^ 1][1] = apb[(ks + 1) * 256 + 64];
-                fb[q ^ 1][0] = bpb[(ks + 1) * 256]; fb[q ^ 1][1] = bpb[(ks + 1) * 256 + 64];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][0], fb[q][1], acc[0][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks >= 1 && ks <= 4) xwrite(ks - 1, buf ^ 1);
-            if (ks == 5) awrite_v(0, buf ^ 1);
-            if (ks == 6) awrite_u(0, buf ^ 1, pub);
-            if (ks == 7) awrite_v(1, buf ^ 1);
-            if (ks == 8) awrite_u(1, buf ^ 1, pub);
-            __builtin_amdgcn_sched_barrier(0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][1], fb[q][0], acc[1][0], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks >= 1 && ks <= 4) xload(ks - 1, row2);
-            if (ks == 6) aload(0, row2);
-            if (ks == 8) aload(1, row2);
-            __builtin_amdgcn_sched_barrier(0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][1], fb[q][1], acc[1][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        const bool pub = ((sl + 1) % NJ) == c.jt;                   // the slice being written now is sl + 1
+        dw_slice_f32<64>(ap + buf * GB_BKR * 128, bp + buf * GB_BKR * 128, acc, [&](DwStage what, int i) {
+            if (what == DW_XWRITE) xwrite(i, buf ^ 1);
+            if (what == DW_XLOAD) src.xload(i, row2);
+            if (what == DW_AWRITE_V) awrite_v(i, buf ^ 1);
+            if (what == DW_AWRITE_U) awrite_u(i, buf ^ 1, pub);
+            if (what == DW_ALOAD) src.aload(i, row2);
+        });
     };
     int sl = 0;
-    for (; sl + 1 < nloop; sl += 2) {
+    for (; sl + 1 < rw.nloop; sl += 2) {
         slice(sl, std::integral_constant<int, 0>{});
         __syncthreads();
         slice(sl + 1, std::integral_constant<int, 1>{});
         __syncthreads();
     }
-    if (sl < nloop) {
+    if (sl < rw.nloop) {
         slice(sl, std::integral_constant<int, 0>{});
         __syncthreads();
     }
 
-    dw2_store_tile(smem_all, acc, part, s, m, L, j0, grp, wave, lane);
-    dw2_publish_sums(smem_all, pbias, s, NJ, jt, m, arow + 16 * grp, ad4, acc_bv, acc_bu, acc_w, acc_ds);
+    dw_store_tile<2, false>(smem_all, acc, part, c, L, grp, wave, lane);
+    dw_publish_sums<2>(smem_all, pbias + ((size_t)c.s * NJ + c.jt) * 4 * 192, c.m, arow + 16 * grp, ad4, sums);
 }
 
 // ================================================================================ K1 backward: gate dW, split-bf16 K loop
@@ -586,68 +543,30 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
                                                              int KC, int NJ, const uint32_t* __restrict__ xbits,
                                                              const int32_t* __restrict__ rows_dev) {
     // 128 KiB: the two stages take 120 KiB, the epilogue's eight 64 x 64 fp32 tiles all of it
-    __shared__ __attribute__((aligned(16))) float smem_all[2 * 2 * 2 * GB_BKR * 128];
+    __shared__ __attribute__((aligned(16))) float smem_all[2 * DW_GRP_FLOATS];
     static_assert(2 * GQ_BUF * 2 <= (int)sizeof(smem_all), "stages exceed the LDS image");
     unsigned short* const img = reinterpret_cast<unsigned short*>(smem_all);
-    if (rows_dev != nullptr) R = min(R, __builtin_amdgcn_readfirstlane(rows_dev[0]));      // bucketed batches: true row count on the device
+    R = dw_true_rows(R, rows_dev);
     const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));               // which 16 rows of every slice
     const int T = threadIdx.x, tid = T & 255, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1;
     const int h = lane >> 5;
     const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;                  // transpose-read address roles
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
-    }
-    const int jt = bid % NJ, m = (bid / NJ) % 3, s = bid / (3 * NJ);
-    const int j0 = jt * 128;
-    const int rbeg = min(s * KC, R), rend = min(R, rbeg + KC);
-    const int nloop = (rend - rbeg + GB_BKR - 1) / GB_BKR;
+    const DwCoord c = dw_coord(NJ);
+    const DwRows rw = dw_rows<1>(c.s, KC, R, 0);         // one K group in the rows: all eight waves walk the whole chunk
+    const int rbeg = rw.rbeg;
 
-    // per-lane byte offsets inside a slice (loop invariants)
-    const int xrow = T >> 5, xc4 = T & 31;        // x: rows xrow + 16i (i < 2), 16-byte chunk xc4 of the 128-column tile
-    const int arow = T >> 4, ad4 = T & 15;        // gates: row arow, d = 64m + 4 ad4
-    const int LW = L >> 5;
-    int vx[2], vm[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        vx[i] = ((xrow + 16 * i) * L + j0 + 4 * xc4) * 4;
-        vm[i] = ((xrow + 16 * i) * LW + ((j0 + 4 * xc4) >> 5)) * 4;
-    }
-    const int vg = (arow * GF_NG + 64 * m + 4 * ad4) * 4, vd = arow * 4;
-    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wvec + 64 * m + 4 * ad4);
+    DwSrdSource<DROP, 2, 1> src(x, gates, ds, xbits, L, rw.rend, T, c);
+    const int xrow = T >> 5, xc4 = T & 31, arow = T >> 4, ad4 = T & 15;      // the source's staging map (512 threads)
+    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wvec + 64 * c.m + 4 * ad4);
     unsigned short* const xw = img + 3 * GQ_PSZ + xrow * WB_S + 4 * xc4;     // + buf * GQ_BUF + 16 i * WB_S; piece q: + q * GQ_PSZ
     unsigned short* const aw = img + arow * WB_S + 4 * ad4;                  // V columns 0..63; U: + 64
     const int frow = 16 * grp + 8 * h + tq;
     const int acol = 64 * wi + 16 * tg + 4 * tp;                             // + 32 a
     const int bcol = 64 * wj + 16 * tg + 4 * tp;                             // + 32 b
 
-    u32x4_t rx[2], rv, ru;
-    unsigned rm[2] = {0, 0};
-    float rds;
     f32x4 rt;
-    f32x4 acc_bv = {0, 0, 0, 0}, acc_bu = {0, 0, 0, 0}, acc_w = {0, 0, 0, 0};
-    float acc_ds = 0.f;
-
-    // resources of slice `row0`: rows >= rend are out of range -> the loads return zeros
-    auto xload = [&](int i, int row0) {
-        const int left = max(rend - row0, 0);
-        rx[i] = __builtin_amdgcn_raw_buffer_load_b128(
-            __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)row0 * L), 0, left * L * 4, MIL_SRD_FLAGS), vx[i], 0, 0);
-        if (DROP)
-            rm[i] = __builtin_amdgcn_raw_buffer_load_b32(
-                __builtin_amdgcn_make_buffer_rsrc((void*)(xbits + (size_t)row0 * LW), 0, left * LW * 4, MIL_SRD_FLAGS), vm[i], 0, 0);
-    };
-    auto aload = [&](int row0) {
-        const int left = max(rend - row0, 0);
-        const __amdgpu_buffer_rsrc_t g =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(gates + (size_t)row0 * GF_NG), 0, left * GF_NG * 4, MIL_SRD_FLAGS);
-        rv = __builtin_amdgcn_raw_buffer_load_b128(g, vg, 0, 0);
-        ru = __builtin_amdgcn_raw_buffer_load_b128(g, vg + 192 * 4, 0, 0);
-        rds = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-            __builtin_amdgcn_make_buffer_rsrc((void*)(ds + row0), 0, left * 4, MIL_SRD_FLAGS), vd, 0, 0));
-    };
+    DwSums sums;
     auto put3 = [&](unsigned short* dst, const f32x4 v) {          // four columns of one row: one 8-byte store per piece
         ushort4 o[3];
         gp_split3(v[0], o[0].x, o[1].x, o[2].x);
@@ -658,41 +577,17 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
         for (int q = 0; q < 3; ++q) *reinterpret_cast<ushort4*>(dst + q * GQ_PSZ) = o[q];
     };
     auto xwrite = [&](int i, int buf) {
-        f32x4 v = __builtin_bit_cast(f32x4, rx[i]);
-        if (DROP) {
-            const unsigned mm = rm[i] >> (4 * (xc4 & 7));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = keep_if(v[e], mm, e);
-        }
-        put3(xw + buf * GQ_BUF + 16 * i * WB_S, v);
+        put3(xw + buf * GQ_BUF + 16 * i * WB_S, DROP ? dw_keep4(src.xval(i), src.rm[i], xc4) : src.xval(i));
     };
-    auto awrite_v = [&](int buf) {                  // dPreV = a - (a V) V,  a = ds w U
-        const f32x4 v = __builtin_bit_cast(f32x4, rv);
-        const f32x4 a = (rds * w4) * __builtin_bit_cast(f32x4, ru);
-        const f32x4 t = a * v;
-        rt = t;
-        put3(aw + buf * GQ_BUF, a - t * v);
-    };
-    auto awrite_u = [&](int buf, bool pub) {        // dPreU = t - t U,  t = ds w U V
-        const f32x4 t = rt, u = __builtin_bit_cast(f32x4, ru);
-        const f32x4 pu = t - t * u;
+    auto awrite_v = [&](int buf) { put3(aw + buf * GQ_BUF, DwPre::v(src.rds[0] * w4, src.V(0), src.U(0), rt)); };
+    auto awrite_u = [&](int buf, bool pub) {
+        const f32x4 pu = DwPre::u(rt, src.U(0));
         put3(aw + buf * GQ_BUF + 64, pu);
-        if (pub) {                                    // scalar branch: this slice's sums belong to this workgroup
-            const f32x4 v = __builtin_bit_cast(f32x4, rv);
-            acc_bv += (rds * w4) * u - t * v;
-            acc_bu += pu;
-            acc_w += (rds * v) * u;
-            if (ad4 == 0) acc_ds += rds;
-        }
+        if (pub) sums.add_pub(src.rds[0], w4, src.V(0), src.U(0), rt, pu, ad4);      // scalar branch: this slice's sums belong to this workgroup
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+    dw_zero(acc);
 
     gp_u16x8 fa[2][3][2], fb[2][3][2];              // [register set][piece][tile]
     auto frags = [&](auto set_c, int buf) {         // smallest piece first: the small terms are multiplied first
@@ -708,9 +603,9 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
     };
 
     // prologue: slice 0 -> stage 0 -> fragment set 0, slice 1 -> registers
-    xload(0, rbeg); xload(1, rbeg); aload(rbeg);
-    xwrite(0, 0); xwrite(1, 0); awrite_v(0); awrite_u(0, jt == 0);
-    xload(0, rbeg + GB_BKR); xload(1, rbeg + GB_BKR); aload(rbeg + GB_BKR);
+    src.xload(0, rbeg); src.xload(1, rbeg); src.aload(0, rbeg);
+    xwrite(0, 0); xwrite(1, 0); awrite_v(0); awrite_u(0, c.jt == 0);
+    src.xload(0, rbeg + GB_BKR); src.xload(1, rbeg + GB_BKR); src.aload(0, rbeg + GB_BKR);
     __syncthreads();
     frags(std::integral_constant<int, 0>{}, 0);
 
@@ -719,7 +614,7 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
         constexpr int set = decltype(set_c)::value;      // fragment set = stage of slice sl
         constexpr int TP[6] = {0, 1, 2, 0, 1, 0}, TQ[6] = {2, 1, 0, 1, 0, 0};
         const int row2 = rbeg + (sl + 2) * GB_BKR;
-        const bool pub = ((sl + 1) % NJ) == jt;          // the slice being staged now is sl + 1
+        const bool pub = ((sl + 1) % NJ) == c.jt;        // the slice being staged now is sl + 1
         auto mfma = [&](int t, int g) {
             const int a = g >> 1, b = g & 1;
             acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gp_bf16x8, fa[set][TP[t]][a]),
@@ -733,18 +628,18 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
                 __builtin_amdgcn_sched_barrier(0);
                 switch (4 * t + g) {                     // seven staging parts behind the first MFMAs
                     case 0: xwrite(0, set ^ 1); break;
-                    case 1: xload(0, row2); break;
+                    case 1: src.xload(0, row2); break;
                     case 2: xwrite(1, set ^ 1); break;
-                    case 3: xload(1, row2); break;
+                    case 3: src.xload(1, row2); break;
                     case 4: awrite_v(set ^ 1); break;
                     case 5: awrite_u(set ^ 1, pub); break;
-                    case 6: aload(row2); break;
+                    case 6: src.aload(0, row2); break;
                     default: break;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         __syncthreads();                                 // stage set ^ 1 holds slice sl + 1; every wave has read stage `set`
-        if (sl + 1 < nloop) frags(std::integral_constant<int, set ^ 1>{}, set ^ 1);
+        if (sl + 1 < rw.nloop) frags(std::integral_constant<int, set ^ 1>{}, set ^ 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 3; t < 6; ++t)
@@ -752,15 +647,15 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
             for (int g = 0; g < 4; ++g) mfma(t, g);
     };
     int sl = 0;
-    for (; sl + 1 < nloop; sl += 2) {
+    for (; sl + 1 < rw.nloop; sl += 2) {
         slice(sl, std::integral_constant<int, 0>{});
         slice(sl + 1, std::integral_constant<int, 1>{});
     }
-    if (sl < nloop) slice(sl, std::integral_constant<int, 0>{});
+    if (sl < rw.nloop) slice(sl, std::integral_constant<int, 0>{});
     __syncthreads();                                     // the stages are dead from here on
 
-    dw2_store_tile(smem_all, acc, part, s, m, L, j0, grp, wave, lane);
-    dw2_publish_sums(smem_all, pbias, s, NJ, jt, m, arow, ad4, acc_bv, acc_bu, acc_w, acc_ds);
+    dw_store_tile<2, false>(smem_all, acc, part, c, L, grp, wave, lane);
+    dw_publish_sums<2>(smem_all, pbias + ((size_t)c.s * NJ + c.jt) * 4 * 192, c.m, arow, ad4, sums);
 }
 
 // ================================================================================ host side
@@ -782,26 +677,15 @@ GateDwPlan gate_dw_plan(int R, int L, int ncu) {
     return d;
 }
 
-template <bool XB16>
-static void launch_gate_bwd_dw(const void* x, const float* gates, const float* ds, const float* w, float* part, float* pbias,
-                               int R, int L, int kc, int NJ, int S, int kg, const uint32_t* xbits, hipStream_t st,
-                               const int32_t* rows_dev = nullptr) {
-    const dim3 grid(S * 3 * NJ);
-    if (kg == 2) {
-        if (xbits) hipLaunchKernelGGL((k_gate_bwd_dw<XB16, 2, true>), grid, dim3(512), 0, st, x, gates, ds, w, part, pbias, R, L, kc, NJ, xbits, rows_dev);
-        else hipLaunchKernelGGL((k_gate_bwd_dw<XB16, 2, false>), grid, dim3(512), 0, st, x, gates, ds, w, part, pbias, R, L, kc, NJ, xbits, rows_dev);
-    } else {
-        if (xbits) hipLaunchKernelGGL((k_gate_bwd_dw<XB16, 1, true>), grid, dim3(256), 0, st, x, gates, ds, w, part, pbias, R, L, kc, NJ, xbits, rows_dev);
-        else hipLaunchKernelGGL((k_gate_bwd_dw<XB16, 1, false>), grid, dim3(256), 0, st, x, gates, ds, w, part, pbias, R, L, kc, NJ, xbits, rows_dev);
-    }
-}
-
-static inline size_t gate_bwd_ws_floats(int S, int L) { return (size_t)S * GF_NG * L + (size_t)S * (L / 128) * 4 * 192; }
-
-extern "C" size_t mil_gate_bwd_workspace_floats(int R, int L) {
-    if (R <= 0 || L <= 0 || (L % 128) != 0) return 0;
-    return gate_bwd_ws_floats(gate_dw_plan(R, L, MIL_NUM_CU).S, L);
-}
+// Every instantiation, by name: 8 + 2 + 2
+using DwKernel = decltype(&k_gate_bwd_dw<false, 1, false>);
+static const DwKernel DW_KERNELS[2][2][2] = {                                   // [x is bf16][KG - 1][keep bits]
+    {{k_gate_bwd_dw<false, 1, false>, k_gate_bwd_dw<false, 1, true>}, {k_gate_bwd_dw<false, 2, false>, k_gate_bwd_dw<false, 2, true>}},
+    {{k_gate_bwd_dw<true, 1, false>, k_gate_bwd_dw<true, 1, true>}, {k_gate_bwd_dw<true, 2, false>, k_gate_bwd_dw<true, 2, true>}}};
+using Dw2Kernel = decltype(&k_gate_bwd_dw2<false>);
+static const Dw2Kernel DW2_KERNELS[2][2] = {                                    // [split-bf16 K loop][keep bits]
+    {k_gate_bwd_dw2<false>, k_gate_bwd_dw2<true>},
+    {k_gate_bwd_dw2_pieces<false>, k_gate_bwd_dw2_pieces<true>}};
 
 // The K loop of the dw2 route: the split-bf16 kernel (k_gate_bwd_dw2_pieces) unless MIL_DW_PIECES=0 asks for the f32-MFMA
 // one.  Read per call (under a hipGraph: at capture), so A/B runs and tests toggle it inside one process; the route plan,
@@ -811,38 +695,42 @@ static inline bool dw_pieces_on() {
     return e == nullptr || atoi(e) != 0;
 }
 
+// bf16 x has no dw2 kernel: where the plan says dw2 it runs k_gate_bwd_dw<true, 2>
+static inline bool gate_dw_is_dw2(const GateDwPlan& p, bool xb16) { return !xb16 && p.dw == MIL_ROUTE_DW2; }
+// How many [4][192] groups of bias / w / b sums the plan's launch leaves in the workspace: one per (row chunk, column tile)
+// from the dw2 kernels, one per row chunk from k_gate_bwd_dw
+static inline int gate_dw_bias_groups(const GateDwPlan& p, int L, bool xb16) { return gate_dw_is_dw2(p, xb16) ? p.S * (L / 128) : p.S; }
+static inline size_t gate_bwd_ws_floats(int S, int L) { return (size_t)S * GF_NG * L + (size_t)S * (L / 128) * 4 * 192; }
+
+extern "C" size_t mil_gate_bwd_workspace_floats(int R, int L) {
+    if (R <= 0 || L <= 0 || (L % 128) != 0) return 0;
+    return gate_bwd_ws_floats(gate_dw_plan(R, L, MIL_NUM_CU).S, L);
+}
+
+static void gate_dw_launch(const GateDwPlan& p, bool xb16, const void* x, const float* gates, const float* ds, const float* w, float* part,
+                           float* pbias, int R, int L, const uint32_t* xbits, const int32_t* rows_dev, hipStream_t st) {
+    const int NJ = L / 128, drop = xbits != nullptr;
+    const dim3 grid(p.S * 3 * NJ);
+    if (gate_dw_is_dw2(p, xb16)) {
+        hipLaunchKernelGGL(DW2_KERNELS[dw_pieces_on()][drop], grid, dim3(512), 0, st, (const float*)x, gates, ds, w, part, pbias, R, L, p.kc,
+                           NJ, xbits, rows_dev);
+    } else {
+        const int kg = p.dw == MIL_ROUTE_DW_KG1 ? 1 : 2;
+        hipLaunchKernelGGL(DW_KERNELS[xb16][kg - 1][drop], grid, dim3(256 * kg), 0, st, x, gates, ds, w, part, pbias, R, L, p.kc, NJ, xbits,
+                           rows_dev);
+    }
+}
+
 // The two launches of mil_gate_bwd_params as separate entry points (bench.py times the MFMA kernel alone).
-static int gate_bwd_partials_impl(const float* x, const float* gates, const float* ds, const float* w, int R, int L,
+// x: fp32, or bf16 with xb16.  Workspace: the partial tiles [S][384][L], then the groups of bias / w / b sums.
+static int gate_bwd_partials_impl(const void* x, bool xb16, const float* gates, const float* ds, const float* w, int R, int L,
                                   int D, float* workspace, size_t workspace_floats, const uint32_t* xbits,
                                   const int32_t* rows_dev, void* stream) {
     if (!x || !gates || !ds || !w || !workspace) return MIL_EINVAL;
     if (D != MIL_GATE_D || L <= 0 || (L % 128) != 0 || R <= 0) return MIL_EINVAL;
     const GateDwPlan p = gate_dw_plan(R, L, MIL_NUM_CU);
-    const int S = p.S, kc = p.kc, NJ = L / 128;
-    if (workspace_floats < gate_bwd_ws_floats(S, L)) return MIL_ENOSPC;
-    float* pb = workspace + (size_t)S * GF_NG * L;
-    if (p.dw == MIL_ROUTE_DW2 && dw_pieces_on()) {
-        if (xbits)
-            hipLaunchKernelGGL(k_gate_bwd_dw2_pieces<true>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,
-                               R, L, kc, NJ, xbits, rows_dev);
-        else
-            hipLaunchKernelGGL(k_gate_bwd_dw2_pieces<false>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,
-                               R, L, kc, NJ, xbits, rows_dev);
-        MIL_CHECK_LAUNCH();
-        return MIL_OK;
-    }
-    if (p.dw == MIL_ROUTE_DW2) {
-        if (xbits)
-            hipLaunchKernelGGL(k_gate_bwd_dw2<true>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,
-                               R, L, kc, NJ, xbits, rows_dev);
-        else
-            hipLaunchKernelGGL(k_gate_bwd_dw2<false>, dim3(S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace, pb,
-                               R, L, kc, NJ, xbits, rows_dev);
-        MIL_CHECK_LAUNCH();
-        return MIL_OK;
-    }
-    launch_gate_bwd_dw<false>((const void*)x, gates, ds, w, workspace, pb, R, L, kc, NJ, S, p.dw == MIL_ROUTE_DW_KG2 ? 2 : 1, xbits,
-                              (hipStream_t)stream, rows_dev);
+    if (workspace_floats < gate_bwd_ws_floats(p.S, L)) return MIL_ENOSPC;
+    gate_dw_launch(p, xb16, x, gates, ds, w, workspace, workspace + (size_t)p.S * GF_NG * L, R, L, xbits, rows_dev, (hipStream_t)stream);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
@@ -850,7 +738,7 @@ static int gate_bwd_partials_impl(const float* x, const float* gates, const floa
 extern "C" int mil_gate_bwd_partials(const float* x, const float* gates, const float* ds, const float* w, int R, int L,
                                      int D, float* workspace, size_t workspace_floats, const uint32_t* xbits,
                                      void* stream) {
-    return gate_bwd_partials_impl(x, gates, ds, w, R, L, D, workspace, workspace_floats, xbits, nullptr, stream);
+    return gate_bwd_partials_impl(x, false, gates, ds, w, R, L, D, workspace, workspace_floats, xbits, nullptr, stream);
 }
 // rows_dev: device int32 holding the TRUE number of rows (<= R).  R then is the bucket the launch is sized for (grid,
 // split-K plan, workspace); rows beyond the true count contribute nothing.  One launch configuration - one captured
@@ -858,17 +746,16 @@ extern "C" int mil_gate_bwd_partials(const float* x, const float* gates, const f
 extern "C" int mil_gate_bwd_partials_rows(const float* x, const float* gates, const float* ds, const float* w, int R, int L,
                                           int D, float* workspace, size_t workspace_floats, const uint32_t* xbits,
                                           const int32_t* rows_dev, void* stream) {
-    return gate_bwd_partials_impl(x, gates, ds, w, R, L, D, workspace, workspace_floats, xbits, rows_dev, stream);
+    return gate_bwd_partials_impl(x, false, gates, ds, w, R, L, D, workspace, workspace_floats, xbits, rows_dev, stream);
 }
 
-// The fold of the workspace gate_bwd_partials_impl filled for (R, L): the same plan gives its layout
+// The fold of the workspace gate_bwd_partials_impl filled for (R, L, xb16): the same plan gives its layout
 static int gate_bwd_fold(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu, float* dw, float* db,
                          int accumulate, float wscale, void* stream, const HeadBwdArgs* head = nullptr,
-                         const AdamFuse* ad = nullptr, uint16_t* Wp = nullptr) {
+                         const AdamFuse* ad = nullptr, uint16_t* Wp = nullptr, bool xb16 = false) {
     const GateDwPlan p = gate_dw_plan(R, L, MIL_NUM_CU);
-    return launch_gate_bwd_reduce(workspace, workspace + (size_t)p.S * GF_NG * L, p.S, p.dw == MIL_ROUTE_DW2 ? p.S * (L / 128) : p.S,
-                                  L, dWv, dbv, dWu, dbu, dw, db, accumulate, wscale, (hipStream_t)stream, head, ad, nullptr,
-                                  nullptr, Wp);
+    return launch_gate_bwd_reduce(workspace, workspace + (size_t)p.S * GF_NG * L, p.S, gate_dw_bias_groups(p, L, xb16), L, dWv, dbv, dWu,
+                                  dbu, dw, db, accumulate, wscale, (hipStream_t)stream, head, ad, nullptr, nullptr, Wp);
 }
 
 extern "C" int mil_gate_bwd_reduce(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu,
@@ -944,20 +831,14 @@ extern "C" int mil_gate_bwd_params(const float* x, const float* gates, const flo
     return mil_gate_bwd_reduce(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xbits ? xscale : 1.0f, stream);
 }
 
+// bf16 x: k_gate_bwd_dw<true, KG> where fp32 x would take k_gate_bwd_dw2
 extern "C" int mil_gate_bwd_params_x16(const uint16_t* x, const float* gates, const float* ds, const float* w, int R,
                                        int L, int D, float* workspace, size_t workspace_floats, float* dWv, float* dbv,
                                        float* dWu, float* dbu, float* dw, float* db, int accumulate, const uint32_t* xbits,
                                        float xscale, void* stream) {
-    if (!x || !gates || !ds || !w || !workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db) return MIL_EINVAL;
-    if (D != MIL_GATE_D || L <= 0 || (L % 128) != 0 || R <= 0) return MIL_EINVAL;
-    const GateDwPlan p = gate_dw_plan(R, L, MIL_NUM_CU);          // bf16 x: k_gate_bwd_dw<true, KG> where fp32 x would take k_gate_bwd_dw2
-    const int S = p.S;
-    if (workspace_floats < gate_bwd_ws_floats(S, L)) return MIL_ENOSPC;
-    float* part = workspace;
-    float* pbias = workspace + (size_t)S * GF_NG * L;
-    hipStream_t st = (hipStream_t)stream;
-    launch_gate_bwd_dw<true>((const void*)x, gates, ds, w, part, pbias, R, L, p.kc, L / 128, S, p.dw == MIL_ROUTE_DW_KG1 ? 1 : 2, xbits,
-                             st);
-    MIL_CHECK_LAUNCH();
-    return launch_gate_bwd_reduce(part, pbias, S, S, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xbits ? xscale : 1.0f, st);
+    if (!dWv || !dbv || !dWu || !dbu || !dw || !db) return MIL_EINVAL;
+    const int rc = gate_bwd_partials_impl(x, true, gates, ds, w, R, L, D, workspace, workspace_floats, xbits, nullptr, stream);
+    if (rc != MIL_OK) return rc;
+    return gate_bwd_fold(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xbits ? xscale : 1.0f, stream, nullptr, nullptr, nullptr,
+                         true);
 }

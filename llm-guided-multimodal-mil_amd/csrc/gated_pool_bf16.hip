@@ -872,11 +872,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int wi = wave >> 1, wj = wave & 1;
     const int h = lane >> 5;
     const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;     // transpose-read address roles
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
-    }
+    const int bid = xcd_order(blockIdx.x, gridDim.x);
     const int jt = bid % NJ, m = (bid / NJ) % 3, s = bid / (3 * NJ);
     const int j0 = jt * 256;
     const int rbeg = s * KC, rend = min(R, rbeg + KC);
@@ -1088,11 +1084,7 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw_bf16_w8(const u16* __restri
     const int wi = wave >> 2, wj = wave & 3;
     const int h = lane >> 5;
     const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
-    }
+    const int bid = xcd_order(blockIdx.x, gridDim.x);
     const int jt = bid % NJ, m = (bid / NJ) % 3, s = bid / (3 * NJ);
     const int j0 = jt * 512;
     const int rbeg = s * KC, rend = min(R, rbeg + KC);

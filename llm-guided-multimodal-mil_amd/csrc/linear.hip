@@ -125,9 +125,7 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int l
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     {
         const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy * gridDim.z;
-        int lin = bx + gx * (by + gy * bz);
-        const int q = nwg >> 3, rem = nwg & 7, xcd = lin & 7;
-        lin = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (lin >> 3);
+        const int lin = xcd_order(bx + gx * (by + gy * bz), nwg);
         bx = lin % gx;
         by = (lin / gx) % gy;
         bz = lin / (gx * gy);

@@ -36,11 +36,7 @@ __global__ __launch_bounds__(512) void k_gemm_nt2(const float* __restrict__ A, i
     // XCD-aware order: the nct column tiles of a row tile read the same 256 rows of A; the hardware deals workgroup ids
     // round-robin over the 8 XCDs, which put them on different L2s (PMC: 198 MiB fetched for 96 MiB of A at 32 768 x 768).
     // logical = (id % 8) * share + id / 8 (bijective for any grid size) keeps them on consecutive slots of one XCD.
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
-    }
+    const int bid = xcd_order(blockIdx.x, gridDim.x);
     const int ct = bid % nct, rt = bid / nct;
     const int row0 = rt * NT2_TM, col0 = ct * NT2_TN;
     const int nslice = K / NT2_BK;
@@ -205,11 +201,7 @@ __global__ __launch_bounds__(512) void k_gemm_tn2(const float* __restrict__ dY, 
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1;
     const int r = lane & 31, h = lane >> 5;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
-    }
+    const int bid = xcd_order(blockIdx.x, gridDim.x);
     const int jt = bid % NJ, m = (bid / NJ) % NM, s = bid / (NM * NJ);
     const int j0 = jt * 128, n0 = m * 128;
     const int cbeg = min(s * KC, rows), cend = min(rows, cbeg + KC);

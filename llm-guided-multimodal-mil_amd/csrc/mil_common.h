@@ -39,6 +39,15 @@ static inline int mil_num_cu() {
         if (e_ != hipSuccess) return (int)e_;            \
     } while (0)
 
+// XCD-aware workgroup order.  The hardware deals workgroup ids round-robin over the 8 XCDs (id % 8 shares an L2), so workgroups
+// with consecutive ids - the column tiles of one row tile or row chunk, which re-read the same operand rows - sit on 8
+// different L2s.  logical = (id % 8) * share + id / 8 gives consecutive LOGICAL ids consecutive slots of ONE XCD; with the
+// ceil-share of the first nwg % 8 XCDs it is a bijection of [0, nwg) for any grid size.
+__device__ __forceinline__ int xcd_order(int bid, int nwg) {
+    const int q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
+    return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
+}
+
 // Cross-lane primitives of the wave reductions below, none of which touches the LDS crossbar (ds_bpermute, what
 // __shfl_xor compiles to, costs an LDS issue slot per step; k_apool_partial spent a third of its time in them):
 //   swap32_add(x, y): lanes 0-31 get x[l] + x[l + 32], lanes 32-63 get y[l - 32] + y[l]      (v_permlane32_swap, gfx950)

@@ -12,8 +12,8 @@ import torch
 from mil_amd import ops, synthetic as syn
 from mil_amd.bags import BagLayout, bucket_rows
 from mil_amd.trainer import PARAM_ORDER, ImageOnlyTrainer, RaggedImageOnlyStepper
-from step_ref import (BU, BV, GF_TM, WB, WU, WV, WW, gates_ref, keep_from_bits, lib_route, max_err, num_cu, step_ref,
-                      step_route)
+from step_ref import (BU, BV, GF_TM, WB, WU, WV, WW, dw_split, gates_ref, keep_from_bits, lib_route, max_err, num_cu, split_kg,
+                      step_ref, step_route)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -151,6 +151,54 @@ def test_dw_kg2_route_against_float64():
     """k_gate_bwd_dw<.., KG = 2>: R * L >= 2^29, where k_gate_bwd_dw2 (32-bit offsets) hands over.  512 bags x 1024 rows
     x 1024 columns, 2 GiB of x, eval mode."""
     _route_case("dw_kg2 eval", [1024] * 512, 1024, 2, dict(PW, dw="dw<2>", bits=None), False)
+
+
+# ------------------------------------------------------------------------------------------ k_gate_bwd_dw<true, KG> (bf16 x)
+def _x16_dw_shape(kg):
+    """KG = 2: L = 1024 and 29 rows more than the smallest row count that plans two K groups (5 149 rows on 256 CUs: ten
+    chunks of 544, the last of 253 rows).  KG = 1: 100 x 128, four chunks of one 32-row slice each, the last of 4 rows."""
+    if kg == 1:
+        return 100, 128
+    L = 1024
+    rmin = 512 * (num_cu() // (3 * (L // 128)))
+    assert split_kg(rmin - 1, L, num_cu()) == 1 and split_kg(rmin, L, num_cu()) == 2, rmin
+    return rmin + 29, L
+
+
+@pytest.mark.parametrize("keep", [False, True], ids=["eval", "keep_bits"])
+@pytest.mark.parametrize("kg", [2, 1], ids=["kg2", "kg1"])
+def test_x16_weight_gradient_against_float64(kg, keep):
+    """k_gate_bwd_dw<true, KG, *> through ops.gate_bwd_params_x16 (the x16 shapes of test_gpu_bf16.py all plan KG = 1; bf16 x
+    has no dw2 kernel, so where fp32 x would take it the plan's two K groups run here).  dWv, dbv, dWu, dbu, dw, db against
+    float64 on the bf16-rounded x, max|got - ref| <= 1e-4 max|ref| (TOL_GRAD).  Measured (docs/lab_notes.md; the same bits
+    on the build before the kernels were rebuilt from parts): at most 3.5e-7 (kg2) and 1.8e-7 (kg1) over the six outputs."""
+    R, L = _x16_dw_shape(kg)
+    S, kc = dw_split(R, L, num_cu())
+    assert split_kg(R, L, num_cu()) == kg and lib_route(R, L, 2, False)["dw"] == ("dw2" if kg == 2 else "dw<1>"), (R, L)
+    assert R % 32 != 0 and R % kc != 0 and S > 1, (R, kc, S)
+    g = torch.Generator(device=DEV).manual_seed(500 + R + L)
+    x16 = torch.randn((R, L), device=DEV, generator=g).to(torch.bfloat16)
+    pre = torch.randn((R, 384), device=DEV, generator=g)
+    gates = torch.cat([torch.tanh(pre[:, :192]), torch.sigmoid(pre[:, 192:])], 1).contiguous()
+    ds = torch.randn(R, device=DEV, generator=g) * 1e-3
+    w = torch.randn(192, device=DEV, generator=g) * 0.1
+    bits = torch.randint(-2 ** 31, 2 ** 31, (R, L // 32), device=DEV, generator=g).to(torch.int32) if keep else None
+    xscale = 2.0 if keep else 1.0
+    got = dict(dWv=torch.empty((192, L), device=DEV), dbv=torch.empty(192, device=DEV), dWu=torch.empty((192, L), device=DEV),
+               dbu=torch.empty(192, device=DEV), dw=torch.empty(192, device=DEV), db=torch.empty(1, device=DEV))
+    ops.gate_bwd_params_x16(x16, gates, ds, w, *got.values(), xbits=bits, xscale=xscale)
+    torch.cuda.synchronize()
+    # float64: dPreV = ds w U (1 - V^2), dPreU = ds w V U (1 - U); dW = dPre^T (x keep) xscale
+    xd = x16.double() * (keep_from_bits(bits, L) if keep else 1.0)
+    V, U = gates[:, :192].double(), gates[:, 192:].double()
+    d, wd = ds.double().unsqueeze(1), w.double().unsqueeze(0)
+    pv, pu = d * wd * U * (1 - V * V), d * wd * V * U * (1 - U)
+    ref = dict(dWv=pv.t() @ xd * xscale, dbv=pv.sum(0), dWu=pu.t() @ xd * xscale, dbu=pu.sum(0), dw=(d * V * U).sum(0),
+               db=d.sum().view(1))
+    err = {k: max_err(got[k], ref[k]) for k in got}
+    print(f"x16 dw kg{kg} {R} x {L} {'keep bits' if keep else 'eval'}: " + " ".join(f"{k} {v:.2e}" for k, v in err.items()))
+    for k, v in err.items():
+        assert v <= TOL_GRAD, (kg, keep, k, v)
 
 
 # ------------------------------------------------------------------------------------------ k_gate_fwd (L > 4096)

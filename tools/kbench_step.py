@@ -1,5 +1,6 @@
 """Scratch: A/B the image-only step's stages across library builds (main + tools/variants/*.so), interleaved rounds in one
-process, HIP-event timing from C (mil_image_only_step_time).  Usage: kbench_step.py [--bf16] [--eval] [--rounds 3]"""
+process, HIP-event timing from C (mil_image_only_step_time).  Usage: kbench_step.py [--bf16 [--x16-dw]] [--eval] [--rounds 3]
+--x16-dw: with --bf16, the weight gradient as an fp32 product of the widened x (k_gate_bwd_dw<true, KG>, bf16_grad_mfma=False)."""
 import argparse, ctypes, glob, os, statistics, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,6 +12,7 @@ from mil_amd.trainer import ImageOnlyTrainer
 ap = argparse.ArgumentParser()
 ap.add_argument("--bf16", action="store_true")
 ap.add_argument("--eval", action="store_true")
+ap.add_argument("--x16-dw", action="store_true")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--bags", type=int, default=32)
 ap.add_argument("--patches", type=int, default=0)
@@ -48,7 +50,7 @@ res, grads = {}, {}
 for rnd in range(a.rounds):
     for name, h in libs:
         _lib._lib = h
-        tr = ImageOnlyTrainer(p, dev, train_mode=not a.eval and not a.bf16)
+        tr = ImageOnlyTrainer(p, dev, train_mode=not a.eval and not a.bf16, bf16_grad_mfma=not a.x16_dw)
         kb = tr.time_pieces(x, lay, y, iters=30, warm=5)
         tr.reset_dropout_stream()
         tr.forward(x, lay, y)
