@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 13 */
+int mil_abi_version(void);   /* 14 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1129,6 +1129,22 @@ int mil_tm_tok_attn_fwd(const float* qkv, const float* kL, const float* U, int n
                         void* stream);
 int mil_tm_tok_attn_bwd(const float* qkv, const float* kL, const float* U, const float* lse, const float* dO, int n_pad,
                         float* dqkv, float* dU, float* dkL, float* ws, void* stream);
+/* mil_tm_cls_attn's output from the operands of the two fused passes, with neither A1 nor A3 formed (csrc/cls_attn_fused.hip).
+ * qkv [n_pad, 1536] merged rows (row `pad` = n_pad - s^2 - 1 is the cls token; its q columns are read unscaled and 64^-0.5 is
+ * applied here, the k columns of every row from pad + 1 on are read in place), qL [8, 256, 64] scaled as mil_tm_landmarks
+ * leaves it, kL [8, 256, 64] not scaled, Z [8, 256, 256] the last pseudo-inverse iterate, lse3 [8, 256] as
+ * mil_tm_lmk_attn_fwd returns it.  Per head:
+ *   a1 = softmax_m(64^-0.5 q[pad] . kL[m]),  t = a1 Z,  r[j] = sum_m t[m] exp(qL[m] . k[j] - lse3[m]),
+ *   out[h][i] = r[pad + 1 + i] + (i < s^2 - N ? r[pad + 1 + N + i] : 0) for i < N, 0 for N <= i < s^2     (out [8, s^2]).
+ * N: `n` when len_dev is null ((s - 1)^2 < n <= s^2 or MIL_EINVAL), else len_dev[bag] read on the device and clamped into
+ * that bucket.  ws: mil_tm_cls_attn_fused_ws_floats(n_pad) = 8 x 256 + 8 x n_pad floats from the caller (t and r); 0 for an
+ * n_pad that is not a positive multiple of 256, which the status entry refuses with MIL_EINVAL before any launch, as it does
+ * pad + 1 + s^2 != n_pad, a null pointer, or a qkv, qL or kL that is not 16-byte aligned.  fp32 MFMA for the scores, no
+ * atomics, every sum in a fixed order: two runs give the same bits.  Three launches on `stream`, no host sync, nothing
+ * allocated. */
+size_t mil_tm_cls_attn_fused_ws_floats(int n_pad);
+int mil_tm_cls_attn_fused(const float* qkv, const float* qL, const float* kL, const float* Z, const float* lse3, int n_pad,
+                          int pad, int s, int n, const int32_t* len_dev, int bag, float* ws, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -159,15 +159,17 @@ class TransLayer(nn.Module):
         self.norm = norm_layer(dim)
         self.attn = NystromAttention(dim=dim)
 
-    def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn, cls: Optional[dict] = None):
+    def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn, cls: Optional[dict] = None,
+            fused_cls: Optional[bool] = None):
         """x [seq, 512] of one bag -> (x + to_out(Nystrom(LN(x)))[last seq rows], attn map / cls attention [8, s^2] / None).
-        cls: the bag length for need_attn="cls", dict(n=N) or dict(len_dev=.., bag=b)."""
+        cls: the bag length for need_attn="cls", dict(n=N) or dict(len_dev=.., bag=b); fused_cls: ops.nystrom_core's switch of
+        that output (None = the environment)."""
         a = self.attn
         ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         xp = ops.tm_row_gather(ln, None, pad_idx)                                   # zero rows in front: [n_pad, 512]
         qkv = ops.linear_act(xp, a.to_qkv.weight, None)
         if cls is not None:
-            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, pad=g["pad"], s=g["s"], **cls)
+            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, pad=g["pad"], s=g["s"], fused_cls=fused_cls, **cls)
         else:
             o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn)
         o = o[g["pad"]:]
@@ -209,6 +211,7 @@ class TransMIL(nn.Module):
         self._drop_ctr: Optional[torch.Tensor] = None
         self.last_bits: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None
         self.force_bits: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None   # tests: masks supplied from outside
+        self.fused_cls: Optional[bool] = None        # need_attn="cls" on the fused passes (ops.nystrom_core); None = MIL_TM_FUSED_CLS
 
     def _drop_state(self, device):
         if self._drop_seed is None:
@@ -307,9 +310,9 @@ class TransMIL(nn.Module):
             cls = None
             if want_cls:
                 cls = dict(len_dev=geom.len_dev, bag=b) if geom is not None else dict(n=g["N"])
-            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls)
+            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls, self.fused_cls)
             xb = self.pos_layer.run(xb, g["s"])
-            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls)
+            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls, self.fused_cls)
             if want_cls and geom is None:
                 a0, a1 = a0[:, :g["N"]], a1[:, :g["N"]]
             cls_rows.append(xb[:1])

@@ -171,6 +171,31 @@ def tm_cls_attention(A1, Z, A3, pad: int, s: int, n=None, len_dev=None, bag: int
     return out
 
 
+def tm_cls_attention_fused(qkv, qL, kL, Z, lse3, pad: int, s: int, n=None, len_dev=None, bag: int = 0):
+    """tm_cls_attention's output from the operands of the two fused passes, with neither A1 nor A3 formed
+    (mil_tm_cls_attn_fused, csrc/cls_attn_fused.hip): qkv [n_pad, 1536] the merged rows, qL (scaled) and kL [8, 256, 64] as
+    mil_tm_landmarks leaves them, Z [8, 256, 256] the last pseudo-inverse iterate, lse3 [8, 256] as tm_lmk_attn returns it,
+    pad = n_pad - s^2 - 1 the cls row.  The length is the host int `n`, or len_dev[bag] read on the device (clamped into the
+    side's bucket).  Returns [8, s^2] fp32, zeros from N on.  The workspace is one torch.empty of 8 x (256 + n_pad) floats;
+    three launches, no atomics, no host sync, bit-reproducible."""
+    if (n is None) == (len_dev is None):
+        raise ValueError("tm_cls_attention_fused: give the bag length either as n or as len_dev (+ bag)")
+    qkv, qL, kL, Z, lse3 = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (qL, "qL"), (kL, "kL"), (Z, "Z"), (lse3, "lse3")))
+    n_pad, f32 = _fused_operands("tm_cls_attention_fused", qkv, qL=qL, kL=kL)
+    if tuple(Z.shape) != (TM_H, TM_M, TM_M) or lse3.numel() != TM_H * TM_M:
+        raise _lib.MilHipError(f"tm_cls_attention_fused: Z {tuple(Z.shape)} / lse3 {tuple(lse3.shape)} outside the built shape")
+    if Z.device != qkv.device or lse3.device != qkv.device:
+        raise _lib.MilHipError("tm_cls_attention_fused: qkv, Z and lse3 must be on one device")
+    if len_dev is not None and (len_dev.dtype != torch.int32 or len_dev.device != qkv.device
+                                or not 0 <= int(bag) < len_dev.numel()):
+        raise _lib.MilHipError("tm_cls_attention_fused: len_dev must be int32 on qkv's device and hold entry `bag`")
+    out = torch.empty((TM_H, int(s) * int(s)), **f32)
+    ws = torch.empty(_lib.lib().mil_tm_cls_attn_fused_ws_floats(n_pad), **f32)
+    _lib.checked().mil_tm_cls_attn_fused(_p(qkv), _p(qL), _p(kL), _p(Z), _p(lse3), n_pad, int(pad), int(s),
+                                         int(n) if n is not None else 0, _p(len_dev), int(bag), _p(ws), _p(out), _stream())
+    return out
+
+
 def _fused_operands(op, qkv, **small):
     """The operands of a fused pass: qkv [n_pad, 1536] with n_pad a positive multiple of 256, every keyword an [8, 256, 64] tensor
     on qkv's device; `op` is the caller the message names.  Returns n_pad and the keywords of the outputs' torch.empty."""
@@ -266,7 +291,17 @@ def _tm_fused_a1(fused_a1, need_attn) -> bool:      # the token-query pass
     return _tm_switch(fused_a1, "MIL_TM_FUSED_A1", need_attn)
 
 
-def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
+def _tm_fused_cls(value, need_attn) -> bool:
+    """The switch of the cls attention on the fused passes (tm_cls_attention_fused): the keyword, else MIL_TM_FUSED_CLS
+    (default 0), read per call.  It applies with need_attn "cls" only, and then puts both passes on their fused entries."""
+    if value is None:
+        value = os.environ.get("MIL_TM_FUSED_CLS", "0") not in ("", "0")
+    return bool(value) and isinstance(need_attn, str) and need_attn == "cls"
+
+
+def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False):
+    if fused_cls:       # the cls attention reads qL, kL, Z and lse3 only: neither map is formed, whatever the two switches say
+        fused_a3 = fused_a1 = True
     n = qkv.shape[0]
     dev = qkv.device
     f32 = dict(device=dev, dtype=torch.float32)
@@ -318,7 +353,7 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
     _lib.checked().mil_tm_resconv(_p(qkv), _p(w), n, _p(O), _stream())
     attn = None
     if need_attn == "cls":  # the cls row of that map folded onto the patches, [8, s^2]: no map is formed
-        attn = tm_cls_attention(A1, Z, A3, **cls)
+        attn = tm_cls_attention_fused(qkv, qL, kL, Z, lse3, **cls) if fused_cls else tm_cls_attention(A1, Z, A3, **cls)
     elif need_attn:         # A1 Z A3 [8, n_pad, n_pad] (nystrom_attention return_attn), forward only
         T = tm_bgemm(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
         attn = tm_bgemm(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
@@ -395,12 +430,12 @@ def _tm_bwd(dO, qkv, w, saved):
 
 class _NystromCore(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False):
+    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False):
         qkv = _f32c(qkv, "qkv")
         w = _f32c(w, "res_conv.weight")
         if qkv.shape[1] != 3 * TM_D or qkv.shape[0] % TM_M or w.numel() != TM_H * TM_CONV:
             raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
-        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1)
+        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1, fused_cls)
         ctx.saved = saved
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
@@ -413,11 +448,11 @@ class _NystromCore(torch.autograd.Function):
         qkv, w = ctx.saved_tensors
         dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved)
         ctx.saved = None
-        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None
+        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None, None
 
 
 def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0, fused_a3=None,
-                 fused_a1=None):
+                 fused_a1=None, fused_cls=None):
     """qkv [n_pad, 1536] (to_qkv of the front-zero-padded rows, n_pad % 256 == 0), w = res_conv.weight [8, 1, 33, 1] ->
     (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
     [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
@@ -426,11 +461,15 @@ def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=N
     [8, 256, n_pad] map (tm_lmk_attn); None reads the environment switch MIL_TM_FUSED_A3 (default 0) at every call.  It applies
     with need_attn False only: True and "cls" read the map and keep the materialised route whatever the switch says.
     fused_a1: the same for the token-query pass (softmax(q kL^T) U and its backward, tm_tok_attn), which never forms the
-    [8, n_pad, 256] map; None reads MIL_TM_FUSED_A1 (default 0).  The two switches are independent of each other."""
+    [8, n_pad, 256] map; None reads MIL_TM_FUSED_A1 (default 0).  The two switches are independent of each other.
+    fused_cls: with need_attn "cls", the cls attention from the fused passes' operands (tm_cls_attention_fused); None reads
+    MIL_TM_FUSED_CLS (default 0).  When it applies BOTH passes run fused, forward and backward, whatever fused_a1 / fused_a3
+    say, and no map is formed; with need_attn False or True it changes nothing."""
     if isinstance(need_attn, bool):
         return _NystromCore.apply(qkv, w, need_attn, None, _tm_fused_a3(fused_a3, need_attn), _tm_fused_a1(fused_a1, need_attn))
     if not (isinstance(need_attn, str) and need_attn == "cls"):
         raise ValueError(f"nystrom_core: need_attn must be False, True or 'cls', got {need_attn!r}")
     if pad is None or s is None or (n is None) == (len_dev is None):
         raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
-    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False, False)
+    return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False, False,
+                              _tm_fused_cls(fused_cls, "cls"))

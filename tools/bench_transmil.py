@@ -10,7 +10,8 @@ memory of the graph's pool are reported with it.
 --ragged K: K bags drawn from U[2000, 15592] in turn through the stepper: ms/step, replay / eager counts, eager steps after a
 key's second visit (must be 0), graphs, the memory of their shared pool and the free memory the whole run took.
 --attn cls: per N, the eval forward without attention and with the per-patch cls attention (need_attn="cls"), and the peak
-allocated bytes of both, in one process.
+allocated bytes of both, in one process; then the same forward with the attention on the fused passes (fused_cls, the route of
+MIL_TM_FUSED_CLS=1), and a train-mode forward + backward of the extractor with the attention on either route (ms and peak).
 --fused-a3: per N, the eager TRAINING step (model.train(), BCE, backward, counted FlatAdam) with the landmark-query pass
 materialised (MIL_TM_FUSED_A3=0: the A3 map, its softmax and their products), fused (=1: csrc/landmark_attn.hip), and
 materialised again - same model, same bag, same process, the switch read per call; median (min - max) of --reps regions each
@@ -146,23 +147,52 @@ def attn_rows(a, dev, args):
     torch.manual_seed(1234)
     net = get_model(args).to(dev).eval().extractor_pathology
     med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+
+    def measure(res, fn, tag, times=True):
+        """tag_ms / _min_ms / _max_ms of --reps regions of fn (times), tag_peak_mib of one more call."""
+        if times:
+            ts = region_times(fn, a.reps, a.warmup)
+            res.update({tag + "_ms": round(med(ts), 3), tag + "_min_ms": round(min(ts), 3), tag + "_max_ms": round(max(ts), 3)})
+        else:
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            out = fn()
+            torch.cuda.synchronize()
+            res[tag + "_peak_mib"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 3)
+            del out
+
     for N in a.N:
         x = syn.make_bags(N, 1, N, 768)[0].to(dev)
-        run = {want: (lambda want=want: net(x, [N], need_attn=want)) for want in (False, "cls")}
+        gw = torch.randn(512, generator=torch.Generator().manual_seed(3)).to(dev)
+
+        def fwd(want, fused=None):
+            net.fused_cls = fused
+            return net(x, [N], need_attn=want)
+
+        def train_step(fused):
+            net.zero_grad(set_to_none=True)
+            h, attn = fwd("cls", fused)
+            (h[0] * gw).sum().backward()
+            return attn
+
+        run = {"fwd": lambda: fwd(False), "fwd_cls": lambda: fwd("cls", False), "fwd_again": lambda: fwd(False),
+               "fwd_cls_fused": lambda: fwd("cls", True)}
         res = dict(N=N, n_pad=geometry(N)["n_pad"])
+        net.eval()
         with torch.no_grad():
-            for want, tag in ((False, "fwd"), ("cls", "fwd_cls"), (False, "fwd_again")):
-                ts = region_times(run[want], a.reps, a.warmup)
-                res.update({tag + "_ms": round(med(ts), 3), tag + "_min_ms": round(min(ts), 3), tag + "_max_ms": round(max(ts), 3)})
-            for want, tag in ((False, "fwd"), ("cls", "fwd_cls")):
-                torch.cuda.synchronize()
-                torch.cuda.reset_peak_memory_stats()
-                base = torch.cuda.memory_allocated()
-                out = run[want]()
-                torch.cuda.synchronize()
-                res[tag + "_peak_mib"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 3)
-                del out
+            for tag in ("fwd", "fwd_cls", "fwd_again", "fwd_cls_fused"):
+                measure(res, run[tag], tag)
+            for tag in ("fwd", "fwd_cls", "fwd_cls_fused"):
+                measure(res, run[tag], tag, times=False)
+        net.train()                                  # forward + backward of the extractor, the attention asked for
+        for fused, tag in ((False, "train_cls"), (True, "train_cls_fused")):
+            measure(res, lambda: train_step(fused), tag)
+            measure(res, lambda: train_step(fused), tag, times=False)
+        net.zero_grad(set_to_none=True)
+        net.fused_cls = None
         res["cls_cost_pct"] = round(100.0 * (res["fwd_cls_ms"] - res["fwd_ms"]) / res["fwd_ms"], 2)
+        res["cls_fused_cost_pct"] = round(100.0 * (res["fwd_cls_fused_ms"] - res["fwd_ms"]) / res["fwd_ms"], 2)
         res["full_map_mib_per_layer"] = round(8 * res["n_pad"] ** 2 * 4 / 2 ** 20, 1)
         print(json.dumps(res), flush=True)
         del x
