@@ -830,6 +830,14 @@ int mil_sgd_step(float* param, const float* grad, size_t n, float lr, float weig
  * call (fp32 x, C == 2, hrow given) the pool partial pass then runs in the epilogue of the gate-forward launch instead of
  * as a launch of its own (same partials / hrow; ABMIL.py:52-59 in one kernel).  Never set it for multi-segment maps. */
 #define MIL_STAGE_POOL_FUSED 0x100u
+/* Hint, not a stage: the caller asserts what MIL_STAGE_POOL_FUSED asserts about tile_map, passes this hint with EVERY stage
+ * mask of the step (one call or several), and accepts M / Mdrop valid at the END of the step (after MIL_STAGE_REDUCE) instead
+ * of after MIL_STAGE_TAIL.  The fp32 step may then take its "deferred pool" route (mil_gate_route.pool_deferred): no pool pass
+ * over x at all - the head projections hrow come out of the gate forward's K loop, the row weights a_n out of the tail, the
+ * sums M_b = sum a_n x~_n out of the weight-gradient launch (mpart) and M, Mdrop, dWf out of the fold.  Where the plan
+ * refuses the route the step runs as without the hint.  MIL_POOL_DEFERRED=0 (read per call) turns the route off. */
+#define MIL_STAGE_POOL_DEFERRED 0x200u
+#define MIL_POOL_DEFERRED_SLOTS 4    /* bags a row chunk of the weight gradient may touch on that route */
 typedef struct mil_image_only_step {
     uint32_t struct_bytes;          /* sizeof(mil_image_only_step): ABI check */
     uint32_t stages;                /* MIL_STAGE_* to run */
@@ -888,9 +896,18 @@ typedef struct mil_image_only_step {
     const uint16_t* Wp;             /* nullable, fp32 x: three-piece bf16 planes of [Wv; Wu] (mil_gate_pieces layout, 3 * 384 * L
                                      * halves).  Given, the gate forward runs its split-bf16 MFMA loop and every Adam update this
                                      * call applies rewrites the planes; NULL: the fp32-MFMA gate forward */
+    /* the deferred pool (MIL_STAGE_POOL_DEFERRED) */
+    float* mpart;                   /* nullable: mil_pool_deferred_workspace_floats(R, L) floats, the weight gradient's M sums */
+    uint64_t mpart_floats;
+    int32_t dw_chunk_bags;          /* most bag slots any row chunk of the weight gradient needs (chunks of mil_gate_route.kc rows
+                                     * from row 0): index of the last bag with a row in the chunk - that of the first + 1; the
+                                     * host knows the lengths.  0: unknown - the route is refused */
+    int32_t reserved0;
 } mil_image_only_step;
 
 int mil_image_only_step_run(const mil_image_only_step* a, void* stream);
+/* Workspace of the deferred pool for (R, L): [row chunks][MIL_POOL_DEFERRED_SLOTS][16 staging rows][L] floats (0: no such route) */
+size_t mil_pool_deferred_workspace_floats(int R, int L);
 /* Measurement helper: runs the given stage subset `iters` times back to back on `stream` between two HIP events (after
  * `warm` untimed runs) and returns the average duration of one run in *ms_out.  Synchronises the stream.  The state a
  * stage reads must exist (run the whole step once first).  bench.py's per-kernel figures come from here: the launches
@@ -908,7 +925,9 @@ int mil_image_only_step_time(const mil_image_only_step* a, uint32_t stages, int 
  *               (mil_linear_small_fwd + k_gate_tail_scores without keep bits, else the r32 kernel with tail_rt)
  *   bits        keep bits: none, given by the caller, drawn inside k_gate_fwd2 or by a generator launch in front of it
  *   pool_fused  the pool partial pass runs in k_gate_fwd2's epilogue
- *   dw, S, kc   weight-gradient kernel, its row chunks (split-K factor) and rows per chunk (L % 128 == 0, else dw = -1) */
+ *   dw, S, kc   weight-gradient kernel, its row chunks (split-K factor) and rows per chunk (L % 128 == 0, else dw = -1)
+ *   pool_deferred  the deferred pool (MIL_STAGE_POOL_DEFERRED): no pool pass; pool_fused is 0 then.  Only
+ *               mil_image_only_step_route reports it: it depends on more of the step than mil_gate_step_route is told */
 #define MIL_ROUTE_MAIN_R32 0
 #define MIL_ROUTE_MAIN_FWD2 1
 #define MIL_ROUTE_MAIN_FWD2_PW 2
@@ -931,6 +950,7 @@ typedef struct mil_gate_route {
     int32_t tail, tail_rows, tail_kernel, tail_rt;
     int32_t bits, pool_fused;
     int32_t dw, S, kc;
+    int32_t pool_deferred;
 } mil_gate_route;
 /* R rows (a bucketed batch: its capacity), L % 32 == 0, C classes.  save_gates: the forward keeps the gates (a step with
  * labels).  keep: MIL_ROUTE_BITS_NONE (eval), _GIVEN, or any other value for "to be drawn by this step".  pieces: weight
@@ -940,6 +960,10 @@ typedef struct mil_gate_route {
  * ncu: compute units to plan for, <= 0: those of the current device. */
 int mil_gate_step_route(int R, int L, int C, int save_gates, int keep, int pieces, int fused_pool, int bucketed, int ncu,
                         mil_gate_route* out);
+/* The route mil_image_only_step_run takes for this descriptor when called with `stages` (hints included; bf16 x has kernels
+ * of its own: only pool_deferred = 0 speaks of it): the same
+ * plan, from the same reading of the struct.  Host-only: no pointer is dereferenced, no launch, and with ncu > 0 no device call. */
+int mil_image_only_step_route(const mil_image_only_step* a, uint32_t stages, int ncu, mil_gate_route* out);
 
 /* Which kernel the generic fp32 linear launches for a shape: the plan mil_gemm / mil_gemm_rows / mil_gemm_aux and
  * mil_linear_bwd_params(_rows) execute and their workspace queries size from, as a host-only query (no launch, no

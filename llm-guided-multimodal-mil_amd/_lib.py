@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -62,6 +62,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_image_only_step_run": (c_int, [_P, _P]),
     "mil_image_only_step_time": (c_int, [_P, c_uint32, c_int, c_int, _P, _P]),
     "mil_gate_step_route": (c_int, [c_int] * 9 + [_P]),
+    "mil_image_only_step_route": (c_int, [_P, c_uint32, c_int, _P]),
+    "mil_pool_deferred_workspace_floats": (c_size_t, [c_int, c_int]),
     "mil_gemm_route": (c_int, [c_int] * 16 + [_P]),
     "mil_linear_bwd_params_route": (c_int, [c_int] * 8 + [_P]),
     "mil_image_only_step_profile": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
@@ -210,6 +212,8 @@ STAGE_DROPBITS, STAGE_GATE_FWD, STAGE_POOL, STAGE_TAIL, STAGE_GATE_BWD, STAGE_RE
 STAGE_TILEMAP = 0x80
 STAGE_ALL = 0xff
 STAGE_POOL_FUSED = 0x100      # hint: all tiles full and aligned (include/mil_hip.h) - pool partial pass inside the forward launch
+STAGE_POOL_DEFERRED = 0x200   # hint, with every stage mask of a step on such a layout: M / Mdrop may come at the END of the step
+POOL_DEFERRED_SLOTS = 4       # MIL_POOL_DEFERRED_SLOTS
 
 
 class SmallDwDesc(ctypes.Structure):
@@ -223,7 +227,7 @@ class GateRoute(ctypes.Structure):
     """Mirror of mil_gate_route (include/mil_hip.h, with the MIL_ROUTE_* values of its fields); layout checked against the
     header by tests/test_abi.py."""
     _fields_ = [(n, c_int32) for n in ("main", "rt", "tail", "tail_rows", "tail_kernel", "tail_rt", "bits", "pool_fused",
-                                       "dw", "S", "kc")]
+                                       "dw", "S", "kc", "pool_deferred")]
 
 
 class GemmPlan(ctypes.Structure):
@@ -266,7 +270,8 @@ class ImageOnlyStep(ctypes.Structure):
         + [(n, _P) for n in ("param_flat", "grad_flat", "exp_avg", "exp_avg_sq")]
         + [("n_param", c_uint64), ("adam_step", c_int32), ("adam_step_dev", _P)]
         + [(n, c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale")]
-        + [("lr_dev", _P), ("tail_ws", _P), ("done_dev", _P), ("Wp", _P)])
+        + [("lr_dev", _P), ("tail_ws", _P), ("done_dev", _P), ("Wp", _P)]
+        + [("mpart", _P), ("mpart_floats", c_uint64), ("dw_chunk_bags", c_int32), ("reserved0", c_int32)])
 
 
 _lib = None

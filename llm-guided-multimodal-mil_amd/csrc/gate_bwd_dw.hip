@@ -536,15 +536,24 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2(const float* __restrict__ 
 // hides VALU and LDS issue, tools/mfma_valu_mix.hip).
 #define GQ_PSZ (GB_BKR * WB_S)          /* one piece of one operand: [32][160] bf16 (10 KiB) */
 #define GQ_BUF (6 * GQ_PSZ)             /* one stage: dPre pieces 0..2, x pieces 0..2 (60 KiB) */
-template <bool DROP>
-__global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __restrict__ x, const float* __restrict__ gates,
-                                                             const float* __restrict__ ds, const float* __restrict__ wvec,
-                                                             float* __restrict__ part, float* __restrict__ pbias, int R, int L,
-                                                             int KC, int NJ, const uint32_t* __restrict__ xbits,
-                                                             const int32_t* __restrict__ rows_dev) {
+// MP (the deferred pool, gate_route_plan): the m == 0 workgroups also form the chunk's share of the bag embeddings
+// M_b = sum_n a_n x~_n from the keep-masked x values their staging threads hold anyway.  a_n (the tail's row weights) and the
+// bag of every 32-row slice (aligned layout: tile t = rows 32 t ..) come in as wave-uniform scalars one slice ahead: wave w
+// stages rows 2 w, 2 w + 1 (+ 16) of a slice, its lanes 0-31 the even row.  Every staging thread keeps the sum of its rows in
+// a private float4 of the 8 KiB the two stages leave free in the LDS image - no registers held across the slice - and stores
+// it to mpart[s][bag - first bag of the chunk][staging row][L] whenever the bag changes and at the end of the chunk; the fold
+// launch sums chunk by chunk, staging row by staging row (gate_reduce.h).  No atomics, nothing crosses threads in here.
+template <bool DROP, bool MP>
+__device__ __forceinline__ void gate_bwd_dw2_pieces_body(const float* __restrict__ x, const float* __restrict__ gates,
+                                                         const float* __restrict__ ds, const float* __restrict__ wvec,
+                                                         float* __restrict__ part, float* __restrict__ pbias, int R, int L,
+                                                         int KC, int NJ, const uint32_t* __restrict__ xbits,
+                                                         const int32_t* __restrict__ rows_dev, const float* __restrict__ mp_a,
+                                                         const int32_t* __restrict__ mp_tile_map, float* __restrict__ mpart) {
     // 128 KiB: the two stages take 120 KiB, the epilogue's eight 64 x 64 fp32 tiles all of it
     __shared__ __attribute__((aligned(16))) float smem_all[2 * DW_GRP_FLOATS];
     static_assert(2 * GQ_BUF * 2 <= (int)sizeof(smem_all), "stages exceed the LDS image");
+    static_assert(2 * GQ_BUF * 2 + MP_ROWS * 128 * 4 <= (int)sizeof(smem_all), "no room for the M sums behind the stages");
     unsigned short* const img = reinterpret_cast<unsigned short*>(smem_all);
     R = dw_true_rows(R, rows_dev);
     const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));               // which 16 rows of every slice
@@ -576,8 +585,56 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
 #pragma unroll
         for (int q = 0; q < 3; ++q) *reinterpret_cast<ushort4*>(dst + q * GQ_PSZ) = o[q];
     };
+    // MP: scalar state of the M sums
+    const bool mpw = MP && c.m == 0;
+    const int wave8 = __builtin_amdgcn_readfirstlane(T >> 6);
+    f32x4* const macc = reinterpret_cast<f32x4*>(smem_all + GQ_BUF + xrow * 128 + 4 * xc4);       // behind the two stages
+    int mp_bag = -1, mp_bag0 = -1;
+    float mp_a00 = 0.f, mp_a01 = 0.f, mp_a10 = 0.f, mp_a11 = 0.f;     // a_n of rows 2 w, 2 w + 1, 2 w + 16, 2 w + 17 of the next slice
+    int mp_next = -1;                                                 // ... its bag ...
+    bool mp_in = false;                                               // ... and whether it lies in the chunk at all
+    // The scalars of the slice that starts at row0, one slice ahead of their use.  Nothing here may depend on the loaded values:
+    // a select behind the loads would wait for two scalar-memory round trips in the middle of the slice (measured: the kernel
+    // 82 -> 103 us).  A slice beyond the chunk reads the values of row 0 (finite; its x rows are zero by the range check of
+    // the buffer loads, so the products are zeros) and is kept from the bag bookkeeping by mp_in.
+    auto mp_fetch = [&](int row0) {
+        mp_in = row0 < rw.rend;
+        const int rs = mp_in ? row0 : 0;
+        const float* ap = mp_a + rs + 2 * wave8;
+        mp_a00 = ap[0]; mp_a01 = ap[1]; mp_a10 = ap[16]; mp_a11 = ap[17];
+        mp_next = mp_tile_map[4 * (rs >> 5)];
+    };
+    auto mp_flush = [&]() {                               // the sums of bag mp_bag -> its slot of this chunk
+        // Rare (once per bag and chunk): the store address is formed here from the thread index, behind an empty asm so that
+        // it is not hoisted out of the K loop as loop invariants - the kernel sits at its 256 VGPRs and they would be spilled
+        int t = T;
+        asm volatile("" : "+v"(t));
+        const int slot = mp_bag - mp_bag0;
+        f32x4* const m4 = reinterpret_cast<f32x4*>(smem_all + GQ_BUF + (t >> 5) * 128 + 4 * (t & 31));
+        if ((unsigned)slot < MP_SLOTS)
+            *reinterpret_cast<f32x4*>(mpart + (((c.s * MP_SLOTS + slot) * MP_ROWS + (t >> 5)) * L + c.j0 + 4 * (t & 31))) = *m4;
+        *m4 = f32x4{0, 0, 0, 0};
+    };
+    auto mp_turn = [&]() {                                // in front of a slice's first xwrite
+        if (mpw && mp_in && mp_next != mp_bag) {
+            if (mp_bag >= 0) mp_flush();
+            else mp_bag0 = mp_next;
+            mp_bag = mp_next;
+        }
+    };
     auto xwrite = [&](int i, int buf) {
-        put3(xw + buf * GQ_BUF + 16 * i * WB_S, DROP ? dw_keep4(src.xval(i), src.rm[i], xc4) : src.xval(i));
+        // MP: ONE read-modify-write of the sums per slice, with the second row: they come out of LDS in FRONT of the split (its
+        // ~60 VALU instructions cover the trip) and go back behind it with both rows' terms (the first row's chunk is still in
+        // its staging registers: the MP slice reloads them behind both writes, and its keep select is formed again)
+        f32x4 msum = {0, 0, 0, 0};
+        if (MP && i == 1 && mpw) msum = *macc;
+        const f32x4 xv = DROP ? dw_keep4(src.xval(i), src.rm[i], xc4) : src.xval(i);
+        put3(xw + buf * GQ_BUF + 16 * i * WB_S, xv);
+        if (MP && i == 1 && mpw) {
+            const f32x4 x0 = DROP ? dw_keep4(src.xval(0), src.rm[0], xc4) : src.xval(0);
+            msum += ((T & 32) ? mp_a01 : mp_a00) * x0;
+            *macc = msum + ((T & 32) ? mp_a11 : mp_a10) * xv;
+        }
     };
     auto awrite_v = [&](int buf) { put3(aw + buf * GQ_BUF, DwPre::v(src.rds[0] * w4, src.V(0), src.U(0), rt)); };
     auto awrite_u = [&](int buf, bool pub) {
@@ -604,8 +661,14 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
 
     // prologue: slice 0 -> stage 0 -> fragment set 0, slice 1 -> registers
     src.xload(0, rbeg); src.xload(1, rbeg); src.aload(0, rbeg);
+    if (mpw) {
+        *macc = f32x4{0, 0, 0, 0};
+        mp_fetch(rbeg);
+        mp_turn();
+    }
     xwrite(0, 0); xwrite(1, 0); awrite_v(0); awrite_u(0, c.jt == 0);
     src.xload(0, rbeg + GB_BKR); src.xload(1, rbeg + GB_BKR); src.aload(0, rbeg + GB_BKR);
+    if (mpw) mp_fetch(rbeg + GB_BKR);
     __syncthreads();
     frags(std::integral_constant<int, 0>{}, 0);
 
@@ -627,10 +690,10 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
                 mfma(t, g);
                 __builtin_amdgcn_sched_barrier(0);
                 switch (4 * t + g) {                     // seven staging parts behind the first MFMAs
-                    case 0: xwrite(0, set ^ 1); break;
-                    case 1: src.xload(0, row2); break;
-                    case 2: xwrite(1, set ^ 1); break;
-                    case 3: src.xload(1, row2); break;
+                    case 0: mp_turn(); xwrite(0, set ^ 1); break;
+                    case 1: if (MP) xwrite(1, set ^ 1); else src.xload(0, row2); break;
+                    case 2: if (MP) src.xload(0, row2); else xwrite(1, set ^ 1); break;
+                    case 3: src.xload(1, row2); if (mpw) mp_fetch(row2); break;
                     case 4: awrite_v(set ^ 1); break;
                     case 5: awrite_u(set ^ 1, pub); break;
                     case 6: src.aload(0, row2); break;
@@ -652,10 +715,29 @@ __global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __rest
         slice(sl + 1, std::integral_constant<int, 1>{});
     }
     if (sl < rw.nloop) slice(sl, std::integral_constant<int, 0>{});
+    if (mpw && mp_bag >= 0) mp_flush();                  // the chunk's last bag (the slot is the thread's own: no barrier)
     __syncthreads();                                     // the stages are dead from here on
 
     dw_store_tile<2, false>(smem_all, acc, part, c, L, grp, wave, lane);
     dw_publish_sums<2>(smem_all, pbias + ((size_t)c.s * NJ + c.jt) * 4 * 192, c.m, arow, ad4, sums);
+}
+template <bool DROP>
+__global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces(const float* __restrict__ x, const float* __restrict__ gates,
+                                                             const float* __restrict__ ds, const float* __restrict__ wvec,
+                                                             float* __restrict__ part, float* __restrict__ pbias, int R, int L,
+                                                             int KC, int NJ, const uint32_t* __restrict__ xbits,
+                                                             const int32_t* __restrict__ rows_dev) {
+    gate_bwd_dw2_pieces_body<DROP, false>(x, gates, ds, wvec, part, pbias, R, L, KC, NJ, xbits, rows_dev, nullptr, nullptr, nullptr);
+}
+// mp_a [R] row weights a_n, mp_tile_map [T][4] of an aligned layout, mpart [S][MP_SLOTS][MP_ROWS][L]
+template <bool DROP>
+__global__ __launch_bounds__(512) void k_gate_bwd_dw2_pieces_mp(const float* __restrict__ x, const float* __restrict__ gates,
+                                                                const float* __restrict__ ds, const float* __restrict__ wvec,
+                                                                float* __restrict__ part, float* __restrict__ pbias, int R, int L,
+                                                                int KC, int NJ, const uint32_t* __restrict__ xbits,
+                                                                const float* __restrict__ mp_a,
+                                                                const int32_t* __restrict__ mp_tile_map, float* __restrict__ mpart) {
+    gate_bwd_dw2_pieces_body<DROP, true>(x, gates, ds, wvec, part, pbias, R, L, KC, NJ, xbits, nullptr, mp_a, mp_tile_map, mpart);
 }
 
 // ================================================================================ host side
@@ -686,14 +768,17 @@ using Dw2Kernel = decltype(&k_gate_bwd_dw2<false>);
 static const Dw2Kernel DW2_KERNELS[2][2] = {                                    // [split-bf16 K loop][keep bits]
     {k_gate_bwd_dw2<false>, k_gate_bwd_dw2<true>},
     {k_gate_bwd_dw2_pieces<false>, k_gate_bwd_dw2_pieces<true>}};
+using Dw2MpKernel = decltype(&k_gate_bwd_dw2_pieces_mp<false>);
+static const Dw2MpKernel DW2_MP_KERNELS[2] = {k_gate_bwd_dw2_pieces_mp<false>, k_gate_bwd_dw2_pieces_mp<true>};   // [keep bits]
 
 // The K loop of the dw2 route: the split-bf16 kernel (k_gate_bwd_dw2_pieces) unless MIL_DW_PIECES=0 asks for the f32-MFMA
 // one.  Read per call (under a hipGraph: at capture), so A/B runs and tests toggle it inside one process; the route plan,
 // the workspace and the fold are the same for both.
-static inline bool dw_pieces_on() {
+bool gate_dw_pieces_on() {
     const char* e = getenv("MIL_DW_PIECES");
     return e == nullptr || atoi(e) != 0;
 }
+static inline bool dw_pieces_on() { return gate_dw_pieces_on(); }
 
 // bf16 x has no dw2 kernel: where the plan says dw2 it runs k_gate_bwd_dw<true, 2>
 static inline bool gate_dw_is_dw2(const GateDwPlan& p, bool xb16) { return !xb16 && p.dw == MIL_ROUTE_DW2; }
@@ -735,6 +820,26 @@ static int gate_bwd_partials_impl(const void* x, bool xb16, const float* gates, 
     return MIL_OK;
 }
 
+// The weight gradient of the deferred pool (gate_route_plan: the dw2 plan on the pieces kernel, R % 32 == 0, whole slices inside
+// one bag, at most MP_SLOTS bags per chunk): k_gate_bwd_dw2_pieces_mp, same workspace, plus the M sums in mp.mpart
+extern "C" size_t mil_pool_deferred_workspace_floats(int R, int L) {
+    if (R <= 0 || L <= 0 || (L % 128) != 0) return 0;
+    return (size_t)gate_dw_plan(R, L, MIL_NUM_CU).S * MP_SLOTS * MP_ROWS * L;
+}
+int gate_bwd_partials_mp(const float* x, const float* gates, const float* ds, const float* w, int R, int L, float* workspace,
+                         size_t workspace_floats, const uint32_t* xbits, const GateDwMpool& mp, void* stream) {
+    if (!x || !gates || !ds || !w || !workspace || !mp.a || !mp.tile_map || !mp.mpart) return MIL_EINVAL;
+    if (L <= 0 || (L % 128) != 0 || R <= 0 || (R % MIL_POOL_TILE) != 0) return MIL_EINVAL;
+    const GateDwPlan p = gate_dw_plan(R, L, MIL_NUM_CU);
+    if (p.dw != MIL_ROUTE_DW2 || (p.kc % GB_BKR) != 0) return MIL_EINVAL;
+    if (workspace_floats < gate_bwd_ws_floats(p.S, L)) return MIL_ENOSPC;
+    const int NJ = L / 128;
+    hipLaunchKernelGGL(DW2_MP_KERNELS[xbits != nullptr], dim3(p.S * 3 * NJ), dim3(512), 0, (hipStream_t)stream, x, gates, ds, w, workspace,
+                       workspace + (size_t)p.S * GF_NG * L, R, L, p.kc, NJ, xbits, mp.a, mp.tile_map, mp.mpart);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
 extern "C" int mil_gate_bwd_partials(const float* x, const float* gates, const float* ds, const float* w, int R, int L,
                                      int D, float* workspace, size_t workspace_floats, const uint32_t* xbits,
                                      void* stream) {
@@ -750,6 +855,21 @@ extern "C" int mil_gate_bwd_partials_rows(const float* x, const float* gates, co
 }
 
 // The fold of the workspace gate_bwd_partials_impl filled for (R, L, xb16): the same plan gives its layout
+// the head arguments of a fold launch that forms M itself (the deferred pool)
+static HeadBwdArgs head_args_mp(const float* dz, float* dWf, float* dbf, const float* loss_bag, float* loss_out, int B, int L, int C,
+                                int accumulate, float xscale, const GateDwMpool& mp, int R) {
+    HeadBwdArgs h{dz, mp.M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
+    h.mpart = mp.mpart;
+    h.tile_map = mp.tile_map;
+    h.bag_tile_off = mp.bag_tile_off;
+    h.M_out = mp.M;
+    h.Mdrop_out = mp.Mdrop;
+    h.mbits = mp.mbits;
+    h.mscale = mp.mscale;
+    h.xscale = xscale;
+    h.kc = gate_dw_plan(R, L, MIL_NUM_CU).kc;
+    return h;
+}
 static int gate_bwd_fold(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu, float* dw, float* db,
                          int accumulate, float wscale, void* stream, const HeadBwdArgs* head = nullptr,
                          const AdamFuse* ad = nullptr, uint16_t* Wp = nullptr, bool xb16 = false) {
@@ -810,15 +930,27 @@ int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* 
                                    float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
                                    float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
                                    float beta2, float eps, float weight_decay, float grad_scale, void* stream, int* done,
-                                   uint16_t* Wp) {
+                                   uint16_t* Wp, const GateDwMpool* mp) {
     if (!workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db || !dz || !M || !dWf || !dbf) return MIL_EINVAL;
     if (L <= 0 || (L % 128) != 0 || R <= 0 || B <= 0 || C <= 0 || C > 32 || (loss_bag && !loss_out)) return MIL_EINVAL;
-    const HeadBwdArgs head{dz, M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
+    if (mp != nullptr && (C != 2 || !mp->mpart || !mp->tile_map || !mp->bag_tile_off || !mp->M)) return MIL_EINVAL;
+    const HeadBwdArgs head = mp != nullptr ? head_args_mp(dz, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate, xscale, *mp, R)
+                                           : HeadBwdArgs{dz, M, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate};
     AdamFuse ad{};
     const int rc = gate_adam_fuse(dWv, dbv, dWu, dbu, dw, db, head, param_flat, grad_flat, n_param, exp_avg, exp_avg_sq, step, step_dev,
                                   lr, lr_dev, beta1, beta2, eps, weight_decay, grad_scale, done, &ad);
     if (rc != MIL_OK) return rc;
     return gate_bwd_fold(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xscale, stream, &head, &ad, Wp);
+}
+
+int gate_bwd_reduce_head_mp(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu, float* dw,
+                            float* db, int accumulate, float xscale, const float* dz, float* dWf, float* dbf, int B, int C,
+                            const float* loss_bag, float* loss_out, const GateDwMpool& mp, void* stream) {
+    if (!workspace || !dWv || !dbv || !dWu || !dbu || !dw || !db || !dz || !dWf || !dbf) return MIL_EINVAL;
+    if (L <= 0 || (L % 128) != 0 || R <= 0 || B <= 0 || C != 2 || (loss_bag && !loss_out)) return MIL_EINVAL;
+    if (!mp.mpart || !mp.tile_map || !mp.bag_tile_off || !mp.M) return MIL_EINVAL;
+    const HeadBwdArgs head = head_args_mp(dz, dWf, dbf, loss_bag, loss_out, B, L, C, accumulate, xscale, mp, R);
+    return gate_bwd_fold(workspace, R, L, dWv, dbv, dWu, dbu, dw, db, accumulate, xscale, stream, &head);
 }
 
 extern "C" int mil_gate_bwd_params(const float* x, const float* gates, const float* ds, const float* w, int R, int L,

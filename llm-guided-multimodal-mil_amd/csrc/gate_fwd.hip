@@ -9,6 +9,7 @@
 // gate_fwd_scores_epilogue, and the fused pool pass (gate_pool_request_rows / gate_fwd_pool_pass).
 #include "mil_internal.h"
 #include "philox.h"
+#include <stdlib.h>
 #include <type_traits>
 
 // ================================================================================ K1a gate forward
@@ -430,9 +431,13 @@ __device__ __forceinline__ void gate_kloop_f32(const GateFwdCoord co, const Gate
 //     NaN in that gate column, where the f32 loop gives +-inf (tanh/sigmoid then +-1 / 0 / 1): rows with an infinite
 //     feature are not carried through this path with the f32 loop's values.
 // Owns everything from the slice-0 load to the barrier behind the last slice.
-template <bool DROP, bool GEN>
+// HR (the deferred pool): the loop also forms this wave's column of the head projections, hacc = x~_row . head[wc] over the
+// lane's k (head: the wave's own staged head row, gate_head_rows_stage; LDS byte address), from the fragment values behind
+// the keep select - 8 FMA and two broadcast ds_read_b128 per lane and 16-deep slice, under the bf16 MFMAs.
+template <bool DROP, bool GEN, bool HR = false>
 __device__ __forceinline__ void gate_kloop_pw(const GateFwdCoord co, const GateKeepWords<DROP, GEN>& kw, const float* x,
-                                              const unsigned short* Wp, int L, f32x16 (&acc)[3][2]) {
+                                              const unsigned short* Wp, int L, f32x16 (&acc)[3][2], unsigned head = 0,
+                                              float* hacc = nullptr) {
     const int lane = co.lane, wave = co.wave, wr = co.wr, wc = co.wc, r = co.r, h = co.h;
     const unsigned lds0 = co.lds0;
     const int nslice = L / GF_BK, n16 = L / 16;
@@ -460,6 +465,8 @@ __device__ __forceinline__ void gate_kloop_pw(const GateFwdCoord co, const GateK
     const unsigned pa0 = xr + 16u * (unsigned)((2 * h) ^ ((r >> 2) & 3));
     const unsigned pa1 = xr + 16u * (unsigned)((2 * h + 1) ^ ((r >> 2) & 3));
     const unsigned pb = (unsigned)(2 * GP_XS_BYTES + (h * GF_NG + 96 * wc + r) * 16);
+    const unsigned ph = head + 32u * (unsigned)h;                     // HR: the head row's k = 8 h .. 8 h + 7 of slice 0
+    float hsum = 0.f;
     // one 16-deep slice from buffer `buf`; mw = keep bits of this lane's 8 k in bits 0..7
     auto slice16 = [&](int s16, unsigned mw, auto buf_c) {
         constexpr int buf = decltype(buf_c)::value;
@@ -475,11 +482,17 @@ __device__ __forceinline__ void gate_kloop_pw(const GateFwdCoord co, const GateK
                     bq[q][c][u] = *(lds_cf4*)(uintptr_t)(lds0 + pb + (unsigned)(buf * GP_WS_BYTES + (q * 2 * GF_NG + u * 192 + 32 * c) * 16));
         // the next slice goes to the other buffer (after this slice's reads in program order: no LDS wait in between)
         dma16(buf ^ 1, min(s16 + 1, n16 - 1));
+        f32x4 hw0 = {0, 0, 0, 0}, hw1 = {0, 0, 0, 0};
+        if (HR) {
+            hw0 = *(lds_cf4*)(uintptr_t)(ph + (unsigned)(s16 * 64));
+            hw1 = *(lds_cf4*)(uintptr_t)(ph + (unsigned)(s16 * 64) + 16u);
+        }
         gp_bf16x8 ap[3];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float v = j < 4 ? xa0[j] : xa1[j - 4];
             if (DROP) v = keep_if(v, mw, j);
+            if (HR) hsum = fmaf(v, j < 4 ? hw0[j] : hw1[j - 4], hsum);
             unsigned short p0, p1, p2;
             gp_split3(v, p0, p1, p2);
             ap[0][j] = __builtin_bit_cast(__bf16, p0);
@@ -513,6 +526,7 @@ __device__ __forceinline__ void gate_kloop_pw(const GateFwdCoord co, const GateK
         slice16(2 * s + 1, mw >> (16 + 8 * h), std::integral_constant<int, 1>{});
         __syncthreads();
     }
+    if (HR) *hacc = hsum;
 }
 
 // ---- fused pool pass (PQ > 0, = L / 256): the attention-pool PARTIAL PASS of the workgroup's four 32-row tiles runs
@@ -670,7 +684,50 @@ __device__ __forceinline__ void gate_fwd_pool_pass(const GateFwdCoord co, const 
     }
 }
 
-template <bool DROP, bool GEN, int PQ, bool PW = false>
+// ---- head projections from the K loop (HR; the deferred pool of gate_route_plan).  hrow[n][c] = x~_n . (Wf[c] keep_b mscale
+// xscale), the pool pass's by-product (gate_fwd_pool_pass), needs no pass over x of its own: gate_kloop_pw holds every x~ value
+// in registers.  Wave (wr, wc) stages head row c = wc as the bag of ITS 32-row tile sees it (aligned layout: a tile lies in one
+// bag) into its own [L] floats of LDS in front of the loop - lane l columns 8 l .. 8 l + 7 (+ 512), under GEN with the head's
+// keep words drawn again from Philox as the pool pass does - and stores the column behind it: only the wave itself reads them.
+#define GF_HR_MAXL 512
+template <bool DROP, bool GEN>
+__device__ __forceinline__ void gate_head_rows_stage(const GateFwdCoord co, const GateKeepWords<DROP, GEN>& kw, int R, int L,
+                                                     float xscale, const GateFwdGen& gen, const GateFwdPool& pool, lds_f32* mine) {
+    const int trow0 = co.row0 + 32 * co.wr;
+    if (trow0 >= R) return;                                // R % 32 == 0 (host): a tile is whole or absent
+    const int bag_ = pool.tile_map[4 * (trow0 >> 5)];
+    const float xs = DROP ? xscale : 1.0f;
+    for (int col = 8 * co.lane; col < L; col += 512) {
+        const float* src = pool.Wf + (size_t)co.wc * L + col;
+        f32x4 w0 = *reinterpret_cast<const f32x4*>(src) * xs, w1 = *reinterpret_cast<const f32x4*>(src + 4) * xs;
+        if (DROP) {
+            const int widx = bag_ * (L >> 5) + (col >> 5);
+            unsigned wd;
+            if (GEN) {      // the word workgroup 0 writes to mbits_out in this same launch: drawn again here
+                const uint2 pr = philox_keep_words_quarter((uint64_t)(widx >> 1), kw.off, gen.mseed_lo, gen.mseed_hi);
+                wd = (widx & 1) ? pr.y : pr.x;
+            } else {
+                wd = pool.mbits[widx];
+            }
+            const unsigned mm = wd >> (col & 31);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                w0[e] = keep_if(w0[e], mm, e) * pool.mscale;
+                w1[e] = keep_if(w1[e], mm, 4 + e) * pool.mscale;
+            }
+        }
+        *(lds_f4*)(mine + col) = w0;
+        *(lds_f4*)(mine + col + 4) = w1;
+    }
+}
+// the two half-lanes of a row hold the two halves of its k: folded once, stored by the lower one
+__device__ __forceinline__ void gate_head_rows_store(const GateFwdCoord co, float hacc, int R, float* hrow) {
+    const float tot = hacc + __shfl_xor(hacc, 32);
+    const int gr = co.row0 + 32 * co.wr + co.r;
+    if (co.h == 0 && gr < R) hrow[(size_t)gr * 2 + co.wc] = tot;
+}
+
+template <bool DROP, bool GEN, int PQ, bool PW = false, bool HR = false>
 __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, const float* __restrict__ Wv,
                                                    const float* __restrict__ bv, const float* __restrict__ Wu,
                                                    const float* __restrict__ bu, const float* __restrict__ wvec,
@@ -680,12 +737,20 @@ __global__ __launch_bounds__(512) void k_gate_fwd2(const float* __restrict__ x, 
                                                    GateFwdPool pool, const unsigned short* __restrict__ Wp = nullptr) {
     __shared__ __attribute__((aligned(16))) float smem[gate_fwd2_smem_floats(PW)];     // the K loop's image, then the epilogue's
     __shared__ __attribute__((aligned(16))) uint32_t mlds[GEN ? GF_TM * 32 : 4];       // keep words [128][nslice <= 32]
+    __shared__ __attribute__((aligned(16))) float hlds[HR ? 4 * 2 * GF_HR_MAXL : 4];   // head rows [4 tiles][2][L <= 512]
+    static_assert(!HR || (PW && PQ == 0), "the head projections come from the split-bf16 loop, in place of the pool pass");
     const GateFwdCoord co = gate_fwd_coord(smem, R);
     GateKeepWords<DROP, GEN> kw;
     kw.init(co, xbits, gen, mlds, L);
     f32x16 acc[3][2];
     gate_acc_clear(acc);
-    if constexpr (PW) gate_kloop_pw<DROP, GEN>(co, kw, x, Wp, L, acc);
+    if constexpr (HR) {
+        lds_f32* mine = (lds_f32*)hlds + (2 * co.wr + co.wc) * L;
+        gate_head_rows_stage<DROP, GEN>(co, kw, R, L, xscale, gen, pool, mine);
+        float hacc = 0.f;
+        gate_kloop_pw<DROP, GEN, true>(co, kw, x, Wp, L, acc, (unsigned)(uintptr_t)(lds_void*)mine, &hacc);
+        gate_head_rows_store(co, hacc, R, pool.hrow);
+    } else if constexpr (PW) gate_kloop_pw<DROP, GEN>(co, kw, x, Wp, L, acc);
     else gate_kloop_f32<DROP, GEN>(co, kw, x, Wv, Wu, L, acc);
     GatePoolRows<(PQ > 0 ? PQ : 1)> pv;
     if constexpr (PQ > 0) gate_pool_request_rows(co, x, R, L, pv);
@@ -865,7 +930,19 @@ struct GateRouteIn {
     int keep;               // MIL_ROUTE_BITS_NONE, _GIVEN, or _GENERATOR for "to be drawn" (the plan says where)
     bool pieces;            // weight pieces Wp given
     bool fused_pool;        // the caller wants the pool partial pass in the epilogue and its tile map is all full, aligned tiles
+    // ---- what the deferred pool asks beyond that (all zero: never; mil_gate_step_route knows none of it)
+    bool defer_hint;        // MIL_STAGE_POOL_DEFERRED came with the call: aligned single-segment layout, M valid at the end of the step
+    bool fp32, labels, hrow, host_lengths;      // x is fp32; y, hrow given; no bag_len_dev / rows_dev
+    int C, T, B;
+    int chunk_bags;         // most bags a row chunk of the weight gradient touches, 0: unknown
+    bool mpart;             // workspace given ...
+    uint64_t mpart_floats;  // ... of this size
 };
+// MIL_POOL_DEFERRED=0 turns the deferred pool off; read per call (under a hipGraph: at capture), as MIL_DW_PIECES is
+static inline bool pool_deferred_enabled() {
+    const char* e = getenv("MIL_POOL_DEFERRED");
+    return e == nullptr || atoi(e) != 0;
+}
 // rows beyond whole rounds of 128-row tiles that fit the few-rows kernels (shared with the input gradient, gate_bwd_dx.hip)
 int gate_tail_rows(int R, int tiles_per_round) {
     const int tail = R % GF_TM, full = R / GF_TM;
@@ -919,7 +996,54 @@ static mil_gate_route gate_route_plan(const GateRouteIn& in, int ncu) {
         p.S = d.S;
         p.kc = d.kc;
     }
+    // The deferred pool: no pool pass over x.  hrow comes out of the split-bf16 K loop (every row on k_gate_fwd2<.., PW, HR>,
+    // head rows of L = GF_HR_MAXL in LDS, C == 2: one column per wave of a row tile), the row weights out of k_pool_tail_h's
+    // chain half (not the few-long-bags tail of mil_pool_merge_head_ws, not MIL_TAIL_H=0), the M sums out of the m == 0
+    // workgroups of k_gate_bwd_dw2_pieces (whole 32-row slices inside one bag, at most MP_SLOTS bags per row chunk), M, Mdrop
+    // and dWf out of the fold.
+    const char* tail_env = getenv("MIL_TAIL_H");
+    p.pool_deferred = in.defer_hint && pool_deferred_enabled() && in.fp32 && p.main == MIL_ROUTE_MAIN_FWD2_PW && all_fwd2 &&
+                      L == GF_HR_MAXL && in.C == 2 && in.labels && in.hrow && in.host_lengths && in.T * MIL_POOL_TILE == R &&
+                      !(in.T >= 64 * in.B && in.B <= 8) && !(tail_env != nullptr && tail_env[0] == '0') &&
+                      p.dw == MIL_ROUTE_DW2 && gate_dw_pieces_on() && in.chunk_bags >= 1 &&
+                      in.chunk_bags <= MIL_POOL_DEFERRED_SLOTS && in.mpart &&
+                      in.mpart_floats >= (uint64_t)p.S * MIL_POOL_DEFERRED_SLOTS * 16 * L;
+    if (p.pool_deferred) p.pool_fused = 0;
     return p;
+}
+
+// The step descriptor as the plan reads it: the one place that turns mil_image_only_step + stage mask into a GateRouteIn
+mil_gate_route gate_step_plan(const mil_image_only_step* a, uint32_t st, int ncu) {
+    const bool train = a->train != 0, grads = a->y != nullptr, fp32 = !a->x_bf16;
+    const bool draw = (st & MIL_STAGE_DROPBITS) && (st & MIL_STAGE_GATE_FWD) && train && fp32;
+    const bool use_h = a->hrow != nullptr && grads && a->C <= 4;
+    GateRouteIn in{};
+    in.R = a->R;
+    in.L = a->L;
+    in.save_gates = grads;
+    in.keep = !train ? MIL_ROUTE_BITS_NONE : draw ? MIL_ROUTE_BITS_GENERATOR : MIL_ROUTE_BITS_GIVEN;
+    in.pieces = fp32 && a->Wp != nullptr;
+    in.fused_pool = fp32 && (st & MIL_STAGE_GATE_FWD) && (st & MIL_STAGE_POOL) && (st & MIL_STAGE_POOL_FUSED) && use_h && a->C == 2 &&
+                    !a->bag_len_dev && (!train || draw) && fuse_pool_enabled() && a->T * MIL_POOL_TILE == a->R;
+    in.defer_hint = (st & MIL_STAGE_POOL_DEFERRED) != 0;
+    in.fp32 = fp32;
+    in.labels = grads;
+    in.hrow = a->hrow != nullptr;
+    in.host_lengths = !a->bag_len_dev && !a->rows_dev;
+    in.C = a->C;
+    in.T = a->T;
+    in.B = a->B;
+    in.chunk_bags = a->dw_chunk_bags;
+    in.mpart = a->mpart != nullptr;
+    in.mpart_floats = a->mpart_floats;
+    return gate_route_plan(in, ncu > 0 ? ncu : MIL_NUM_CU);
+}
+
+extern "C" int mil_image_only_step_route(const mil_image_only_step* a, uint32_t stages, int ncu, mil_gate_route* out) {
+    if (!a || !out || a->struct_bytes != sizeof(mil_image_only_step)) return MIL_EINVAL;       // bf16 x: never deferred
+    if (a->R <= 0 || a->L <= 0 || (a->L % GF_BK) != 0 || a->C <= 0) return MIL_EINVAL;
+    *out = gate_step_plan(a, stages, ncu);
+    return MIL_OK;
 }
 
 // C and bucketed describe the step for the caller's benefit; the plan does not depend on them (whether the fused pool is
@@ -929,7 +1053,14 @@ extern "C" int mil_gate_step_route(int R, int L, int C, int save_gates, int keep
     if (!out || R <= 0 || L <= 0 || (L % GF_BK) != 0 || C <= 0) return MIL_EINVAL;
     if (keep != MIL_ROUTE_BITS_NONE && keep != MIL_ROUTE_BITS_GIVEN) keep = MIL_ROUTE_BITS_GENERATOR;
     (void)bucketed;
-    *out = gate_route_plan(GateRouteIn{R, L, save_gates != 0, keep, pieces != 0, fused_pool != 0}, ncu > 0 ? ncu : MIL_NUM_CU);
+    GateRouteIn in{};
+    in.R = R;
+    in.L = L;
+    in.save_gates = save_gates != 0;
+    in.keep = keep;
+    in.pieces = pieces != 0;
+    in.fused_pool = fused_pool != 0;
+    *out = gate_route_plan(in, ncu > 0 ? ncu : MIL_NUM_CU);
     return MIL_OK;
 }
 
@@ -943,6 +1074,10 @@ static const GateFwd2Kernel GATE_FWD2_KERNELS[3][2][2] = {                      
     {{k_gate_fwd2<false, false, 0, false>, k_gate_fwd2<false, false, 0, true>}, {k_gate_fwd2<false, false, 2, false>, k_gate_fwd2<false, false, 2, true>}},
     {{k_gate_fwd2<true, false, 0, false>, k_gate_fwd2<true, false, 0, true>}, {k_gate_fwd2<true, false, 2, false>, k_gate_fwd2<true, false, 2, true>}},
     {{k_gate_fwd2<true, true, 0, false>, k_gate_fwd2<true, true, 0, true>}, {k_gate_fwd2<true, true, 2, false>, k_gate_fwd2<true, true, 2, true>}}};
+
+// ... with the head projections from the split-bf16 K loop and no pool pass (the deferred pool)
+static const GateFwd2Kernel GATE_FWD2_HROW_KERNELS[3] = {                       // [none / bits given / drawn (GEN)]
+    k_gate_fwd2<false, false, 0, true, true>, k_gate_fwd2<true, false, 0, true, true>, k_gate_fwd2<true, true, 0, true, true>};
 
 static int launch_gate_fwd_r32(const float* x, const float* Wv, const float* bv, const float* Wu, const float* bu,
                                const float* w, const float* b, float* scores, float* gates, int R, int L,
@@ -984,7 +1119,14 @@ static int gate_scores_fwd_impl(const float* x, const float* Wv, const float* bv
                          pool->partials && pool->Wf && pool->hrow &&
                          (gen ? gen->mbits_out != nullptr : (xbits != nullptr) == (pool->mbits != nullptr));
     const int keep = gen ? MIL_ROUTE_BITS_GENERATOR : xbits ? MIL_ROUTE_BITS_GIVEN : MIL_ROUTE_BITS_NONE;
-    const mil_gate_route p = gate_route_plan(GateRouteIn{R, L, gates != nullptr, keep, Wp != nullptr, pool_ok}, MIL_NUM_CU);
+    GateRouteIn in{};
+    in.R = R;
+    in.L = L;
+    in.save_gates = gates != nullptr;
+    in.keep = keep;
+    in.pieces = Wp != nullptr;
+    in.fused_pool = pool_ok;
+    const mil_gate_route p = gate_route_plan(in, MIL_NUM_CU);
 
     int rc = MIL_OK;
     if (p.bits == MIL_ROUTE_BITS_GENERATOR) {
@@ -1099,6 +1241,30 @@ int gate_fwd_with_pool(const float* x, const float* Wv, const float* bv, const f
     const GateFwdGen gen = gate_fwd_gen(xbits, mbits, B, seed, mseed, offset, offset_dev);
     return gate_scores_fwd_impl(x, Wv, bv, Wu, bu, w, b, scores, gates, R, L, MIL_GATE_D, draw ? nullptr : xbits, xscale,
                                 draw ? &gen : nullptr, stream, &pl, fused, nullptr, nullptr, Wp);
+}
+
+int gate_fwd_deferred(const mil_image_only_step* a, const mil_gate_route& p, bool draw, float xscale, float mscale, void* stream) {
+    if (!p.pool_deferred || p.main != MIL_ROUTE_MAIN_FWD2_PW || p.tail != MIL_ROUTE_TAIL_NONE || !a->Wp || !a->hrow || !a->gates)
+        return MIL_EINVAL;
+    if (draw && (p.bits != MIL_ROUTE_BITS_IN_KERNEL || !a->xbits || !a->mbits)) return MIL_EINVAL;
+    if (a->L != GF_HR_MAXL || a->C != 2 || a->T * MIL_POOL_TILE != a->R || !a->tile_map) return MIL_EINVAL;      // the kernel's LDS and tile bounds
+    const bool train = a->train != 0;
+    if (train && (!a->xbits || !a->mbits)) return MIL_EINVAL;
+    GateFwdPool pl{};
+    pl.tile_map = a->tile_map;
+    pl.T = a->T;
+    pl.Wf = a->Wf;
+    pl.hrow = a->hrow;
+    pl.mbits = train && !draw ? a->mbits : nullptr;
+    pl.mscale = mscale;
+    const GateFwdGen gen = draw ? gate_fwd_gen(a->xbits, a->mbits, a->B, a->seed, a->seed ^ 0x9E3779B97F4A7C15ull, a->offset, a->offset_dev)
+                                : GateFwdGen{};
+    const uint32_t* xbits = train ? a->xbits : nullptr;
+    hipLaunchKernelGGL(GATE_FWD2_HROW_KERNELS[draw ? 2 : train ? 1 : 0], dim3((a->R + GF_TM - 1) / GF_TM), dim3(512), 0,
+                       (hipStream_t)stream, (const float*)a->x, a->Wv, a->bv, a->Wu, a->bu, a->w, a->b, a->scores, a->gates, a->R, a->L,
+                       xbits, train ? xscale : 1.0f, gen, pl, (const unsigned short*)a->Wp);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
 }
 
 // The three-piece bf16 planes of [Wv; Wu] the split-bf16 gate forward reads (gp_index layout, 3 * 384 * L halves), formed

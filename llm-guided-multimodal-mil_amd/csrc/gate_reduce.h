@@ -34,11 +34,84 @@ struct HeadBwdArgs {
     float* loss_out;            // [1]
     int B, L, C;
     int accumulate;             // != 0: add to dWf / dbf / loss_out (gradient accumulation over micro-batches)
+    // The deferred pool (mpart != NULL, C == 2): M is formed HERE, from the sums the m == 0 workgroups of
+    // k_gate_bwd_dw2_pieces_mp left in mpart [S][MP_SLOTS][MP_ROWS][L] (chunks of kc rows), and written with Mdrop (NULL in
+    // eval mode: the head saw M itself); the M above is not read
+    const float* mpart;
+    const int32_t* tile_map;    // [T][4] of the aligned layout: tile t = rows 32 t ..
+    const int32_t* bag_tile_off;
+    float *M_out, *Mdrop_out;
+    const uint32_t* mbits;      // [B][L/32] keep words of the head's dropout, with Mdrop_out
+    float mscale, xscale;       // survivors' scales of the head's and of the patches' dropout
+    int kc;
 };
-static __device__ __forceinline__ void head_bwd_params_block(const HeadBwdArgs& a, int blk, float (*red)[64],
+#define MP_SLOTS 4                      /* bags a row chunk may touch (the plan refuses the route beyond) */
+#define MP_ROWS 16                      /* staging rows of k_gate_bwd_dw2_pieces: thread >> 5 */
+static_assert(MP_SLOTS == MIL_POOL_DEFERRED_SLOTS, "header and kernels disagree on the slot count");
+
+// The head's weight gradient on the deferred pool (C == 2).  Workgroup jb owns 16 columns: thread (g = tid >> 2, q = tid & 3)
+// takes the bags g, g + 64, .. and the float4 column q - one bag per thread at 32 bags, so the loads of a bag's one to four
+// chunks are all the thread waits for.  M_b = xscale * (sum over the row chunks the bag's rows lie in, in order, of the sixteen
+// staging rows in order; slot = bag - bag of the chunk's first row), then Mdrop = M keep mscale, both stored here.
+// dWf[c][j] = sum_b dz[b][c] Mhead_b[j]: per thread over its bags, then the 64 groups in order.
+#define MP_HEAD_COLS 16
+static __device__ __forceinline__ void head_bwd_params_mpool(const HeadBwdArgs& a, int jb, float* red, const AdamFuse& ad) {
+    const int q = threadIdx.x & 3, g = threadIdx.x >> 2, j = jb * MP_HEAD_COLS + 4 * q;
+    f32x4 v0 = {0, 0, 0, 0}, v1 = {0, 0, 0, 0};
+    for (int b = g; b < a.B; b += 64) {
+        const int r0 = a.bag_tile_off[b] * MIL_POOL_TILE, r1 = a.bag_tile_off[b + 1] * MIL_POOL_TILE;
+        f32x4 m = {0, 0, 0, 0};
+        if (r1 > r0)
+            for (int s = r0 / a.kc; s <= (r1 - 1) / a.kc; ++s) {
+                const int slot = b - a.tile_map[4 * ((s * a.kc) / MIL_POOL_TILE)];
+                if ((unsigned)slot >= MP_SLOTS) continue;
+                const float* src = a.mpart + (size_t)((s * MP_SLOTS + slot) * MP_ROWS) * a.L + j;
+                f32x4 u[MP_ROWS];
+#pragma unroll
+                for (int e = 0; e < MP_ROWS; ++e) u[e] = *reinterpret_cast<const f32x4*>(src + (size_t)e * a.L);
+#pragma unroll
+                for (int e = 0; e < MP_ROWS; ++e) m += u[e];
+            }
+        m *= a.xscale;
+        f32x4 md = m;
+        if (a.Mdrop_out != nullptr && a.mbits != nullptr) {
+            const unsigned mm = a.mbits[(size_t)b * (a.L >> 5) + (j >> 5)] >> (j & 31);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) md[e] = m[e] * (((mm >> e) & 1u) ? a.mscale : 0.f);
+        }
+        *reinterpret_cast<f32x4*>(a.M_out + (size_t)b * a.L + j) = m;
+        if (a.Mdrop_out != nullptr) *reinterpret_cast<f32x4*>(a.Mdrop_out + (size_t)b * a.L + j) = md;
+        v0 += a.dz[b * 2] * md;
+        v1 += a.dz[b * 2 + 1] * md;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        red[(0 * 64 + g) * MP_HEAD_COLS + 4 * q + e] = v0[e];
+        red[(1 * 64 + g) * MP_HEAD_COLS + 4 * q + e] = v1[e];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * MP_HEAD_COLS) {
+        const int c = threadIdx.x / MP_HEAD_COLS, col = threadIdx.x % MP_HEAD_COLS;
+        float* o = a.dWf + (size_t)c * a.L + jb * MP_HEAD_COLS + col;
+        float t = 0.f;
+#pragma unroll 8
+        for (int gg = 0; gg < 64; ++gg) t += red[(c * 64 + gg) * MP_HEAD_COLS + col];
+        if (a.accumulate) t += *o;
+        *o = t;
+        adam_fused(ad, o, t);
+    }
+}
+static __device__ __forceinline__ void head_bwd_params_block(const HeadBwdArgs& a, int blk, float (*red)[64],   /* [32][64] */
                                                              const AdamFuse& ad) {
     const int nlb = (a.L + 63) / 64;
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    if (a.mpart != nullptr) {            // the deferred pool: L / MP_HEAD_COLS workgroups form M and dWf, the last one dbf and the loss
+        if (blk < a.L / MP_HEAD_COLS) {
+            head_bwd_params_mpool(a, blk, &red[0][0], ad);
+            return;
+        }
+        blk = a.C * nlb;
+    }
     if (blk < a.C * nlb) {
         const int c = blk / nlb, j = (blk % nlb) * 64 + lane;
         float v = 0.f;
@@ -134,7 +207,7 @@ static __global__ __launch_bounds__(256) void k_gate_bwd_reduce(const float* __r
     }
     const AdamFuse ad = adam_fuse_resolve(ad_in, bcs);
     if ((int)blockIdx.x >= head_first) {          // appended workgroups: the head's parameter gradients (uniform branch)
-        __shared__ float hred[4][64];
+        __shared__ float hred[32][64];      // [4][64] of head_bwd_params_block, [2][64][16] of head_bwd_params_mpool
         head_bwd_params_block(head, blockIdx.x - head_first, hred, ad);
         return;
     }
@@ -207,7 +280,8 @@ static inline int launch_gate_bwd_reduce(const float* part, const float* pbias, 
                                          hipStream_t st, const HeadBwdArgs* head = nullptr, const AdamFuse* ad = nullptr,
                                          uint16_t* Wv16 = nullptr, uint16_t* Wu16 = nullptr, uint16_t* Wp = nullptr) {
     const int nthreads = GR_NG * (L / 4) + GR_NB * (3 * 192 + 1);
-    const int nred = (nthreads + 255) / 256, nhead = head ? head->C * ((head->L + 63) / 64) + 1 : 0;
+    const int nred = (nthreads + 255) / 256;
+    const int nhead = !head ? 0 : head->mpart ? head->L / MP_HEAD_COLS + 1 : head->C * ((head->L + 63) / 64) + 1;
     hipLaunchKernelGGL(k_gate_bwd_reduce, dim3(nred + nhead), dim3(256), 0, st, part, pbias, S, SB, L, dWv, dbv, dWu, dbu, dw, db,
                        accumulate, wscale, head ? nred : 1 << 30, head ? *head : HeadBwdArgs{}, ad ? *ad : AdamFuse{},
                        (unsigned short*)Wv16, (unsigned short*)Wu16, (unsigned short*)Wp);

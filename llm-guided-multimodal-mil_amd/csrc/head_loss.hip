@@ -1,7 +1,7 @@
 // K3b: per-bag classifier head, sigmoid, BCE loss and their backward; Adam step.
 // Reference: model/aggregator.py:128-131,200 (fc = Dropout(.25) + Linear(512, C), sigmoid),
 // train_ddp.py:99,323-324 (BCELoss), train_ddp.py:115-118 (Adam).  All tiny, latency-bound kernels.
-#include "mil_common.h"
+#include "mil_internal.h"
 
 template <int NT>
 __device__ __forceinline__ float block_allsum_nt(float v, float* red) {
@@ -581,7 +581,9 @@ __global__ __launch_bounds__(NT) void k_pool_merge_head(const float* __restrict_
 // head's weight gradient reads).  z is now the weighted sum of the rows' projections instead of the projection of the
 // weighted sum: the same number up to summation order (1e-7); a first version that did both halves in ONE workgroup, chain
 // first, was slower than k_pool_merge_head (13.3 vs 12.3 us in the step) - the next kernel waits for the launch, not for ds.
-template <int NT>
+// AW (the deferred pool, gate_route_plan): launched with gridDim.y = 1, the chain half alone - nothing merges partials or
+// writes M here - and it stores the row weights a_n = e_n / l to arow [R]: the weight-gradient launch forms M from them.
+template <int NT, bool AW = false>
 __global__ __launch_bounds__(NT) void k_pool_tail_h(const float* __restrict__ partials, const int32_t* __restrict__ bag_tile_off,
                                                      int T, int L, const float* __restrict__ Wf, const float* __restrict__ bf,
                                                      int C, const float* __restrict__ y, float scale, float* __restrict__ M,
@@ -591,7 +593,8 @@ __global__ __launch_bounds__(NT) void k_pool_tail_h(const float* __restrict__ pa
                                                      const int32_t* __restrict__ tile_map, const float* __restrict__ scores,
                                                      const float* __restrict__ hrow, float* __restrict__ ds,
                                                      const uint32_t* __restrict__ mbits, float mscale,
-                                                     float* __restrict__ Mdrop, int loss_kind) {
+                                                     float* __restrict__ Mdrop, int loss_kind,
+                                                     float* __restrict__ arow = nullptr) {
     constexpr int NW = NT / 64;
     constexpr int JP = 1024 / NT;                 // columns per thread (L <= 1024)
     constexpr int DSP = 4;                        // row passes held in registers (NT / 32 tiles per pass)
@@ -601,7 +604,7 @@ __global__ __launch_bounds__(NT) void k_pool_tail_h(const float* __restrict__ pa
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int t0 = bag_tile_off[b], t1 = bag_tile_off[b + 1], nt = t1 - t0;
     const float* ml = partials + (size_t)T * L;
-    if (blockIdx.y == 1) {
+    if (!AW && blockIdx.y == 1) {
         // ------------------------------------------------------------------ merge of the partials -> M, Mdrop
         float mt = -INFINITY, lt = 0.f;
         if (tid < nt) { mt = ml[2 * (t0 + tid)]; lt = ml[2 * (t0 + tid) + 1]; }
@@ -817,6 +820,7 @@ __global__ __launch_bounds__(NT) void k_pool_tail_h(const float* __restrict__ pa
 #pragma unroll
             for (int c = 0; c < 4; ++c) gd += dzr[c] * ds_h[k][c];
             ds[ds_row[k]] = ek[k] * inv * (gd - dot);
+            if (AW) arow[ds_row[k]] = ek[k] * inv;
         }
     for (int g8 = t0 + (tid >> 5) + DSP * (NT / 32); g8 < t1; g8 += NT / 32) {
         const int row0 = tile_map[4 * g8 + 1], nrows = tile_map[4 * g8 + 2], lr = tid & 31;
@@ -824,7 +828,9 @@ __global__ __launch_bounds__(NT) void k_pool_tail_h(const float* __restrict__ pa
             const size_t row = (size_t)(row0 + lr);
             float gd = 0.f;
             for (int c = 0; c < C; ++c) gd += dzr[c] * hrow[row * C + c];
-            ds[row] = expf(scores[row] - m) * inv * (gd - dot);
+            const float an = expf(scores[row] - m) * inv;
+            ds[row] = an * (gd - dot);
+            if (AW) arow[row] = an;
         }
     }
     if (tid == 0) {
@@ -1138,6 +1144,28 @@ extern "C" int mil_pool_merge_head_ws(const float* partials, const int32_t* bag_
         hipLaunchKernelGGL(k_pool_merge_head<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, partials, bag_tile_off, T, L, Wf,
                            bf, C, y, scale, M, lse, z, p, loss_sum, dz, dM, cdot, tile_map, scores, hrow, ds, mbits, mscale,
                            Mdrop, loss_kind);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+int pool_tail_rows(const int32_t* bag_tile_off, int T, int B, int L, const float* Wf, const float* bf, int C, const float* y,
+                   float scale, float* lse, float* z, float* p, float* loss_sum, float* dz, float* dM, float* cdot,
+                   const int32_t* tile_map, const float* scores, const float* hrow, float* ds, const uint32_t* mbits, float mscale,
+                   int loss_kind, float* arow, void* stream) {
+    if (!bag_tile_off || !Wf || !bf || !y || !lse || !z || !p || !loss_sum || !dz || !dM || !cdot) return MIL_EINVAL;
+    if (!tile_map || !scores || !hrow || !ds || !arow) return MIL_EINVAL;
+    if (loss_kind != MIL_LOSS_BCE && loss_kind != MIL_LOSS_CE_ON_SIGMOID) return MIL_EINVAL;
+    if (!(L == 256 || L == 512 || L == 768 || L == 1024) || C <= 0 || C > 4 || B < 0) return MIL_EINVAL;
+    if (B == 0) return MIL_OK;
+    // the thread counts of mil_pool_merge_head_ws's short chain
+    if (T >= 48 * B)
+        hipLaunchKernelGGL((k_pool_tail_h<1024, true>), dim3(B, 1), dim3(1024), 0, (hipStream_t)stream, (const float*)nullptr,
+                           bag_tile_off, T, L, Wf, bf, C, y, scale, (float*)nullptr, lse, z, p, loss_sum, dz, dM, cdot, tile_map,
+                           scores, hrow, ds, mbits, mscale, (float*)nullptr, loss_kind, arow);
+    else
+        hipLaunchKernelGGL((k_pool_tail_h<256, true>), dim3(B, 1), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr,
+                           bag_tile_off, T, L, Wf, bf, C, y, scale, (float*)nullptr, lse, z, p, loss_sum, dz, dM, cdot, tile_map,
+                           scores, hrow, ds, mbits, mscale, (float*)nullptr, loss_kind, arow);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

@@ -1,9 +1,17 @@
 // Functions one .hip file defines and another calls that are not part of the C ABI (include/mil_hip.h).  Included by the
 // defining file as well, so the compiler holds every definition against the one prototype; default arguments live here only.
 #pragma once
+#include <stdlib.h>
+
 #include "mil_common.h"
 
 #define MIL_HIDDEN __attribute__((visibility("hidden")))      /* host planners: not among the library's dynamic symbols */
+
+// MIL_FUSE_POOL=0: keep the pool partial pass a launch of its own (A/B measurements, bit-equality tests)
+static inline bool fuse_pool_enabled() {
+    const char* e = getenv("MIL_FUSE_POOL");
+    return e == nullptr || e[0] != '0';
+}
 
 // ---- gate_fwd.hip (called from step.hip, gate_bwd_dx.hip)
 // Rows beyond whole rounds of 128-row tiles (tiles_per_round of them per round of the grid) that take the few-rows
@@ -24,7 +32,34 @@ int gate_fwd_rows_dev(const float* x, const float* Wv, const float* bv, const fl
                       uint32_t* mbits, int B, uint64_t seed, uint64_t mseed, uint64_t offset, const int32_t* offset_dev,
                       const int32_t* rows_dev, void* stream, const TileMapJob* tmap, const uint16_t* Wp);
 
+// The plan of the fp32 step for this descriptor and stage mask (hints included), as mil_image_only_step_run executes it
+MIL_HIDDEN mil_gate_route gate_step_plan(const mil_image_only_step* a, uint32_t stages, int ncu);
+// The gate forward of the deferred pool (plan p of gate_step_plan, p.pool_deferred set): scores, gates and hrow in one launch
+int gate_fwd_deferred(const mil_image_only_step* a, const mil_gate_route& p, bool draw, float xscale, float mscale, void* stream);
+
+// ---- head_loss.hip (called from step.hip)
+// The per-bag tail of the deferred pool: k_pool_tail_h's chain half alone, which also stores the row weights a_n to arow [R]
+int pool_tail_rows(const int32_t* bag_tile_off, int T, int B, int L, const float* Wf, const float* bf, int C, const float* y,
+                   float scale, float* lse, float* z, float* p, float* loss_sum, float* dz, float* dM, float* cdot,
+                   const int32_t* tile_map, const float* scores, const float* hrow, float* ds, const uint32_t* mbits, float mscale,
+                   int loss_kind, float* arow, void* stream);
+
 // ---- gate_bwd_dw.hip (called from gate_fwd.hip, step.hip)
+// MIL_DW_PIECES (read per call): the dw2 route runs the split-bf16 kernel
+MIL_HIDDEN bool gate_dw_pieces_on();
+// The deferred pool's share of the weight gradient and of its fold: row weights a [R] and tile map in, mpart as workspace;
+// the fold then writes M / Mdrop (NULL in eval mode: M is what the head saw) and forms dWf from them
+struct GateDwMpool {
+    const float* a;
+    const int32_t* tile_map;
+    const int32_t* bag_tile_off;
+    float* mpart;
+    float *M, *Mdrop;
+    const uint32_t* mbits;
+    float mscale;
+};
+int gate_bwd_partials_mp(const float* x, const float* gates, const float* ds, const float* w, int R, int L, float* workspace,
+                         size_t workspace_floats, const uint32_t* xbits, const GateDwMpool& mp, void* stream);
 // The weight-gradient part of the route plan for (R, L) on ncu compute units; the same plan sizes the workspace
 struct GateDwPlan {
     int dw, S, kc;          // MIL_ROUTE_DW_*, row chunks (split-K factor), rows per chunk
@@ -39,7 +74,11 @@ int gate_bwd_reduce_head_adam_impl(const float* workspace, int R, int L, float* 
                                    float* param_flat, const float* grad_flat, size_t n_param, float* exp_avg,
                                    float* exp_avg_sq, int step, const int* step_dev, float lr, const float* lr_dev, float beta1,
                                    float beta2, float eps, float weight_decay, float grad_scale, void* stream,
-                                   int* done = nullptr, uint16_t* Wp = nullptr);
+                                   int* done = nullptr, uint16_t* Wp = nullptr, const GateDwMpool* mp = nullptr);
+// mil_gate_bwd_reduce_head for the deferred pool
+int gate_bwd_reduce_head_mp(const float* workspace, int R, int L, float* dWv, float* dbv, float* dWu, float* dbu, float* dw,
+                            float* db, int accumulate, float xscale, const float* dz, float* dWf, float* dbf, int B, int C,
+                            const float* loss_bag, float* loss_out, const GateDwMpool& mp, void* stream);
 
 // ---- gated_pool_bf16.hip (called from step.hip)
 // bf16-MFMA weight gradient whose fold launch carries the head gradients, the loss and (param_flat != NULL) Adam + the

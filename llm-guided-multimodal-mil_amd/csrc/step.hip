@@ -24,12 +24,6 @@ static int step_check(const mil_image_only_step* a) {
     return MIL_OK;
 }
 
-// MIL_FUSE_POOL=0: keep the pool partial pass a launch of its own (A/B measurements, bit-equality tests)
-static bool fuse_pool_enabled() {
-    const char* e = getenv("MIL_FUSE_POOL");
-    return e == nullptr || e[0] != '0';
-}
-
 // bf16 step: the pool pass in the deep forward's epilogue (round 4) is OPT-IN (MIL_FUSE_POOL16=1).  Measured at config 5
 // on one box (tools/cfg5_quick.py): eval mode 0.3464 ms fused vs 0.3456 stand-alone - a tie; train mode 0.504 vs 0.415 ms - the
 // keep-word handling of eight rows per unit pushes the 256-register forward into scratch.  The re-read is served by the
@@ -41,7 +35,7 @@ static bool fuse_pool16_enabled(bool train) {
     return e != nullptr && e[0] != '0';
 }
 
-extern "C" int mil_abi_version(void) { return 14; }
+extern "C" int mil_abi_version(void) { return 15; }
 
 extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* stream) {
     int rc = step_check(a);
@@ -58,6 +52,11 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
     const uint16_t* Wp = (!a->x_bf16 && a->Wp) ? a->Wp : nullptr;
     bool adam_in_reduce = false;
     int pool_fused = 0;
+    // the deferred pool (MIL_STAGE_POOL_DEFERRED, gate_route_plan): every stage of the step asks the same plan, whichever
+    // stages this call runs
+    const mil_gate_route plan = a->x_bf16 ? mil_gate_route{} : gate_step_plan(a, st, MIL_NUM_CU);
+    const bool deferred = plan.pool_deferred != 0;
+    const GateDwMpool mp{a->partials, a->tile_map, a->bag_tile_off, a->mpart, a->M, train ? a->Mdrop : nullptr, mbits, mscale};
 
     // keep bits drawn by the forward kernel itself (no generator launches) when both stages run in this call
     const bool draw_in_fwd = (st & MIL_STAGE_DROPBITS) && (st & MIL_STAGE_GATE_FWD) && train && !a->x_bf16;
@@ -87,7 +86,10 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
     if (st & MIL_STAGE_GATE_FWD) {
         float* gates = grads ? a->gates : nullptr;
         const bool g16 = a->x_bf16 && a->bf16_grad_mfma && (a->L % 256) == 0 && a->gates16 != nullptr;
-        if (a->x_bf16 && g16 && grads && (st & MIL_STAGE_POOL) && (st & MIL_STAGE_POOL_FUSED) && use_h && a->C == 2 &&
+        if (deferred)
+            // scores, gates and the head projections hrow in one launch; there is no pool pass (a_n: tail, M: weight gradient + fold)
+            rc = gate_fwd_deferred(a, plan, draw_in_fwd, xscale, mscale, stream);
+        else if (a->x_bf16 && g16 && grads && (st & MIL_STAGE_POOL) && (st & MIL_STAGE_POOL_FUSED) && use_h && a->C == 2 &&
             fuse_pool_enabled() && fuse_pool16_enabled(train))
             // forward + pool partial pass in one launch (falls back inside when the shape does not allow it)
             rc = gate_fwd_bf16_with_pool((const uint16_t*)a->x, a->Wv16, a->bv, a->Wu16, a->bu, a->w, a->b, a->scores, a->gates16,
@@ -123,7 +125,7 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
                                      MIL_GATE_D, xbits, xscale, stream);
         if (rc != MIL_OK) return rc;
     }
-    if ((st & MIL_STAGE_POOL) && !pool_fused) {
+    if ((st & MIL_STAGE_POOL) && !pool_fused && !deferred) {
         if (a->x_bf16) {
             rc = use_h ? mil_attn_pool_partial_h_bf16((const uint16_t*)a->x, a->scores, a->tile_map, a->T, a->L, a->partials,
                                                       a->Wf, a->C, a->hrow, xbits, xscale, mbits, mscale, stream)
@@ -137,7 +139,13 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
         }
         if (rc != MIL_OK) return rc;
     }
-    if (st & MIL_STAGE_TAIL) {
+    if ((st & MIL_STAGE_TAIL) && deferred) {
+        // the chain half of the tail; the row weights go to the (otherwise unused) partials buffer: [T, L + 2] holds [R]
+        rc = pool_tail_rows(a->bag_tile_off, a->T, a->B, a->L, a->Wf, a->bf, a->C, a->y, a->loss_scale, a->lse, a->logits, a->prob,
+                            a->loss_bag, a->dz, a->dM, a->cdot, a->tile_map, a->scores, a->hrow, a->ds, mbits, mscale, a->loss_kind,
+                            a->partials, stream);
+        if (rc != MIL_OK) return rc;
+    } else if (st & MIL_STAGE_TAIL) {
         rc = mil_pool_merge_head_ws(a->partials, a->bag_tile_off, a->T, a->B, a->L, a->Wf, a->bf, a->C, a->y, a->loss_scale, a->M,
                                     a->lse, a->logits, a->prob, grads ? a->loss_bag : nullptr, grads ? a->dz : nullptr,
                                     grads ? a->dM : nullptr, grads ? a->cdot : nullptr, use_h ? a->tile_map : nullptr,
@@ -192,7 +200,11 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
             if (rc != MIL_OK) return rc;
         }
     } else {
-        if (st & MIL_STAGE_GATE_BWD) {
+        if ((st & MIL_STAGE_GATE_BWD) && deferred) {
+            rc = gate_bwd_partials_mp((const float*)a->x, a->gates, a->ds, a->w, a->R, a->L, a->dw_ws, (size_t)a->dw_ws_floats, xbits, mp,
+                                      stream);
+            if (rc != MIL_OK) return rc;
+        } else if (st & MIL_STAGE_GATE_BWD) {
             rc = mil_gate_bwd_partials_rows((const float*)a->x, a->gates, a->ds, a->w, a->R, a->L, MIL_GATE_D, a->dw_ws,
                                             (size_t)a->dw_ws_floats, xbits, a->bag_len_dev ? a->rows_dev : nullptr, stream);
             if (rc != MIL_OK) return rc;
@@ -208,11 +220,14 @@ extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* strea
                                                     a->loss_out, a->param_flat, a->grad_flat, (size_t)a->n_param, a->exp_avg,
                                                     a->exp_avg_sq, a->adam_step, a->adam_step_dev, a->lr, a->lr_dev, a->beta1,
                                                     a->beta2, a->eps, a->weight_decay, a->grad_scale, stream, a->done_dev,
-                                                    const_cast<uint16_t*>(a->Wp));
+                                                    const_cast<uint16_t*>(a->Wp), deferred ? &mp : nullptr);
                 // the device counter moves on after the update, as mil_adam_step_counted does - by the fold launch itself when
                 // the caller gave it a sign-off word (done_dev), by a one-thread launch otherwise
                 if (rc == MIL_OK && a->adam_step_dev && !a->done_dev) rc = mil_counter_add(a->adam_step_dev, 1, stream);
             }
+            else if (deferred)
+                rc = gate_bwd_reduce_head_mp(a->dw_ws, a->R, a->L, a->dWv, a->dbv, a->dWu, a->dbu, a->dw, a->db, a->accumulate, xscale,
+                                             a->dz, a->dWf, a->dbf, a->B, a->C, a->loss_bag, a->loss_out, mp, stream);
             else
                 rc = mil_gate_bwd_reduce_head(a->dw_ws, a->R, a->L, a->dWv, a->dbv, a->dWu, a->dbu, a->dw, a->db, a->accumulate,
                                               xscale, a->dz, Mhead, a->dWf, a->dbf, a->B, a->C, a->loss_bag, a->loss_out, stream);

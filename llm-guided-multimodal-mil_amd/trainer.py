@@ -224,6 +224,14 @@ class ImageOnlyTrainer:
             a.dw_ws_floats = st["dw_ws"].numel()
         if train:
             st.update(xbits=self._buf("xbits", R * (L // 32), torch.int32), mbits=self._buf("mbits", B * (L // 32), torch.int32))
+        if grads and not b16 and getattr(layout, "aligned32", False) and L % 128 == 0:
+            # the deferred pool (STAGE_POOL_DEFERRED): the weight gradient's M sums, and what only the host knows - how many
+            # bags a row chunk of the weight gradient touches at most
+            need = _lib.lib().mil_pool_deferred_workspace_floats(R, L)
+            if need:
+                st.update(mpart=self._buf("mpart", need))
+                a.mpart_floats = need
+                a.dw_chunk_bags = self._chunk_bags(layout, R, L, C)
         for k, t in st.items():
             setattr(a, k, pv(t))
         a.train, a.bf16_grad_mfma, a.seed = int(train), int(self.bf16_grad_mfma), self.seed
@@ -250,6 +258,39 @@ class ImageOnlyTrainer:
             self.last.update(xbits=st["xbits"][:R * (L // 32)].view(R, L // 32), mbits=st["mbits"][:B * (L // 32)].view(B, L // 32))
         return a
 
+    @staticmethod
+    def _chunk_bags(layout, R: int, L: int, C: int) -> int:
+        """Most bag slots any row chunk of the weight gradient needs (chunks of the route's kc rows from row 0): the index
+        of the last bag with a row in the chunk minus that of the first, plus one - an empty bag between them counts."""
+        route = _lib.GateRoute()
+        _lib.checked().mil_gate_step_route(R, L, C, 1, 0, 0, 0, 0, 0, ctypes.byref(route))
+        if route.kc <= 0:
+            return 0
+        spans, off = [], 0                   # (first row, end row, bag) of the bags that have rows
+        for b, n in enumerate(layout.lengths):
+            if n > 0:
+                spans.append((off, off + int(n), b))
+            off += int(n)
+        most, lo = 0, 0
+        for c0 in range(0, R, route.kc):
+            c1 = min(R, c0 + route.kc)
+            while lo < len(spans) and spans[lo][1] <= c0:
+                lo += 1
+            hi = lo
+            while hi + 1 < len(spans) and spans[hi + 1][0] < c1:
+                hi += 1
+            if lo < len(spans):
+                most = max(most, spans[hi][2] - spans[lo][2] + 1)
+        return most
+
+    def _deferred(self, a, stages: int) -> bool:
+        """Whether the step runs its deferred-pool route when called with these stages + the hint (the library's own report)."""
+        if a.x_bf16 or not getattr(self._keep[2], "aligned32", False):
+            return False
+        route = _lib.GateRoute()
+        _lib.checked().mil_image_only_step_route(ctypes.byref(a), stages | _lib.STAGE_POOL_DEFERRED, 0, ctypes.byref(route))
+        return bool(route.pool_deferred)
+
     def _sync_lr(self):
         """Counted mode: the scheduled learning rate goes to its device word (stream-ordered, before the next launch or
         replay that reads it)."""
@@ -257,7 +298,9 @@ class ImageOnlyTrainer:
             self.lr_dev.fill_(float(self.lr))          # never while capturing: the fill would be frozen into the graph
             self._lr_on_dev = float(self.lr)
 
-    def _run(self, a, stages: int, keep=None):
+    def _run(self, a, stages: int, keep=None, whole_step: bool = False):
+        """whole_step: the caller runs every stage of the step (in this call or in several, each flagged) and reads M / Mdrop
+        only at its end - the step may then take its deferred-pool route (STAGE_POOL_DEFERRED, include/mil_hip.h)."""
         self._sync_lr()
         if a.Wp and self._wp_version != self._param_version:
             self._pieces()                          # parameters written on the host since the planes were formed
@@ -265,6 +308,8 @@ class ImageOnlyTrainer:
         # plain single-segment layout with every bag a multiple of 32 rows: the pool partial pass may ride in the forward launch
         if getattr(keep[2], "aligned32", False) and (stages & _lib.STAGE_GATE_FWD) and (stages & _lib.STAGE_POOL):
             stages |= _lib.STAGE_POOL_FUSED
+        if whole_step and getattr(keep[2], "aligned32", False):
+            stages |= _lib.STAGE_POOL_DEFERRED
         a.stages = stages
         a.accumulate = int(self._micro > 0)
         a.lr = self.lr
@@ -321,7 +366,7 @@ class ImageOnlyTrainer:
             self.drop_pass += 1
         last = self._micro == self.accum - 1
         fused_adam = last and not (self.world > 1 or self.force_collectives)
-        self._run(a, _lib.STAGE_ALL if fused_adam else _lib.STAGE_ALL & ~_lib.STAGE_ADAM)
+        self._run(a, _lib.STAGE_ALL if fused_adam else _lib.STAGE_ALL & ~_lib.STAGE_ADAM, whole_step=True)
         if fused_adam:
             self.step_count += 1
             self._param_version += 1
@@ -380,19 +425,23 @@ class ImageOnlyTrainer:
     def time_pieces(self, x: torch.Tensor, layout: BagLayout, y: torch.Tensor, iters: int = 20, warm: int = 3):
         """HIP-event duration (ms) of each launch group of the step, issued from C (mil_image_only_step_time)."""
         a = self._fill(x, layout, y, None)
-        self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM)          # state every stage reads exists
+        self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM, whole_step=True)          # state every stage reads exists
         # train mode: the forward launch draws the keep bits itself when the shape allows (mil_gate_scores_fwd_draw), so
         # the two stages are timed together, as the step runs them
         fwd = _lib.STAGE_GATE_FWD | (_lib.STAGE_DROPBITS if a.train else 0)
         groups = [("gate_fwd", fwd), ("pool_partial", _lib.STAGE_POOL),
                   ("merge_head_loss_ds", _lib.STAGE_TAIL), ("gate_bwd_dw", _lib.STAGE_GATE_BWD),
                   ("gate_bwd_reduce_and_head_params", _lib.STAGE_REDUCE)]
+        if self._deferred(a, _lib.STAGE_ALL):
+            # the step's deferred-pool route: the same entry points carry its kernels when every call brings the hint (there
+            # is no pool pass: that group times an empty call)
+            groups = [(n, m | _lib.STAGE_POOL_DEFERRED) for n, m in groups]
         if a.x_bf16:        # the bf16 weight gradient's launch pair is one entry point: time it as a whole
             groups = [g for g in groups if g[0] not in ("gate_bwd_dw", "gate_bwd_reduce_and_head_params")]
             groups.append(("gate_bwd_dw", _lib.STAGE_GATE_BWD | _lib.STAGE_REDUCE))
         if not a.x_bf16 and getattr(layout, "aligned32", False):
             # what the step actually launches for such a batch: forward with the pool partial pass in its epilogue
-            groups.append(("gate_fwd_with_pool_fused", fwd | _lib.STAGE_POOL | _lib.STAGE_POOL_FUSED))
+            groups.append(("gate_fwd_with_pool_fused", fwd | _lib.STAGE_POOL | _lib.STAGE_POOL_FUSED))       # never with the hint
         out = {}
         ms = ctypes.c_float(0.0)
         for name, stg in groups:
@@ -421,7 +470,7 @@ class ImageOnlyTrainer:
         iterations rotate through - the cache regime of a loop over several resident batches (a single batch
         stays in the Infinity Cache from step to step, which is not what the headline loop runs in)."""
         a = self._fill(x, layout, y, None)
-        self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM)          # state every stage reads exists
+        self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM, whole_step=True)          # state every stage reads exists
         fp = self.fp
         a2 = _lib.ImageOnlyStep.from_buffer_copy(a)
         scratch = [fp.flat.clone(), fp.exp_avg.clone(), fp.exp_avg_sq.clone()]
@@ -431,6 +480,7 @@ class ImageOnlyTrainer:
             a2.Wp = scratch[-1].data_ptr()
         a2.adam_step_dev, a2.lr_dev, a2.adam_step, a2.lr, a2.accumulate = None, None, 1, self.lr, 0
         S = _lib
+        deferred = self._deferred(a2, S.STAGE_ALL)   # the route train_step runs: every group then brings the hint
         fwd = S.STAGE_TILEMAP | S.STAGE_DROPBITS | S.STAGE_GATE_FWD
         # bf16: the deep forward carries the pool pass when the batch fills the chip with 256-row workgroups (csrc/step.hip
         # falls back to two launches inside the group otherwise - the label then names what was asked for)
@@ -439,7 +489,9 @@ class ImageOnlyTrainer:
                                                                                and os.environ.get("MIL_FUSE_POOL", "1") != "0"
                                                                                and os.environ.get("MIL_FUSE_POOL16", "0") != "0"))
         groups = []
-        if fused_pool:
+        if deferred:                                # hrow comes out of the forward's K loop; there is no pool pass to time
+            groups.append(("gate_fwd", fwd | S.STAGE_POOL | S.STAGE_POOL_FUSED))
+        elif fused_pool:
             groups.append(("gate_fwd_with_pool_fused", fwd | S.STAGE_POOL | S.STAGE_POOL_FUSED))
         else:
             groups += [("gate_fwd", fwd), ("pool_partial", S.STAGE_POOL)]
@@ -453,6 +505,8 @@ class ImageOnlyTrainer:
             groups += [("gate_bwd_dw", S.STAGE_GATE_BWD), ("gate_bwd_reduce_head", S.STAGE_REDUCE), ("adam", S.STAGE_ADAM)]
         else:
             groups += [("gate_bwd_dw", S.STAGE_GATE_BWD), ("gate_bwd_reduce_head_adam", S.STAGE_REDUCE | S.STAGE_ADAM)]
+        if deferred:
+            groups = [(n, m | S.STAGE_POOL_DEFERRED) for n, m in groups]
         masks = (ctypes.c_uint32 * len(groups))(*[m for _, m in groups])
         # several short batches, per group the MEDIAN of the batch means: one stalled iteration (a 1 ms hiccup of the box
         # inside 50 steps moved a 107 us group to 126 us once) must not reach the roofline object
@@ -502,18 +556,18 @@ class ImageOnlyTrainer:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM)
+            self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM, whole_step=True)
             if collective_in_graph:
                 self.reduce_only()          # RCCL sets its communicator up on first use: never inside a capture
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             if collective_in_graph:
-                self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM)
+                self._run(a, _lib.STAGE_ALL & ~_lib.STAGE_ADAM, whole_step=True)
                 self.reduce_only()
-                self._run(a, _lib.STAGE_ADAM)
+                self._run(a, _lib.STAGE_ADAM, whole_step=True)
             else:
-                self._run(a, stages)
+                self._run(a, stages, whole_step=True)
         self._graph = dict(graph=graph, keep=(self._keep, dict(self._ws)), args=a, adam=in_graph_adam, last=dict(self.last),
                            collective=collective_in_graph)
         return self
