@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 14 */
+int mil_abi_version(void);   /* 16 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1169,6 +1169,50 @@ int mil_tm_tok_attn_bwd(const float* qkv, const float* kL, const float* U, const
 size_t mil_tm_cls_attn_fused_ws_floats(int n_pad);
 int mil_tm_cls_attn_fused(const float* qkv, const float* qL, const float* kL, const float* Z, const float* lse3, int n_pad,
                           int pad, int s, int n, const int32_t* len_dev, int bag, float* ws, float* out, void* stream);
+/* ---- TransMIL, fixed-order sums (csrc/transmil.hip; ops: deterministic=True / MIL_TM_DETERMINISTIC=1) -----------------
+ * The entries above that add across workgroups with float atomics - mil_tm_bgemm with splits > 1, mil_tm_row_gather_bwd,
+ * mil_tm_pinv_init_bwd, mil_tm_resconv_bwd, mil_tm_ppeg_bwd - each have a `_fixed` twin here.  Same kernels, templated on
+ * where a partial sum goes: every chunk or split writes its partial with plain stores into `ws` (from the caller, at least
+ * the `_ws_floats` value next to the entry; its contents before the call do not matter, nothing behind that size is written),
+ * and a second launch adds the partials in ASCENDING chunk order.  No float atomic, no counter; the order depends on the
+ * shapes alone, so two runs give the same bits.  The outputs named below are OVERWRITTEN: the caller zeroes nothing.
+ *
+ * mil_tm_bgemm_fixed: mil_tm_bgemm's product.  splits == 1: the very launch of mil_tm_bgemm (same bits, ws not touched, may
+ * be null).  splits > 1: split p (K slices [p per, (p + 1) per) of 16, per = ceil(ceil(K / 16) / splits); inside a split the
+ * MFMA chain folds into a second accumulator every 512 of K, as mil_tm_bgemm does) stores alpha x its partial tile into
+ * ws[p][batch][M][N], zeros for an empty split; then C = ((ws[0] + ws[1]) + .. + ws[splits - 1]) + beta D + diag I through C's
+ * strides.  Any beta, D and diag go with any splits.  mil_tm_bgemm_ws_floats = splits x batch x M x N (0 for splits <= 1). */
+size_t mil_tm_bgemm_ws_floats(int batch, int M, int N, int splits);
+int mil_tm_bgemm_fixed(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C, long sCb,
+                       long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta, float diag,
+                       int splits, float* ws, void* stream);
+/* mil_tm_row_gather's backward for ANY index: dsrc [src_rows, E] row i <- the sum of the rows r of ddst with idx[r] == i, r
+ * ascending (zeros when none; an idx[r] >= src_rows is ignored), dextra [E] (nullable) <- the sum of the rows with idx[r] ==
+ * -2, r ascending.  Per source row a count and the first and last naming row are taken with INTEGER atomics (order-free);
+ * then one workgroup per source row writes zeros, a copy, or ddst[first] + ddst[last], and - for a row named more than
+ * twice, and for dextra - walks idx in ascending chunks of 256, ballots the matches and adds them lowest row first.  The two
+ * index writers above name a source row at most twice.  ws: mil_tm_row_gather_ws_floats(src_rows) = 3 x src_rows (read as
+ * int32).  Three launches. */
+size_t mil_tm_row_gather_ws_floats(int src_rows);
+int mil_tm_row_gather_bwd_fixed(const float* ddst, const int32_t* idx, int rows, int E, float* dsrc, int src_rows, float* dextra,
+                                float* ws, void* stream);
+/* mil_tm_pinv_init_bwd with <dZ0, Z0> in a fixed tree: ws[c] <- the sum over elements [2048 c, 2048 c + 2048) (c < 256, per
+ * thread 8 strided terms, then the wave's xor butterfly, then waves 0 + 1 + 2 + 3), and the one-workgroup kernel adds the 256
+ * values the same way (butterfly over 64, then the four waves in order) before it uses ds.  mil_tm_pinv_ws_floats() = 256. */
+size_t mil_tm_pinv_ws_floats(void);
+int mil_tm_pinv_init_bwd_fixed(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
+                               void* stream);
+/* mil_tm_resconv_bwd with dw [8, 33] <- the sum over the chunks of 256 rows, chunk 0, 1, 2 .. in that order (overwritten;
+ * the v columns of dqkv += as before).  ws [ceil(n_pad / 256)][8 x 33] = mil_tm_resconv_ws_floats(n_pad). */
+size_t mil_tm_resconv_ws_floats(int n_pad);
+int mil_tm_resconv_bwd_fixed(const float* dout, const float* qkv, const float* w, int n_pad, float* dqkv, float* dw, float* ws,
+                             void* stream);
+/* mil_tm_ppeg_bwd with dWf [512, 49] and db [512] <- the sums over the chunks of 8 grid rows, chunk 0, 1, 2 .. in that order
+ * (both overwritten; inside a chunk a thread runs over its rows and columns in ascending order, as before).
+ * ws [ceil(s / 8)][50 x 512] = mil_tm_ppeg_ws_floats(s), a chunk's row laid out [dWf | db]. */
+size_t mil_tm_ppeg_ws_floats(int s);
+int mil_tm_ppeg_bwd_fixed(const float* dy, const float* x, int s, const float* W7, const float* W5, const float* W3, float* dx,
+                          float* dWf, float* db, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

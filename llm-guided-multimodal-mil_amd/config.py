@@ -114,6 +114,13 @@ def create_arg_parser(argv=None):
                    "--model_pathology TransMIL's unused extractor) over the multi-modal bag, rows in upstream's sequence "
                    "order, bags one after another; eager autograd path only (refused with --hip_graph 1).  0: both "
                    "values raise NotImplementedError as before")
+    p.add_argument("--deterministic", type=int, default=0, help="train_ddp.py and test_ddp.py: 1 = every sum of the TransMIL "
+                   "forward and backward that crosses workgroups (split-K products, the gather's backward, the res_conv and "
+                   "PPEG weight gradients) is taken in an order fixed by the shapes, without float atomics, so that two runs "
+                   "from one seed on one GPU give the same bits; set on every TransMIL module of the model (--model_pathology "
+                   "TransMIL, --aggregator TransMIL --fusion_transmil 1), eager or replayed (--transmil_graph 1).  Models "
+                   "without a TransMIL module accept the flag and do nothing: their steps hold no float atomic.  0: the "
+                   "environment variable MIL_TM_DETERMINISTIC decides (default off)")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,

@@ -9,6 +9,11 @@
 //  - the PPEG depthwise 7 x 7 (the 7 / 5 / 3 kernels and the identity folded into one) and the row gather of the
 //    sequence assembly ([cls | tokens | repeats], front zero pad).
 // Heads fixed at 8 x 64 (TransLayer: dim 512, dim_head 64), 256 landmarks, conv kernel 33.
+//
+// Every sum that crosses workgroups - the split-K products, the gather's backward, <dZ0, Z0>, the res_conv and PPEG weight
+// gradients - has two forms: float atomics (the default), and the mil_tm_*_fixed entries at the end of the file, whose
+// kernels are the same loops templated on FIXED: partial sums go to a caller's workspace with plain stores and a second
+// launch (k_tm_fold, k_tm_bgemm_fold) adds them in ascending chunk order, so two runs give the same bits.
 #include <hip/hip_runtime.h>
 
 #include "mil_common.h"
@@ -35,6 +40,9 @@ __device__ __forceinline__ float wave_max(float v) {
 // 64 x 64 tile, 2 x 2 waves of one 32 x 32 MFMA accumulator each, K staged 16 at a time through LDS (k-major images,
 // the register copy of the next slice loaded while the current one is multiplied).  blockIdx.z = batch * splits + split;
 // splits > 1 adds the partial products atomically (the caller has C initialised; beta must be 1, D null).
+// FIXED (splits > 1 only): split p stores alpha x its partial tile with plain stores into ws[p][batch][M][N] (C then holds the
+// workspace, D, beta and diag are unused; an empty split stores zeros) and k_tm_bgemm_fold adds the splits in ascending order.
+template <bool FIXED>
 __global__ __launch_bounds__(256) void k_tm_bgemm(const float* __restrict__ A, long sAb, long sAi, long sAk,
                                                   const float* __restrict__ B, long sBb, long sBk, long sBj, float* C,
                                                   long sCb, long sCi, long sCj, const float* D, int M, int N, int K,
@@ -109,7 +117,10 @@ __global__ __launch_bounds__(256) void k_tm_bgemm(const float* __restrict__ A, l
         if (row >= M) continue;
         float* cp = C + row * sCi + col * sCj;
         float v = alpha * acc[i];
-        if (splits == 1) {
+        if constexpr (FIXED) {
+            const long batch = gridDim.z / splits;                        // C = ws + bz M N already (sCb = M N)
+            C[(split * batch * M + row) * N + col] = v;
+        } else if (splits == 1) {
             if (beta != 0.f) v += beta * (D != nullptr ? D[row * sCi + col * sCj] : *cp);
             if (row == col) v += diag;
             *cp = v;
@@ -118,6 +129,35 @@ __global__ __launch_bounds__(256) void k_tm_bgemm(const float* __restrict__ A, l
             atomicAdd(cp, v);
         }
     }
+}
+
+// C[b][i][j] = sum_p ws[p][b][i][j] (p = 0, 1, .. splits - 1 in that order) + beta D[b][i][j] + diag [i == j], thread per element
+// with the lanes along j; D = C when null.  The launch boundary behind k_tm_bgemm<true> is the only ordering it needs.
+__global__ __launch_bounds__(256) void k_tm_bgemm_fold(const float* __restrict__ ws, int splits, float* C, long sCb, long sCi,
+                                                       long sCj, const float* D, int batch, int M, int N, float beta, float diag) {
+    const long per = (long)batch * M * N, e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= per) return;
+    const int col = (int)(e % N), row = (int)((e / N) % M);
+    const long off = (e / ((long)M * N)) * sCb + row * sCi + col * sCj;
+    float v = ws[e];
+    for (int p = 1; p < splits; ++p) v += ws[p * per + e];
+    if (beta != 0.f) v += beta * (D != nullptr ? D[off] : C[off]);
+    if (row == col) v += diag;
+    C[off] = v;
+}
+
+// out[e] = sum_c ws[c * stride + e] for c = 0, 1, .. chunks - 1 in that order, e < n: the second launch of every fixed-order
+// sum whose output is contiguous (the partials come from the launch in front, plain stores, no counters)
+__global__ __launch_bounds__(256) void k_tm_fold(const float* __restrict__ ws, long stride, int chunks, int n, float* __restrict__ out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float v = ws[e];
+    for (int c = 1; c < chunks; ++c) v += ws[c * stride + e];
+    out[e] = v;
+}
+
+inline void tm_fold(const float* ws, long stride, int chunks, int n, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_tm_fold, dim3((n + 255) / 256), dim3(256), 0, stream, ws, stride, chunks, n, out);
 }
 
 // in place: x[row] = softmax(x[row]); one wave per row
@@ -163,6 +203,76 @@ __global__ __launch_bounds__(256) void k_tm_gather_bwd(const float* __restrict__
     if (id == -1 || (id == -2 && dextra == nullptr)) return;
     float* d = id >= 0 ? dsrc + (long)id * E : dextra;
     for (int c = threadIdx.x; c < E; c += 256) atomicAdd(d + c, ddst[(long)r * E + c]);
+}
+
+// The same sums in an order the index alone fixes.  meta [src_rows][3] int32 (zeroed by k_tm_gather_meta_zero): how many rows
+// of idx name source row i, and the first and the last of them as rows - first and last + 1 under atomicMax - integer
+// atomics, whose results do not depend on the order they land in.
+__global__ __launch_bounds__(256) void k_tm_gather_meta_zero(int32_t* __restrict__ meta, int n) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < n) meta[e] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_tm_gather_meta(const int32_t* __restrict__ idx, int rows, int src_rows, int32_t* meta) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int id = idx[r];
+    if (id < 0 || id >= src_rows) return;
+    atomicAdd(meta + 3 * id, 1);
+    atomicMax(meta + 3 * id + 1, rows - r);
+    atomicMax(meta + 3 * id + 2, r + 1);
+}
+
+// out[c] = sum of ddst[r][c] over the rows r in [r_lo, r_hi] with idx[r] == target, r ascending: the whole workgroup walks idx in
+// chunks of 256, each wave ballots its 64 entries, and every thread adds the rows of the set bits, lowest first, to its column
+__device__ __forceinline__ void tm_gather_scan_sum(const float* __restrict__ ddst, const int32_t* __restrict__ idx, int r_lo,
+                                                   int r_hi, int target, int E, float* __restrict__ out) {
+    __shared__ unsigned long long hit[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int c0 = 0; c0 < E; c0 += 256) {
+        const int c = c0 + tid;
+        float acc = 0.f;
+        for (int base = r_lo; base <= r_hi; base += 256) {
+            const int r = base + tid;
+            const unsigned long long b = __ballot(r <= r_hi && idx[r] == target);
+            if (lane == 0) hit[wv] = b;
+            __syncthreads();
+            for (int w = 0; w < 4; ++w) {
+                unsigned long long m = hit[w];
+                while (m) {
+                    const int j = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    if (c < E) acc += ddst[(long)(base + 64 * w + j) * E + c];
+                }
+            }
+            __syncthreads();
+        }
+        if (c < E) out[c] = acc;
+    }
+}
+
+// workgroup i < src_rows writes dsrc[i]: zeros, a copy, ddst[first] + ddst[last], or (named more than twice) the ascending scan
+// between its first and last row; workgroup src_rows (launched when dextra is not null) scans all of idx for the -2 rows
+__global__ __launch_bounds__(256) void k_tm_gather_bwd_fixed(const float* __restrict__ ddst, const int32_t* __restrict__ idx, int rows,
+                                                             int E, const int32_t* __restrict__ meta, int src_rows,
+                                                             float* __restrict__ dsrc, float* __restrict__ dextra) {
+    const int i = blockIdx.x;
+    if (i == src_rows) {
+        tm_gather_scan_sum(ddst, idx, 0, rows - 1, -2, E, dextra);
+        return;
+    }
+    const int cnt = meta[3 * i], first = rows - meta[3 * i + 1], last = meta[3 * i + 2] - 1;
+    float* d = dsrc + (long)i * E;
+    if (cnt > 2) {
+        tm_gather_scan_sum(ddst, idx, first, last, i, E, d);
+        return;
+    }
+    for (int c = threadIdx.x; c < E; c += 256) {
+        float v = 0.f;
+        if (cnt >= 1) v = ddst[(long)first * E + c];
+        if (cnt == 2) v += ddst[(long)last * E + c];
+        d[c] = v;
+    }
 }
 
 // Grid sides of up to TM_MAX_BAGS bags, by value: what a captured step of those sides is keyed by.  The lengths are read from
@@ -354,7 +464,9 @@ __global__ __launch_bounds__(256) void k_tm_pinv_init(const float* __restrict__ 
     }
 }
 
-// ws[0] += <dZ0, Z0> over 2048-element chunks (ws caller-zeroed)
+// ws[0] += <dZ0, Z0> over 2048-element chunks (ws caller-zeroed); FIXED: ws[chunk] = the chunk's sum, a plain store
+constexpr int PINV_CHUNKS = TM_H * TM_M * TM_M / 2048;      // 256: k_tm_pinv_init_bwd_s<true> has one thread per chunk
+template <bool FIXED>
 __global__ __launch_bounds__(256) void k_tm_pinv_dot(const float* __restrict__ dZ0, const float* __restrict__ Z0, float* ws) {
     __shared__ float red[4];
     const int base = blockIdx.x * 2048;
@@ -363,7 +475,11 @@ __global__ __launch_bounds__(256) void k_tm_pinv_dot(const float* __restrict__ d
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(ws, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        const float v = red[0] + red[1] + red[2] + red[3];
+        if constexpr (FIXED) ws[blockIdx.x] = v;
+        else atomicAdd(ws, v);
+    }
 }
 
 // dA2[h][i][j] += dZ0[h][j][i] / s
@@ -376,10 +492,22 @@ __global__ __launch_bounds__(256) void k_tm_pinv_init_bwd_t(const float* __restr
 
 // the scale's gradient ds = -<dZ0, Z0> / s (ws[0], k_tm_pinv_dot) goes to the arg-max column through its column-sum
 // factor: dA2[h*][i][j*] += ds * (max row abs-sum) (A2 > 0 after softmax, so |.|' = 1).  One workgroup, one thread per row.
+// FIXED: <dZ0, Z0> is the sum of the 256 chunk sums in ws, by the xor butterfly of each wave and then wave 0 .. 3 in order.
+template <bool FIXED>
 __global__ __launch_bounds__(256) void k_tm_pinv_init_bwd_s(const float* __restrict__ ws, const float* __restrict__ scale,
                                                             const int32_t* __restrict__ arg, float* dA2) {
     const int t = threadIdx.x;
-    const float ds = -ws[0] / scale[0];
+    float dot;
+    if constexpr (FIXED) {
+        __shared__ float red[4];
+        const float s = wave_sum(ws[t]);
+        if ((t & 63) == 0) red[t >> 6] = s;
+        __syncthreads();
+        dot = red[0] + red[1] + red[2] + red[3];
+    } else {
+        dot = ws[0];
+    }
+    const float ds = -dot / scale[0];
     const int hh = arg[0] >> 8, jc = arg[0] & 255;
     dA2[(hh << 16) + (t << 8) + jc] += ds * scale[1];
 }
@@ -410,7 +538,9 @@ __global__ __launch_bounds__(256) void k_tm_resconv_bwd_dv(const float* __restri
 }
 
 // dw[head][t] += sum over a chunk of rows i and d of dout[i][head, d] v[i + t - 16][head, d]; block (head * 33 + t, chunk)
+// FIXED: dw is the workspace [chunks][8 x 33] and the chunk's sum a plain store into its row (k_tm_fold adds the rows)
 constexpr int RC_CHUNK = 256;
+template <bool FIXED>
 __global__ __launch_bounds__(256) void k_tm_resconv_bwd_dw(const float* __restrict__ dout, const float* __restrict__ qkv, int n,
                                                            float* dw) {
     __shared__ float red[4];
@@ -425,7 +555,11 @@ __global__ __launch_bounds__(256) void k_tm_resconv_bwd_dw(const float* __restri
     s = wave_sum(s);
     if (lane == 0) red[wv] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(dw + blockIdx.x, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        const float v = red[0] + red[1] + red[2] + red[3];
+        if constexpr (FIXED) dw[blockIdx.y * (TM_H * TM_CONV) + blockIdx.x] = v;
+        else atomicAdd(dw + blockIdx.x, v);
+    }
 }
 
 // PPEG: y[1 + i s + j][c] = bias[c] + sum_{a,b < 7} Wf[c][a][b] x[1 + (i + a - 3) s + (j + b - 3)][c], y[0] = x[0];
@@ -472,7 +606,9 @@ __global__ __launch_bounds__(256) void k_tm_ppeg(const float* __restrict__ x, in
 }
 
 // dWf[c][tap] (tap < 49) and db[c] (tap 49) += sums over a chunk of 8 grid rows; thread per (tap, channel)
+// FIXED: dWf is the workspace [chunks][50 x 512], a chunk's row laid out [dWf 512 x 49 | db 512], plain stores (db unused)
 constexpr int PPEG_ROWS = 8;
+template <bool FIXED>
 __global__ __launch_bounds__(256) void k_tm_ppeg_dw(const float* __restrict__ dy, const float* __restrict__ x, int s, float* dWf,
                                                     float* db) {
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -490,8 +626,12 @@ __global__ __launch_bounds__(256) void k_tm_ppeg_dw(const float* __restrict__ dy
         for (int j = max(0, -b); j < min(s, s - b); ++j)
             acc += dy[(long)(1 + i * s + j) * TM_D + c] * x[(long)(1 + ii * s + j + b) * TM_D + c];
     }
-    if (tap == 49) atomicAdd(db + c, acc);
-    else atomicAdd(dWf + c * 49 + tap, acc);
+    if constexpr (FIXED) {
+        dWf[(long)blockIdx.y * (50 * TM_D) + (tap == 49 ? 49 * TM_D + c : c * 49 + tap)] = acc;
+    } else {
+        if (tap == 49) atomicAdd(db + c, acc);
+        else atomicAdd(dWf + c * 49 + tap, acc);
+    }
 }
 
 // Per-patch cls-token attention: the cls row (padded row `pad`) of A1 Z A3 without the [n_pad, n_pad] map, in two launches.
@@ -594,7 +734,7 @@ int mil_tm_bgemm(const float* A, long sAb, long sAi, long sAk, const float* B, l
         return MIL_EINVAL;
     if ((M + 63) / 64 > 65535 || (long)batch * splits > 65535) return MIL_EINVAL;
     dim3 grid((N + 63) / 64, (M + 63) / 64, batch * splits);
-    hipLaunchKernelGGL(k_tm_bgemm, grid, dim3(256), 0, (hipStream_t)stream, A, sAb, sAi, sAk, B, sBb, sBk, sBj, C, sCb, sCi,
+    hipLaunchKernelGGL(k_tm_bgemm<false>, grid, dim3(256), 0, (hipStream_t)stream, A, sAb, sAi, sAk, B, sBb, sBk, sBj, C, sCb, sCi,
                        sCj, D, M, N, K, alpha, beta, diag, splits);
     return launch_rc();
 }
@@ -679,8 +819,8 @@ int mil_tm_pinv_init_bwd(const float* dZ0, const float* Z0, const float* scale, 
                          void* stream) {
     if (!dZ0 || !Z0 || !scale || !arg || !dA2 || !ws) return MIL_EINVAL;
     hipLaunchKernelGGL(k_tm_pinv_init_bwd_t, dim3(TM_H * TM_M * TM_M / 256), dim3(256), 0, (hipStream_t)stream, dZ0, scale, dA2);
-    hipLaunchKernelGGL(k_tm_pinv_dot, dim3(TM_H * TM_M * TM_M / 2048), dim3(256), 0, (hipStream_t)stream, dZ0, Z0, ws);
-    hipLaunchKernelGGL(k_tm_pinv_init_bwd_s, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, scale, arg, dA2);
+    hipLaunchKernelGGL(k_tm_pinv_dot<false>, dim3(TM_H * TM_M * TM_M / 2048), dim3(256), 0, (hipStream_t)stream, dZ0, Z0, ws);
+    hipLaunchKernelGGL(k_tm_pinv_init_bwd_s<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, scale, arg, dA2);
     return launch_rc();
 }
 
@@ -693,7 +833,7 @@ int mil_tm_resconv(const float* qkv, const float* w, int n_pad, float* out, void
 int mil_tm_resconv_bwd(const float* dout, const float* qkv, const float* w, int n_pad, float* dqkv, float* dw, void* stream) {
     if (!dout || !qkv || !w || !dqkv || !dw || n_pad <= 0) return MIL_EINVAL;
     hipLaunchKernelGGL(k_tm_resconv_bwd_dv, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, dout, w, n_pad, dqkv);
-    hipLaunchKernelGGL(k_tm_resconv_bwd_dw, dim3(TM_H * TM_CONV, (n_pad + RC_CHUNK - 1) / RC_CHUNK), dim3(256), 0,
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dw<false>, dim3(TM_H * TM_CONV, (n_pad + RC_CHUNK - 1) / RC_CHUNK), dim3(256), 0,
                        (hipStream_t)stream, dout, qkv, n_pad, dw);
     return launch_rc();
 }
@@ -709,7 +849,7 @@ int mil_tm_ppeg_bwd(const float* dy, const float* x, int s, const float* W7, con
                     float* dWf, float* db, void* stream) {
     if (!dy || !x || !W7 || !W5 || !W3 || !dx || !dWf || !db || s <= 0) return MIL_EINVAL;
     hipLaunchKernelGGL(k_tm_ppeg, dim3(s, 2, (s + PPEG_COLS - 1) / PPEG_COLS), dim3(256), 0, (hipStream_t)stream, dy, s, W7, W7, W5, W5, W3, W3, 1, dx);
-    hipLaunchKernelGGL(k_tm_ppeg_dw, dim3((50 * TM_D + 255) / 256, (s + PPEG_ROWS - 1) / PPEG_ROWS), dim3(256), 0,
+    hipLaunchKernelGGL(k_tm_ppeg_dw<false>, dim3((50 * TM_D + 255) / 256, (s + PPEG_ROWS - 1) / PPEG_ROWS), dim3(256), 0,
                        (hipStream_t)stream, dy, x, s, dWf, db);
     return launch_rc();
 }
@@ -728,6 +868,82 @@ int mil_tm_cls_attn(const float* A1, const float* Z, const float* A3, int n_pad,
     else
         hipLaunchKernelGGL(k_tm_cls_row<1>, dim3((unsigned)((S2 + 63) / 64), TM_H), dim3(256), 0, (hipStream_t)stream, t_ws, A3,
                            n_pad, pad, s, n, len_dev, bag, out);
+    return launch_rc();
+}
+
+// ---- the fixed-order entries: every partial sum a plain store into the caller's workspace, added in ascending order by a
+// second launch; no float atomic, no counter, the launch boundary is the barrier
+size_t mil_tm_bgemm_ws_floats(int batch, int M, int N, int splits) {
+    if (batch <= 0 || M <= 0 || N <= 0 || splits <= 1) return 0;
+    return (size_t)splits * batch * M * N;
+}
+
+int mil_tm_bgemm_fixed(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C,
+                       long sCb, long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta,
+                       float diag, int splits, float* ws, void* stream) {
+    if (splits == 1)
+        return mil_tm_bgemm(A, sAb, sAi, sAk, B, sBb, sBk, sBj, C, sCb, sCi, sCj, D, batch, M, N, K, alpha, beta, diag, 1, stream);
+    if (!A || !B || !C || !ws || batch <= 0 || M <= 0 || N <= 0 || K <= 0 || splits <= 0) return MIL_EINVAL;
+    if ((M + 63) / 64 > 65535 || (long)batch * splits > 65535) return MIL_EINVAL;
+    const long per = (long)batch * M * N;
+    if ((per + 255) / 256 > 0x7fffffffL) return MIL_EINVAL;
+    dim3 grid((N + 63) / 64, (M + 63) / 64, batch * splits);
+    hipLaunchKernelGGL(k_tm_bgemm<true>, grid, dim3(256), 0, (hipStream_t)stream, A, sAb, sAi, sAk, B, sBb, sBk, sBj, ws,
+                       (long)M * N, (long)N, 1L, (const float*)nullptr, M, N, K, alpha, 0.f, 0.f, splits);
+    hipLaunchKernelGGL(k_tm_bgemm_fold, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, splits, C, sCb,
+                       sCi, sCj, D, batch, M, N, beta, diag);
+    return launch_rc();
+}
+
+size_t mil_tm_row_gather_ws_floats(int src_rows) { return src_rows > 0 ? (size_t)3 * src_rows : 0; }
+
+int mil_tm_row_gather_bwd_fixed(const float* ddst, const int32_t* idx, int rows, int E, float* dsrc, int src_rows, float* dextra,
+                                float* ws, void* stream) {
+    if (!ddst || !idx || !dsrc || !ws || rows <= 0 || E <= 0 || src_rows <= 0 || src_rows > (1 << 29)) return MIL_EINVAL;
+    int32_t* meta = reinterpret_cast<int32_t*>(ws);
+    hipLaunchKernelGGL(k_tm_gather_meta_zero, dim3((3 * src_rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, meta, 3 * src_rows);
+    hipLaunchKernelGGL(k_tm_gather_meta, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, idx, rows, src_rows, meta);
+    hipLaunchKernelGGL(k_tm_gather_bwd_fixed, dim3(src_rows + (dextra != nullptr ? 1 : 0)), dim3(256), 0, (hipStream_t)stream, ddst,
+                       idx, rows, E, meta, src_rows, dsrc, dextra);
+    return launch_rc();
+}
+
+size_t mil_tm_pinv_ws_floats(void) { return PINV_CHUNKS; }
+
+int mil_tm_pinv_init_bwd_fixed(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
+                               void* stream) {
+    if (!dZ0 || !Z0 || !scale || !arg || !dA2 || !ws) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_pinv_init_bwd_t, dim3(TM_H * TM_M * TM_M / 256), dim3(256), 0, (hipStream_t)stream, dZ0, scale, dA2);
+    hipLaunchKernelGGL(k_tm_pinv_dot<true>, dim3(PINV_CHUNKS), dim3(256), 0, (hipStream_t)stream, dZ0, Z0, ws);
+    hipLaunchKernelGGL(k_tm_pinv_init_bwd_s<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, scale, arg, dA2);
+    return launch_rc();
+}
+
+size_t mil_tm_resconv_ws_floats(int n_pad) {
+    return n_pad > 0 ? (size_t)((n_pad + RC_CHUNK - 1) / RC_CHUNK) * (TM_H * TM_CONV) : 0;
+}
+
+int mil_tm_resconv_bwd_fixed(const float* dout, const float* qkv, const float* w, int n_pad, float* dqkv, float* dw, float* ws,
+                             void* stream) {
+    if (!dout || !qkv || !w || !dqkv || !dw || !ws || n_pad <= 0) return MIL_EINVAL;
+    const int chunks = (n_pad + RC_CHUNK - 1) / RC_CHUNK;
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dv, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, dout, w, n_pad, dqkv);
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dw<true>, dim3(TM_H * TM_CONV, chunks), dim3(256), 0, (hipStream_t)stream, dout, qkv, n_pad, ws);
+    tm_fold(ws, TM_H * TM_CONV, chunks, TM_H * TM_CONV, dw, (hipStream_t)stream);
+    return launch_rc();
+}
+
+size_t mil_tm_ppeg_ws_floats(int s) { return s > 0 ? (size_t)((s + PPEG_ROWS - 1) / PPEG_ROWS) * (50 * TM_D) : 0; }
+
+int mil_tm_ppeg_bwd_fixed(const float* dy, const float* x, int s, const float* W7, const float* W5, const float* W3, float* dx,
+                          float* dWf, float* db, float* ws, void* stream) {
+    if (!dy || !x || !W7 || !W5 || !W3 || !dx || !dWf || !db || !ws || s <= 0) return MIL_EINVAL;
+    const int chunks = (s + PPEG_ROWS - 1) / PPEG_ROWS;
+    hipLaunchKernelGGL(k_tm_ppeg, dim3(s, 2, (s + PPEG_COLS - 1) / PPEG_COLS), dim3(256), 0, (hipStream_t)stream, dy, s, W7, W7, W5, W5, W3, W3, 1, dx);
+    hipLaunchKernelGGL(k_tm_ppeg_dw<true>, dim3((50 * TM_D + 255) / 256, chunks), dim3(256), 0, (hipStream_t)stream, dy, x, s, ws,
+                       (float*)nullptr);
+    tm_fold(ws, 50 * TM_D, chunks, 49 * TM_D, dWf, (hipStream_t)stream);
+    tm_fold(ws + 49 * TM_D, 50 * TM_D, chunks, TM_D, db, (hipStream_t)stream);
     return launch_rc();
 }
 

@@ -8,7 +8,8 @@ column sum of softmax(qL kL^T)) is taken per bag over its 8 heads, where upstrea
 
 Hot path: _fc1 / to_qkv / to_out on mil_gemm (ops.linear_act), LayerNorm on mil_layernorm_*, the Nystrom core, PPEG and the
 sequence assembly on csrc/transmil.hip (ops.nystrom_core, ops.tm_ppeg, ops.tm_row_gather).  Train mode: to_out's Dropout(0.1)
-draws Philox keep bits from the module's seed and a device pass counter, as ABMIL's masks do."""
+draws Philox keep bits from the module's seed and a device pass counter, as ABMIL's masks do.  `TransMIL.deterministic` (None =
+MIL_TM_DETERMINISTIC) puts every sum that crosses workgroups on its fixed-order entry: two runs then give the same bits."""
 import math
 from typing import List, Optional, Sequence, Tuple
 
@@ -160,18 +161,20 @@ class TransLayer(nn.Module):
         self.attn = NystromAttention(dim=dim)
 
     def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn, cls: Optional[dict] = None,
-            fused_cls: Optional[bool] = None):
+            fused_cls: Optional[bool] = None, deterministic: Optional[bool] = None):
         """x [seq, 512] of one bag -> (x + to_out(Nystrom(LN(x)))[last seq rows], attn map / cls attention [8, s^2] / None).
         cls: the bag length for need_attn="cls", dict(n=N) or dict(len_dev=.., bag=b); fused_cls: ops.nystrom_core's switch of
-        that output (None = the environment)."""
+        that output (None = the environment); deterministic: the fixed-order sums of ops.nystrom_core and ops.tm_row_gather
+        (None = MIL_TM_DETERMINISTIC)."""
         a = self.attn
         ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
-        xp = ops.tm_row_gather(ln, None, pad_idx)                                   # zero rows in front: [n_pad, 512]
+        xp = ops.tm_row_gather(ln, None, pad_idx, deterministic)                    # zero rows in front: [n_pad, 512]
         qkv = ops.linear_act(xp, a.to_qkv.weight, None)
         if cls is not None:
-            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, pad=g["pad"], s=g["s"], fused_cls=fused_cls, **cls)
+            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, pad=g["pad"], s=g["s"], fused_cls=fused_cls,
+                                       deterministic=deterministic, **cls)
         else:
-            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn)
+            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, deterministic=deterministic)
         o = o[g["pad"]:]
         lin = a.to_out[0]
         if bits is None:
@@ -188,9 +191,9 @@ class PPEG(nn.Module):
         self.proj1 = nn.Conv2d(dim, dim, 5, 1, 5 // 2, groups=dim)
         self.proj2 = nn.Conv2d(dim, dim, 3, 1, 3 // 2, groups=dim)
 
-    def run(self, x: torch.Tensor, s: int) -> torch.Tensor:
+    def run(self, x: torch.Tensor, s: int, deterministic: Optional[bool] = None) -> torch.Tensor:
         return ops.tm_ppeg(x, s, self.proj.weight, self.proj.bias, self.proj1.weight, self.proj1.bias, self.proj2.weight,
-                           self.proj2.bias)
+                           self.proj2.bias, deterministic)
 
 
 class TransMIL(nn.Module):
@@ -212,6 +215,7 @@ class TransMIL(nn.Module):
         self.last_bits: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None
         self.force_bits: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None   # tests: masks supplied from outside
         self.fused_cls: Optional[bool] = None        # need_attn="cls" on the fused passes (ops.nystrom_core); None = MIL_TM_FUSED_CLS
+        self.deterministic: Optional[bool] = None    # every cross-workgroup sum in a fixed order (ops.tm_deterministic); None = MIL_TM_DETERMINISTIC
 
     def _drop_state(self, device):
         if self._drop_seed is None:
@@ -263,7 +267,7 @@ class TransMIL(nn.Module):
             geo = [geometry(n) for n in lengths]
             # [cls | tokens | first `add` tokens again] per bag, one gather for all bags; index -2 = the cls row
             idx_dev = torch.tensor(seq_index(lengths), dtype=torch.int32).to(dev, non_blocking=True)
-        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev)
+        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev, self.deterministic)
         return self._run_bags(seqs, geo, need_attn, geom)
 
     def flat_segments(self, x0: torch.Tensor, segs: Sequence[Sequence[Tuple[int, int]]], need_attn=False):
@@ -286,7 +290,7 @@ class TransMIL(nn.Module):
         table = torch.tensor(rows, dtype=torch.int32).to(x0.device, non_blocking=True)
         h = ops.linear_act(x0, self._fc1[0].weight, self._fc1[0].bias, "relu")        # [R, 512]
         idx_dev = ops.tm_seq_index_segs(table, total, R)
-        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev)
+        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev, self.deterministic)
         return self._run_bags(seqs, [geometry(sum(n for _, n in bag)) for bag in segs], need_attn, None)
 
     def _run_bags(self, seqs: torch.Tensor, geo: List[dict], need_attn, geom: Optional[DeviceGeometry]):
@@ -310,9 +314,9 @@ class TransMIL(nn.Module):
             cls = None
             if want_cls:
                 cls = dict(len_dev=geom.len_dev, bag=b) if geom is not None else dict(n=g["N"])
-            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls, self.fused_cls)
-            xb = self.pos_layer.run(xb, g["s"])
-            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls, self.fused_cls)
+            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls, self.fused_cls, self.deterministic)
+            xb = self.pos_layer.run(xb, g["s"], self.deterministic)
+            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls, self.fused_cls, self.deterministic)
             if want_cls and geom is None:
                 a0, a1 = a0[:, :g["N"]], a1[:, :g["N"]]
             cls_rows.append(xb[:1])

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from types import SimpleNamespace
 
@@ -25,11 +26,31 @@ def _tm_splits(M: int, N: int, batch: int, K: int) -> int:
     return max(1, min(K // 256, 512 // tiles))
 
 
+def tm_deterministic(value=None) -> bool:
+    """The switch of the fixed-order sums: the keyword (a module passes its `deterministic` attribute here), else the
+    environment variable MIL_TM_DETERMINISTIC (default 0), read per call."""
+    if value is None:
+        value = os.environ.get("MIL_TM_DETERMINISTIC", "0") not in ("", "0")
+    return bool(value)
+
+
+def _ws(nfloats: int, like):
+    """A fixed-order entry's workspace: one torch.empty (inside a capture it comes from the graph's pool)."""
+    return torch.empty(int(nfloats), device=like.device, dtype=torch.float32)
+
+
 def tm_bgemm(A, sA, B, sB, C, sC, batch: int, M: int, N: int, K: int, alpha: float = 1.0, beta: float = 0.0,
-             diag: float = 0.0, D=None, split: bool = True):
+             diag: float = 0.0, D=None, split: bool = True, deterministic: bool = False):
     """C[b] = alpha A[b] B[b] + beta D[b] (D = C if None) + diag I over general strides (sA = (batch, row, k) etc., in floats);
-    A, B, C, D are tensors or views whose data_ptr is element (0, 0) of batch 0 (mil_tm_bgemm)."""
+    A, B, C, D are tensors or views whose data_ptr is element (0, 0) of batch 0 (mil_tm_bgemm).
+    deterministic (a bool, resolved by the caller): the same split count, but the splits meet in a workspace and are added in
+    ascending order (mil_tm_bgemm_fixed), and C is not zeroed for beta == 0."""
     splits = _tm_splits(M, N, batch, K) if (split and D is None and diag == 0.0 and beta in (0.0, 1.0)) else 1
+    if deterministic and splits > 1:
+        ws = _ws(_lib.lib().mil_tm_bgemm_ws_floats(batch, M, N, splits), C)
+        _lib.checked().mil_tm_bgemm_fixed(_p(A), *sA, _p(B), *sB, _p(C), *sC, _p(D), batch, M, N, K, float(alpha), float(beta),
+                                          float(diag), splits, _p(ws), _stream())
+        return C
     if splits > 1 and beta == 0.0:
         C.zero_()
         beta = 1.0
@@ -52,7 +73,7 @@ class _TmRowGather(torch.autograd.Function):
     """dst[r] = src[idx[r]] (idx >= 0) / extra (idx == -2) / 0 (idx == -1); repeated rows add their gradients."""
 
     @staticmethod
-    def forward(ctx, src, extra, idx):
+    def forward(ctx, src, extra, idx, deterministic=False):
         src = _f32c(src, "src")
         E = src.shape[1]
         dst = torch.empty((idx.numel(), E), device=src.device, dtype=torch.float32)
@@ -61,6 +82,7 @@ class _TmRowGather(torch.autograd.Function):
         ctx.save_for_backward(idx)
         ctx.src_rows, ctx.has_extra = src.shape[0], extra is not None
         ctx.extra_shape = extra.shape if extra is not None else None
+        ctx.deterministic = deterministic
         return dst
 
     @staticmethod
@@ -68,15 +90,23 @@ class _TmRowGather(torch.autograd.Function):
         (idx,) = ctx.saved_tensors
         ddst = _f32c(ddst, "ddst")
         E = ddst.shape[1]
+        if ctx.deterministic:       # every row of dsrc and dextra is written: nothing to zero
+            dsrc = torch.empty((ctx.src_rows, E), device=ddst.device, dtype=torch.float32)
+            dex = torch.empty(E, device=ddst.device, dtype=torch.float32) if ctx.has_extra else None
+            ws = _ws(_lib.lib().mil_tm_row_gather_ws_floats(ctx.src_rows), ddst)
+            _lib.checked().mil_tm_row_gather_bwd_fixed(_p(ddst), _p(idx), idx.numel(), E, _p(dsrc), ctx.src_rows, _p(dex), _p(ws),
+                                                       _stream())
+            return dsrc, (dex.reshape(ctx.extra_shape) if dex is not None else None), None, None
         dsrc = torch.zeros((ctx.src_rows, E), device=ddst.device, dtype=torch.float32)
         dex = torch.zeros(E, device=ddst.device, dtype=torch.float32) if ctx.has_extra else None
         _lib.checked().mil_tm_row_gather_bwd(_p(ddst), _p(idx), idx.numel(), E, _p(dsrc), _p(dex), _stream())
-        return dsrc, (dex.reshape(ctx.extra_shape) if dex is not None else None), None
+        return dsrc, (dex.reshape(ctx.extra_shape) if dex is not None else None), None, None
 
 
-def tm_row_gather(src, extra, idx):
-    """idx: device int32 [rows] (model/dim1/TransMIL.py builds it per bag on the host)."""
-    return _TmRowGather.apply(src, extra, idx)
+def tm_row_gather(src, extra, idx, deterministic=None):
+    """idx: device int32 [rows] (model/dim1/TransMIL.py builds it per bag on the host).  deterministic: the backward adds
+    repeated rows in ascending row order instead of atomically (mil_tm_row_gather_bwd_fixed); None reads MIL_TM_DETERMINISTIC."""
+    return _TmRowGather.apply(src, extra, idx, tm_deterministic(deterministic))
 
 
 def tm_seq_index(len_dev, sides, idx_out, rows_dev=None, flag=None, x_tail=None):
@@ -121,14 +151,14 @@ def tm_seq_index_segs(table, total: int, x_rows: int, idx_out=None, flag=None):
 
 class _TmPPEG(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, s: int, W7, b7, W5, b5, W3, b3):
+    def forward(ctx, x, s: int, W7, b7, W5, b5, W3, b3, deterministic=False):
         x = _f32c(x, "x")
         W7, W5, W3 = _f32c(W7, "W7"), _f32c(W5, "W5"), _f32c(W3, "W3")
         y = torch.empty_like(x)
         _lib.checked().mil_tm_ppeg_fwd(_p(x), s, _p(W7), _p(_f32c(b7, "b7")), _p(W5), _p(_f32c(b5, "b5")), _p(W3),
                                        _p(_f32c(b3, "b3")), _p(y), _stream())
         ctx.save_for_backward(x, W7, W5, W3)
-        ctx.s = s
+        ctx.s, ctx.deterministic = s, deterministic
         return y
 
     @staticmethod
@@ -136,17 +166,25 @@ class _TmPPEG(torch.autograd.Function):
         x, W7, W5, W3 = ctx.saved_tensors
         dy = _f32c(dy, "dy")
         dx = torch.empty_like(x)
-        dWf = torch.zeros((TM_D, 1, 7, 7), device=x.device, dtype=torch.float32)
-        db = torch.zeros(TM_D, device=x.device, dtype=torch.float32)
-        _lib.checked().mil_tm_ppeg_bwd(_p(dy), _p(x), ctx.s, _p(W7), _p(W5), _p(W3), _p(dx), _p(dWf), _p(db), _stream())
+        if ctx.deterministic:       # the fold overwrites dWf and db
+            dWf = torch.empty((TM_D, 1, 7, 7), device=x.device, dtype=torch.float32)
+            db = torch.empty(TM_D, device=x.device, dtype=torch.float32)
+            ws = _ws(_lib.lib().mil_tm_ppeg_ws_floats(ctx.s), x)
+            _lib.checked().mil_tm_ppeg_bwd_fixed(_p(dy), _p(x), ctx.s, _p(W7), _p(W5), _p(W3), _p(dx), _p(dWf), _p(db), _p(ws),
+                                                 _stream())
+        else:
+            dWf = torch.zeros((TM_D, 1, 7, 7), device=x.device, dtype=torch.float32)
+            db = torch.zeros(TM_D, device=x.device, dtype=torch.float32)
+            _lib.checked().mil_tm_ppeg_bwd(_p(dy), _p(x), ctx.s, _p(W7), _p(W5), _p(W3), _p(dx), _p(dWf), _p(db), _stream())
         # one 7 x 7 correlation map: dW7 is all of it, dW5 / dW3 its central 5 x 5 / 3 x 3; the three biases share db
-        return (dx, None, dWf, db, dWf[:, :, 1:6, 1:6].contiguous(), db.clone(), dWf[:, :, 2:5, 2:5].contiguous(), db.clone())
+        return (dx, None, dWf, db, dWf[:, :, 1:6, 1:6].contiguous(), db.clone(), dWf[:, :, 2:5, 2:5].contiguous(), db.clone(), None)
 
 
-def tm_ppeg(x, s: int, W7, b7, W5, b5, W3, b3):
+def tm_ppeg(x, s: int, W7, b7, W5, b5, W3, b3, deterministic=None):
     """PPEG (TransMIL.py:32-47) on one bag's [1 + s^2, 512] rows: cls passed through, the s x s grid through the folded
-    depthwise 7 x 7."""
-    return _TmPPEG.apply(x, s, W7, b7, W5, b5, W3, b3)
+    depthwise 7 x 7.  deterministic: the weight and bias gradients from per-chunk partials added in ascending order
+    (mil_tm_ppeg_bwd_fixed); None reads MIL_TM_DETERMINISTIC."""
+    return _TmPPEG.apply(x, s, W7, b7, W5, b5, W3, b3, tm_deterministic(deterministic))
 
 
 def tm_cls_attention(A1, Z, A3, pad: int, s: int, n=None, len_dev=None, bag: int = 0):
@@ -299,7 +337,9 @@ def _tm_fused_cls(value, need_attn) -> bool:
     return bool(value) and isinstance(need_attn, str) and need_attn == "cls"
 
 
-def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False):
+def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False, det=False):
+    """det: the split-K products on mil_tm_bgemm_fixed; kept in `saved`, so that the backward takes the fixed-order entries too."""
+    bg = functools.partial(tm_bgemm, deterministic=True) if det else tm_bgemm
     if fused_cls:       # the cls attention reads qL, kL, Z and lse3 only: neither map is formed, whatever the two switches say
         fused_a3 = fused_a1 = True
     n = qkv.shape[0]
@@ -314,21 +354,21 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_c
     maps = []                                                   # the bag-sized maps this call forms, softmaxed below
     if not fused_a1:
         A1 = torch.empty((H, n, M), **f32)
-        tm_bgemm(q, (DH, L3, 1), kL, (M * DH, 1, DH), A1, (n * M, M, 1), H, n, M, DH, alpha=TM_QSCALE)
+        bg(q, (DH, L3, 1), kL, (M * DH, 1, DH), A1, (n * M, M, 1), H, n, M, DH, alpha=TM_QSCALE)
         maps.append(A1)
     A2 = torch.empty((H, M, M), **f32)
-    tm_bgemm(qL, (M * DH, DH, 1), kL, (M * DH, 1, DH), A2, (M * M, M, 1), H, M, M, DH)
+    bg(qL, (M * DH, DH, 1), kL, (M * DH, 1, DH), A2, (M * M, M, 1), H, M, M, DH)
     if fused_a3:        # no A3: W and the rows' logsumexp straight from qL and the k | v columns
         for A in maps + [A2]:
             tm_softmax_rows(A)
         W, lse3 = tm_lmk_attn(qkv, qL)
     else:
         A3 = torch.empty((H, M, n), **f32)
-        tm_bgemm(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
+        bg(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
         for A in maps + [A2, A3]:
             tm_softmax_rows(A)
         W = torch.empty((H, M, DH), **f32)
-        tm_bgemm(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
+        bg(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
     # Newton-Schulz pseudo-inverse of A2: Z0 = A2^T / (max row sum x max column sum over the bag's 8 heads), then
     # X = A2 Z, T2 = 15 I - X (7 I - X) = X X - 7 X + 15 I, T3 = 13 I - X T2, Z = Z T3 / 4
     scale = torch.empty(3 + 2 * H, **f32)                       # (s, max row sum, max column sum), per-head maxima behind
@@ -338,46 +378,51 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_c
     _lib.checked().mil_tm_pinv_init(_p(A2), _p(scale), _p(arg), _p(Z), _stream())
     sq = (M * M, M, 1)
     for _ in range(TM_PINV_ITERS):
-        X = tm_bgemm(A2, sq, Z, sq, torch.empty_like(Z), sq, H, M, M, M)
-        T2 = tm_bgemm(X, sq, X, sq, torch.empty_like(Z), sq, H, M, M, M, beta=-7.0, diag=15.0, D=X)
-        T3 = tm_bgemm(X, sq, T2, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, diag=13.0)
-        Zn = tm_bgemm(Z, sq, T3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
+        X = bg(A2, sq, Z, sq, torch.empty_like(Z), sq, H, M, M, M)
+        T2 = bg(X, sq, X, sq, torch.empty_like(Z), sq, H, M, M, M, beta=-7.0, diag=15.0, D=X)
+        T3 = bg(X, sq, T2, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, diag=13.0)
+        Zn = bg(Z, sq, T3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
         Zs.append(Z); Xs.append(X); T2s.append(T2); T3s.append(T3)
         Z = Zn
-    U = tm_bgemm(Z, sq, W, (M * DH, DH, 1), torch.empty((H, M, DH), **f32), (M * DH, DH, 1), H, M, DH, M)
+    U = bg(Z, sq, W, (M * DH, DH, 1), torch.empty((H, M, DH), **f32), (M * DH, DH, 1), H, M, DH, M)
     if fused_a1:        # no A1: O and the rows' logsumexp straight from the q columns, kL and U
         O, lse1 = tm_tok_attn(qkv, kL, U)
     else:
         O = torch.empty((n, TM_D), **f32)
-        tm_bgemm(A1, (n * M, M, 1), U, (M * DH, DH, 1), O, (DH, TM_D, 1), H, n, DH, M)
+        bg(A1, (n * M, M, 1), U, (M * DH, DH, 1), O, (DH, TM_D, 1), H, n, DH, M)
     _lib.checked().mil_tm_resconv(_p(qkv), _p(w), n, _p(O), _stream())
     attn = None
     if need_attn == "cls":  # the cls row of that map folded onto the patches, [8, s^2]: no map is formed
         attn = tm_cls_attention_fused(qkv, qL, kL, Z, lse3, **cls) if fused_cls else tm_cls_attention(A1, Z, A3, **cls)
     elif need_attn:         # A1 Z A3 [8, n_pad, n_pad] (nystrom_attention return_attn), forward only
-        T = tm_bgemm(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
-        attn = tm_bgemm(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
+        T = bg(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
+        attn = bg(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
     saved = SimpleNamespace(qL=qL, kL=kL, A1=A1, lse1=lse1, A2=A2, A3=A3, lse3=lse3, W=W, U=U, Z=Z,
-                            pinv=(scale, arg, Zs, Xs, T2s, T3s))
+                            pinv=(scale, arg, Zs, Xs, T2s, T3s), det=det)
     return O, attn, saved
 
 
-def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s):
+def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s, det=False):
     """dA2 from dZ (the gradient of the last iterate) by the reverse sweep of the six iterations and of Z0."""
+    bg = functools.partial(tm_bgemm, deterministic=True) if det else tm_bgemm
     H, M = TM_H, TM_M
     sq = (M * M, M, 1)
     dA2 = torch.zeros_like(A2)
     for t in reversed(range(TM_PINV_ITERS)):
         Z, X, T2, T3 = Zs[t], Xs[t], T2s[t], T3s[t]
-        dZ = tm_bgemm(G, sq, T3, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)      # Zn = Z T3 / 4
-        dT3 = tm_bgemm(Z, (M * M, 1, M), G, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
-        dT2 = tm_bgemm(X, (M * M, 1, M), dT3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0)   # T3 = 13 I - X T2
-        dX = tm_bgemm(dT3, sq, T2, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, beta=-7.0, D=dT2)
-        tm_bgemm(dT2, sq, X, (M * M, 1, M), dX, sq, H, M, M, M, beta=1.0)                           # T2 = X X - 7 X + 15 I
-        tm_bgemm(X, (M * M, 1, M), dT2, sq, dX, sq, H, M, M, M, beta=1.0)
-        tm_bgemm(dX, sq, Z, (M * M, 1, M), dA2, sq, H, M, M, M, beta=1.0)                           # X = A2 Z
-        tm_bgemm(A2, (M * M, 1, M), dX, sq, dZ, sq, H, M, M, M, beta=1.0)
+        dZ = bg(G, sq, T3, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)      # Zn = Z T3 / 4
+        dT3 = bg(Z, (M * M, 1, M), G, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
+        dT2 = bg(X, (M * M, 1, M), dT3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0)   # T3 = 13 I - X T2
+        dX = bg(dT3, sq, T2, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, beta=-7.0, D=dT2)
+        bg(dT2, sq, X, (M * M, 1, M), dX, sq, H, M, M, M, beta=1.0)                           # T2 = X X - 7 X + 15 I
+        bg(X, (M * M, 1, M), dT2, sq, dX, sq, H, M, M, M, beta=1.0)
+        bg(dX, sq, Z, (M * M, 1, M), dA2, sq, H, M, M, M, beta=1.0)                           # X = A2 Z
+        bg(A2, (M * M, 1, M), dX, sq, dZ, sq, H, M, M, M, beta=1.0)
         G = dZ
+    if det:
+        ws = _ws(_lib.lib().mil_tm_pinv_ws_floats(), A2)
+        _lib.checked().mil_tm_pinv_init_bwd_fixed(_p(G), _p(Zs[0]), _p(scale), _p(arg), _p(dA2), _p(ws), _stream())
+        return dA2
     ws = torch.zeros(1, device=A2.device, dtype=torch.float32)
     _lib.checked().mil_tm_pinv_init_bwd(_p(G), _p(Zs[0]), _p(scale), _p(arg), _p(dA2), _p(ws), _stream())
     return dA2
@@ -389,53 +434,59 @@ def _tm_bwd(dO, qkv, w, saved):
     s = saved
     qL, kL, A1, A2, A3, W, U, Z = s.qL, s.kL, s.A1, s.A2, s.A3, s.W, s.U, s.Z
     fused_a1, fused_a3 = s.lse1 is not None, s.lse3 is not None
+    det = s.det
+    bg = functools.partial(tm_bgemm, deterministic=True) if det else tm_bgemm
     n = qkv.shape[0]
     f32 = dict(device=qkv.device, dtype=torch.float32)
     H, M, DH, L3 = TM_H, TM_M, TM_DH, 3 * TM_D
     q, k, v = qkv, qkv[:, TM_D:], qkv[:, 2 * TM_D:]
     sq, sl = (M * M, M, 1), (M * DH, DH, 1)
     dqkv = torch.empty((n, L3), **f32)
-    dw = torch.zeros(H * TM_CONV, **f32)
+    dw = torch.empty(H * TM_CONV, **f32) if det else torch.zeros(H * TM_CONV, **f32)      # the fold overwrites dw
     if fused_a1:        # dq into columns 0 .. 511 of dqkv before anything adds onto them, dU, and the pass's share of dkL
         _, dU, dkL = tm_tok_attn_bwd(qkv, kL, U, s.lse1, dO, dqkv)
     else:
-        dA1 = tm_bgemm(dO, (DH, TM_D, 1), U, (M * DH, 1, DH), torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, DH)
-        dU = tm_bgemm(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
-    dZ = tm_bgemm(dU, sl, W, (M * DH, 1, DH), torch.empty((H, M, M), **f32), sq, H, M, M, DH)
-    dW = tm_bgemm(Z, (M * M, 1, M), dU, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
+        dA1 = bg(dO, (DH, TM_D, 1), U, (M * DH, 1, DH), torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, DH)
+        dU = bg(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
+    dZ = bg(dU, sl, W, (M * DH, 1, DH), torch.empty((H, M, M), **f32), sq, H, M, M, DH)
+    dW = bg(Z, (M * M, 1, M), dU, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
     if fused_a3:        # dk | dv into dqkv and the pass's share of dqL, before the stages that add onto them
         _, dqL = tm_lmk_attn_bwd(qkv, qL, W, s.lse3, dW, dqkv)
     else:
-        dA3 = tm_bgemm(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
-        tm_bgemm(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)            # dv = A3^T dW
-    _lib.checked().mil_tm_resconv_bwd(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw), _stream())
+        dA3 = bg(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
+        bg(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)            # dv = A3^T dW
+    if det:
+        _lib.checked().mil_tm_resconv_bwd_fixed(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw),
+                                                _p(_ws(_lib.lib().mil_tm_resconv_ws_floats(n), qkv)), _stream())
+    else:
+        _lib.checked().mil_tm_resconv_bwd(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw), _stream())
     if not fused_a1:
         dS1 = tm_softmax_rows_bwd(A1, dA1)
     if not fused_a3:
         dS3 = tm_softmax_rows_bwd(A3, dA3)
-    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv))
+    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv, det=det))
     if not fused_a1:
-        tm_bgemm(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)        # dq
-        dkL = tm_bgemm(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
-    tm_bgemm(dS2, (M * M, 1, M), qL, sl, dkL, sl, H, M, DH, M, beta=1.0)
+        bg(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)        # dq
+        dkL = bg(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
+    bg(dS2, (M * M, 1, M), qL, sl, dkL, sl, H, M, DH, M, beta=1.0)
     if fused_a3:
-        tm_bgemm(dS2, sq, kL, sl, dqL, sl, H, M, DH, M, beta=1.0)
+        bg(dS2, sq, kL, sl, dqL, sl, H, M, DH, M, beta=1.0)
     else:
-        dqL = tm_bgemm(dS2, sq, kL, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
-        tm_bgemm(dS3, (M * n, n, 1), k, (DH, L3, 1), dqL, sl, H, M, DH, n, beta=1.0)
-        tm_bgemm(dS3, (M * n, 1, n), qL, sl, dqkv[:, TM_D:], (DH, L3, 1), H, n, DH, M)              # dk
+        dqL = bg(dS2, sq, kL, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
+        bg(dS3, (M * n, n, 1), k, (DH, L3, 1), dqL, sl, H, M, DH, n, beta=1.0)
+        bg(dS3, (M * n, 1, n), qL, sl, dqkv[:, TM_D:], (DH, L3, 1), H, n, DH, M)              # dk
     _lib.checked().mil_tm_landmarks_bwd(_p(dqL), _p(dkL), n, TM_QSCALE, _p(dqkv), _stream())
     return dqkv, dw
 
 
 class _NystromCore(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False):
+    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False, det=False):
         qkv = _f32c(qkv, "qkv")
         w = _f32c(w, "res_conv.weight")
         if qkv.shape[1] != 3 * TM_D or qkv.shape[0] % TM_M or w.numel() != TM_H * TM_CONV:
             raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
-        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1, fused_cls)
+        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1, fused_cls, det)
         ctx.saved = saved
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
@@ -448,11 +499,11 @@ class _NystromCore(torch.autograd.Function):
         qkv, w = ctx.saved_tensors
         dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved)
         ctx.saved = None
-        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None, None
+        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None, None, None
 
 
 def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0, fused_a3=None,
-                 fused_a1=None, fused_cls=None):
+                 fused_a1=None, fused_cls=None, deterministic=None):
     """qkv [n_pad, 1536] (to_qkv of the front-zero-padded rows, n_pad % 256 == 0), w = res_conv.weight [8, 1, 33, 1] ->
     (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
     [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
@@ -464,12 +515,17 @@ def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=N
     [8, n_pad, 256] map; None reads MIL_TM_FUSED_A1 (default 0).  The two switches are independent of each other.
     fused_cls: with need_attn "cls", the cls attention from the fused passes' operands (tm_cls_attention_fused); None reads
     MIL_TM_FUSED_CLS (default 0).  When it applies BOTH passes run fused, forward and backward, whatever fused_a1 / fused_a3
-    say, and no map is formed; with need_attn False or True it changes nothing."""
+    say, and no map is formed; with need_attn False or True it changes nothing.
+    deterministic: every sum that crosses workgroups in a fixed order (the mil_tm_*_fixed entries: split-K products, the
+    pseudo-inverse scale's gradient, the res_conv weight gradient), forward and backward, so that two runs give the same bits;
+    None reads MIL_TM_DETERMINISTIC (default 0).  It goes with every need_attn and every fused switch."""
+    det = tm_deterministic(deterministic)
     if isinstance(need_attn, bool):
-        return _NystromCore.apply(qkv, w, need_attn, None, _tm_fused_a3(fused_a3, need_attn), _tm_fused_a1(fused_a1, need_attn))
+        return _NystromCore.apply(qkv, w, need_attn, None, _tm_fused_a3(fused_a3, need_attn), _tm_fused_a1(fused_a1, need_attn),
+                                  False, det)
     if not (isinstance(need_attn, str) and need_attn == "cls"):
         raise ValueError(f"nystrom_core: need_attn must be False, True or 'cls', got {need_attn!r}")
     if pad is None or s is None or (n is None) == (len_dev is None):
         raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
     return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False, False,
-                              _tm_fused_cls(fused_cls, "cls"))
+                              _tm_fused_cls(fused_cls, "cls"), det)

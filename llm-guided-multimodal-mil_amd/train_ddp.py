@@ -39,6 +39,12 @@ def build_model(args):
     else:
         from .model.utils import get_model
     model = get_model(args)
+    if getattr(args, "deterministic", 0):
+        # every TransMIL module of the model (the image-only extractor; the fusion model's aggregator and its unused
+        # extractor); a model without one has no float atomic in its step and nothing to set
+        for m in model.modules():
+            if type(m).__name__ == "TransMIL":
+                m.deterministic = True
     if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
             and getattr(args, "transmil_graph", 0)):
         model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward

@@ -126,7 +126,10 @@ class RaggedTransMILStepper:
         training = bool(m.training)
         attn = bool(getattr(m, "patch_attn", False))
         # a graph captured without the attention outputs is never replayed for a request with them, and the other way round
-        key = ("transmil-sides", slot.sides, training, self.backward) + (("patch_attn",) if attn else ())
+        # ... nor is one captured on the atomic sums replayed for a model that asks for the fixed-order ones
+        det = ops.tm_deterministic(m.extractor_pathology.deterministic)
+        key = (("transmil-sides", slot.sides, training, self.backward) + (("patch_attn",) if attn else ())
+               + (("deterministic",) if det else ()))
         body = lambda: self._body(slot)      # noqa: E731
         ctr = m.extractor_pathology._drop_ctr
         # the warm-up passes in front of a capture draw masks too: the pass counter goes back, so the stream of a replayed

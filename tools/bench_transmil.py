@@ -17,7 +17,11 @@ materialised (MIL_TM_FUSED_A3=0: the A3 map, its softmax and their products), fu
 materialised again - same model, same bag, same process, the switch read per call; median (min - max) of --reps regions each
 and the peak allocated bytes of one step per route.
 --fused-a1: the same three columns for the token-query pass (MIL_TM_FUSED_A1=0: the A1 map, its softmax and their products;
-=1: csrc/token_attn.hip).  MIL_TM_FUSED_A3 is left as the environment has it and reported: run it once with 0 and once with 1."""
+=1: csrc/token_attn.hip).  MIL_TM_FUSED_A3 is left as the environment has it and reported: run it once with 0 and once with 1.
+--deterministic: per N, the eager TRAINING step with the fixed-order sums off and on (TransMIL.deterministic, the switch of
+MIL_TM_DETERMINISTIC / --deterministic 1) in ALTERNATING regions - off, on, off, on .. - of one process, same model, same bag;
+median (min - max) of --reps regions each; a region is one untimed step behind the flip and one timed step.  With --graph the replayed step as well: the stepper keeps one graph per setting
+(the flag is part of its key) and the regions alternate between the two."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -244,6 +248,60 @@ def fused_rows(a, dev, args, env="MIL_TM_FUSED_A3", name="a3"):
         torch.cuda.empty_cache()
 
 
+def det_rows(a, dev, args):
+    from mil_amd import ops
+    from mil_amd.optim import FlatAdam
+    from mil_amd.transmil_step import RaggedTransMILStepper
+    bce = torch.nn.BCELoss()
+    y = syn.make_labels(3, 1).to(dev)
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+
+    def alternate(fn, ext, res, tag):
+        for on in (False, True, False, True):     # both settings warm (with a stepper: eager visit, capture) before any is timed
+            ext.deterministic = on
+            for _ in range(max(a.warmup, 2)):
+                fn()
+        ts = {False: [], True: []}
+        for _ in range(a.reps):
+            for on in (False, True):            # a region: one untimed step behind the flip (it runs on what the other
+                ext.deterministic = on          # setting left in the caches; a training run never alternates), one timed
+                ts[on] += region_times(fn, 1, 1)
+        for on, name in ((False, "off"), (True, "on")):
+            res.update({f"{tag}_{name}_ms": round(med(ts[on]), 3), f"{tag}_{name}_min_ms": round(min(ts[on]), 3),
+                        f"{tag}_{name}_max_ms": round(max(ts[on]), 3)})
+        res[f"{tag}_on_minus_off_us"] = round(1e3 * (med(ts[True]) - med(ts[False])), 1)
+
+    for N in a.N:
+        torch.manual_seed(1234)
+        model = get_model(args).to(dev).train()
+        opt = FlatAdam(list(model.parameters()), lr=1e-5, counted=True)
+        x = syn.make_bags(N, 1, N, 768)[0].to(dev)
+
+        def eager():
+            opt.zero_grad()
+            _, prob = model([x], [N])
+            ops.backward(bce(prob, y))
+            opt.step()
+
+        res = dict(N=N, n_pad=geometry(N)["n_pad"], regions=a.reps)
+        alternate(eager, model.extractor_pathology, res, "eager")
+        if a.graph:
+            torch.manual_seed(1234)
+            m_r = get_model(args).to(dev).train()
+            o_r = FlatAdam(list(m_r.parameters()), lr=1e-5, counted=True)
+            st = RaggedTransMILStepper(m_r, o_r, B=1, drop_seed=1)
+            slot = st.slot([N])
+            slot.x[:N].copy_(x)
+            slot.y.copy_(y)
+            alternate(lambda: st.step(slot, [N]), m_r.extractor_pathology, res, "replay")
+            assert st.n_graphs == 2, st.n_graphs
+            res["graphs"] = st.n_graphs
+            del st, slot, m_r, o_r
+        print(json.dumps(res), flush=True)
+        del model, opt, x
+        torch.cuda.empty_cache()
+
+
 def region_times(fn, reps, warm):
     for _ in range(warm):
         fn()
@@ -274,6 +332,8 @@ def main():
                     "pass materialised, fused (MIL_TM_FUSED_A3=1), materialised again: ms and peak allocated bytes")
     ap.add_argument("--fused-a1", dest="fused_a1", action="store_true", help="the same for the token-query pass "
                     "(MIL_TM_FUSED_A1); MIL_TM_FUSED_A3 stays as the environment has it")
+    ap.add_argument("--deterministic", action="store_true", help="eager training step per N with the fixed-order sums off and "
+                    "on in alternating regions; with --graph the replayed step too")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
@@ -286,6 +346,9 @@ def main():
         return
     if a.fused_a1:
         fused_rows(a, dev, args, "MIL_TM_FUSED_A1", "a1")
+        return
+    if a.deterministic:
+        det_rows(a, dev, args)
         return
     if a.graph or a.ragged:
         if a.graph:
