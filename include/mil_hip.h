@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 16 */
+int mil_abi_version(void);   /* 17 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1186,6 +1186,23 @@ size_t mil_tm_bgemm_ws_floats(int batch, int M, int N, int splits);
 int mil_tm_bgemm_fixed(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C, long sCb,
                        long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta, float diag,
                        int splits, float* ws, void* stream);
+/* ---- TransMIL, the batched product on split-bf16 MFMA (csrc/tm_bgemm_pieces.hip; ops: pieces=3 / MIL_TM_PIECES=3) ----
+ * mil_tm_bgemm_pieces: mil_tm_bgemm's operation over the same strides, with the contraction on v_mfma_f32_32x32x16_bf16:
+ * every fp32 element of A and B is split into three bf16 pieces as it is staged (exact: a = a0 + a1 + a2) and the six cross
+ * terms (p, q), p + q <= 2, are added smallest first into one fp32 accumulator, which folds into a second one every 512
+ * of K - fp32-level error (tests/test_gpu_tm_pieces_stages.py holds it to float64 at the bound of mil_tm_bgemm).  Nothing
+ * is pre-split in memory.  `pieces` must be 3 (anything else: MIL_EINVAL, nothing launched); every rule of mil_tm_bgemm
+ * holds (splits > 1: beta 1, D null, atomic adds onto an initialised C).  K slices are 32 deep: split p takes slices
+ * [p per, (p + 1) per), per = ceil(ceil(K / 32) / splits).  The entry picks the tile (64 x 64, or 128 x 64 for M > 256).
+ * Non-finite inputs give non-finite outputs, not necessarily of the same kind (an infinity times a zero piece is a NaN).
+ * mil_tm_bgemm_pieces_fixed: as mil_tm_bgemm_fixed - splits == 1 is the very launch of mil_tm_bgemm_pieces; splits > 1
+ * stores the partial tiles into ws (mil_tm_bgemm_ws_floats) and the same fold launch adds them in ascending order. */
+int mil_tm_bgemm_pieces(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C,
+                        long sCb, long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta,
+                        float diag, int splits, int pieces, void* stream);
+int mil_tm_bgemm_pieces_fixed(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C,
+                              long sCb, long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta,
+                              float diag, int splits, int pieces, float* ws, void* stream);
 /* mil_tm_row_gather's backward for ANY index: dsrc [src_rows, E] row i <- the sum of the rows r of ddst with idx[r] == i, r
  * ascending (zeros when none; an idx[r] >= src_rows is ignored), dextra [E] (nullable) <- the sum of the rows with idx[r] ==
  * -2, r ascending.  Per source row a count and the first and last naming row are taken with INTEGER atomics (order-free);

@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -205,6 +205,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_bgemm_ws_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mil_tm_bgemm_fixed": (c_int, [_P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P]
                            + [c_int] * 4 + [c_float] * 3 + [c_int, _P, _P]),
+    "mil_tm_bgemm_pieces": (c_int, [_P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P]
+                            + [c_int] * 4 + [c_float] * 3 + [c_int, c_int, _P]),
+    "mil_tm_bgemm_pieces_fixed": (c_int, [_P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P, c_long, c_long, c_long, _P]
+                                  + [c_int] * 4 + [c_float] * 3 + [c_int, c_int, _P, _P]),
     "mil_tm_row_gather_ws_floats": (c_size_t, [c_int]),
     "mil_tm_row_gather_bwd_fixed": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, _P, _P]),
     "mil_tm_pinv_ws_floats": (c_size_t, []),

@@ -121,6 +121,11 @@ def create_arg_parser(argv=None):
                    "TransMIL, --aggregator TransMIL --fusion_transmil 1), eager or replayed (--transmil_graph 1).  Models "
                    "without a TransMIL module accept the flag and do nothing: their steps hold no float atomic.  0: the "
                    "environment variable MIL_TM_DETERMINISTIC decides (default off)")
+    p.add_argument("--tm_gemm_pieces", type=int, default=0, choices=[0, 3],
+                   help="train_ddp.py and test_ddp.py: 3 = the Nystrom core's products with K >= 256 (the pseudo-inverse chain, "
+                        "W, U, O and their gradients) as three-piece split-bf16 products on bf16 MFMA, six cross terms, "
+                        "fp32-level error; set on every TransMIL module of the model.  Models without a TransMIL module accept "
+                        "the flag and ignore it.  0: the environment variable MIL_TM_PIECES decides (default 0 = fp32 MFMA)")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,

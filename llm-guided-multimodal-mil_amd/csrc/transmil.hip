@@ -17,12 +17,13 @@
 #include <hip/hip_runtime.h>
 
 #include "mil_common.h"
+#include "tm_bgemm.h"
 #include "../../include/mil_hip.h"
 
 namespace {
 
 constexpr int TM_H = 8, TM_DH = 64, TM_D = 512, TM_QKV = 3 * TM_D, TM_M = 256, TM_CONV = 33;
-constexpr int BG_BK = 16, BG_LD = 64 + 4, BG_FOLD = 32;
+constexpr int BG_BK = 16, BG_LD = 64 + 4, BG_FOLD = BG_FOLD_K / BG_BK;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -109,41 +110,7 @@ __global__ __launch_bounds__(256) void k_tm_bgemm(const float* __restrict__ A, l
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] += tot[i];
 
-    const int col = j0 + 32 * wj + r;
-    if (col >= N) return;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int row = i0 + 32 * wi + mfma32_row(i, h);
-        if (row >= M) continue;
-        float* cp = C + row * sCi + col * sCj;
-        float v = alpha * acc[i];
-        if constexpr (FIXED) {
-            const long batch = gridDim.z / splits;                        // C = ws + bz M N already (sCb = M N)
-            C[(split * batch * M + row) * N + col] = v;
-        } else if (splits == 1) {
-            if (beta != 0.f) v += beta * (D != nullptr ? D[row * sCi + col * sCj] : *cp);
-            if (row == col) v += diag;
-            *cp = v;
-        } else {
-            if (row == col && split == 0) v += diag;
-            atomicAdd(cp, v);
-        }
-    }
-}
-
-// C[b][i][j] = sum_p ws[p][b][i][j] (p = 0, 1, .. splits - 1 in that order) + beta D[b][i][j] + diag [i == j], thread per element
-// with the lanes along j; D = C when null.  The launch boundary behind k_tm_bgemm<true> is the only ordering it needs.
-__global__ __launch_bounds__(256) void k_tm_bgemm_fold(const float* __restrict__ ws, int splits, float* C, long sCb, long sCi,
-                                                       long sCj, const float* D, int batch, int M, int N, float beta, float diag) {
-    const long per = (long)batch * M * N, e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= per) return;
-    const int col = (int)(e % N), row = (int)((e / N) % M);
-    const long off = (e / ((long)M * N)) * sCb + row * sCi + col * sCj;
-    float v = ws[e];
-    for (int p = 1; p < splits; ++p) v += ws[p * per + e];
-    if (beta != 0.f) v += beta * (D != nullptr ? D[off] : C[off]);
-    if (row == col) v += diag;
-    C[off] = v;
+    tm_bgemm_store<FIXED>(acc, C, sCi, sCj, D, M, N, i0 + 32 * wi, j0 + 32 * wj + r, h, alpha, beta, diag, splits, split);
 }
 
 // out[e] = sum_c ws[c * stride + e] for c = 0, 1, .. chunks - 1 in that order, e < n: the second launch of every fixed-order
@@ -729,10 +696,7 @@ extern "C" {
 int mil_tm_bgemm(const float* A, long sAb, long sAi, long sAk, const float* B, long sBb, long sBk, long sBj, float* C, long sCb,
                  long sCi, long sCj, const float* D, int batch, int M, int N, int K, float alpha, float beta, float diag,
                  int splits, void* stream) {
-    if (!A || !B || !C || batch <= 0 || M <= 0 || N <= 0 || K <= 0 || splits <= 0 ||
-        (splits > 1 && (beta != 1.f || D != nullptr)))
-        return MIL_EINVAL;
-    if ((M + 63) / 64 > 65535 || (long)batch * splits > 65535) return MIL_EINVAL;
+    if (!tm_bgemm_args_ok(A, B, C, batch, M, N, K, splits, 64) || !tm_bgemm_atomic_ok(beta, D, splits)) return MIL_EINVAL;
     dim3 grid((N + 63) / 64, (M + 63) / 64, batch * splits);
     hipLaunchKernelGGL(k_tm_bgemm<false>, grid, dim3(256), 0, (hipStream_t)stream, A, sAb, sAi, sAk, B, sBb, sBk, sBj, C, sCb, sCi,
                        sCj, D, M, N, K, alpha, beta, diag, splits);
@@ -883,15 +847,11 @@ int mil_tm_bgemm_fixed(const float* A, long sAb, long sAi, long sAk, const float
                        float diag, int splits, float* ws, void* stream) {
     if (splits == 1)
         return mil_tm_bgemm(A, sAb, sAi, sAk, B, sBb, sBk, sBj, C, sCb, sCi, sCj, D, batch, M, N, K, alpha, beta, diag, 1, stream);
-    if (!A || !B || !C || !ws || batch <= 0 || M <= 0 || N <= 0 || K <= 0 || splits <= 0) return MIL_EINVAL;
-    if ((M + 63) / 64 > 65535 || (long)batch * splits > 65535) return MIL_EINVAL;
-    const long per = (long)batch * M * N;
-    if ((per + 255) / 256 > 0x7fffffffL) return MIL_EINVAL;
+    if (!ws || !tm_bgemm_args_ok(A, B, C, batch, M, N, K, splits, 64) || !tm_bgemm_fold_ok(batch, M, N)) return MIL_EINVAL;
     dim3 grid((N + 63) / 64, (M + 63) / 64, batch * splits);
     hipLaunchKernelGGL(k_tm_bgemm<true>, grid, dim3(256), 0, (hipStream_t)stream, A, sAb, sAi, sAk, B, sBb, sBk, sBj, ws,
                        (long)M * N, (long)N, 1L, (const float*)nullptr, M, N, K, alpha, 0.f, 0.f, splits);
-    hipLaunchKernelGGL(k_tm_bgemm_fold, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, splits, C, sCb,
-                       sCi, sCj, D, batch, M, N, beta, diag);
+    tm_bgemm_fold(ws, splits, C, sCb, sCi, sCj, D, batch, M, N, beta, diag, (hipStream_t)stream);
     return launch_rc();
 }
 

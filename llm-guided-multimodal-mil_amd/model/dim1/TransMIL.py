@@ -9,7 +9,8 @@ column sum of softmax(qL kL^T)) is taken per bag over its 8 heads, where upstrea
 Hot path: _fc1 / to_qkv / to_out on mil_gemm (ops.linear_act), LayerNorm on mil_layernorm_*, the Nystrom core, PPEG and the
 sequence assembly on csrc/transmil.hip (ops.nystrom_core, ops.tm_ppeg, ops.tm_row_gather).  Train mode: to_out's Dropout(0.1)
 draws Philox keep bits from the module's seed and a device pass counter, as ABMIL's masks do.  `TransMIL.deterministic` (None =
-MIL_TM_DETERMINISTIC) puts every sum that crosses workgroups on its fixed-order entry: two runs then give the same bits."""
+MIL_TM_DETERMINISTIC) puts every sum that crosses workgroups on its fixed-order entry: two runs then give the same bits.
+`TransMIL.gemm_pieces` (None = MIL_TM_PIECES; 0 or 3) runs the Nystrom core's K >= 256 products on three-piece split-bf16 MFMA."""
 import math
 from typing import List, Optional, Sequence, Tuple
 
@@ -161,20 +162,20 @@ class TransLayer(nn.Module):
         self.attn = NystromAttention(dim=dim)
 
     def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn, cls: Optional[dict] = None,
-            fused_cls: Optional[bool] = None, deterministic: Optional[bool] = None):
+            fused_cls: Optional[bool] = None, deterministic: Optional[bool] = None, gemm_pieces: Optional[int] = None):
         """x [seq, 512] of one bag -> (x + to_out(Nystrom(LN(x)))[last seq rows], attn map / cls attention [8, s^2] / None).
         cls: the bag length for need_attn="cls", dict(n=N) or dict(len_dev=.., bag=b); fused_cls: ops.nystrom_core's switch of
         that output (None = the environment); deterministic: the fixed-order sums of ops.nystrom_core and ops.tm_row_gather
-        (None = MIL_TM_DETERMINISTIC)."""
+        (None = MIL_TM_DETERMINISTIC); gemm_pieces: ops.nystrom_core's `pieces` (None = MIL_TM_PIECES)."""
         a = self.attn
         ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         xp = ops.tm_row_gather(ln, None, pad_idx, deterministic)                    # zero rows in front: [n_pad, 512]
         qkv = ops.linear_act(xp, a.to_qkv.weight, None)
         if cls is not None:
             o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, pad=g["pad"], s=g["s"], fused_cls=fused_cls,
-                                       deterministic=deterministic, **cls)
+                                       deterministic=deterministic, pieces=gemm_pieces, **cls)
         else:
-            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, deterministic=deterministic)
+            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, deterministic=deterministic, pieces=gemm_pieces)
         o = o[g["pad"]:]
         lin = a.to_out[0]
         if bits is None:
@@ -216,6 +217,7 @@ class TransMIL(nn.Module):
         self.force_bits: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None   # tests: masks supplied from outside
         self.fused_cls: Optional[bool] = None        # need_attn="cls" on the fused passes (ops.nystrom_core); None = MIL_TM_FUSED_CLS
         self.deterministic: Optional[bool] = None    # every cross-workgroup sum in a fixed order (ops.tm_deterministic); None = MIL_TM_DETERMINISTIC
+        self.gemm_pieces: Optional[int] = None       # 3: the Nystrom core's products on split-bf16 MFMA (ops.tm_pieces); None = MIL_TM_PIECES
 
     def _drop_state(self, device):
         if self._drop_seed is None:
@@ -314,9 +316,9 @@ class TransMIL(nn.Module):
             cls = None
             if want_cls:
                 cls = dict(len_dev=geom.len_dev, bag=b) if geom is not None else dict(n=g["N"])
-            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls, self.fused_cls, self.deterministic)
+            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls, self.fused_cls, self.deterministic, self.gemm_pieces)
             xb = self.pos_layer.run(xb, g["s"], self.deterministic)
-            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls, self.fused_cls, self.deterministic)
+            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls, self.fused_cls, self.deterministic, self.gemm_pieces)
             if want_cls and geom is None:
                 a0, a1 = a0[:, :g["N"]], a1[:, :g["N"]]
             cls_rows.append(xb[:1])

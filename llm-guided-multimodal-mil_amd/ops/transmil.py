@@ -14,7 +14,8 @@ from ._base import _f32c, _p, _stream
 
 # Nystrom attention of one bag (nystrom_attention: 8 heads x 64, 256 landmarks, 6 pseudo-inverse iterations, 33-tap residual
 # conv on v) on the [n_pad, 1536] to_qkv rows of its front-zero-padded LayerNorm output; PPEG; the row gather of the
-# sequence assembly.  Every product runs on mil_tm_bgemm, reading per-head operands in place out of the merged rows.
+# sequence assembly.  Every product runs on mil_tm_bgemm, reading per-head operands in place out of the merged rows; with
+# pieces=3 (MIL_TM_PIECES=3) the products that _tm_pieces_route names run on mil_tm_bgemm_pieces (split-bf16 MFMA) instead.
 TM_H, TM_DH, TM_D, TM_M, TM_CONV, TM_PINV_ITERS = 8, 64, 512, 256, 33, 6
 TM_QSCALE = TM_DH ** -0.5
 
@@ -34,26 +35,59 @@ def tm_deterministic(value=None) -> bool:
     return bool(value)
 
 
+def tm_pieces(value=None) -> int:
+    """The switch of the split-bf16 products: the keyword (a module passes its `gemm_pieces` attribute here), else the
+    environment variable MIL_TM_PIECES (default 0), read per call.  0: every product on fp32 MFMA; 3: the products that
+    _tm_pieces_route names on three-piece split-bf16 MFMA (mil_tm_bgemm_pieces).  Anything else raises ValueError."""
+    if value is None:
+        value = os.environ.get("MIL_TM_PIECES", "") or "0"
+    try:
+        pieces = int(value)
+    except (TypeError, ValueError):
+        pieces = -1
+    if isinstance(value, bool) or pieces not in (0, 3):
+        raise ValueError(f"TransMIL gemm pieces must be 0 or 3, got {value!r}")
+    return pieces
+
+
+def _tm_pieces_route(M: int, N: int, K: int) -> bool:
+    """Which products take mil_tm_bgemm_pieces when pieces == 3: those with K >= 256 - the pseudo-inverse chain and its
+    backward (256^3), W, U, O, dU, dW, dq, dk, dv, dqL, dkL, and the whole-map products of need_attn True.  The K = 64
+    products (A1, A2, A3, dA1, dA3, dZ) stay on mil_tm_bgemm: those that write a bag-sized map are bound by their output,
+    not by the matrix pipe, and two 32-deep slices do not pay for the split."""
+    return K >= 256
+
+
 def _ws(nfloats: int, like):
     """A fixed-order entry's workspace: one torch.empty (inside a capture it comes from the graph's pool)."""
     return torch.empty(int(nfloats), device=like.device, dtype=torch.float32)
 
 
 def tm_bgemm(A, sA, B, sB, C, sC, batch: int, M: int, N: int, K: int, alpha: float = 1.0, beta: float = 0.0,
-             diag: float = 0.0, D=None, split: bool = True, deterministic: bool = False):
+             diag: float = 0.0, D=None, split: bool = True, deterministic: bool = False, pieces: int = 0):
     """C[b] = alpha A[b] B[b] + beta D[b] (D = C if None) + diag I over general strides (sA = (batch, row, k) etc., in floats);
     A, B, C, D are tensors or views whose data_ptr is element (0, 0) of batch 0 (mil_tm_bgemm).
     deterministic (a bool, resolved by the caller): the same split count, but the splits meet in a workspace and are added in
-    ascending order (mil_tm_bgemm_fixed), and C is not zeroed for beta == 0."""
+    ascending order (mil_tm_bgemm_fixed), and C is not zeroed for beta == 0.
+    pieces (0 or 3, resolved by the caller): 3 puts the product on the split-bf16 entries (mil_tm_bgemm_pieces, _fixed) when
+    _tm_pieces_route takes its shape; the split count and what deterministic means are the same on either arithmetic."""
+    if pieces not in (0, 3):
+        raise ValueError(f"tm_bgemm: pieces must be 0 or 3, got {pieces!r}")
     splits = _tm_splits(M, N, batch, K) if (split and D is None and diag == 0.0 and beta in (0.0, 1.0)) else 1
+    pw = (pieces,) if pieces and _tm_pieces_route(M, N, K) else ()          # the extra argument of the split-bf16 entries
     if deterministic and splits > 1:
         ws = _ws(_lib.lib().mil_tm_bgemm_ws_floats(batch, M, N, splits), C)
-        _lib.checked().mil_tm_bgemm_fixed(_p(A), *sA, _p(B), *sB, _p(C), *sC, _p(D), batch, M, N, K, float(alpha), float(beta),
-                                          float(diag), splits, _p(ws), _stream())
+        entry = _lib.checked().mil_tm_bgemm_pieces_fixed if pw else _lib.checked().mil_tm_bgemm_fixed
+        entry(_p(A), *sA, _p(B), *sB, _p(C), *sC, _p(D), batch, M, N, K, float(alpha), float(beta), float(diag), splits, *pw,
+              _p(ws), _stream())
         return C
     if splits > 1 and beta == 0.0:
         C.zero_()
         beta = 1.0
+    if pw:
+        _lib.checked().mil_tm_bgemm_pieces(_p(A), *sA, _p(B), *sB, _p(C), *sC, _p(D), batch, M, N, K, float(alpha), float(beta),
+                                           float(diag), splits, *pw, _stream())
+        return C
     _lib.checked().mil_tm_bgemm(_p(A), *sA, _p(B), *sB, _p(C), *sC, _p(D), batch, M, N, K, float(alpha), float(beta),
                                 float(diag), splits, _stream())
     return C
@@ -337,9 +371,43 @@ def _tm_fused_cls(value, need_attn) -> bool:
     return bool(value) and isinstance(need_attn, str) and need_attn == "cls"
 
 
-def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False, det=False):
-    """det: the split-K products on mil_tm_bgemm_fixed; kept in `saved`, so that the backward takes the fixed-order entries too."""
-    bg = functools.partial(tm_bgemm, deterministic=True) if det else tm_bgemm
+def _tm_bg(det: bool, pieces: int):
+    """tm_bgemm with the arithmetic of one core call bound: the fixed-order split-K form and / or the split-bf16 route."""
+    kw = {}
+    if det:
+        kw["deterministic"] = True
+    if pieces:
+        kw["pieces"] = pieces
+    return functools.partial(tm_bgemm, **kw) if kw else tm_bgemm
+
+
+def _tm_pinv_fwd(A2, det=False, pieces=0):
+    """Newton-Schulz pseudo-inverse of A2 [8, 256, 256]: Z0 = A2^T / (max row sum x max column sum over the bag's 8 heads), then
+    six times X = A2 Z, T2 = 15 I - X (7 I - X) = X X - 7 X + 15 I, T3 = 13 I - X T2, Z = Z T3 / 4.  Returns the last Z and what
+    _tm_pinv_bwd takes: (scale, arg, Zs, Xs, T2s, T3s)."""
+    bg = _tm_bg(det, pieces)
+    H, M = TM_H, TM_M
+    f32 = dict(device=A2.device, dtype=torch.float32)
+    scale = torch.empty(3 + 2 * H, **f32)                       # (s, max row sum, max column sum), per-head maxima behind
+    arg = torch.empty(1 + H, device=A2.device, dtype=torch.int32)
+    Zs, Xs, T2s, T3s = [], [], [], []
+    Z = torch.empty((H, M, M), **f32)
+    _lib.checked().mil_tm_pinv_init(_p(A2), _p(scale), _p(arg), _p(Z), _stream())
+    sq = (M * M, M, 1)
+    for _ in range(TM_PINV_ITERS):
+        X = bg(A2, sq, Z, sq, torch.empty_like(Z), sq, H, M, M, M)
+        T2 = bg(X, sq, X, sq, torch.empty_like(Z), sq, H, M, M, M, beta=-7.0, diag=15.0, D=X)
+        T3 = bg(X, sq, T2, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, diag=13.0)
+        Zn = bg(Z, sq, T3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
+        Zs.append(Z); Xs.append(X); T2s.append(T2); T3s.append(T3)
+        Z = Zn
+    return Z, (scale, arg, Zs, Xs, T2s, T3s)
+
+
+def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False, det=False, pieces=0):
+    """det: the split-K products on mil_tm_bgemm_fixed; kept in `saved`, so that the backward takes the fixed-order entries too.
+    pieces: 3 routes the products of _tm_pieces_route to mil_tm_bgemm_pieces; kept in `saved` the same way."""
+    bg = _tm_bg(det, pieces)
     if fused_cls:       # the cls attention reads qL, kL, Z and lse3 only: neither map is formed, whatever the two switches say
         fused_a3 = fused_a1 = True
     n = qkv.shape[0]
@@ -369,21 +437,8 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_c
             tm_softmax_rows(A)
         W = torch.empty((H, M, DH), **f32)
         bg(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
-    # Newton-Schulz pseudo-inverse of A2: Z0 = A2^T / (max row sum x max column sum over the bag's 8 heads), then
-    # X = A2 Z, T2 = 15 I - X (7 I - X) = X X - 7 X + 15 I, T3 = 13 I - X T2, Z = Z T3 / 4
-    scale = torch.empty(3 + 2 * H, **f32)                       # (s, max row sum, max column sum), per-head maxima behind
-    arg = torch.empty(1 + H, device=dev, dtype=torch.int32)
-    Zs, Xs, T2s, T3s = [], [], [], []
-    Z = torch.empty((H, M, M), **f32)
-    _lib.checked().mil_tm_pinv_init(_p(A2), _p(scale), _p(arg), _p(Z), _stream())
+    Z, pinv = _tm_pinv_fwd(A2, det, pieces)
     sq = (M * M, M, 1)
-    for _ in range(TM_PINV_ITERS):
-        X = bg(A2, sq, Z, sq, torch.empty_like(Z), sq, H, M, M, M)
-        T2 = bg(X, sq, X, sq, torch.empty_like(Z), sq, H, M, M, M, beta=-7.0, diag=15.0, D=X)
-        T3 = bg(X, sq, T2, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, diag=13.0)
-        Zn = bg(Z, sq, T3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
-        Zs.append(Z); Xs.append(X); T2s.append(T2); T3s.append(T3)
-        Z = Zn
     U = bg(Z, sq, W, (M * DH, DH, 1), torch.empty((H, M, DH), **f32), (M * DH, DH, 1), H, M, DH, M)
     if fused_a1:        # no A1: O and the rows' logsumexp straight from the q columns, kL and U
         O, lse1 = tm_tok_attn(qkv, kL, U)
@@ -398,13 +453,13 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_c
         T = bg(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
         attn = bg(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
     saved = SimpleNamespace(qL=qL, kL=kL, A1=A1, lse1=lse1, A2=A2, A3=A3, lse3=lse3, W=W, U=U, Z=Z,
-                            pinv=(scale, arg, Zs, Xs, T2s, T3s), det=det)
+                            pinv=pinv, det=det, pieces=pieces)
     return O, attn, saved
 
 
-def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s, det=False):
+def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s, det=False, pieces=0):
     """dA2 from dZ (the gradient of the last iterate) by the reverse sweep of the six iterations and of Z0."""
-    bg = functools.partial(tm_bgemm, deterministic=True) if det else tm_bgemm
+    bg = _tm_bg(det, pieces)
     H, M = TM_H, TM_M
     sq = (M * M, M, 1)
     dA2 = torch.zeros_like(A2)
@@ -434,8 +489,8 @@ def _tm_bwd(dO, qkv, w, saved):
     s = saved
     qL, kL, A1, A2, A3, W, U, Z = s.qL, s.kL, s.A1, s.A2, s.A3, s.W, s.U, s.Z
     fused_a1, fused_a3 = s.lse1 is not None, s.lse3 is not None
-    det = s.det
-    bg = functools.partial(tm_bgemm, deterministic=True) if det else tm_bgemm
+    det, pieces = s.det, getattr(s, "pieces", 0)
+    bg = _tm_bg(det, pieces)
     n = qkv.shape[0]
     f32 = dict(device=qkv.device, dtype=torch.float32)
     H, M, DH, L3 = TM_H, TM_M, TM_DH, 3 * TM_D
@@ -464,7 +519,7 @@ def _tm_bwd(dO, qkv, w, saved):
         dS1 = tm_softmax_rows_bwd(A1, dA1)
     if not fused_a3:
         dS3 = tm_softmax_rows_bwd(A3, dA3)
-    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv, det=det))
+    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv, det=det, pieces=pieces))
     if not fused_a1:
         bg(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)        # dq
         dkL = bg(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
@@ -481,12 +536,12 @@ def _tm_bwd(dO, qkv, w, saved):
 
 class _NystromCore(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False, det=False):
+    def forward(ctx, qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False, det=False, pieces=0):
         qkv = _f32c(qkv, "qkv")
         w = _f32c(w, "res_conv.weight")
         if qkv.shape[1] != 3 * TM_D or qkv.shape[0] % TM_M or w.numel() != TM_H * TM_CONV:
             raise _lib.MilHipError(f"nystrom_core: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape")
-        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1, fused_cls, det)
+        O, attn, saved = _tm_fwd(qkv, w, need_attn, cls, fused_a3, fused_a1, fused_cls, det, pieces)
         ctx.saved = saved
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
@@ -499,11 +554,11 @@ class _NystromCore(torch.autograd.Function):
         qkv, w = ctx.saved_tensors
         dqkv, dw = _tm_bwd(_f32c(dO, "dO"), qkv, w, ctx.saved)
         ctx.saved = None
-        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None, None, None
+        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None, None, None, None
 
 
 def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=None, bag: int = 0, fused_a3=None,
-                 fused_a1=None, fused_cls=None, deterministic=None):
+                 fused_a1=None, fused_cls=None, deterministic=None, pieces=None):
     """qkv [n_pad, 1536] (to_qkv of the front-zero-padded rows, n_pad % 256 == 0), w = res_conv.weight [8, 1, 33, 1] ->
     (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
     [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
@@ -518,14 +573,19 @@ def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=N
     say, and no map is formed; with need_attn False or True it changes nothing.
     deterministic: every sum that crosses workgroups in a fixed order (the mil_tm_*_fixed entries: split-K products, the
     pseudo-inverse scale's gradient, the res_conv weight gradient), forward and backward, so that two runs give the same bits;
-    None reads MIL_TM_DETERMINISTIC (default 0).  It goes with every need_attn and every fused switch."""
+    None reads MIL_TM_DETERMINISTIC (default 0).  It goes with every need_attn and every fused switch.
+    pieces: 0 or 3.  3 runs the core's products with K >= 256 (_tm_pieces_route) as three-piece split-bf16 products on
+    v_mfma_f32_32x32x16_bf16 (mil_tm_bgemm_pieces; fp32-level error), forward and backward; None reads MIL_TM_PIECES (default 0;
+    any value but 0 / 3 raises ValueError).  It goes with every need_attn, every fused switch and deterministic; the fused
+    passes have kernels of their own and are untouched."""
     det = tm_deterministic(deterministic)
+    pieces = tm_pieces(pieces)
     if isinstance(need_attn, bool):
         return _NystromCore.apply(qkv, w, need_attn, None, _tm_fused_a3(fused_a3, need_attn), _tm_fused_a1(fused_a1, need_attn),
-                                  False, det)
+                                  False, det, pieces)
     if not (isinstance(need_attn, str) and need_attn == "cls"):
         raise ValueError(f"nystrom_core: need_attn must be False, True or 'cls', got {need_attn!r}")
     if pad is None or s is None or (n is None) == (len_dev is None):
         raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
     return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False, False,
-                              _tm_fused_cls(fused_cls, "cls"), det)
+                              _tm_fused_cls(fused_cls, "cls"), det, pieces)

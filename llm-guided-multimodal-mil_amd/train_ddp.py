@@ -45,6 +45,10 @@ def build_model(args):
         for m in model.modules():
             if type(m).__name__ == "TransMIL":
                 m.deterministic = True
+    if getattr(args, "tm_gemm_pieces", 0):
+        for m in model.modules():           # the same modules; a model without one ignores the flag
+            if type(m).__name__ == "TransMIL":
+                m.gemm_pieces = int(args.tm_gemm_pieces)
     if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
             and getattr(args, "transmil_graph", 0)):
         model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward

@@ -128,8 +128,10 @@ class RaggedTransMILStepper:
         # a graph captured without the attention outputs is never replayed for a request with them, and the other way round
         # ... nor is one captured on the atomic sums replayed for a model that asks for the fixed-order ones
         det = ops.tm_deterministic(m.extractor_pathology.deterministic)
+        # ... nor one captured on the fp32 products for a model that asks for the split-bf16 ones
+        pieces = ops.tm_pieces(m.extractor_pathology.gemm_pieces)
         key = (("transmil-sides", slot.sides, training, self.backward) + (("patch_attn",) if attn else ())
-               + (("deterministic",) if det else ()))
+               + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ()))
         body = lambda: self._body(slot)      # noqa: E731
         ctr = m.extractor_pathology._drop_ctr
         # the warm-up passes in front of a capture draw masks too: the pass counter goes back, so the stream of a replayed

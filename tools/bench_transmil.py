@@ -21,7 +21,10 @@ and the peak allocated bytes of one step per route.
 --deterministic: per N, the eager TRAINING step with the fixed-order sums off and on (TransMIL.deterministic, the switch of
 MIL_TM_DETERMINISTIC / --deterministic 1) in ALTERNATING regions - off, on, off, on .. - of one process, same model, same bag;
 median (min - max) of --reps regions each; a region is one untimed step behind the flip and one timed step.  With --graph the replayed step as well: the stepper keeps one graph per setting
-(the flag is part of its key) and the regions alternate between the two."""
+(the flag is part of its key) and the regions alternate between the two.
+--pieces 3: the default rows (eval forward, forward + backward) with the Nystrom core's K >= 256 products on three-piece
+split-bf16 MFMA (TransMIL.gemm_pieces, the switch of MIL_TM_PIECES / --tm_gemm_pieces); --pieces 0 pins the fp32 products.  The
+rows carry the value and the min - max of the regions next to the median: run 0 and 3 one after the other on one machine."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -334,6 +337,8 @@ def main():
                     "(MIL_TM_FUSED_A1); MIL_TM_FUSED_A3 stays as the environment has it")
     ap.add_argument("--deterministic", action="store_true", help="eager training step per N with the fixed-order sums off and "
                     "on in alternating regions; with --graph the replayed step too")
+    ap.add_argument("--pieces", type=int, choices=[0, 3], default=None, help="the default rows with TransMIL.gemm_pieces set: 3 = "
+                    "split-bf16 products in the Nystrom core, 0 = fp32 products; unset: MIL_TM_PIECES decides")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
@@ -358,6 +363,8 @@ def main():
         return
     torch.manual_seed(1234)
     model = get_model(args).to(dev).eval()        # eval: dropout off, gradients still flow
+    if a.pieces is not None:
+        model.extractor_pathology.gemm_pieces = a.pieces
     p = {k.replace("extractor_pathology.", ""): v.detach() for k, v in model.state_dict().items()}
     pr = {k: v.clone().requires_grad_(True) for k, v in p.items()}
     y = syn.make_labels(3, 1).to(dev)
@@ -385,8 +392,14 @@ def main():
             bce(torch.sigmoid(h @ pr["fc.1.weight"].t() + pr["fc.1.bias"]).unsqueeze(0), y).backward()
 
         gf = transmil_flops(N) / 1e9
-        res = dict(N=N, n_pad=geometry(N)["n_pad"], gf_fwd=round(gf, 2), gf_step=round(3 * gf, 2),
-                   fwd_ms=round(timed(fwd, a.reps, a.warmup), 3), step_ms=round(timed(step, a.reps, a.warmup), 3))
+        res = dict(N=N, n_pad=geometry(N)["n_pad"], gf_fwd=round(gf, 2), gf_step=round(3 * gf, 2))
+        for tag, fn in (("fwd", fwd), ("step", step)):
+            ts = region_times(fn, a.reps, a.warmup)
+            res[tag + "_ms"] = round(sorted(ts)[len(ts) // 2], 3)
+            if a.pieces is not None:
+                res.update({tag + "_min_ms": round(min(ts), 3), tag + "_max_ms": round(max(ts), 3)})
+        if a.pieces is not None:
+            res["pieces"] = a.pieces
         res["step_frac_peak"] = round(3 * gf / (res["step_ms"] * 1e-3) / (PEAK_TF * 1e3), 4)
         if not a.no_torch:
             res["torch_fwd_ms"] = round(timed(t_fwd, a.reps, a.warmup), 3)
