@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 17 */
+int mil_abi_version(void);   /* 18 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1084,6 +1084,17 @@ int mil_tm_seq_index(const int32_t* len_dev, int B, const int32_t* s_of_bag, int
  * dropped. */
 int mil_tm_seq_index_segs(const int32_t* table_dev, int B, int total, int x_rows, int32_t* idx_out, int idx_rows, int32_t* flag_dev,
                           void* stream);
+/* The same index for the fusion model's capacity bucket, from the bag lengths ON THE DEVICE (a step replayed from a hipGraph).
+ * The source rows are [cap patch rows | B x tail[0] | B x tail[1] | ..]: `tail` is a HOST array of ntail <= 4 per-bag row counts
+ * (>= 1 each), s_of_bag a HOST array of B <= 16 grid sides, both by value in the launch.  Bag b's pieces in sequence order are
+ * (cap + B (tail[0] + .. + tail[j-1]) + b tail[j], tail[j]) for every j, then its patches (len[0] + .. + len[b-1], len[b]); the
+ * entries are those of mil_tm_seq_index_segs on these pieces with x_rows = cap + B sum(tail) (<= 2^29): 1 + s_b^2 per bag, -2,
+ * the pieces' rows, the first s_b^2 - L_b again, the position clamped into the bag, a row outside the source -> -1.  A length is
+ * read as min(max(len, 0), x_rows).  L_dev_out [B] (nullable) = len[b] + sum(tail), the bag's sequence rows.  flag_dev [1]
+ * (nullable) is set to 1 (never cleared here) when an L_b lies outside ((s_b - 1)^2, s_b^2], a length had to be clamped, a
+ * row was dropped, or the lengths together exceed cap.  One launch, no table, no host sync. */
+int mil_tm_seq_index_bucket(const int32_t* len_dev, int B, int cap, const int32_t* tail, int ntail, const int32_t* s_of_bag,
+                            int32_t* idx_out, int idx_rows, int32_t* L_dev_out, int32_t* flag_dev, void* stream);
 /* Landmarks: qL, kL [8, 256, 64] = means of l = n_pad / 256 consecutive rows of q (times qscale) and k, zero pad rows
  * counted.  Backward: dqkv's q and k columns += the spread-out landmark gradients. */
 int mil_tm_landmarks(const float* qkv, int n_pad, float qscale, float* qL, float* kL, void* stream);

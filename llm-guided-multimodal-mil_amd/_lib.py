@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -185,6 +185,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_row_gather_bwd": (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
     "mil_tm_seq_index": (c_int, [_P, c_int, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P]),
     "mil_tm_seq_index_segs": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P]),
+    "mil_tm_seq_index_bucket": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P]),
     "mil_tm_landmarks": (c_int, [_P, c_int, c_float, _P, _P, _P]),
     "mil_tm_landmarks_bwd": (c_int, [_P, _P, c_int, c_float, _P, _P]),
     "mil_tm_pinv_init": (c_int, [_P] * 4 + [_P]),

@@ -112,8 +112,15 @@ def create_arg_parser(argv=None):
                    "all-reduce and one Adam launch per step (optim.FlatAdam); 0 = torch DDP + torch.optim.Adam")
     p.add_argument("--fusion_transmil", type=int, default=0, help="--variant fusion: 1 = build --aggregator TransMIL (and "
                    "--model_pathology TransMIL's unused extractor) over the multi-modal bag, rows in upstream's sequence "
-                   "order, bags one after another; eager autograd path only (refused with --hip_graph 1).  0: both "
+                   "order, bags one after another; eager autograd path (refused with --hip_graph 1; its graph path is "
+                   "--fusion_transmil_graph 1).  0: both "
                    "values raise NotImplementedError as before")
+    p.add_argument("--fusion_transmil_graph", type=int, default=0, help="--variant fusion --aggregator TransMIL "
+                   "--fusion_transmil 1 --flat_adam 1, modality ['pathology'] or ['CT','pathology']: replay the step from one "
+                   "hipGraph per (row capacity, grid sides of the multi-modal bags), bag lengths and TransMIL's gather index on "
+                   "the device (fusion_step.RaggedFusionTransMILStepper); Adam inside the graph at world size 1; the training "
+                   "step runs on TransMIL's fixed-order sums (--deterministic 1 implied).  test_ddp.py "
+                   "replays its per-bag eval forward from the same graphs.  Refused with --hip_graph 1 and --learnablePrompt 1")
     p.add_argument("--deterministic", type=int, default=0, help="train_ddp.py and test_ddp.py: 1 = every sum of the TransMIL "
                    "forward and backward that crosses workgroups (split-K products, the gather's backward, the res_conv and "
                    "PPEG weight gradients) is taken in an order fixed by the shapes, without float atomics, so that two runs "
@@ -131,6 +138,18 @@ def create_arg_parser(argv=None):
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,
         # TransMIL's shapes follow the grid side of each bag
         raise ValueError("--fusion_transmil 1 runs on the eager autograd path only: drop --hip_graph 1")
+    if args.fusion_transmil_graph:
+        # refused here too: the stepper replays the fusion model's TransMIL-aggregator step with a counted FlatAdam inside
+        if (args.variant != "fusion" or args.aggregator != "TransMIL" or not args.fusion_transmil or not args.flat_adam):
+            raise ValueError("--fusion_transmil_graph 1 needs --variant fusion --aggregator TransMIL --fusion_transmil 1 "
+                             "--flat_adam 1")
+        if list(args.modality) not in (["pathology"], ["CT", "pathology"]):
+            raise ValueError("--fusion_transmil_graph 1 is built for --modality \"['pathology']\" and \"['CT','pathology']\"")
+        if args.learnablePrompt:
+            raise ValueError("--fusion_transmil_graph 1: learnable prompts (their SGD inside the graph) are not built, "
+                             "drop --learnablePrompt 1")
+        if args.save_note_attn:
+            raise ValueError("--fusion_transmil_graph 1 keeps no attention weights: drop --save_note_attn")
     if args.save_patch_attn and (args.variant != "image_only" or args.model_pathology != "TransMIL"):
         # refused here, before an entry point touches the GPU
         raise ValueError("--save_patch_attn writes TransMIL's cls-token attention: it needs --variant image_only "

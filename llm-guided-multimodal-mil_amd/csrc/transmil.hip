@@ -357,6 +357,77 @@ __global__ __launch_bounds__(256) void k_tm_seq_index_segs(const int32_t* __rest
     idx[r] = (int32_t)row;
 }
 
+// The same index for the fusion model's CAPACITY BUCKET (segments.FusionBucket), from the bag lengths on the device: the source
+// rows are [cap patch rows | B tail_0 | B tail_1 | ..], bag b's pieces in sequence order are its tail segments in row order,
+// (cap + B sum_{k<j} tail_k + b tail_j, tail_j), then its patches (len[0] + .. + len[b-1], len[b]).  Sides and tail counts come
+// by value (what the captured step is keyed by), so there is no table and no host hop.  Entry by entry this is
+// k_tm_seq_index_segs on those pieces: the position clamped into [0, L_b - 1], a row outside [0, cap + B sum tail) -> -1.
+// Thread 0 of bag b's cls entry writes L_out[b] = len[b] + tail and raises `flag` (sticky) when L_b lies outside
+// ((s_b - 1)^2, s_b^2]; thread 0 of the grid raises it when the lengths together exceed cap.
+struct TmBucketGeo {
+    int s[TM_MAX_BAGS];
+    int tail[TM_SEG_MAX];
+    int ntail;
+};
+
+__device__ __forceinline__ int tm_bucket_len(const int32_t* __restrict__ len_dev, int b, int x_rows) {
+    return min(max(len_dev[b], 0), x_rows);                  // x_rows <= 2^29: L fits an int, the offsets are summed in long
+}
+
+__global__ __launch_bounds__(256) void k_tm_seq_index_bucket(const int32_t* __restrict__ len_dev, int B, int cap, TmBucketGeo geo,
+                                                             int total, int x_rows, int32_t* __restrict__ idx,
+                                                             int32_t* __restrict__ L_out, int32_t* __restrict__ flag) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r == 0 && flag) {
+        long rows = 0;
+        for (int b = 0; b < B; ++b) rows += max(len_dev[b], 0);
+        if (rows > cap) flag[0] = 1;
+    }
+    if (r >= total) return;
+    int b = 0, first = 0;
+    long off = 0;
+    for (; b < B - 1; ++b) {
+        const int seq = 1 + geo.s[b] * geo.s[b];
+        if (r < first + seq) break;
+        first += seq;
+        off += tm_bucket_len(len_dev, b, x_rows);
+    }
+    const int s = geo.s[b], j = r - first, n = tm_bucket_len(len_dev, b, x_rows);
+    int tails = 0;
+#pragma unroll
+    for (int k = 0; k < TM_SEG_MAX; ++k) tails += k < geo.ntail ? geo.tail[k] : 0;
+    const int L = tails + n;                                 // >= 1: every tail segment holds a row
+    if (j == 0) {
+        if (L_out) L_out[b] = L;
+        if ((L > s * s || L <= (s - 1) * (s - 1) || n != len_dev[b]) && flag) flag[0] = 1;
+        idx[r] = -2;
+        return;
+    }
+    int pos = j - 1;
+    if (pos >= L) pos -= L;                                  // the repeat of the first s^2 - L rows
+    pos = min(max(pos, 0), L - 1);
+    long row = -1, base = cap;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < TM_SEG_MAX; ++k) {
+        const int t = k < geo.ntail ? geo.tail[k] : 0;
+        if (found) continue;
+        if (pos < t) {
+            row = base + (long)b * t + pos;
+            found = true;
+        } else {
+            pos -= t;
+            base += (long)B * t;
+        }
+    }
+    if (!found) row = off + pos;                      // the patches: behind those of the bags in front
+    if (row < 0 || row >= x_rows) {
+        if (flag) flag[0] = 1;
+        row = -1;
+    }
+    idx[r] = (int32_t)row;
+}
+
 // qL [8, 256, 64] = qscale * mean of l consecutive q rows, kL the same of k (no scale); thread per (landmark, q|k column)
 __global__ __launch_bounds__(256) void k_tm_landmarks(const float* __restrict__ qkv, int l, float qscale, float* qL, float* kL) {
     const int j = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;        // c < 1024
@@ -757,6 +828,30 @@ int mil_tm_seq_index_segs(const int32_t* table_dev, int B, int total, int x_rows
         return MIL_EINVAL;
     hipLaunchKernelGGL(k_tm_seq_index_segs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table_dev, B,
                        total, x_rows, idx_out, flag_dev);
+    return launch_rc();
+}
+
+int mil_tm_seq_index_bucket(const int32_t* len_dev, int B, int cap, const int32_t* tail, int ntail, const int32_t* s_of_bag,
+                            int32_t* idx_out, int idx_rows, int32_t* L_dev_out, int32_t* flag_dev, void* stream) {
+    if (!len_dev || !tail || !s_of_bag || !idx_out || B <= 0 || B > TM_MAX_BAGS || cap <= 0 || ntail < 1 || ntail > TM_SEG_MAX)
+        return MIL_EINVAL;
+    TmBucketGeo geo{};
+    long total = 0, x_rows = cap;
+    for (int b = 0; b < B; ++b) {
+        const int s = s_of_bag[b];
+        if (s < 1 || s > 4096) return MIL_EINVAL;
+        geo.s[b] = s;
+        total += 1 + (long)s * s;
+    }
+    for (int k = 0; k < ntail; ++k) {
+        if (tail[k] < 1 || tail[k] > (1 << 20)) return MIL_EINVAL;
+        geo.tail[k] = tail[k];
+        x_rows += (long)B * tail[k];
+    }
+    geo.ntail = ntail;
+    if (total > idx_rows || x_rows > (1 << 29)) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_seq_index_bucket, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, len_dev, B,
+                       cap, geo, (int)total, (int)x_rows, idx_out, L_dev_out, flag_dev);
     return launch_rc();
 }
 

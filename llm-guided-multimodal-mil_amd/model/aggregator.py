@@ -19,7 +19,9 @@ they always did): the multi-modal bag is aggregated by TransMIL (dim1/TransMIL.p
 the bag's pieces in upstream's sequence order (aggregator.py:173,184,192,195) while the rows stay where they lie in memory;
 the sequence is assembled through an index written on the device (ops.tm_seq_index_segs).  Upstream feeds TransMIL's
 returned TUPLE `(h, attn)` into `self.fc` (aggregator.py:199-200), which cannot run; the dataflow built here is element 0,
-`h [B, 512]`, into `fc`.  Bags run one after another, eager autograd path only (no `bucket=`, no hipGraph replay).
+`h [B, 512]`, into `fc`.  Bags run one after another, on the eager autograd path; `bucket=` is taken only from
+fusion_step.RaggedFusionTransMILStepper, whose bucket carries the TransMIL geometry of the step's key (`bucket.tm_geom`: sides
+from the key, gather index written on the device, TransMIL.flat_bucket) - any other bucket raises as before.
 `model_pathology="TransMIL"` builds `extractor_pathology` for the state_dict alone (aggregator.py:54-56): never called."""
 import math
 from typing import List, Optional
@@ -33,6 +35,7 @@ from ..bags import BagLayout
 from .sam.transformer import TwoWayTransformer
 
 EMBED = 512
+HEAD_DROP_KEY = 0x48656164467573      # the head's Dropout(0.25) on the replayed TransMIL-aggregator step: seed ^ this
 
 
 def _arg(args, name, default):
@@ -112,6 +115,13 @@ class aggregator(nn.Module):
         self.last_note_attn = None
         self.last_bag_attn = None
         self._tm_bag_attn = None
+        self._tm_geom, self._tm_len_dev = None, None       # set per forward from bucket.tm_geom (the replayed TransMIL step)
+        self.last_head_bits = None
+        # graph_eval (train_ddp.build_model sets it for --fusion_transmil_graph 1): an eval-mode, no-grad forward of ONE bag
+        # given as the reference gives it - model([ct,] x [1, N, F], ids) - is replayed from the graph of its key
+        # (fusion_step.RaggedFusionTransMILStepper without backward, the text tower inside the replay); test_ddp.py's loop
+        self.graph_eval = False
+        self._eval_stepper = None
         self._note_dir, self._note_names, self._note_kept, self._note_done = None, None, [], 0
 
     NOTE_KEEP_BYTES = 1 << 30
@@ -196,8 +206,16 @@ class aggregator(nn.Module):
     def _lin_tanh(self, seq: nn.Sequential, x, rows_dev=None):
         return ops.linear_act(x, seq[0].weight, seq[0].bias, "tanh", rows_dev=rows_dev)
 
-    def _head(self, M):
-        if self.training:
+    def _head(self, M, geom=None):
+        if self.training and geom is not None:
+            # the replayed step: torch's generator cannot be rewound after the warm-up passes of a capture, so Dropout(0.25)
+            # draws Philox keep bits at the aggregator's device pass counter (which _run_bags has just advanced); the bits are
+            # an output of the step (last_head_bits)
+            tm = self.aggregator
+            self.last_head_bits = ops.dropout_keep_bits(M.shape[0], EMBED, 0.25, tm._drop_seed ^ HEAD_DROP_KEY, 0, M.device,
+                                                        offset_dev=tm._drop_ctr)
+            M = ops.dropout_bits(M, self.last_head_bits, 1.0 / 0.75)
+        elif self.training:
             M = F.dropout(M, 0.25, True)
         p, z = ops.head_sigmoid(M, self.fc[1].weight, self.fc[1].bias)
         self.last_logits = z
@@ -222,7 +240,12 @@ class aggregator(nn.Module):
                                                         1 if ce else 0, head_train=self.training)
             self.last_logits, self.last_loss = z, loss
             return p
-        if self._is_transmil():
+        geom = self._tm_geom
+        if self._is_transmil() and geom is not None:
+            # the capacity-bucket form (fusion_step.RaggedFusionTransMILStepper): lengths on the device, sides from the key
+            M, _ = self.aggregator.flat_bucket(x0, geom, self._tm_len_dev)
+            self._tm_bag_attn = None
+        elif self._is_transmil():
             # TransMIL returns (h, attn); element 0 feeds fc.  need_attn="cls" only under note_attn (eval, no grad)
             want = self._wants_note_attn()
             M, attn = self.aggregator.flat_segments(x0, segs, need_attn="cls" if want else False)
@@ -240,7 +263,7 @@ class aggregator(nn.Module):
         else:
             M = self.aggregator.flat(x0, layout) if hasattr(self, "aggregator") else x0
         self.last_pooled = M                               # [B, 512]: what the head saw (parity checks, like last_logits)
-        p = self._head(M)
+        p = self._head(M, geom)
         if y is not None:
             crit = torch.nn.CrossEntropyLoss() if C > 2 else torch.nn.BCELoss()
             self.last_loss = crit(p, y) * (1.0 if self._loss_scale is None else
@@ -341,6 +364,43 @@ class aggregator(nn.Module):
         x0 = ops.append_rows(k_p, torch.cat([q_ct, k_ct, q_p], 0), tail_reserved=True)        # :173 (no concat of the patches)
         return self._pool_head(x0, bucket.layout, None), q_ct.view(B, P, EMBED), q_p.view(B, P, EMBED)
 
+    def _graph_eval_forward(self, x_list, x_CI):
+        """One bag through the replayed forward, or None when the call is not one the stepper takes (then the eager forward
+        runs as always).  Returns the shipped module's tuple; the tensors are the graph's static outputs, valid until the next
+        forward of that key."""
+        modality = list(self.args.modality)
+        with_ct = modality == ["CT", "pathology"]
+        if not self._is_transmil() or (modality != ["pathology"] and not with_ct) or len(x_list) != (2 if with_ct else 1):
+            return None
+        x = x_list[-1]
+        if x.dim() == 2:
+            x = x.unsqueeze(0)
+        ct = x_list[0] if with_ct else None
+        if (x.dim() != 3 or x.shape[0] != 1 or not x.is_cuda or x_CI is None or x_CI.dim() != 3 or x_CI.shape[0] != 1
+                or x_CI.shape[1] > 12 or (ct is not None and ct.shape[0] != 1)):
+            return None
+        st = self._eval_stepper
+        if st is None:
+            # tower_in_graph=True switches the text tower to its fixed-shape form (clinic_extractor.model.static_rows) for
+            # good, as RaggedFusionStepper / RaggedFusionInference do: a later call that falls back to the eager forward
+            # below (a bag the bucket cannot take) runs the tower in that form too - the same values, padded launches
+            from ..fusion_step import RaggedFusionTransMILStepper
+            st = self._eval_stepper = RaggedFusionTransMILStepper(
+                self, None, B=1, P=int(x_CI.shape[1]), in_dim=int(x.shape[2]), ctx_len=int(x_CI.shape[2]), backward=False,
+                ct_shape=tuple(ct.shape[1:]) if ct is not None else None, tower_in_graph=True)
+        n = int(x.shape[1])
+        slot = st.slot(n)
+        if (not slot.bucket.fits([n]) or x.shape[2] != st.in_dim or tuple(x_CI.shape[1:]) != tuple(slot.ids.shape[1:])
+                or (ct is not None and tuple(ct.shape) != tuple(slot.ct.shape))):
+            return None
+        slot.x[:n].copy_(x[0], non_blocking=True)
+        if ct is not None:
+            slot.ct.copy_(ct, non_blocking=True)
+        slot.ids.copy_(x_CI, non_blocking=True)             # the text tower is part of the replayed forward
+        _, prob = st.step(slot, [n])
+        self.last_pooled, self.last_logits = st.last["h"], st.last["logits"]
+        return (prob, *st.last["tokens"])
+
     # ------------------------------------------------------------------ forward (aggregator.py:134-209)
     def forward(self, x_list: List[torch.Tensor], x_CI: torch.Tensor, lengths: Optional[List[int]] = None,
                 text_features: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
@@ -368,11 +428,24 @@ class aggregator(nn.Module):
         # labels [B, C] float one-hot (optional, an extension of the reference signature): the criterion of
         # train_ddp.py:323-324 evaluated inside, result in `self.last_loss` (mean loss unless loss_scale is given);
         # the return tuple is unchanged
+        if (self.graph_eval and bucket is None and not self.training and not torch.is_grad_enabled() and lengths is None
+                and text_features is None and labels is None and not self._wants_note_attn()):
+            out = self._graph_eval_forward(x_list, x_CI)
+            if out is not None:
+                return out
         self._labels, self._loss_scale, self.last_loss, self.last_pooled = labels, loss_scale, None, None
+        self.last_head_bits = None
         modality = self.args.modality
-        if bucket is not None and self._is_transmil():
+        self._tm_geom = getattr(bucket, "tm_geom", None) if self._is_transmil() else None
+        self._tm_len_dev = bucket.len_dev if self._tm_geom is not None else None
+        if bucket is not None and self._is_transmil() and self._tm_geom is None:
             raise NotImplementedError("bucket=: the capacity-bucket forward is built for the ABMIL aggregator; TransMIL's "
-                                      "shapes follow the grid side ceil(sqrt(rows)) of each bag (eager path only)")
+                                      "shapes follow the grid side ceil(sqrt(rows)) of each bag (eager path, or a bucket that "
+                                      "carries the TransMIL geometry: fusion_step.RaggedFusionTransMILStepper)")
+        if self._tm_geom is not None and (self._tm_geom.cap != bucket.cap or self._tm_geom.B != bucket.B
+                                          or list(self._tm_geom.tail) != list(bucket.tail)):
+            raise ValueError(f"bucket of {bucket.B} bags x {bucket.cap} rows, tail {bucket.tail}: its TransMIL geometry is for "
+                             f"{self._tm_geom.B} bags x {self._tm_geom.cap} rows, tail {list(self._tm_geom.tail)}")
         want = self._wants_note_attn()
         if want:
             self.last_note_attn = self.last_bag_attn = None

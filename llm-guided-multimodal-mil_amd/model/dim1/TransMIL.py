@@ -98,6 +98,32 @@ def seq_index_segments(segs: Sequence[Sequence[Tuple[int, int]]], sides: Optiona
     return idx
 
 
+def bucket_segments(lengths: Sequence[int], cap: int, tail: Sequence[int]) -> Tuple[List[List[Tuple[int, int]]], int]:
+    """(the pieces of every bag of a capacity bucket in sequence order, the rows of the source): the source is [cap patch rows
+    | B x tail[0] | B x tail[1] | ..], bag b's sequence is its tail segments in row order, then its patches (upstream
+    aggregator.py:173,192).  A length is read as min(max(len, 0), rows of the source), as the kernel reads it."""
+    B, cap, tail = len(lengths), int(cap), [int(t) for t in tail]
+    x_rows = cap + B * sum(tail)
+    lens = [min(max(int(n), 0), x_rows) for n in lengths]
+    segs, off = [], 0
+    for b in range(B):
+        bag, base = [], cap
+        for t in tail:
+            bag.append((base + b * t, t))
+            base += B * t
+        bag.append((off, lens[b]))
+        off += lens[b]
+        segs.append(bag)
+    return segs, x_rows
+
+
+def seq_index_bucket(lengths: Sequence[int], cap: int, tail: Sequence[int], sides: Optional[Sequence[int]] = None) -> List[int]:
+    """The host mirror of ops.tm_seq_index_bucket (csrc/transmil.hip: k_tm_seq_index_bucket), entry by entry: the pieces from
+    the lengths, then seq_index_segments on them.  sides default to the side of each bag's len + sum(tail) rows."""
+    segs, x_rows = bucket_segments(lengths, cap, tail)
+    return seq_index_segments(segs, sides, x_rows)
+
+
 def segment_table(segs: Sequence[Sequence[Tuple[int, int]]], sides: Optional[Sequence[int]] = None) -> Tuple[List[List[int]], int]:
     """(rows of the int32 table ops.tm_seq_index_segs reads - per bag [s, first0, len0, .. first3, len3] -, the number of
     index entries sum(1 + s^2))."""
@@ -140,6 +166,40 @@ class DeviceGeometry:
     def update(self, x_tail: Optional[torch.Tensor] = None):
         """Index and row count from the lengths now in len_dev; x_tail: the slot's input buffer, its rows behind the bags zeroed."""
         ops.tm_seq_index(self.len_dev, self.sides, self.idx, self.rows_dev, self.flag, x_tail)
+        return self
+
+
+class BucketGeometry:
+    """DeviceGeometry's counterpart for the fusion model's capacity bucket (segments.FusionBucket): the bags' rows lie in
+    pieces of [cap patch rows | B x tail_j ..], the patch counts sit in the bucket's `len_dev`, and a captured step is keyed by
+    (cap, sides).  Holds the gather index ops.tm_seq_index_bucket writes from those lengths, the sequence lengths `L_dev`, the
+    STATIC index that puts the cls row in front of every bag (cls_idx: -2 at a bag's first entry, the entry's own row elsewhere),
+    the per-side pad index and the out-of-bucket flag."""
+
+    def __init__(self, cap: int, tail: Sequence[int], sides: Sequence[int], device, pad_cache: Optional[dict] = None,
+                 flag: Optional[torch.Tensor] = None):
+        self.cap, self.tail = int(cap), tuple(int(t) for t in tail)
+        self.sides = tuple(int(s) for s in sides)
+        self.B = len(self.sides)
+        self.x_rows = self.cap + self.B * sum(self.tail)                  # rows of the multi-modal bag buffer
+        i32 = dict(device=device, dtype=torch.int32)
+        self.total = sum(1 + s * s for s in self.sides)
+        self.idx = torch.zeros(self.total, **i32)
+        self.len_dev = self.L_dev = torch.zeros(self.B, **i32)            # the SEQUENCE rows per bag (patches + tail)
+        self.flag = flag if flag is not None else torch.zeros(1, **i32)
+        cls_idx, row = [], 0
+        for s in self.sides:
+            cls_idx += [-2] + list(range(row + 1, row + 1 + s * s))
+            row += 1 + s * s
+        self.cls_idx = torch.tensor(cls_idx, dtype=torch.int32).to(device)
+        self.pad_idx = pad_cache if pad_cache is not None else {}
+        for s in self.sides:
+            if s not in self.pad_idx:
+                self.pad_idx[s] = torch.tensor(pad_index(side_geometry(s)), dtype=torch.int32).to(device)
+
+    def update(self, patch_len_dev: torch.Tensor):
+        """Index and sequence lengths from the patch counts now on the device (the bucket's len_dev)."""
+        ops.tm_seq_index_bucket(patch_len_dev, self.cap, self.tail, self.sides, self.idx, self.L_dev, self.flag)
         return self
 
 
@@ -294,6 +354,26 @@ class TransMIL(nn.Module):
         idx_dev = ops.tm_seq_index_segs(table, total, R)
         seqs = ops.tm_row_gather(h, self.cls_token, idx_dev, self.deterministic)
         return self._run_bags(seqs, [geometry(sum(n for _, n in bag)) for bag in segs], need_attn, None)
+
+    def flat_bucket(self, x0: torch.Tensor, geom: BucketGeometry, patch_len_dev: torch.Tensor):
+        """flat_segments() in its capture-safe form, for a step replayed from a hipGraph: x0 [cap + B sum(tail), L] is the
+        bucket's multi-modal bag buffer, the patch counts are on the device, the sides come from geom - nothing below touches
+        the host.  Rows [sum of the lengths, cap) of x0 hold whatever an earlier step left there; x0 is an autograd intermediate
+        and cannot be cleared, and although those rows are never gathered (zero gradient rows), _fc1's weight gradient over all
+        of x0 would still multiply what they hold.  So the order is turned round: the bags' rows are gathered FIRST (the cls
+        entries read as zero rows), _fc1 + ReLU runs over the gathered [sum(1 + s_b^2), L] rows - it is row-wise, so the values
+        are those of flat_segments, and a repeated row adds twice in dW as it does through the gather's backward there -, and a
+        second gather through the static cls_idx puts the cls token in front of every bag.  No product ever reads a row of x0
+        that no bag names.  Returns (h [B, D], [None, None])."""
+        if x0.dim() != 2 or x0.shape[1] != self.L or x0.shape[0] != geom.x_rows:
+            raise ValueError(f"TransMIL: flat_bucket wants rows [{geom.x_rows}, {self.L}], got {tuple(x0.shape)}")
+        if self.training and (self._drop_seed is None or self._drop_ctr is None or self._drop_ctr.device != x0.device):
+            raise ValueError("TransMIL: fix the dropout stream (_drop_state) before a forward with geom")
+        geom.update(patch_len_dev)
+        rows = ops.tm_row_gather(x0, None, geom.idx, self.deterministic)               # [sum(1 + s^2), L]
+        h = ops.linear_act(rows, self._fc1[0].weight, self._fc1[0].bias, "relu")
+        seqs = ops.tm_row_gather(h, self.cls_token, geom.cls_idx, self.deterministic)
+        return self._run_bags(seqs, [side_geometry(s) for s in geom.sides], False, geom)
 
     def _run_bags(self, seqs: torch.Tensor, geo: List[dict], need_attn, geom: Optional[DeviceGeometry]):
         """The assembled sequences [sum(1 + s_b^2), 512], one bag after another: layer1 -> PPEG -> layer2 -> norm of the cls rows."""

@@ -183,6 +183,29 @@ def tm_seq_index_segs(table, total: int, x_rows: int, idx_out=None, flag=None):
     return idx_out[:total]
 
 
+def tm_seq_index_bucket(len_dev, cap: int, tail, sides, idx_out, L_dev=None, flag=None):
+    """tm_row_gather's index for the fusion model's capacity bucket (mil_tm_seq_index_bucket), from the bag lengths on the
+    device: len_dev int32 [B]; cap patch rows in front of the source, then B x tail[j] rows per tail segment (host ints, at most
+    TM_SEG_MAX); sides: the bags' grid sides (host ints: the launch shape).  Per bag [-2 | its tail segments | its patches | the
+    first s^2 - L of those again]; nothing leaves [0, cap + B sum(tail)).  L_dev [B] (optional) <- len[b] + sum(tail); flag [1]
+    (optional) <- 1 if a bag does not fit its side or the lengths exceed cap.  One launch, no host sync.  Returns
+    idx_out[:sum(1 + s^2)]."""
+    sides, tail = [int(s) for s in sides], [int(t) for t in tail]
+    total = sum(1 + s * s for s in sides)
+    if len_dev.dtype != torch.int32 or len_dev.numel() != len(sides) or not len_dev.is_contiguous():
+        raise _lib.MilHipError(f"tm_seq_index_bucket: len_dev must be contiguous int32 [{len(sides)}]")
+    if idx_out.dtype != torch.int32 or not idx_out.is_contiguous() or idx_out.device != len_dev.device or idx_out.numel() < total:
+        raise _lib.MilHipError(f"tm_seq_index_bucket: idx_out must be a contiguous int32 tensor of >= {total} entries on len_dev's device")
+    if L_dev is not None and (L_dev.dtype != torch.int32 or L_dev.numel() < len(sides)):
+        raise _lib.MilHipError(f"tm_seq_index_bucket: L_dev must be int32 [{len(sides)}]")
+    if flag is not None and (flag.dtype != torch.int32 or flag.numel() < 1):
+        raise _lib.MilHipError("tm_seq_index_bucket: flag must be int32 [1]")
+    _lib.checked().mil_tm_seq_index_bucket(_p(len_dev), len(sides), int(cap), (ctypes.c_int32 * len(tail))(*tail), len(tail),
+                                           (ctypes.c_int32 * len(sides))(*sides), _p(idx_out), idx_out.numel(), _p(L_dev),
+                                           _p(flag), _stream())
+    return idx_out[:total]
+
+
 class _TmPPEG(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, s: int, W7, b7, W5, b5, W3, b3, deterministic=False):

@@ -126,6 +126,9 @@ class FusionBucket:
         # the ABMIL pool's score gradient: real rows are written by the fused tail, padding rows zeroed by refresh()
         self.ds = torch.zeros(cap + B * tail_rows, device=device, dtype=torch.float32)
         self.lengths = self._uploaded = None
+        # TransMIL aggregator (fusion_step.RaggedFusionTransMILStepper): the geometry of the step's key (grid sides, gather
+        # index), set before the step's body runs; None = the ABMIL aggregator's bucket
+        self.tm_geom = None
         tok = AttnSegs.make([P] * B, [P] * B, device)
         self.s_tt = tok
         ones = [P] * B

@@ -52,6 +52,9 @@ def build_model(args):
     if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
             and getattr(args, "transmil_graph", 0)):
         model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward
+    if getattr(args, "fusion_transmil_graph", 0) and args.variant == "fusion":
+        # evaluation (test_ddp.py: batch 1, eval mode, no grad): the per-bag forward replayed from the graph of its key
+        model.graph_eval = True
     save = getattr(args, "save_patch_attn", "") or ""
     if save:
         if args.variant != "image_only" or getattr(args, "model_pathology", "ABMIL") != "TransMIL":
@@ -91,6 +94,9 @@ def main_worker(local_rank: int, nprocs: int, args):
         raise ValueError("--transmil_graph 1 is the graph path of --variant image_only --model_pathology TransMIL")
     if tm_graph and (args.learnablePrompt or not getattr(args, "flat_adam", 1)):
         raise ValueError("--transmil_graph 1 needs --flat_adam 1 (the counted FlatAdam rides inside the graph)")
+    # --fusion_transmil_graph 1 (config.py refuses it outside --variant fusion --aggregator TransMIL --fusion_transmil 1
+    # --flat_adam 1): the TransMIL-aggregator step replayed per (row capacity, grid sides), fusion_step.py
+    ftm_graph = bool(getattr(args, "fusion_transmil_graph", 0))
     torch.cuda.set_device(gpu)
     dev = torch.device("cuda", gpu)
     if world > 1:
@@ -153,7 +159,7 @@ def main_worker(local_rank: int, nprocs: int, args):
                         and list(args.modality) in (["pathology"], ["CT", "pathology"]))
             # --transmil_graph 1 at world size 1: the same, inside the per-side graphs of transmil_step.RaggedTransMILStepper
             optimizer = FlatAdam(trainable, lr=lr0, betas=(args.b1, args.b2), weight_decay=1e-7, world_size=world,
-                                 counted=bucketed or (tm_graph and world == 1))
+                                 counted=bucketed or ((tm_graph or ftm_graph) and world == 1))
         else:
             optimizer = torch.optim.Adam(trainable, lr=lr0, betas=(args.b1, args.b2), weight_decay=1e-7)
         if flat_opt and world > 1:
@@ -208,6 +214,17 @@ def main_worker(local_rank: int, nprocs: int, args):
                                            cossim="textCosSim" in args.loss,
                                            # frozen tower: inside the replay too, unless its embeddings are cached per note
                                            tower_in_graph=not args.learnablePrompt and not getattr(args, "cache_text", 0))
+        if ftm_graph:
+            # the same regime with the TransMIL aggregator: one graph per (row capacity, grid sides of the multi-modal bags),
+            # the gather index written on the device; counted Adam inside the graph at world size 1, all-reduce and update
+            # outside otherwise.  Same slots as above, so the loop below feeds it the same way
+            from .fusion_step import RaggedFusionTransMILStepper
+            fstepper = RaggedFusionTransMILStepper(model, optimizer, B=per_gpu, P=prompts, in_dim=args.patch_dim,
+                                                   ct_shape=CT_SHAPE if "CT" in args.modality else None,
+                                                   loss_mult=3.0 if (args.loss_point == "CT-Pth-Last" and "CT" in args.modality) else 1.0,
+                                                   cossim="textCosSim" in args.loss, drop_seed=args.seed,
+                                                   tower_in_graph=not getattr(args, "cache_text", 0),
+                                                   max_graphs=int(getattr(args, "transmil_max_graphs", 0)) or None)
         if getattr(args, "hip_graph", 0):
             # replay the step body from a hipGraph once a batch shape repeats (graph_step.py); optimizer and the
             # gradient all-reduce stay outside, so this needs the flat optimizers when world > 1 (no DDP hooks)
@@ -290,13 +307,14 @@ def main_worker(local_rank: int, nprocs: int, args):
                         if slot.ct is not None:
                             for b_, j_ in enumerate(take):
                                 slot.ct[b_].copy_(ct_pool[int(j_) % ct_pool.shape[0]], non_blocking=True)
-                        loss, prob, _ = fstepper.step(slot, ks, on_device=True)
+                        loss, prob = fstepper.step(slot, ks, on_device=True)[:2]
                         y, nb_ = slot.y, len(take)
                     else:
                         slot = None
                 if slot is not None:
                     if it % 10 == 0 or it == steps - 1:
-                        losses.update(tstepper.read_loss(loss) if tstepper is not None else float(loss.detach()), nb_)
+                        reader = tstepper if tstepper is not None else (fstepper if ftm_graph else None)
+                        losses.update(reader.read_loss(loss) if reader is not None else float(loss.detach()), nb_)
                         accs.update(float(calculate_accuracy(prob.detach(), y)), nb_)
                         bt.update(time.time() - end)
                         progress.display(it)
@@ -340,7 +358,7 @@ def main_worker(local_rank: int, nprocs: int, args):
                         slot.ids.copy_(batch["CI"], non_blocking=True)                    # the text tower runs inside the step
                     else:
                         fstepper.encode_notes(slot, batch["CI"].to(dev))                  # --cache_text 1: a lookup per note
-                    loss, prob, _ = fstepper.step(slot, lengths)
+                    loss, prob = fstepper.step(slot, lengths)[:2]
                 elif tstepper is not None and len(lengths) == per_gpu:
                     slot = tstepper.slot(lengths)                                         # host-fed: the side's static inputs
                     r0 = 0
@@ -401,6 +419,8 @@ def main_worker(local_rank: int, nprocs: int, args):
             state = {"epoch": epoch + 1, "state_dict": sd,
                      "optimizer": tr.optimizer_state_dict() if fused else optimizer.state_dict()}
             save_checkpoint(state, True, args.save_dir, f"checkpoint_{epoch:04d}.pth.tar")
+    if not fused and ftm_graph:
+        print(f"fusion TransMIL graphs {fstepper.n_graphs}  replays {fstepper.replays}  eager {fstepper.eager_steps}")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -5,7 +5,11 @@ with their spread.  Prints one JSON line per N.
 
 --index: per N, the HOST time per step of the two ways to the sequence index of the multi-modal bag: the Python list of
 1 + s^2 ints uploaded (what the image-only eager path does) and the [B, 9] table + one launch of ops.tm_seq_index_segs;
-wall-clock of the host thread, the device idle at the start of every region, plus the device time of the launch."""
+wall-clock of the host thread, the device idle at the start of every region, plus the device time of the launch.
+
+--graph: per N, the same eager TransMIL-aggregator step next to the step replayed from its hipGraph
+(fusion_step.RaggedFusionTransMILStepper, counted FlatAdam inside the graph; --fusion_transmil_graph 1), one region = one
+step, and the bytes the graph keeps resident in the stepper's memory pool."""
 import argparse, json, os, sys, time
 from types import SimpleNamespace
 import torch
@@ -69,6 +73,48 @@ def step_rows(a, dev):
         print(json.dumps(res), flush=True)
 
 
+def graph_rows(a, dev):
+    from mil_amd.fusion_step import RaggedFusionTransMILStepper
+    y = syn.make_labels(3, 1).to(dev)
+    ids = syn.make_token_ids(4, 1, P).to(dev)
+    ct = torch.randn((1, D_CT, 512), generator=torch.Generator().manual_seed(5)).to(dev)
+    for N in a.N:
+        x = syn.make_bags(N, 1, N, 768).to(dev)
+        res = dict(N=N, rows=N + 2 * P + D_CT)
+        for tag in ("eager", "replayed"):
+            torch.manual_seed(1234)
+            model = get_model(make_args("TransMIL", a.clip_layers)).to(dev).train()
+            opt = FlatAdam([p for p in model.parameters() if p.requires_grad], lr=1e-5, counted=(tag == "replayed"))
+            with torch.no_grad():
+                t = model.clinic_extractor(ids)              # the frozen tower: outside the region, as with --cache_text 1
+            if tag == "eager":
+                def step():
+                    opt.zero_grad()
+                    model([ct, x], None, text_features=t, labels=y, loss_scale=3.0 / 2)
+                    ops.backward(model.last_loss)
+                    opt.step()
+            else:
+                st = RaggedFusionTransMILStepper(model, opt, B=1, P=P, ct_shape=(D_CT, 512), loss_mult=3.0, drop_seed=1234)
+                slot = st.slot(N)
+                slot.x[:N].copy_(x[0])
+                slot.ct.copy_(ct)
+                slot.text.copy_(t)
+                slot.y.copy_(y)
+
+                def step():
+                    st.step(slot, [N])
+            ts = region_times(step, a.reps, max(a.warmup, 3))   # eager visit, capture, first replay: before the regions
+            res.update({tag + "_ms": round(med(ts), 3), tag + "_min_ms": round(min(ts), 3), tag + "_max_ms": round(max(ts), 3)})
+            if tag == "replayed":
+                assert st.n_graphs == 1 and st.replays >= a.reps, (st.n_graphs, st.replays)
+                assert int(st.flag.item()) == 0              # no length on the device left its key
+                res.update(cap=slot.cap, side=st.sides([N])[0], graph_MiB=round(st.pool_bytes() / 2 ** 20, 1))
+                del st, slot
+            del model, opt
+            torch.cuda.empty_cache()
+        print(json.dumps(res), flush=True)
+
+
 def index_rows(a, dev):
     for N in a.N:
         R = N + 2 * P + D_CT
@@ -108,10 +154,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--clip_layers", type=int, default=1, help="the frozen text tower runs outside the timed region")
     ap.add_argument("--index", action="store_true")
+    ap.add_argument("--graph", action="store_true", help="the eager step next to the step replayed from its hipGraph")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    (index_rows if a.index else step_rows)(a, dev)
+    (graph_rows if a.graph else index_rows if a.index else step_rows)(a, dev)
 
 
 if __name__ == "__main__":
