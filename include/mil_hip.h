@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 18 */
+int mil_abi_version(void);   /* 19 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1107,6 +1107,15 @@ int mil_tm_landmarks_bwd(const float* dqL, const float* dkL, int n_pad, float qs
 int mil_tm_pinv_init(const float* A2, float* scale, int32_t* arg, float* Z0, void* stream);
 int mil_tm_pinv_init_bwd(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
                          void* stream);
+/* The same over nb bags in one set of launches (1 <= nb <= 1024, else MIL_EINVAL and no launch): A2, Z0, dZ0, dA2
+ * [nb, 8, 256, 256], scale [nb, 19], arg [nb, 9], dense over the bags, each bag's 19 floats and 9 ints laid out as above with
+ * arg = head * 256 + column LOCAL to the bag, first on ties.  Bag b's scale is taken over bag b's 8 heads only, never over
+ * the batch.  The kernels are those of the single-bag entries with the bag read off the block index (grids nb x 8,
+ * nb x 2048, nb x 256, nb), so bag b's outputs are bit-equal to the single-bag entry on bag b's slices at any nb.
+ * Backward: ws holds nb caller-zeroed floats, one float atomic sum per bag. */
+int mil_tm_pinv_init_bags(const float* A2, int nb, float* scale, int32_t* arg, float* Z0, void* stream);
+int mil_tm_pinv_init_bwd_bags(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, int nb, float* dA2,
+                              float* ws, void* stream);
 /* Residual depthwise conv on v (33 x 1 per head along the sequence, zero padding 16, no bias): out [n_pad, 512] (merged
  * heads) += conv(v).  Backward: the v columns of dqkv += conv^T(dout); dw [8, 33] += (atomic, caller-initialised). */
 int mil_tm_resconv(const float* qkv, const float* w, int n_pad, float* out, void* stream);
@@ -1230,6 +1239,11 @@ int mil_tm_row_gather_bwd_fixed(const float* ddst, const int32_t* idx, int rows,
 size_t mil_tm_pinv_ws_floats(void);
 int mil_tm_pinv_init_bwd_fixed(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
                                void* stream);
+/* mil_tm_pinv_init_bwd_bags with each bag's <dZ0, Z0> in that fixed tree: ws [nb, 256] = mil_tm_pinv_ws_floats_bags(nb) floats
+ * (0 for nb outside [1, 1024]), plain stores, no atomic; bag b's bits are those of mil_tm_pinv_init_bwd_fixed on its slices. */
+size_t mil_tm_pinv_ws_floats_bags(int nb);
+int mil_tm_pinv_init_bwd_bags_fixed(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, int nb, float* dA2,
+                                    float* ws, void* stream);
 /* mil_tm_resconv_bwd with dw [8, 33] <- the sum over the chunks of 256 rows, chunk 0, 1, 2 .. in that order (overwritten;
  * the v columns of dqkv += as before).  ws [ceil(n_pad / 256)][8 x 33] = mil_tm_resconv_ws_floats(n_pad). */
 size_t mil_tm_resconv_ws_floats(int n_pad);

@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -190,6 +190,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_landmarks_bwd": (c_int, [_P, _P, c_int, c_float, _P, _P]),
     "mil_tm_pinv_init": (c_int, [_P] * 4 + [_P]),
     "mil_tm_pinv_init_bwd": (c_int, [_P] * 6 + [_P]),
+    "mil_tm_pinv_init_bags": (c_int, [_P, c_int, _P, _P, _P, _P]),
+    "mil_tm_pinv_init_bwd_bags": (c_int, [_P] * 4 + [c_int, _P, _P, _P]),
     "mil_tm_resconv": (c_int, [_P, _P, c_int, _P, _P]),
     "mil_tm_resconv_bwd": (c_int, [_P, _P, _P, c_int, _P, _P, _P]),
     "mil_tm_ppeg_fwd": (c_int, [_P, c_int] + [_P] * 7 + [_P]),
@@ -214,6 +216,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_row_gather_bwd_fixed": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, _P, _P]),
     "mil_tm_pinv_ws_floats": (c_size_t, []),
     "mil_tm_pinv_init_bwd_fixed": (c_int, [_P] * 6 + [_P]),
+    "mil_tm_pinv_ws_floats_bags": (c_size_t, [c_int]),
+    "mil_tm_pinv_init_bwd_bags_fixed": (c_int, [_P] * 4 + [c_int, _P, _P, _P]),
     "mil_tm_resconv_ws_floats": (c_size_t, [c_int]),
     "mil_tm_resconv_bwd_fixed": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P]),
     "mil_tm_ppeg_ws_floats": (c_size_t, [c_int]),

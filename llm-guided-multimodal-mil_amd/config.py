@@ -133,6 +133,13 @@ def create_arg_parser(argv=None):
                         "W, U, O and their gradients) as three-piece split-bf16 products on bf16 MFMA, six cross terms, "
                         "fp32-level error; set on every TransMIL module of the model.  Models without a TransMIL module accept "
                         "the flag and ignore it.  0: the environment variable MIL_TM_PIECES decides (default 0 = fp32 MFMA)")
+    p.add_argument("--tm_batch_bags", type=int, default=0, choices=[0, 1],
+                   help="train_ddp.py and test_ddp.py: 1 = a TransMIL step of several bags (--batch_size > 1, several bags per "
+                        "slot, the fusion model's TransMIL aggregator) runs the landmark-side chain of its bags - A2, the "
+                        "pseudo-inverse, U and their gradients - as one set of launches at batch 8 x bags instead of once per "
+                        "bag; each bag keeps its own pseudo-inverse scale.  Set on every TransMIL module of the model; a step "
+                        "of one bag and a request for attention outputs keep the bag-by-bag route.  Models without a TransMIL "
+                        "module accept the flag and ignore it.  0: the environment variable MIL_TM_BATCH_BAGS decides (default 0)")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,

@@ -447,13 +447,24 @@ __global__ __launch_bounds__(256) void k_tm_landmarks_bwd(const float* __restric
     dqkv[(long)i * TM_QKV + c] += g;
 }
 
-// per head h (one workgroup each): out[3 + h] = max row abs-sum, out[11 + h] = max column abs-sum, arg[1 + h] = h * 256 +
-// column of the largest column sum (first on ties).  Rows: one wave per row, coalesced; columns: one thread per column.
+// The start of the pseudo-inverse and its backward, over nb bags at once: A2, Z0, dZ0, dA2 [nb, 8, 256, 256], scale
+// [nb, PINV_SCALE] and arg [nb, PINV_ARG] dense over the bags.  Every kernel finds its bag from the block index and works on that
+// bag's slices alone, so a bag's values and the order of its sums do not depend on nb; the single-bag entries launch the
+// same kernels with nb = 1.  Offsets are long: nb <= 1024 bags of 2^19 floats reach 2^29 elements.
+constexpr int PINV_SCALE = 3 + 2 * TM_H, PINV_ARG = 1 + TM_H;          // floats / ints per bag
+constexpr int PINV_BAG = TM_H * TM_M * TM_M;                          // 2^19 elements of one bag's A2
+constexpr int PINV_MAX_BAGS = 1024;
+
+// per (bag, head h) (one workgroup each): out[3 + h] = max row abs-sum, out[11 + h] = max column abs-sum, arg[1 + h] = h * 256 +
+// column of the largest column sum (first on ties), all local to the bag.  Rows: one wave per row, coalesced; columns: one
+// thread per column.
 __global__ __launch_bounds__(256) void k_tm_pinv_scale(const float* __restrict__ A2, float* out, int32_t* arg) {
     __shared__ float sr[4], sc[256];
     __shared__ int si[256];
-    const int t = threadIdx.x, hh = blockIdx.x, lane = t & 63, wv = t >> 6;
-    const float* a = A2 + (long)hh * TM_M * TM_M;
+    const int t = threadIdx.x, bag = blockIdx.x / TM_H, hh = blockIdx.x % TM_H, lane = t & 63, wv = t >> 6;
+    const float* a = A2 + (long)blockIdx.x * TM_M * TM_M;
+    out += bag * PINV_SCALE;
+    arg += bag * PINV_ARG;
     float mr = 0.f;
     for (int i = wv; i < TM_M; i += 4) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(a + i * TM_M + 4 * lane);
@@ -480,9 +491,12 @@ __global__ __launch_bounds__(256) void k_tm_pinv_scale(const float* __restrict__
     }
 }
 
-// the bag's scale from the 8 heads' maxima (every thread, from cache), then Z0[h][i][j] = A2[h][j][i] / scale; the first
-// thread stores out[0] = max row abs-sum x max column abs-sum, out[1] / out[2] the two factors, arg[0] the arg-max column
+// the bag's scale from its own 8 heads' maxima (every thread, from cache), then Z0[h][i][j] = A2[h][j][i] / scale; the bag's
+// first thread stores out[0] = max row abs-sum x max column abs-sum, out[1] / out[2] the two factors, arg[0] the arg-max column
 __global__ __launch_bounds__(256) void k_tm_pinv_init(const float* __restrict__ A2, float* scale, int32_t* arg, float* Z) {
+    const int bag = blockIdx.x / (PINV_BAG / 256);
+    scale += bag * PINV_SCALE;
+    arg += bag * PINV_ARG;
     float mr = 0.f, mc = -1.f;
     int ic = 0;
 #pragma unroll
@@ -491,9 +505,10 @@ __global__ __launch_bounds__(256) void k_tm_pinv_init(const float* __restrict__ 
         if (scale[3 + TM_H + hh] > mc) { mc = scale[3 + TM_H + hh]; ic = arg[1 + hh]; }
     }
     const float sv = mr * mc;
-    const int e = blockIdx.x * 256 + threadIdx.x;              // < 8 * 256 * 256
+    const int e = (blockIdx.x % (PINV_BAG / 256)) * 256 + threadIdx.x;  // < 8 * 256 * 256, within the bag
     const int hh = e >> 16, i = (e >> 8) & 255, j = e & 255;
-    Z[e] = A2[(hh << 16) + (j << 8) + i] / sv;
+    const long off = (long)bag * PINV_BAG;
+    Z[off + e] = A2[off + (hh << 16) + (j << 8) + i] / sv;
     if (e == 0) {
         scale[0] = sv;
         scale[1] = mr;
@@ -502,52 +517,57 @@ __global__ __launch_bounds__(256) void k_tm_pinv_init(const float* __restrict__ 
     }
 }
 
-// ws[0] += <dZ0, Z0> over 2048-element chunks (ws caller-zeroed); FIXED: ws[chunk] = the chunk's sum, a plain store
-constexpr int PINV_CHUNKS = TM_H * TM_M * TM_M / 2048;      // 256: k_tm_pinv_init_bwd_s<true> has one thread per chunk
+// ws[bag] += <dZ0, Z0> over the bag's 2048-element chunks (ws caller-zeroed); FIXED: ws[bag * 256 + chunk] = the chunk's sum,
+// a plain store
+constexpr int PINV_CHUNKS = PINV_BAG / 2048;                 // 256 per bag: k_tm_pinv_init_bwd_s<true> has one thread per chunk
 template <bool FIXED>
 __global__ __launch_bounds__(256) void k_tm_pinv_dot(const float* __restrict__ dZ0, const float* __restrict__ Z0, float* ws) {
     __shared__ float red[4];
-    const int base = blockIdx.x * 2048;
+    const long base = (long)blockIdx.x * 2048;
     float s = 0.f;
-    for (int e = base + threadIdx.x; e < base + 2048; e += 256) s += dZ0[e] * Z0[e];
+    for (long e = base + threadIdx.x; e < base + 2048; e += 256) s += dZ0[e] * Z0[e];
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
         const float v = red[0] + red[1] + red[2] + red[3];
         if constexpr (FIXED) ws[blockIdx.x] = v;
-        else atomicAdd(ws, v);
+        else atomicAdd(ws + blockIdx.x / PINV_CHUNKS, v);
     }
 }
 
-// dA2[h][i][j] += dZ0[h][j][i] / s
+// dA2[h][i][j] += dZ0[h][j][i] / s, s the bag's own
 __global__ __launch_bounds__(256) void k_tm_pinv_init_bwd_t(const float* __restrict__ dZ0, const float* __restrict__ scale,
                                                             float* dA2) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int bag = blockIdx.x / (PINV_BAG / 256);
+    const int e = (blockIdx.x % (PINV_BAG / 256)) * 256 + threadIdx.x;
     const int hh = e >> 16, i = (e >> 8) & 255, j = e & 255;
-    dA2[e] += dZ0[(hh << 16) + (j << 8) + i] / scale[0];
+    const long off = (long)bag * PINV_BAG;
+    dA2[off + e] += dZ0[off + (hh << 16) + (j << 8) + i] / scale[bag * PINV_SCALE];
 }
 
-// the scale's gradient ds = -<dZ0, Z0> / s (ws[0], k_tm_pinv_dot) goes to the arg-max column through its column-sum
-// factor: dA2[h*][i][j*] += ds * (max row abs-sum) (A2 > 0 after softmax, so |.|' = 1).  One workgroup, one thread per row.
-// FIXED: <dZ0, Z0> is the sum of the 256 chunk sums in ws, by the xor butterfly of each wave and then wave 0 .. 3 in order.
+// the scale's gradient ds = -<dZ0, Z0> / s (ws[bag], k_tm_pinv_dot) goes to the arg-max column through its column-sum
+// factor: dA2[h*][i][j*] += ds * (max row abs-sum) (A2 > 0 after softmax, so |.|' = 1).  One workgroup per bag, one thread per row.
+// FIXED: <dZ0, Z0> is the sum of the bag's 256 chunk sums in ws, by the xor butterfly of each wave and then wave 0 .. 3 in order.
 template <bool FIXED>
 __global__ __launch_bounds__(256) void k_tm_pinv_init_bwd_s(const float* __restrict__ ws, const float* __restrict__ scale,
                                                             const int32_t* __restrict__ arg, float* dA2) {
-    const int t = threadIdx.x;
+    const int t = threadIdx.x, bag = blockIdx.x;
+    scale += bag * PINV_SCALE;
+    arg += bag * PINV_ARG;
     float dot;
     if constexpr (FIXED) {
         __shared__ float red[4];
-        const float s = wave_sum(ws[t]);
+        const float s = wave_sum(ws[bag * PINV_CHUNKS + t]);
         if ((t & 63) == 0) red[t >> 6] = s;
         __syncthreads();
         dot = red[0] + red[1] + red[2] + red[3];
     } else {
-        dot = ws[0];
+        dot = ws[bag];
     }
     const float ds = -dot / scale[0];
     const int hh = arg[0] >> 8, jc = arg[0] & 255;
-    dA2[(hh << 16) + (t << 8) + jc] += ds * scale[1];
+    dA2[(long)bag * PINV_BAG + (hh << 16) + (t << 8) + jc] += ds * scale[1];
 }
 
 // out[i][c] += sum_t w[head][t] v[i + t - 16][c] (v = columns 1024.. of qkv, zero outside [0, n_pad))
@@ -760,6 +780,20 @@ inline int launch_rc() {
     return e == hipSuccess ? MIL_OK : (int)e;
 }
 
+// the launches of the pseudo-inverse's start over nb bags; the entries below check their arguments first
+void tm_pinv_init_launch(const float* A2, int nb, float* scale, int32_t* arg, float* Z0, hipStream_t st) {
+    hipLaunchKernelGGL(k_tm_pinv_scale, dim3(nb * TM_H), dim3(256), 0, st, A2, scale, arg);
+    hipLaunchKernelGGL(k_tm_pinv_init, dim3(nb * (PINV_BAG / 256)), dim3(256), 0, st, A2, scale, arg, Z0);
+}
+
+template <bool FIXED>
+void tm_pinv_init_bwd_launch(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, int nb, float* dA2,
+                                    float* ws, hipStream_t st) {
+    hipLaunchKernelGGL(k_tm_pinv_init_bwd_t, dim3(nb * (PINV_BAG / 256)), dim3(256), 0, st, dZ0, scale, dA2);
+    hipLaunchKernelGGL(k_tm_pinv_dot<FIXED>, dim3(nb * PINV_CHUNKS), dim3(256), 0, st, dZ0, Z0, ws);
+    hipLaunchKernelGGL(k_tm_pinv_init_bwd_s<FIXED>, dim3(nb), dim3(256), 0, st, ws, scale, arg, dA2);
+}
+
 }  // namespace
 
 extern "C" {
@@ -869,17 +903,27 @@ int mil_tm_landmarks_bwd(const float* dqL, const float* dkL, int n_pad, float qs
 
 int mil_tm_pinv_init(const float* A2, float* scale, int32_t* arg, float* Z0, void* stream) {
     if (!A2 || !scale || !arg || !Z0) return MIL_EINVAL;
-    hipLaunchKernelGGL(k_tm_pinv_scale, dim3(TM_H), dim3(256), 0, (hipStream_t)stream, A2, scale, arg);
-    hipLaunchKernelGGL(k_tm_pinv_init, dim3(TM_H * TM_M * TM_M / 256), dim3(256), 0, (hipStream_t)stream, A2, scale, arg, Z0);
+    tm_pinv_init_launch(A2, 1, scale, arg, Z0, (hipStream_t)stream);
     return launch_rc();
 }
 
 int mil_tm_pinv_init_bwd(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
                          void* stream) {
     if (!dZ0 || !Z0 || !scale || !arg || !dA2 || !ws) return MIL_EINVAL;
-    hipLaunchKernelGGL(k_tm_pinv_init_bwd_t, dim3(TM_H * TM_M * TM_M / 256), dim3(256), 0, (hipStream_t)stream, dZ0, scale, dA2);
-    hipLaunchKernelGGL(k_tm_pinv_dot<false>, dim3(TM_H * TM_M * TM_M / 2048), dim3(256), 0, (hipStream_t)stream, dZ0, Z0, ws);
-    hipLaunchKernelGGL(k_tm_pinv_init_bwd_s<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, scale, arg, dA2);
+    tm_pinv_init_bwd_launch<false>(dZ0, Z0, scale, arg, 1, dA2, ws, (hipStream_t)stream);
+    return launch_rc();
+}
+
+int mil_tm_pinv_init_bags(const float* A2, int nb, float* scale, int32_t* arg, float* Z0, void* stream) {
+    if (!A2 || !scale || !arg || !Z0 || nb < 1 || nb > PINV_MAX_BAGS) return MIL_EINVAL;
+    tm_pinv_init_launch(A2, nb, scale, arg, Z0, (hipStream_t)stream);
+    return launch_rc();
+}
+
+int mil_tm_pinv_init_bwd_bags(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, int nb, float* dA2,
+                              float* ws, void* stream) {
+    if (!dZ0 || !Z0 || !scale || !arg || !dA2 || !ws || nb < 1 || nb > PINV_MAX_BAGS) return MIL_EINVAL;
+    tm_pinv_init_bwd_launch<false>(dZ0, Z0, scale, arg, nb, dA2, ws, (hipStream_t)stream);
     return launch_rc();
 }
 
@@ -968,9 +1012,16 @@ size_t mil_tm_pinv_ws_floats(void) { return PINV_CHUNKS; }
 int mil_tm_pinv_init_bwd_fixed(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, float* dA2, float* ws,
                                void* stream) {
     if (!dZ0 || !Z0 || !scale || !arg || !dA2 || !ws) return MIL_EINVAL;
-    hipLaunchKernelGGL(k_tm_pinv_init_bwd_t, dim3(TM_H * TM_M * TM_M / 256), dim3(256), 0, (hipStream_t)stream, dZ0, scale, dA2);
-    hipLaunchKernelGGL(k_tm_pinv_dot<true>, dim3(PINV_CHUNKS), dim3(256), 0, (hipStream_t)stream, dZ0, Z0, ws);
-    hipLaunchKernelGGL(k_tm_pinv_init_bwd_s<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, scale, arg, dA2);
+    tm_pinv_init_bwd_launch<true>(dZ0, Z0, scale, arg, 1, dA2, ws, (hipStream_t)stream);
+    return launch_rc();
+}
+
+size_t mil_tm_pinv_ws_floats_bags(int nb) { return nb >= 1 && nb <= PINV_MAX_BAGS ? (size_t)nb * PINV_CHUNKS : 0; }
+
+int mil_tm_pinv_init_bwd_bags_fixed(const float* dZ0, const float* Z0, const float* scale, const int32_t* arg, int nb, float* dA2,
+                                    float* ws, void* stream) {
+    if (!dZ0 || !Z0 || !scale || !arg || !dA2 || !ws || nb < 1 || nb > PINV_MAX_BAGS) return MIL_EINVAL;
+    tm_pinv_init_bwd_launch<true>(dZ0, Z0, scale, arg, nb, dA2, ws, (hipStream_t)stream);
     return launch_rc();
 }
 

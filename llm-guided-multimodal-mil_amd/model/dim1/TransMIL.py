@@ -244,6 +244,28 @@ class TransLayer(nn.Module):
             y = x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
         return y, attn
 
+    def run_bags(self, xs: Sequence[torch.Tensor], geo: Sequence[dict], pad_idxs: Sequence[torch.Tensor], bits: Sequence[Optional[torch.Tensor]],
+                 deterministic: Optional[bool] = None, gemm_pieces: Optional[int] = None) -> List[torch.Tensor]:
+        """run() (need_attn False) over all bags of a step, stage by stage: per bag LayerNorm, pad gather and to_qkv; the Nystrom
+        cores of all bags as one ops.nystrom_core_bags, whose landmark-side chain is one set of launches at batch 8 x bags; per bag
+        the slice, to_out and the dropout / residual.  Bag b's values are those of run() on bag b."""
+        a = self.attn
+        qkvs = []
+        for x, pad_idx in zip(xs, pad_idxs):
+            ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
+            xp = ops.tm_row_gather(ln, None, pad_idx, deterministic)
+            qkvs.append(ops.linear_act(xp, a.to_qkv.weight, None))
+        outs = ops.nystrom_core_bags(qkvs, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces)
+        lin = a.to_out[0]
+        ys = []
+        for x, g, o, keep in zip(xs, geo, outs, bits):
+            o = o[g["pad"]:]
+            if keep is None:
+                ys.append(ops.linear_act(o, lin.weight, lin.bias, residual=x))
+            else:
+                ys.append(x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), keep, 1.0 / (1.0 - TM_DROP_P)))
+        return ys
+
 
 class PPEG(nn.Module):
     def __init__(self, dim: int = 512):
@@ -258,6 +280,15 @@ class PPEG(nn.Module):
 
 
 class TransMIL(nn.Module):
+    """The reference's TransMIL extractor on the HIP kernels of csrc/transmil.hip: _fc1, the cls token, two Nystrom layers with
+    PPEG between them, LayerNorm of the cls rows; one bag or a ragged batch of bags per call.
+    Switches, each an attribute that overrides its environment variable when not None: fused_cls (MIL_TM_FUSED_CLS),
+    deterministic (MIL_TM_DETERMINISTIC), gemm_pieces (MIL_TM_PIECES), and batch_bags (MIL_TM_BATCH_BAGS, default off): a call
+    that holds more than one bag and asks for no attention output runs stage by stage across the bags, with the landmark-side
+    chain of each layer - A2, the pseudo-inverse, U and their gradients - as one set of launches for all bags
+    (ops.nystrom_core_bags) instead of one set per bag.  Every bag keeps its own pseudo-inverse scale and its values are those
+    of the bag-by-bag route (bit-equal under deterministic); the token-side passes, the dense layers and PPEG stay per bag."""
+
     def __init__(self, n_classes: int, L: int = 768, D: int = 512, K: int = 1):
         super().__init__()
         if D != ops.TM_D or K != 1:
@@ -278,6 +309,7 @@ class TransMIL(nn.Module):
         self.fused_cls: Optional[bool] = None        # need_attn="cls" on the fused passes (ops.nystrom_core); None = MIL_TM_FUSED_CLS
         self.deterministic: Optional[bool] = None    # every cross-workgroup sum in a fixed order (ops.tm_deterministic); None = MIL_TM_DETERMINISTIC
         self.gemm_pieces: Optional[int] = None       # 3: the Nystrom core's products on split-bf16 MFMA (ops.tm_pieces); None = MIL_TM_PIECES
+        self.batch_bags: Optional[bool] = None       # a step's bags through one landmark-side chain (ops.tm_batch_bags); None = MIL_TM_BATCH_BAGS
 
     def _drop_state(self, device):
         if self._drop_seed is None:
@@ -376,12 +408,19 @@ class TransMIL(nn.Module):
         return self._run_bags(seqs, [side_geometry(s) for s in geom.sides], False, geom)
 
     def _run_bags(self, seqs: torch.Tensor, geo: List[dict], need_attn, geom: Optional[DeviceGeometry]):
-        """The assembled sequences [sum(1 + s_b^2), 512], one bag after another: layer1 -> PPEG -> layer2 -> norm of the cls rows."""
+        """The assembled sequences [sum(1 + s_b^2), 512], one bag after another: layer1 -> PPEG -> layer2 -> norm of the cls rows.
+        With batch_bags (ops.tm_batch_bags: the attribute, else MIL_TM_BATCH_BAGS; default off), more than one bag and need_attn
+        False the bags run stage by stage instead (_run_bags_batched): the same values per bag, the landmark-side chain of each
+        layer - A2, the pseudo-inverse, U and their gradients, whose shapes do not depend on the bag - once for all bags.  The
+        token-side passes, the dense layers and PPEG stay per bag.  With one bag, the switch off or need_attn set, the launches
+        are the bag-by-bag ones."""
         want_cls = not isinstance(need_attn, bool)
         dev = seqs.device
         train = self.training
         if train:
             self._drop_state(dev)
+        if need_attn is False and len(geo) > 1 and ops.tm_batch_bags(self.batch_bags):
+            return self._run_bags_batched(seqs, geo, geom)
         cls_rows, attn0, attn1, bits_used = [], [], [], []
         row = 0
         for b, g in enumerate(geo):
@@ -416,3 +455,28 @@ class TransMIL(nn.Module):
         if len(geo) == 1:
             return out, [attn0[0].unsqueeze(0), attn1[0].unsqueeze(0)]
         return out, [attn0, attn1]                   # ragged bags: one [8, n_pad, n_pad] map per bag
+
+    def _run_bags_batched(self, seqs: torch.Tensor, geo: List[dict], geom: Optional[DeviceGeometry]):
+        """_run_bags (need_attn False, several bags) stage by stage across the bags.  The keep bits of (bag, layer) are those of
+        the bag-by-bag route and the pass counter advances once.  All bags' layer tensors are alive at once: in eval mode,
+        where the bag-by-bag route frees a bag's before the next, the peak grows with the number of bags."""
+        dev = seqs.device
+        train = self.training
+        xs, pad_idxs, bits_used = [], [], []
+        row = 0
+        for b, g in enumerate(geo):
+            xs.append(seqs[row:row + g["seq"]])
+            row += g["seq"]
+            if geom is not None:
+                pad_idxs.append(geom.pad_idx[g["s"]])
+            else:
+                pad_idxs.append(torch.tensor(pad_index(g), dtype=torch.int32).to(dev, non_blocking=True))
+            bits_used.append(self._bits(b, g["seq"], dev) if train else (None, None))
+        xs = self.layer1.run_bags(xs, geo, pad_idxs, [k[0] for k in bits_used], self.deterministic, self.gemm_pieces)
+        xs = [self.pos_layer.run(x, g["s"], self.deterministic) for x, g in zip(xs, geo)]
+        xs = self.layer2.run_bags(xs, geo, pad_idxs, [k[1] for k in bits_used], self.deterministic, self.gemm_pieces)
+        if train and self.force_bits is None:
+            ops.counter_add(self._drop_ctr, 1)
+        self.last_bits = bits_used if train else None
+        hc = torch.cat([x[:1] for x in xs], 0)
+        return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), [None, None]

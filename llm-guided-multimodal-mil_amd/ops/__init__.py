@@ -36,7 +36,8 @@ from .absorbed import (_AbsorbQuery, _dkeys_buffer, _AbsorbedPool, _ValueProj, _
 from .grouped import (_gg, _gg_nt, _gg_nn, _gg_tn, _gcs_ws, _seg_colsum, _GroupedNT, _GroupedNN, _GroupedTN, _GrpColSoftmax,
                       _RowSoftmaxT, multi_token_ok, _MultiTokenPoolCore, _MultiTokenRowsCore, multi_token_pool_attention,
                       multi_token_rows_attention)
-from .transmil import (TM_H, TM_DH, TM_D, TM_M, TM_CONV, TM_PINV_ITERS, TM_QSCALE, _tm_splits, tm_deterministic, tm_pieces, _tm_pieces_route, tm_bgemm, tm_softmax_rows,
+from .transmil import (TM_H, TM_DH, TM_D, TM_M, TM_CONV, TM_PINV_ITERS, TM_QSCALE, _tm_splits, tm_deterministic, tm_pieces, tm_batch_bags, _tm_pieces_route, tm_bgemm, tm_softmax_rows,
                        tm_softmax_rows_bwd, _TmRowGather, tm_row_gather, tm_seq_index, TM_SEG_MAX, TM_SEG_STRIDE, tm_seq_index_segs, tm_seq_index_bucket, _TmPPEG, tm_ppeg,
                        tm_cls_attention, tm_cls_attention_fused, tm_lmk_attn, tm_lmk_attn_bwd, tm_tok_attn, tm_tok_attn_bwd, _tm_fused_a3,
-                       _tm_fused_a1, _tm_fused_cls, _tm_pinv_fwd, _tm_fwd, _tm_pinv_bwd, _tm_bwd, _NystromCore, nystrom_core)
+                       _tm_fused_a1, _tm_fused_cls, _tm_pinv_fwd, _tm_fwd, _tm_fwd_bags, _tm_pinv_bwd, _tm_bwd, _tm_bwd_bags, _NystromCore, nystrom_core,
+                       _NystromCoreBags, nystrom_core_bags)

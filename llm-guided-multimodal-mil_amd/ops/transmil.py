@@ -50,6 +50,14 @@ def tm_pieces(value=None) -> int:
     return pieces
 
 
+def tm_batch_bags(value=None) -> bool:
+    """The switch of the batched landmark-side chain (nystrom_core_bags): the keyword (a module passes its `batch_bags`
+    attribute here), else the environment variable MIL_TM_BATCH_BAGS (default 0), read per call."""
+    if value is None:
+        value = os.environ.get("MIL_TM_BATCH_BAGS", "0") not in ("", "0")
+    return bool(value)
+
+
 def _tm_pieces_route(M: int, N: int, K: int) -> bool:
     """Which products take mil_tm_bgemm_pieces when pieces == 3: those with K >= 256 - the pseudo-inverse chain and its
     backward (256^3), W, U, O, dU, dW, dq, dk, dv, dqL, dkL, and the whole-map products of need_attn True.  The K = 64
@@ -312,29 +320,39 @@ def _fused_dqkv(op, dqkv, qkv):
     return dqkv
 
 
-def tm_lmk_attn(qkv, qL):
+def _small_out(op, name, out, like):
+    """An [8, 256, 64] output of a fused pass: the caller's `out` (say a bag's slice of a stacked buffer), or a fresh torch.empty."""
+    if out is None:
+        return torch.empty((TM_H, TM_M, TM_DH), device=like.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (TM_H, TM_M, TM_DH) or out.device != like.device:
+        raise _lib.MilHipError(f"{op}: {name} must be a contiguous float32 [8, 256, 64] tensor on qkv's device")
+    return out
+
+
+def tm_lmk_attn(qkv, qL, out=None):
     """The landmark-query pass without its map (mil_tm_lmk_attn_fwd, csrc/landmark_attn.hip): qkv [n_pad, 1536], qL [8, 256, 64]
     (scaled, as mil_tm_landmarks leaves it) -> (W [8, 256, 64] = softmax(qL k^T) v, lse [8, 256]) over all n_pad keys.  The
-    workspace is one torch.empty below the size of one map; two launches, no host sync, bit-reproducible."""
+    workspace is one torch.empty below the size of one map; two launches, no host sync, bit-reproducible.  out: where W goes
+    (default: a fresh tensor)."""
     qkv, qL = _f32c(qkv, "qkv"), _f32c(qL, "qL")
     n, f32 = _fused_operands("tm_lmk_attn", qkv, qL=qL)
-    W = torch.empty((TM_H, TM_M, TM_DH), **f32)
+    W = _small_out("tm_lmk_attn", "out", out, qkv)
     lse = torch.empty((TM_H, TM_M), **f32)
     ws = torch.empty(_lib.lib().mil_tm_lmk_attn_ws_floats(n, 0), **f32)
     _lib.checked().mil_tm_lmk_attn_fwd(_p(qkv), _p(qL), n, _p(W), _p(lse), _p(ws), _stream())
     return W, lse
 
 
-def tm_lmk_attn_bwd(qkv, qL, W, lse, dW, dqkv=None):
+def tm_lmk_attn_bwd(qkv, qL, W, lse, dW, dqkv=None, dqL=None):
     """Backward of tm_lmk_attn (mil_tm_lmk_attn_bwd): -> (dqkv, dqL).  Columns 512 .. 1535 of dqkv [n_pad, 1536] (a fresh
-    torch.empty when None) are overwritten with dk | dv, columns 0 .. 511 are left as they are; dqL [8, 256, 64] is overwritten.
-    Three launches, no atomics, no host sync."""
+    torch.empty when None) are overwritten with dk | dv, columns 0 .. 511 are left as they are; dqL [8, 256, 64] (the caller's,
+    or a fresh tensor when None) is overwritten.  Three launches, no atomics, no host sync."""
     qkv, qL, W, lse, dW = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (qL, "qL"), (W, "W"), (lse, "lse"), (dW, "dW")))
     n, f32 = _fused_operands("tm_lmk_attn_bwd", qkv, qL=qL)
     if tuple(W.shape) != (TM_H, TM_M, TM_DH) or tuple(dW.shape) != (TM_H, TM_M, TM_DH) or lse.numel() != TM_H * TM_M:
         raise _lib.MilHipError(f"tm_lmk_attn_bwd: W {tuple(W.shape)} / dW {tuple(dW.shape)} / lse {tuple(lse.shape)} outside the built shape")
     dqkv = _fused_dqkv("tm_lmk_attn_bwd", dqkv, qkv)
-    dqL = torch.empty((TM_H, TM_M, TM_DH), **f32)
+    dqL = _small_out("tm_lmk_attn_bwd", "dqL", dqL, qkv)
     ws = torch.empty(_lib.lib().mil_tm_lmk_attn_ws_floats(n, 1), **f32)
     _lib.checked().mil_tm_lmk_attn_bwd(_p(qkv), _p(qL), _p(W), _p(lse), _p(dW), n, _p(dqkv), _p(dqL), _p(ws), _stream())
     return dqkv, dqL
@@ -354,17 +372,18 @@ def tm_tok_attn(qkv, kL, U):
     return O, lse
 
 
-def tm_tok_attn_bwd(qkv, kL, U, lse, dO, dqkv=None):
+def tm_tok_attn_bwd(qkv, kL, U, lse, dO, dqkv=None, dU=None, dkL=None):
     """Backward of tm_tok_attn (mil_tm_tok_attn_bwd): -> (dqkv, dU, dkL).  Columns 0 .. 511 of dqkv [n_pad, 1536] (a fresh
-    torch.empty when None) are overwritten with dq, columns 512 .. 1535 are left as they are; dU and dkL [8, 256, 64] are
-    overwritten.  The workspace is one torch.empty of half a map; two launches, no atomics, no host sync."""
+    torch.empty when None) are overwritten with dq, columns 512 .. 1535 are left as they are; dU and dkL [8, 256, 64] (the
+    caller's, or fresh tensors when None) are overwritten.  The workspace is one torch.empty of half a map; two launches, no
+    atomics, no host sync."""
     qkv, kL, U, lse, dO = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (kL, "kL"), (U, "U"), (lse, "lse"), (dO, "dO")))
     n, f32 = _fused_operands("tm_tok_attn_bwd", qkv, kL=kL, U=U)
     if tuple(lse.shape) != (TM_H, n) or tuple(dO.shape) != (n, TM_D) or lse.device != qkv.device or dO.device != qkv.device:
         raise _lib.MilHipError(f"tm_tok_attn_bwd: lse {tuple(lse.shape)} / dO {tuple(dO.shape)} outside the built shape or on another device")
     dqkv = _fused_dqkv("tm_tok_attn_bwd", dqkv, qkv)
-    dU = torch.empty((TM_H, TM_M, TM_DH), **f32)
-    dkL = torch.empty((TM_H, TM_M, TM_DH), **f32)
+    dU = _small_out("tm_tok_attn_bwd", "dU", dU, qkv)
+    dkL = _small_out("tm_tok_attn_bwd", "dkL", dkL, qkv)
     ws = torch.empty(_lib.lib().mil_tm_tok_attn_ws_floats(n, 1), **f32)
     _lib.checked().mil_tm_tok_attn_bwd(_p(qkv), _p(kL), _p(U), _p(lse), _p(dO), n, _p(dqkv), _p(dU), _p(dkL), _p(ws), _stream())
     return dqkv, dU, dkL
@@ -404,27 +423,98 @@ def _tm_bg(det: bool, pieces: int):
     return functools.partial(tm_bgemm, **kw) if kw else tm_bgemm
 
 
-def _tm_pinv_fwd(A2, det=False, pieces=0):
+# ---- the Nystrom core in phases.  _tm_fwd / _tm_bwd (one bag) and _tm_fwd_bags / _tm_bwd_bags (all bags of a step) issue the
+# same phases: the token-side ones per bag, the landmark-side ones on [8, 256, .] operands of one bag or on the stacked
+# [nb, 8, 256, .] operands of all bags as one launch of batch 8 nb.  Every landmark-side product has K <= 256, so it runs
+# unsplit at any batch (_tm_splits) and a bag's tiles are computed with the arithmetic of the batch-8 launch.
+_SQ = (TM_M * TM_M, TM_M, 1)            # [., 256, 256] row-major, and its transpose
+_SQT = (TM_M * TM_M, 1, TM_M)
+_SL = (TM_M * TM_DH, TM_DH, 1)          # [., 256, 64] row-major, and its transpose
+_SLT = (TM_M * TM_DH, 1, TM_DH)
+
+
+def _tm_pinv_fwd(A2, det=False, pieces=0, nb=None):
     """Newton-Schulz pseudo-inverse of A2 [8, 256, 256]: Z0 = A2^T / (max row sum x max column sum over the bag's 8 heads), then
     six times X = A2 Z, T2 = 15 I - X (7 I - X) = X X - 7 X + 15 I, T3 = 13 I - X T2, Z = Z T3 / 4.  Returns the last Z and what
-    _tm_pinv_bwd takes: (scale, arg, Zs, Xs, T2s, T3s)."""
+    _tm_pinv_bwd takes: (scale, arg, Zs, Xs, T2s, T3s).
+    nb: A2 is [nb, 8, 256, 256], nb bags' maps stacked; each bag's Z0 is scaled by its own 8 heads (mil_tm_pinv_init_bags) and
+    the products run at batch 8 nb.  None is the single bag on mil_tm_pinv_init."""
     bg = _tm_bg(det, pieces)
     H, M = TM_H, TM_M
     f32 = dict(device=A2.device, dtype=torch.float32)
-    scale = torch.empty(3 + 2 * H, **f32)                       # (s, max row sum, max column sum), per-head maxima behind
-    arg = torch.empty(1 + H, device=A2.device, dtype=torch.int32)
+    lead = () if nb is None else (nb,)
+    scale = torch.empty(lead + (3 + 2 * H,), **f32)             # (s, max row sum, max column sum), per-head maxima behind
+    arg = torch.empty(lead + (1 + H,), device=A2.device, dtype=torch.int32)
     Zs, Xs, T2s, T3s = [], [], [], []
-    Z = torch.empty((H, M, M), **f32)
-    _lib.checked().mil_tm_pinv_init(_p(A2), _p(scale), _p(arg), _p(Z), _stream())
-    sq = (M * M, M, 1)
+    Z = torch.empty_like(A2)
+    if nb is None:
+        _lib.checked().mil_tm_pinv_init(_p(A2), _p(scale), _p(arg), _p(Z), _stream())
+    else:
+        _lib.checked().mil_tm_pinv_init_bags(_p(A2), nb, _p(scale), _p(arg), _p(Z), _stream())
+    sq, batch = _SQ, H * (nb or 1)
     for _ in range(TM_PINV_ITERS):
-        X = bg(A2, sq, Z, sq, torch.empty_like(Z), sq, H, M, M, M)
-        T2 = bg(X, sq, X, sq, torch.empty_like(Z), sq, H, M, M, M, beta=-7.0, diag=15.0, D=X)
-        T3 = bg(X, sq, T2, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, diag=13.0)
-        Zn = bg(Z, sq, T3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
+        X = bg(A2, sq, Z, sq, torch.empty_like(Z), sq, batch, M, M, M)
+        T2 = bg(X, sq, X, sq, torch.empty_like(Z), sq, batch, M, M, M, beta=-7.0, diag=15.0, D=X)
+        T3 = bg(X, sq, T2, sq, torch.empty_like(Z), sq, batch, M, M, M, alpha=-1.0, diag=13.0)
+        Zn = bg(Z, sq, T3, sq, torch.empty_like(Z), sq, batch, M, M, M, alpha=0.25)
         Zs.append(Z); Xs.append(X); T2s.append(T2); T3s.append(T3)
         Z = Zn
     return Z, (scale, arg, Zs, Xs, T2s, T3s)
+
+
+def _tm_fwd_landmarks(qkv, qL, kL, bg, fused_a1):
+    """Token side, one bag: the landmarks into qL / kL [8, 256, 64] and, unless the token-query pass runs fused, its map
+    A1 [8, n_pad, 256] (not yet softmaxed).  Returns A1 or None."""
+    n = qkv.shape[0]
+    _lib.checked().mil_tm_landmarks(_p(qkv), n, TM_QSCALE, _p(qL), _p(kL), _stream())
+    if fused_a1:
+        return None
+    A1 = torch.empty((TM_H, n, TM_M), device=qkv.device, dtype=torch.float32)
+    bg(qkv, (TM_DH, 3 * TM_D, 1), kL, _SLT, A1, (n * TM_M, TM_M, 1), TM_H, n, TM_M, TM_DH, alpha=TM_QSCALE)
+    return A1
+
+
+def _tm_fwd_a2(qL, kL, A2, bg, batch):
+    """Landmark side: A2 = qL kL^T (not yet softmaxed) over `batch` heads."""
+    return bg(qL, _SL, kL, _SLT, A2, _SQ, batch, TM_M, TM_M, TM_DH)
+
+
+def _tm_fwd_lmk(qkv, qL, A1, A2, W, bg, fused_a3):
+    """Token side, one bag: the row softmax of the maps at hand - A1 (or None), A2 (None when the caller softmaxes it
+    itself, stacked over the bags), A3 - and W [8, 256, 64] = softmax(qL k^T) v into `W`.  Returns (A3, lse3): the softmaxed
+    map, or (fused) its rows' logsumexp."""
+    n = qkv.shape[0]
+    maps = [A for A in (A1, A2) if A is not None]
+    if fused_a3:        # no A3: W and the rows' logsumexp straight from qL and the k | v columns
+        for A in maps:
+            tm_softmax_rows(A)
+        _, lse3 = tm_lmk_attn(qkv, qL, W)
+        return None, lse3
+    A3 = torch.empty((TM_H, TM_M, n), device=qkv.device, dtype=torch.float32)
+    bg(qL, _SL, qkv[:, TM_D:], (TM_DH, 1, 3 * TM_D), A3, (TM_M * n, n, 1), TM_H, TM_M, n, TM_DH)
+    for A in maps + [A3]:
+        tm_softmax_rows(A)
+    bg(A3, (TM_M * n, n, 1), qkv[:, 2 * TM_D:], (TM_DH, 3 * TM_D, 1), W, _SL, TM_H, TM_M, TM_DH, n)
+    return A3, None
+
+
+def _tm_fwd_u(Z, W, U, bg, batch):
+    """Landmark side: U = Z W over `batch` heads."""
+    return bg(Z, _SQ, W, _SL, U, _SL, batch, TM_M, TM_DH, TM_M)
+
+
+def _tm_fwd_tok(qkv, w, A1, kL, U, bg, fused_a1):
+    """Token side, one bag: O [n_pad, 512] = A1 U with the heads merged (fused: straight from the q columns, kL and U), plus
+    the residual conv of v.  Returns (O, lse1)."""
+    n = qkv.shape[0]
+    lse1 = None
+    if fused_a1:        # no A1: O and the rows' logsumexp straight from the q columns, kL and U
+        O, lse1 = tm_tok_attn(qkv, kL, U)
+    else:
+        O = torch.empty((n, TM_D), device=qkv.device, dtype=torch.float32)
+        bg(A1, (n * TM_M, TM_M, 1), U, _SL, O, (TM_DH, TM_D, 1), TM_H, n, TM_DH, TM_M)
+    _lib.checked().mil_tm_resconv(_p(qkv), _p(w), n, _p(O), _stream())
+    return O, lse1
 
 
 def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_cls=False, det=False, pieces=0):
@@ -434,69 +524,80 @@ def _tm_fwd(qkv, w, need_attn, cls=None, fused_a3=False, fused_a1=False, fused_c
     if fused_cls:       # the cls attention reads qL, kL, Z and lse3 only: neither map is formed, whatever the two switches say
         fused_a3 = fused_a1 = True
     n = qkv.shape[0]
-    dev = qkv.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    H, M, DH, L3 = TM_H, TM_M, TM_DH, 3 * TM_D
-    q, k, v = qkv, qkv[:, TM_D:], qkv[:, 2 * TM_D:]
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    H, M, DH = TM_H, TM_M, TM_DH
     qL = torch.empty((H, M, DH), **f32)
     kL = torch.empty((H, M, DH), **f32)
-    _lib.checked().mil_tm_landmarks(_p(qkv), n, TM_QSCALE, _p(qL), _p(kL), _stream())
-    A1 = A3 = lse1 = lse3 = None                                # per pass its softmaxed map, or (fused) its rows' logsumexp
-    maps = []                                                   # the bag-sized maps this call forms, softmaxed below
-    if not fused_a1:
-        A1 = torch.empty((H, n, M), **f32)
-        bg(q, (DH, L3, 1), kL, (M * DH, 1, DH), A1, (n * M, M, 1), H, n, M, DH, alpha=TM_QSCALE)
-        maps.append(A1)
-    A2 = torch.empty((H, M, M), **f32)
-    bg(qL, (M * DH, DH, 1), kL, (M * DH, 1, DH), A2, (M * M, M, 1), H, M, M, DH)
-    if fused_a3:        # no A3: W and the rows' logsumexp straight from qL and the k | v columns
-        for A in maps + [A2]:
-            tm_softmax_rows(A)
-        W, lse3 = tm_lmk_attn(qkv, qL)
-    else:
-        A3 = torch.empty((H, M, n), **f32)
-        bg(qL, (M * DH, DH, 1), k, (DH, 1, L3), A3, (M * n, n, 1), H, M, n, DH)
-        for A in maps + [A2, A3]:
-            tm_softmax_rows(A)
-        W = torch.empty((H, M, DH), **f32)
-        bg(A3, (M * n, n, 1), v, (DH, L3, 1), W, (M * DH, DH, 1), H, M, DH, n)
+    A1 = _tm_fwd_landmarks(qkv, qL, kL, bg, fused_a1)
+    A2 = _tm_fwd_a2(qL, kL, torch.empty((H, M, M), **f32), bg, H)
+    W = torch.empty((H, M, DH), **f32)
+    A3, lse3 = _tm_fwd_lmk(qkv, qL, A1, A2, W, bg, fused_a3)
     Z, pinv = _tm_pinv_fwd(A2, det, pieces)
-    sq = (M * M, M, 1)
-    U = bg(Z, sq, W, (M * DH, DH, 1), torch.empty((H, M, DH), **f32), (M * DH, DH, 1), H, M, DH, M)
-    if fused_a1:        # no A1: O and the rows' logsumexp straight from the q columns, kL and U
-        O, lse1 = tm_tok_attn(qkv, kL, U)
-    else:
-        O = torch.empty((n, TM_D), **f32)
-        bg(A1, (n * M, M, 1), U, (M * DH, DH, 1), O, (DH, TM_D, 1), H, n, DH, M)
-    _lib.checked().mil_tm_resconv(_p(qkv), _p(w), n, _p(O), _stream())
+    U = _tm_fwd_u(Z, W, torch.empty((H, M, DH), **f32), bg, H)
+    O, lse1 = _tm_fwd_tok(qkv, w, A1, kL, U, bg, fused_a1)
     attn = None
     if need_attn == "cls":  # the cls row of that map folded onto the patches, [8, s^2]: no map is formed
         attn = tm_cls_attention_fused(qkv, qL, kL, Z, lse3, **cls) if fused_cls else tm_cls_attention(A1, Z, A3, **cls)
     elif need_attn:         # A1 Z A3 [8, n_pad, n_pad] (nystrom_attention return_attn), forward only
-        T = bg(A1, (n * M, M, 1), Z, sq, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
+        T = bg(A1, (n * M, M, 1), Z, _SQ, torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, M)
         attn = bg(T, (n * M, M, 1), A3, (M * n, n, 1), torch.empty((H, n, n), **f32), (n * n, n, 1), H, n, n, M)
     saved = SimpleNamespace(qL=qL, kL=kL, A1=A1, lse1=lse1, A2=A2, A3=A3, lse3=lse3, W=W, U=U, Z=Z,
                             pinv=pinv, det=det, pieces=pieces)
     return O, attn, saved
 
 
-def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s, det=False, pieces=0):
-    """dA2 from dZ (the gradient of the last iterate) by the reverse sweep of the six iterations and of Z0."""
+def _tm_fwd_bags(qkvs, w, fused_a3=False, fused_a1=False, det=False, pieces=0):
+    """_tm_fwd (need_attn False) over the bags of a step: the token-side phases per bag, writing each bag's landmarks and W
+    into its slice of buffers stacked [nb, 8, 256, .]; then A2, its softmax, the pseudo-inverse and U once for all bags at
+    batch 8 nb; then each bag's O.  Returns ([O_b], saved): the stacked landmark-side tensors plus, per bag, its maps / lse."""
     bg = _tm_bg(det, pieces)
-    H, M = TM_H, TM_M
-    sq = (M * M, M, 1)
+    nb = len(qkvs)
+    f32 = dict(device=qkvs[0].device, dtype=torch.float32)
+    H, M, DH = TM_H, TM_M, TM_DH
+    qL, kL, W = (torch.empty((nb, H, M, DH), **f32) for _ in range(3))
+    bags = []
+    for b, qkv in enumerate(qkvs):
+        A1 = _tm_fwd_landmarks(qkv, qL[b], kL[b], bg, fused_a1)
+        A3, lse3 = _tm_fwd_lmk(qkv, qL[b], A1, None, W[b], bg, fused_a3)
+        bags.append(SimpleNamespace(A1=A1, A3=A3, lse1=None, lse3=lse3))
+    A2 = tm_softmax_rows(_tm_fwd_a2(qL, kL, torch.empty((nb, H, M, M), **f32), bg, nb * H))
+    Z, pinv = _tm_pinv_fwd(A2, det, pieces, nb=nb)
+    U = _tm_fwd_u(Z, W, torch.empty((nb, H, M, DH), **f32), bg, nb * H)
+    outs = []
+    for b, qkv in enumerate(qkvs):
+        O, bags[b].lse1 = _tm_fwd_tok(qkv, w, bags[b].A1, kL[b], U[b], bg, fused_a1)
+        outs.append(O)
+    saved = SimpleNamespace(qL=qL, kL=kL, A2=A2, W=W, U=U, Z=Z, pinv=pinv, det=det, pieces=pieces, bags=bags,
+                            fused_a1=fused_a1, fused_a3=fused_a3)
+    return outs, saved
+
+
+def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s, det=False, pieces=0, nb=None):
+    """dA2 from dZ (the gradient of the last iterate) by the reverse sweep of the six iterations and of Z0.  nb: as in
+    _tm_pinv_fwd - the stacked form, with the grouped backward of the start."""
+    bg = _tm_bg(det, pieces)
+    M, batch = TM_M, TM_H * (nb or 1)
+    sq, sqt = _SQ, _SQT
     dA2 = torch.zeros_like(A2)
     for t in reversed(range(TM_PINV_ITERS)):
         Z, X, T2, T3 = Zs[t], Xs[t], T2s[t], T3s[t]
-        dZ = bg(G, sq, T3, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)      # Zn = Z T3 / 4
-        dT3 = bg(Z, (M * M, 1, M), G, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=0.25)
-        dT2 = bg(X, (M * M, 1, M), dT3, sq, torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0)   # T3 = 13 I - X T2
-        dX = bg(dT3, sq, T2, (M * M, 1, M), torch.empty_like(Z), sq, H, M, M, M, alpha=-1.0, beta=-7.0, D=dT2)
-        bg(dT2, sq, X, (M * M, 1, M), dX, sq, H, M, M, M, beta=1.0)                           # T2 = X X - 7 X + 15 I
-        bg(X, (M * M, 1, M), dT2, sq, dX, sq, H, M, M, M, beta=1.0)
-        bg(dX, sq, Z, (M * M, 1, M), dA2, sq, H, M, M, M, beta=1.0)                           # X = A2 Z
-        bg(A2, (M * M, 1, M), dX, sq, dZ, sq, H, M, M, M, beta=1.0)
+        dZ = bg(G, sq, T3, sqt, torch.empty_like(Z), sq, batch, M, M, M, alpha=0.25)           # Zn = Z T3 / 4
+        dT3 = bg(Z, sqt, G, sq, torch.empty_like(Z), sq, batch, M, M, M, alpha=0.25)
+        dT2 = bg(X, sqt, dT3, sq, torch.empty_like(Z), sq, batch, M, M, M, alpha=-1.0)         # T3 = 13 I - X T2
+        dX = bg(dT3, sq, T2, sqt, torch.empty_like(Z), sq, batch, M, M, M, alpha=-1.0, beta=-7.0, D=dT2)
+        bg(dT2, sq, X, sqt, dX, sq, batch, M, M, M, beta=1.0)                                  # T2 = X X - 7 X + 15 I
+        bg(X, sqt, dT2, sq, dX, sq, batch, M, M, M, beta=1.0)
+        bg(dX, sq, Z, sqt, dA2, sq, batch, M, M, M, beta=1.0)                                  # X = A2 Z
+        bg(A2, sqt, dX, sq, dZ, sq, batch, M, M, M, beta=1.0)
         G = dZ
+    if nb is not None:
+        if det:
+            ws = _ws(_lib.lib().mil_tm_pinv_ws_floats_bags(nb), A2)
+            _lib.checked().mil_tm_pinv_init_bwd_bags_fixed(_p(G), _p(Zs[0]), _p(scale), _p(arg), nb, _p(dA2), _p(ws), _stream())
+            return dA2
+        ws = torch.zeros(nb, device=A2.device, dtype=torch.float32)
+        _lib.checked().mil_tm_pinv_init_bwd_bags(_p(G), _p(Zs[0]), _p(scale), _p(arg), nb, _p(dA2), _p(ws), _stream())
+        return dA2
     if det:
         ws = _ws(_lib.lib().mil_tm_pinv_ws_floats(), A2)
         _lib.checked().mil_tm_pinv_init_bwd_fixed(_p(G), _p(Zs[0]), _p(scale), _p(arg), _p(dA2), _p(ws), _stream())
@@ -506,55 +607,128 @@ def _tm_pinv_bwd(G, A2, scale, arg, Zs, Xs, T2s, T3s, det=False, pieces=0):
     return dA2
 
 
-def _tm_bwd(dO, qkv, w, saved):
-    """`saved` as _tm_fwd left it: a pass that ran fused has its lse (lse1 [8, n_pad], lse3 [8, 256]) and no map, and its
-    backward takes the fused entry too."""
-    s = saved
-    qL, kL, A1, A2, A3, W, U, Z = s.qL, s.kL, s.A1, s.A2, s.A3, s.W, s.U, s.Z
-    fused_a1, fused_a3 = s.lse1 is not None, s.lse3 is not None
-    det, pieces = s.det, getattr(s, "pieces", 0)
-    bg = _tm_bg(det, pieces)
+def _tm_bwd_tok(dO, qkv, A1, lse1, kL, U, dqkv, dU, dkL, bg):
+    """Token side, one bag: dU into `dU`; fused (lse1 given) also dq into columns 0 .. 511 of dqkv before anything adds onto
+    them and the pass's share of dkL into `dkL`; else dA1, returned."""
     n = qkv.shape[0]
-    f32 = dict(device=qkv.device, dtype=torch.float32)
-    H, M, DH, L3 = TM_H, TM_M, TM_DH, 3 * TM_D
-    q, k, v = qkv, qkv[:, TM_D:], qkv[:, 2 * TM_D:]
-    sq, sl = (M * M, M, 1), (M * DH, DH, 1)
-    dqkv = torch.empty((n, L3), **f32)
-    dw = torch.empty(H * TM_CONV, **f32) if det else torch.zeros(H * TM_CONV, **f32)      # the fold overwrites dw
-    if fused_a1:        # dq into columns 0 .. 511 of dqkv before anything adds onto them, dU, and the pass's share of dkL
-        _, dU, dkL = tm_tok_attn_bwd(qkv, kL, U, s.lse1, dO, dqkv)
+    if lse1 is not None:
+        tm_tok_attn_bwd(qkv, kL, U, lse1, dO, dqkv, dU, dkL)
+        return None
+    dA1 = bg(dO, (TM_DH, TM_D, 1), U, _SLT, torch.empty((TM_H, n, TM_M), device=qkv.device, dtype=torch.float32),
+             (n * TM_M, TM_M, 1), TM_H, n, TM_M, TM_DH)
+    bg(A1, (n * TM_M, 1, TM_M), dO, (TM_DH, TM_D, 1), dU, _SL, TM_H, TM_M, TM_DH, n)
+    return dA1
+
+
+def _tm_bwd_zw(dU, W, Z, dZ, dW, bg, batch):
+    """Landmark side: dZ = dU W^T and dW = Z^T dU over `batch` heads."""
+    bg(dU, _SL, W, _SLT, dZ, _SQ, batch, TM_M, TM_M, TM_DH)
+    bg(Z, _SQT, dU, _SL, dW, _SL, batch, TM_M, TM_DH, TM_M)
+
+
+def _tm_bwd_lmk(dO, qkv, w, A3, lse3, qL, W, dW, dqkv, dqL, dw, det, bg):
+    """Token side, one bag: fused (lse3 given) dk | dv into dqkv and the pass's share of dqL into `dqL`, before the stages that
+    add onto them; else dA3 (returned) and dv.  Then the residual conv's backward: the v columns of dqkv and dw [8 x 33]."""
+    n = qkv.shape[0]
+    dA3 = None
+    if lse3 is not None:
+        tm_lmk_attn_bwd(qkv, qL, W, lse3, dW, dqkv, dqL)
     else:
-        dA1 = bg(dO, (DH, TM_D, 1), U, (M * DH, 1, DH), torch.empty((H, n, M), **f32), (n * M, M, 1), H, n, M, DH)
-        dU = bg(A1, (n * M, 1, M), dO, (DH, TM_D, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n)
-    dZ = bg(dU, sl, W, (M * DH, 1, DH), torch.empty((H, M, M), **f32), sq, H, M, M, DH)
-    dW = bg(Z, (M * M, 1, M), dU, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
-    if fused_a3:        # dk | dv into dqkv and the pass's share of dqL, before the stages that add onto them
-        _, dqL = tm_lmk_attn_bwd(qkv, qL, W, s.lse3, dW, dqkv)
-    else:
-        dA3 = bg(dW, sl, v, (DH, 1, L3), torch.empty((H, M, n), **f32), (M * n, n, 1), H, M, n, DH)
-        bg(A3, (M * n, 1, n), dW, sl, dqkv[:, 2 * TM_D:], (DH, L3, 1), H, n, DH, M)            # dv = A3^T dW
+        dA3 = bg(dW, _SL, qkv[:, 2 * TM_D:], (TM_DH, 1, 3 * TM_D), torch.empty((TM_H, TM_M, n), device=qkv.device, dtype=torch.float32),
+                 (TM_M * n, n, 1), TM_H, TM_M, n, TM_DH)
+        bg(A3, (TM_M * n, 1, n), dW, _SL, dqkv[:, 2 * TM_D:], (TM_DH, 3 * TM_D, 1), TM_H, n, TM_DH, TM_M)    # dv = A3^T dW
     if det:
         _lib.checked().mil_tm_resconv_bwd_fixed(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw),
                                                 _p(_ws(_lib.lib().mil_tm_resconv_ws_floats(n), qkv)), _stream())
     else:
         _lib.checked().mil_tm_resconv_bwd(_p(dO), _p(qkv), _p(w), n, _p(dqkv), _p(dw), _stream())
-    if not fused_a1:
-        dS1 = tm_softmax_rows_bwd(A1, dA1)
-    if not fused_a3:
-        dS3 = tm_softmax_rows_bwd(A3, dA3)
-    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv, det=det, pieces=pieces))
-    if not fused_a1:
-        bg(dS1, (n * M, M, 1), kL, sl, dqkv, (DH, L3, 1), H, n, DH, M, alpha=TM_QSCALE)        # dq
-        dkL = bg(dS1, (n * M, 1, M), q, (DH, L3, 1), torch.empty((H, M, DH), **f32), sl, H, M, DH, n, alpha=TM_QSCALE)
-    bg(dS2, (M * M, 1, M), qL, sl, dkL, sl, H, M, DH, M, beta=1.0)
-    if fused_a3:
-        bg(dS2, sq, kL, sl, dqL, sl, H, M, DH, M, beta=1.0)
-    else:
-        dqL = bg(dS2, sq, kL, sl, torch.empty((H, M, DH), **f32), sl, H, M, DH, M)
-        bg(dS3, (M * n, n, 1), k, (DH, L3, 1), dqL, sl, H, M, DH, n, beta=1.0)
-        bg(dS3, (M * n, 1, n), qL, sl, dqkv[:, TM_D:], (DH, L3, 1), H, n, DH, M)              # dk
+    return dA3
+
+
+def _tm_bwd_s1(dS1, qkv, kL, dqkv, dkL, bg):
+    """Token side, one bag, materialised A1: dq into dqkv and the map's share of dkL (overwritten) from dS1."""
+    n = qkv.shape[0]
+    bg(dS1, (n * TM_M, TM_M, 1), kL, _SL, dqkv, (TM_DH, 3 * TM_D, 1), TM_H, n, TM_DH, TM_M, alpha=TM_QSCALE)        # dq
+    bg(dS1, (n * TM_M, 1, TM_M), qkv, (TM_DH, 3 * TM_D, 1), dkL, _SL, TM_H, TM_M, TM_DH, n, alpha=TM_QSCALE)
+
+
+def _tm_bwd_s2(dS2, qL, kL, dkL, dqL, fused_a3, bg, batch):
+    """Landmark side: dkL += dS2^T qL; dqL += dS2 kL behind the fused landmark pass's share, else dqL = dS2 kL."""
+    bg(dS2, _SQT, qL, _SL, dkL, _SL, batch, TM_M, TM_DH, TM_M, beta=1.0)
+    bg(dS2, _SQ, kL, _SL, dqL, _SL, batch, TM_M, TM_DH, TM_M, beta=1.0 if fused_a3 else 0.0)
+
+
+def _tm_bwd_tail(dS3, qkv, qL, dqL, dkL, dqkv, bg):
+    """Token side, one bag: with a materialised A3 its share of dqL and dk from dS3; then the landmark gradients spread onto
+    the q and k columns of dqkv."""
+    n = qkv.shape[0]
+    if dS3 is not None:
+        bg(dS3, (TM_M * n, n, 1), qkv[:, TM_D:], (TM_DH, 3 * TM_D, 1), dqL, _SL, TM_H, TM_M, TM_DH, n, beta=1.0)
+        bg(dS3, (TM_M * n, 1, n), qL, _SL, dqkv[:, TM_D:], (TM_DH, 3 * TM_D, 1), TM_H, n, TM_DH, TM_M)      # dk
     _lib.checked().mil_tm_landmarks_bwd(_p(dqL), _p(dkL), n, TM_QSCALE, _p(dqkv), _stream())
+
+
+def _tm_bwd(dO, qkv, w, saved):
+    """`saved` as _tm_fwd left it: a pass that ran fused has its lse (lse1 [8, n_pad], lse3 [8, 256]) and no map, and its
+    backward takes the fused entry too."""
+    s = saved
+    qL, kL, A1, A2, A3, W, U, Z = s.qL, s.kL, s.A1, s.A2, s.A3, s.W, s.U, s.Z
+    fused_a3 = s.lse3 is not None
+    det, pieces = s.det, getattr(s, "pieces", 0)
+    bg = _tm_bg(det, pieces)
+    n = qkv.shape[0]
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    H, M, DH = TM_H, TM_M, TM_DH
+    dqkv = torch.empty((n, 3 * TM_D), **f32)
+    dw = torch.empty(H * TM_CONV, **f32) if det else torch.zeros(H * TM_CONV, **f32)      # the fold overwrites dw
+    dU, dkL, dqL, dW = (torch.empty((H, M, DH), **f32) for _ in range(4))
+    dA1 = _tm_bwd_tok(dO, qkv, A1, s.lse1, kL, U, dqkv, dU, dkL, bg)
+    dZ = torch.empty((H, M, M), **f32)
+    _tm_bwd_zw(dU, W, Z, dZ, dW, bg, H)
+    dA3 = _tm_bwd_lmk(dO, qkv, w, A3, s.lse3, qL, W, dW, dqkv, dqL, dw, det, bg)
+    dS1 = tm_softmax_rows_bwd(A1, dA1) if dA1 is not None else None
+    dS3 = tm_softmax_rows_bwd(A3, dA3) if dA3 is not None else None
+    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv, det=det, pieces=pieces))
+    if dS1 is not None:
+        _tm_bwd_s1(dS1, qkv, kL, dqkv, dkL, bg)
+    _tm_bwd_s2(dS2, qL, kL, dkL, dqL, fused_a3, bg, H)
+    _tm_bwd_tail(dS3, qkv, qL, dqL, dkL, dqkv, bg)
     return dqkv, dw
+
+
+def _tm_bwd_bags(dOs, qkvs, w, saved):
+    """_tm_bwd over the bags of a step, `saved` as _tm_fwd_bags left it: per bag dU (and dA1 or the fused token backward) into
+    stacked buffers; dZ and dW at batch 8 nb; per bag the A3 side, the residual conv and the maps' softmax backward; the
+    pseudo-inverse's reverse sweep, A2's softmax backward and the two dS2 products at batch 8 nb; per bag what remains.
+    Returns ([dqkv_b], dw) with dw the bags' dw_b added in bag order."""
+    s = saved
+    qL, kL, A2, W, U, Z = s.qL, s.kL, s.A2, s.W, s.U, s.Z
+    det, pieces = s.det, s.pieces
+    bg = _tm_bg(det, pieces)
+    nb = len(qkvs)
+    f32 = dict(device=w.device, dtype=torch.float32)
+    H, M, DH = TM_H, TM_M, TM_DH
+    dqkvs = [torch.empty((qkv.shape[0], 3 * TM_D), **f32) for qkv in qkvs]
+    dws = torch.empty((nb, H * TM_CONV), **f32) if det else torch.zeros((nb, H * TM_CONV), **f32)
+    dU, dkL, dqL, dW = (torch.empty((nb, H, M, DH), **f32) for _ in range(4))
+    dA1s = [_tm_bwd_tok(dOs[b], qkvs[b], g.A1, g.lse1, kL[b], U[b], dqkvs[b], dU[b], dkL[b], bg) for b, g in enumerate(s.bags)]
+    dZ = torch.empty((nb, H, M, M), **f32)
+    _tm_bwd_zw(dU, W, Z, dZ, dW, bg, nb * H)
+    dS3s = []
+    for b, g in enumerate(s.bags):
+        dA3 = _tm_bwd_lmk(dOs[b], qkvs[b], w, g.A3, g.lse3, qL[b], W[b], dW[b], dqkvs[b], dqL[b], dws[b], det, bg)
+        dS3s.append(tm_softmax_rows_bwd(g.A3, dA3) if dA3 is not None else None)
+        if dA1s[b] is not None:
+            _tm_bwd_s1(tm_softmax_rows_bwd(g.A1, dA1s[b]), qkvs[b], kL[b], dqkvs[b], dkL[b], bg)
+            dA1s[b] = None
+    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv, det=det, pieces=pieces, nb=nb))
+    _tm_bwd_s2(dS2, qL, kL, dkL, dqL, s.fused_a3, bg, nb * H)
+    for b in range(nb):
+        _tm_bwd_tail(dS3s[b], qkvs[b], qL[b], dqL[b], dkL[b], dqkvs[b], bg)
+    dw = dws[0]
+    for b in range(1, nb):
+        dw = dw + dws[b]
+    return dqkvs, dw
 
 
 class _NystromCore(torch.autograd.Function):
@@ -612,3 +786,51 @@ def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=N
         raise ValueError("nystrom_core: need_attn='cls' needs pad, s and the bag length (n, or len_dev and bag)")
     return _NystromCore.apply(qkv, w, "cls", dict(pad=int(pad), s=int(s), n=n, len_dev=len_dev, bag=int(bag)), False, False,
                               _tm_fused_cls(fused_cls, "cls"), det, pieces)
+
+
+TM_MAX_BATCH_BAGS = 1024            # the bags one grouped pseudo-inverse start takes (csrc/transmil.hip)
+
+
+class _NystromCoreBags(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w, fused_a3, fused_a1, det, pieces, *qkvs):
+        w = _f32c(w, "res_conv.weight")
+        qkvs = [_f32c(qkv, "qkv") for qkv in qkvs]
+        if not 1 <= len(qkvs) <= TM_MAX_BATCH_BAGS:
+            raise _lib.MilHipError(f"nystrom_core_bags: {len(qkvs)} bags, built for 1 .. {TM_MAX_BATCH_BAGS}")
+        for qkv in qkvs:
+            if (qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] <= 0 or qkv.shape[0] % TM_M or qkv.device != w.device
+                    or w.numel() != TM_H * TM_CONV):
+                raise _lib.MilHipError(f"nystrom_core_bags: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built "
+                                       "shape, or on two devices")
+        outs, saved = _tm_fwd_bags(qkvs, w, fused_a3, fused_a1, det, pieces)
+        ctx.saved = saved
+        ctx.save_for_backward(w, *qkvs)
+        ctx.w_shape = w.shape
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *dOs):
+        w, *qkvs = ctx.saved_tensors
+        dqkvs, dw = _tm_bwd_bags([_f32c(dO, "dO") for dO in dOs], qkvs, w, ctx.saved)
+        ctx.saved = None
+        return (dw.reshape(ctx.w_shape), None, None, None, None, *dqkvs)
+
+
+def nystrom_core_bags(qkvs, w, *, fused_a3=None, fused_a1=None, deterministic=None, pieces=None):
+    """nystrom_core (need_attn False) for all bags of a step as ONE autograd function: qkvs = one [n_pad_b, 1536] per bag (each
+    n_pad_b a positive multiple of 256, they may differ; 1 .. 1024 bags), w = res_conv.weight -> [out_b [n_pad_b, 512]].
+    The token-side stages - the landmarks, the A1 / A3 maps or the fused passes, the residual conv - run per bag as in
+    nystrom_core.  The landmark-side chain, whose shapes do not depend on the bag, runs once on buffers stacked
+    [nb, 8, 256, .]: A2 and its softmax, the pseudo-inverse's start (mil_tm_pinv_init_bags: every bag scaled by the maxima of ITS
+    8 heads, as the reference does with one bag per call), the 24 + 48 chain products, U, dZ, dW and the two dS2 products, each
+    one launch of batch 8 nb.  These products have K <= 256 and so one split at any batch: a bag's tiles see the arithmetic
+    of the bag-by-bag launch, and with deterministic=True every out_b and dqkv_b is bit-equal to nystrom_core on that bag.
+    dw is the bags' dw_b added in bag order 0, 1, 2, ...
+    fused_a3, fused_a1, deterministic, pieces: as in nystrom_core (None reads the environment).  need_attn is not offered:
+    callers keep the bag-by-bag route for True and "cls".  No host read; every workspace is a torch.empty, so the call can be
+    captured into a graph.  The switch that sends a module's step here is tm_batch_bags (MIL_TM_BATCH_BAGS, default 0)."""
+    return list(_NystromCoreBags.apply(w, _tm_fused_a3(fused_a3, False), _tm_fused_a1(fused_a1, False),
+                                       tm_deterministic(deterministic), tm_pieces(pieces), *qkvs))
+
+

@@ -130,8 +130,12 @@ class RaggedTransMILStepper:
         det = ops.tm_deterministic(m.extractor_pathology.deterministic)
         # ... nor one captured on the fp32 products for a model that asks for the split-bf16 ones
         pieces = ops.tm_pieces(m.extractor_pathology.gemm_pieces)
+        # ... nor one captured bag by bag for a model that asks for the batched landmark-side chain (several bags, no attention
+        # outputs: what TransMIL._run_bags takes that route for)
+        batched = ops.tm_batch_bags(m.extractor_pathology.batch_bags) and len(slot.sides) > 1 and not attn
         key = (("transmil-sides", slot.sides, training, self.backward) + (("patch_attn",) if attn else ())
-               + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ()))
+               + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
+               + (("batch_bags",) if batched else ()))
         body = lambda: self._body(slot)      # noqa: E731
         ctr = m.extractor_pathology._drop_ctr
         # the warm-up passes in front of a capture draw masks too: the pass counter goes back, so the stream of a replayed

@@ -24,7 +24,12 @@ median (min - max) of --reps regions each; a region is one untimed step behind t
 (the flag is part of its key) and the regions alternate between the two.
 --pieces 3: the default rows (eval forward, forward + backward) with the Nystrom core's K >= 256 products on three-piece
 split-bf16 MFMA (TransMIL.gemm_pieces, the switch of MIL_TM_PIECES / --tm_gemm_pieces); --pieces 0 pins the fp32 products.  The
-rows carry the value and the min - max of the regions next to the median: run 0 and 3 one after the other on one machine."""
+rows carry the value and the min - max of the regions next to the median: run 0 and 3 one after the other on one machine.
+--bags B (B > 1): per N, the TRAINING step over B bags of N patches each - eager (the module called with host lengths) and
+replayed (RaggedTransMILStepper, B bags per slot) - with the landmark-side chain bag by bag (TransMIL.batch_bags = False: the
+route of MIL_TM_BATCH_BAGS=0), batched over the bags (= True: ops.nystrom_core_bags), and bag by bag again, in one process, same
+model, same bags; median (min - max) of --reps regions each and the peak allocated bytes of one eager step per route.  The
+first and third columns are the yardstick.  B = 1 (the default) leaves every other row as it is."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -305,6 +310,63 @@ def det_rows(a, dev, args):
         torch.cuda.empty_cache()
 
 
+def bags_rows(a, dev, args):
+    from mil_amd import ops
+    from mil_amd.optim import FlatAdam
+    from mil_amd.transmil_step import RaggedTransMILStepper
+    B = a.bags
+    bce = torch.nn.BCELoss()
+    y = syn.make_labels(3, B).to(dev)
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    for N in a.N:
+        torch.manual_seed(1234)
+        m_e = get_model(args).to(dev).train()
+        torch.manual_seed(1234)
+        m_r = get_model(args).to(dev).train()
+        o_e = FlatAdam(list(m_e.parameters()), lr=1e-5, counted=True)
+        o_r = FlatAdam(list(m_r.parameters()), lr=1e-5, counted=True)
+        st = RaggedTransMILStepper(m_r, o_r, B=B, drop_seed=1)
+        lengths = [N] * B
+        x = torch.cat([syn.make_bags(N + b, 1, N, 768)[0] for b in range(B)], 0).to(dev)
+        slot = st.slot(lengths)
+        slot.x[:B * N].copy_(x)
+        slot.y.copy_(y)
+
+        def eager():
+            o_e.zero_grad()
+            _, prob = m_e([x], lengths)
+            ops.backward(bce(prob, y))
+            o_e.step()
+
+        def replay():
+            st.step(slot, lengths)
+
+        res = dict(N=N, bags=B, n_pad=geometry(N)["n_pad"], regions=a.reps)
+        for on, tag in ((False, "off"), (True, "on"), (False, "off_again")):
+            m_e.extractor_pathology.batch_bags = m_r.extractor_pathology.batch_bags = on
+            for _ in range(3):                        # the stepper: eager visit, capture, first replay of this route's key
+                replay()
+            for name, fn in (("eager", eager), ("replay", replay)):
+                ts = region_times(fn, a.reps, a.warmup)
+                res.update({f"{name}_{tag}_ms": round(med(ts), 3), f"{name}_{tag}_min_ms": round(min(ts), 3),
+                            f"{name}_{tag}_max_ms": round(max(ts), 3)})
+        for on, tag in ((False, "off"), (True, "on")):
+            m_e.extractor_pathology.batch_bags = on
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            eager()
+            torch.cuda.synchronize()
+            res[f"eager_{tag}_peak_mib"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+        assert st.n_graphs == 2, st.n_graphs          # one graph per route: the switch is part of the key
+        for name in ("eager", "replay"):
+            res[f"{name}_on_over_off"] = round(res[f"{name}_on_ms"] / min(res[f"{name}_off_ms"], res[f"{name}_off_again_ms"]), 4)
+        res["graph_mib"] = {("on" if "batch_bags" in k else "off"): round(v / 2 ** 20, 1) for k, v in st.graph_bytes.items()}
+        print(json.dumps(res), flush=True)
+        del st, slot, m_e, m_r, o_e, o_r, x
+        torch.cuda.empty_cache()
+
+
 def region_times(fn, reps, warm):
     for _ in range(warm):
         fn()
@@ -339,10 +401,15 @@ def main():
                     "on in alternating regions; with --graph the replayed step too")
     ap.add_argument("--pieces", type=int, choices=[0, 3], default=None, help="the default rows with TransMIL.gemm_pieces set: 3 = "
                     "split-bf16 products in the Nystrom core, 0 = fp32 products; unset: MIL_TM_PIECES decides")
+    ap.add_argument("--bags", type=int, default=1, help="B > 1: the training step over B bags of N patches, eager and "
+                    "replayed, with TransMIL.batch_bags off, on, off again: ms and peak allocated bytes")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
     args = SimpleNamespace(modality=["pathology"], model_pathology="TransMIL", num_classes=2, patch_dim=768, variant="image_only")
+    if a.bags > 1:
+        bags_rows(a, dev, args)
+        return
     if a.attn:
         attn_rows(a, dev, args)
         return
