@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 19 */
+int mil_abi_version(void);   /* 20 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1255,6 +1255,51 @@ int mil_tm_resconv_bwd_fixed(const float* dout, const float* qkv, const float* w
 size_t mil_tm_ppeg_ws_floats(int s);
 int mil_tm_ppeg_bwd_fixed(const float* dy, const float* x, int s, const float* W7, const float* W5, const float* W3, float* dx,
                           float* dWf, float* db, float* ws, void* stream);
+/* ---- TransMIL, a step's bags as one packed sequence (csrc/tm_packed.h; ops: nystrom_core_packed / MIL_TM_PACKED=1) -----
+ * The token-side entries above over ALL bags of a step in one launch set: qkv, O, dout, dqkv hold the bags' front-padded rows
+ * one after another, R = 256 x total_blocks rows ([R, 1536] / [R, 512]); every bag's n_pad is a multiple of 256, so a 256-row
+ * block belongs to one bag and no kernel's tile (128 or 256 rows) straddles two.  Each entry takes its single-bag twin's
+ * arguments without n_pad, and three more:
+ *   blk_off       device int32 [nb + 1 + total_blocks]: blk_off[b] (b <= nb) = the 256-row blocks in front of bag b, cumulative,
+ *                 blk_off[nb] = total_blocks; behind them bag_of_blk[k] = the bag of block k (one scalar load per workgroup)
+ *   nb            the bags, 1 .. 1024
+ *   total_blocks  nb <= total_blocks <= INT_MAX / 256 (the conv's backward: <= 65535, its chunks are counted in gridDim.y)
+ * Bag b owns rows [256 blk_off[b], 256 blk_off[b + 1]), its landmark group is l_b = blk_off[b + 1] - blk_off[b], and its small
+ * operands - qL, kL, W, U, dqL, dkL, dW, dU [8, 256, 64], lse3 [8, 256] - are slice b of buffers stacked [nb, 8, 256, .], the
+ * layout of mil_tm_pinv_init_bags' callers.  The kernels are the single-bag ones with the bag read off the block index, and
+ * every sum of a bag keeps its terms and their order: each per-bag output - qL, kL, W, lse3, O, the rows' lse, the conv's
+ * addend, every dqkv row, dqL, dU, dkL - is BIT-EQUAL to the single-bag entry on that bag's rows and slices (lse of the token
+ * pass is [8, R] over the packed rows, where the single-bag entry has [8, n_pad]).  The one sum that crosses bags is the
+ * conv's dw [8, 33]: all bags' chunks, atomically, or (_fixed) in ascending packed order.
+ * A null pointer, nb outside [1, 1024], total_blocks < nb or beyond the limit above: MIL_EINVAL before any launch.  The
+ * kernels trust nothing the table holds: a block whose bag lies outside [0, nb), or a bag whose block range leaves
+ * [0, total_blocks], is skipped (its outputs are not written), so no address leaves the R rows or the nb slices.  No atomics
+ * in the attention and landmark entries, nor in mil_tm_resconv_bwd_packed_fixed.  Workspaces (floats, 0 for refused arguments):
+ *   mil_tm_lmk_attn_packed_ws_floats   forward total_blocks x 8 x 256 x 66; backward nb x 2048 + 2 total_blocks x 8 x 16384
+ *   mil_tm_tok_attn_packed_ws_floats   forward 0 (ws may be null); backward 2 x total_blocks x 8 x 16384
+ *   mil_tm_resconv_packed_ws_floats    forward 0; backward (the _fixed entry) total_blocks x 264
+ * Launches as the twins: landmarks 1 / 1, lmk_attn 2 / 3, tok_attn 1 / 2, resconv 1 / 2 / 3 - whatever nb. */
+int mil_tm_landmarks_packed(const float* qkv, float qscale, float* qL, float* kL, const int32_t* blk_off, int nb, int total_blocks,
+                            void* stream);
+int mil_tm_landmarks_bwd_packed(const float* dqL, const float* dkL, float qscale, float* dqkv, const int32_t* blk_off, int nb,
+                                int total_blocks, void* stream);
+size_t mil_tm_lmk_attn_packed_ws_floats(int total_blocks, int nb, int backward);
+int mil_tm_lmk_attn_fwd_packed(const float* qkv, const float* qL, float* W, float* lse, float* ws, const int32_t* blk_off, int nb,
+                               int total_blocks, void* stream);
+int mil_tm_lmk_attn_bwd_packed(const float* qkv, const float* qL, const float* W, const float* lse, const float* dW, float* dqkv,
+                               float* dqL, float* ws, const int32_t* blk_off, int nb, int total_blocks, void* stream);
+size_t mil_tm_tok_attn_packed_ws_floats(int total_blocks, int nb, int backward);
+int mil_tm_tok_attn_fwd_packed(const float* qkv, const float* kL, const float* U, float* O, float* lse, float* ws,
+                               const int32_t* blk_off, int nb, int total_blocks, void* stream);
+int mil_tm_tok_attn_bwd_packed(const float* qkv, const float* kL, const float* U, const float* lse, const float* dO, float* dqkv,
+                               float* dU, float* dkL, float* ws, const int32_t* blk_off, int nb, int total_blocks, void* stream);
+size_t mil_tm_resconv_packed_ws_floats(int total_blocks, int nb, int backward);
+int mil_tm_resconv_packed(const float* qkv, const float* w, float* out, const int32_t* blk_off, int nb, int total_blocks,
+                          void* stream);
+int mil_tm_resconv_bwd_packed(const float* dout, const float* qkv, const float* w, float* dqkv, float* dw, const int32_t* blk_off,
+                              int nb, int total_blocks, void* stream);
+int mil_tm_resconv_bwd_packed_fixed(const float* dout, const float* qkv, const float* w, float* dqkv, float* dw, float* ws,
+                                    const int32_t* blk_off, int nb, int total_blocks, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -222,6 +222,19 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_resconv_bwd_fixed": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P]),
     "mil_tm_ppeg_ws_floats": (c_size_t, [c_int]),
     "mil_tm_ppeg_bwd_fixed": (c_int, [_P, _P, c_int] + [_P] * 6 + [_P, _P]),
+    # the packed forms: the single-bag twin's arguments without n_pad, then (blk_off, nb, total_blocks) in front of the stream
+    "mil_tm_landmarks_packed": (c_int, [_P, c_float, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_landmarks_bwd_packed": (c_int, [_P, _P, c_float, _P, _P, c_int, c_int, _P]),
+    "mil_tm_lmk_attn_packed_ws_floats": (c_size_t, [c_int, c_int, c_int]),
+    "mil_tm_lmk_attn_fwd_packed": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_lmk_attn_bwd_packed": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_tok_attn_packed_ws_floats": (c_size_t, [c_int, c_int, c_int]),
+    "mil_tm_tok_attn_fwd_packed": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_tok_attn_bwd_packed": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_resconv_packed_ws_floats": (c_size_t, [c_int, c_int, c_int]),
+    "mil_tm_resconv_packed": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_resconv_bwd_packed": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "mil_tm_resconv_bwd_packed_fixed": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
 }
 # entries that return a value, not a status: checked() leaves them without an errcheck
 VALUE_RETURNING = frozenset(n for n, (res, _) in SIGNATURES.items() if res is c_size_t) | frozenset((

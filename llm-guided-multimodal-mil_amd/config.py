@@ -140,6 +140,14 @@ def create_arg_parser(argv=None):
                         "bag; each bag keeps its own pseudo-inverse scale.  Set on every TransMIL module of the model; a step "
                         "of one bag and a request for attention outputs keep the bag-by-bag route.  Models without a TransMIL "
                         "module accept the flag and ignore it.  0: the environment variable MIL_TM_BATCH_BAGS decides (default 0)")
+    p.add_argument("--tm_packed", type=int, default=0, choices=[0, 1],
+                   help="train_ddp.py and test_ddp.py: 1 = a TransMIL step of several bags runs every layer over ONE packed "
+                        "sequence of all bags' rows - LayerNorm, the pad gather, to_qkv, the landmarks, both fused attention "
+                        "passes, the residual conv, to_out, the dropout and the residual one launch set each, whatever the "
+                        "number of bags; PPEG stays per bag.  It wins over --tm_batch_bags.  Set on every TransMIL module of "
+                        "the model; a step of one bag and a request for attention outputs keep the bag-by-bag route.  Models "
+                        "without a TransMIL module accept the flag and ignore it.  0: the environment variable MIL_TM_PACKED "
+                        "decides (default 0)")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,

@@ -24,6 +24,7 @@
 
 #include "mil_common.h"
 #include "nystrom_tile.h"
+#include "tm_packed.h"
 #include "../../include/mil_hip.h"
 
 namespace {
@@ -33,9 +34,19 @@ constexpr int LA_FPART = NY_M * (NY_DH + 2);        // floats of one forward par
 constexpr int LA_BC = 128;                          // keys per backward workgroup (4 waves x 32)
 constexpr int LA_DQPART = NY_M * NY_DH;             // floats of one backward partial: [8 query tiles][64 d][32 queries]
 
-__global__ __launch_bounds__(128) void k_lmk_fwd(const float* __restrict__ qkv, const float* __restrict__ qL,
-                                                 float* __restrict__ ws) {
+// The bodies below serve two kernels each: the single-bag one (PACKED false: tab, nb, total_blocks are constants that fold
+// away, and the kernel compiles to what it was before the bodies were shared) and the packed one (csrc/tm_packed.h), where
+// the chunk index runs over all bags' rows and the small operands are taken at the chunk's bag.  The bodies' pointers carry no
+// __restrict__: inlined, they ARE the kernel's restrict arguments, which is what keeps the single-bag code as it was.
+template <bool PACKED>
+__device__ __forceinline__ void lmk_fwd_body(const float* qkv, const float* qL, float* ws, const int32_t* tab, int nb,
+                                             int total_blocks) {
     const int c = blockIdx.x, hd = blockIdx.y;
+    if constexpr (PACKED) {                     // LA_FC = 256: a forward chunk is a block
+        const int bag = tm_packed_bag(tab, nb, total_blocks, c);
+        if (bag < 0) return;
+        qL += (size_t)bag * NY_H * NY_M * NY_DH;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
     const int q0 = blockIdx.z * 64 + wave * 32;
     float qr[32];
@@ -67,9 +78,19 @@ __global__ __launch_bounds__(128) void k_lmk_fwd(const float* __restrict__ qkv, 
     }
 }
 
-// block = (32 queries, head): thread (q = tid & 31, dg = tid >> 5) owns d = dg + 8 j
-__global__ __launch_bounds__(256) void k_lmk_merge(const float* __restrict__ ws, int nc, float* __restrict__ W,
-                                                   float* __restrict__ lse) {
+__global__ __launch_bounds__(128) void k_lmk_fwd(const float* __restrict__ qkv, const float* __restrict__ qL,
+                                                 float* __restrict__ ws) {
+    lmk_fwd_body<false>(qkv, qL, ws, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(128) void k_lmk_fwd_packed(const float* __restrict__ qkv, const float* __restrict__ qL,
+                                                        float* __restrict__ ws, const int32_t* __restrict__ tab, int nb,
+                                                        int total_blocks) {
+    lmk_fwd_body<true>(qkv, qL, ws, tab, nb, total_blocks);
+}
+
+// block = (32 queries, head): thread (q = tid & 31, dg = tid >> 5) owns d = dg + 8 j.  ws: the first partial, nc: how many
+__device__ __forceinline__ void lmk_merge_body(const float* ws, int nc, float* W, float* lse) {
     const int hd = blockIdx.y, q = blockIdx.x * 32 + (threadIdx.x & 31), dg = threadIdx.x >> 5;
     const float* p0 = ws + (size_t)hd * LA_FPART;
     const size_t step = (size_t)NY_H * LA_FPART;
@@ -91,6 +112,21 @@ __global__ __launch_bounds__(256) void k_lmk_merge(const float* __restrict__ ws,
     if (dg == 0) lse[hd * NY_M + q] = m + logf(L);
 }
 
+__global__ __launch_bounds__(256) void k_lmk_merge(const float* __restrict__ ws, int nc, float* __restrict__ W,
+                                                   float* __restrict__ lse) {
+    lmk_merge_body(ws, nc, W, lse);
+}
+
+// blockIdx.z = the bag: its chunks alone, in ascending order, into slice `bag` of W and lse
+__global__ __launch_bounds__(256) void k_lmk_merge_packed(const float* __restrict__ ws, const int32_t* __restrict__ tab, int nb,
+                                                          int total_blocks, float* __restrict__ W, float* __restrict__ lse) {
+    const int bag = blockIdx.z;
+    int c0, c1;
+    if (bag >= nb || !tm_packed_range(tab, total_blocks, bag, c0, c1)) return;
+    lmk_merge_body(ws + (size_t)c0 * NY_H * LA_FPART, c1 - c0, W + (size_t)bag * NY_H * NY_M * NY_DH,
+                   lse + (size_t)bag * NY_H * NY_M);
+}
+
 __global__ __launch_bounds__(256) void k_lmk_delta(const float* __restrict__ W, const float* __restrict__ dW,
                                                    float* __restrict__ delta) {
     const int row = blockIdx.x * 256 + threadIdx.x;
@@ -108,13 +144,22 @@ __global__ __launch_bounds__(256) void k_lmk_delta(const float* __restrict__ W, 
 // This kernel sits at 256 + 91 registers, and its time hangs on the loads the compiler hoists with them.  Of nystrom_tile.h it
 // takes load32, zero16 and rtile_sum4, which leave its code as it was; the other steps stay written out, each marked with the
 // part it repeats and what that part did to the build (same 160 MFMAs, same bits; the timings are in docs/lab_notes.md)
-__global__ __launch_bounds__(256) void k_lmk_bwd(const float* __restrict__ qkv, const float* __restrict__ qL,
-                                                 const float* __restrict__ lse, const float* __restrict__ dW,
-                                                 const float* __restrict__ delta, float* __restrict__ dqkv,
-                                                 float* __restrict__ wsdq) {
+template <bool PACKED>
+__device__ __forceinline__ void lmk_bwd_body(const float* qkv, const float* qL, const float* lse, const float* dW,
+                                             const float* delta, float* dqkv, float* wsdq, const int32_t* tab, int nb,
+                                             int total_blocks) {
     __shared__ float T[4][32 * NY_TLD];           // per wave: dS [query][key] of the current tile
     __shared__ float R[4][NY_DH * 32];            // per wave: its dQ^T [d][query] of the current tile
     const int c = blockIdx.x, hd = blockIdx.y;
+    if constexpr (PACKED) {                       // two 128-key chunks per block; uniform per workgroup, ahead of every barrier
+        const int bag = tm_packed_bag(tab, nb, total_blocks, c / (TM_PACKED_BLK / LA_BC));
+        if (bag < 0) return;
+        const size_t small = (size_t)bag * NY_H * NY_M * NY_DH, row = (size_t)bag * NY_H * NY_M;
+        qL += small;
+        dW += small;
+        lse += row;
+        delta += row;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
     const size_t key0 = (size_t)c * LA_BC + wave * 32;
     const float* krow = qkv + key0 * NY_QKV + NY_D + hd * NY_DH;      // K[key0][0] of this head; V is NY_D further
@@ -191,6 +236,21 @@ __global__ __launch_bounds__(256) void k_lmk_bwd(const float* __restrict__ qkv, 
     }
 }
 
+__global__ __launch_bounds__(256) void k_lmk_bwd(const float* __restrict__ qkv, const float* __restrict__ qL,
+                                                 const float* __restrict__ lse, const float* __restrict__ dW,
+                                                 const float* __restrict__ delta, float* __restrict__ dqkv,
+                                                 float* __restrict__ wsdq) {
+    lmk_bwd_body<false>(qkv, qL, lse, dW, delta, dqkv, wsdq, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void k_lmk_bwd_packed(const float* __restrict__ qkv, const float* __restrict__ qL,
+                                                        const float* __restrict__ lse, const float* __restrict__ dW,
+                                                        const float* __restrict__ delta, float* __restrict__ dqkv,
+                                                        float* __restrict__ wsdq, const int32_t* __restrict__ tab, int nb,
+                                                        int total_blocks) {
+    lmk_bwd_body<true>(qkv, qL, lse, dW, delta, dqkv, wsdq, tab, nb, total_blocks);
+}
+
 }  // namespace
 
 extern "C" {
@@ -220,7 +280,41 @@ int mil_tm_lmk_attn_bwd(const float* qkv, const float* qL, const float* W, const
     hipLaunchKernelGGL(k_lmk_delta, dim3(NY_H * NY_M / 256), dim3(256), 0, (hipStream_t)stream, W, dW, ws);
     hipLaunchKernelGGL(k_lmk_bwd, dim3(nc, NY_H), dim3(256), 0, (hipStream_t)stream, qkv, qL, lse, dW, ws, dqkv, wsdq);
     hipLaunchKernelGGL(k_ny_reduce<1>, dim3(NY_M / 32, NY_H), dim3(256), 0, (hipStream_t)stream, wsdq, nc, dqL,
-                       (float*)nullptr);
+                       (float*)nullptr, TmPackedArg<false>{});
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+size_t mil_tm_lmk_attn_packed_ws_floats(int total_blocks, int nb, int backward) {
+    if (!tm_packed_ok(&nb, nb, total_blocks)) return 0;
+    if (backward)
+        return (size_t)nb * NY_H * NY_M + (size_t)total_blocks * (TM_PACKED_BLK / LA_BC) * NY_H * LA_DQPART;
+    return (size_t)total_blocks * NY_H * LA_FPART;
+}
+
+int mil_tm_lmk_attn_fwd_packed(const float* qkv, const float* qL, float* W, float* lse, float* ws, const int32_t* blk_off, int nb,
+                               int total_blocks, void* stream) {
+    if (!qkv || !qL || !W || !lse || !ws || !tm_packed_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    if (!ny_aligned(qkv) || !ny_aligned(qL)) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_lmk_fwd_packed, dim3(total_blocks, NY_H, NY_M / 64), dim3(128), 0, (hipStream_t)stream, qkv, qL, ws,
+                       blk_off, nb, total_blocks);
+    hipLaunchKernelGGL(k_lmk_merge_packed, dim3(NY_M / 32, NY_H, nb), dim3(256), 0, (hipStream_t)stream, ws, blk_off, nb,
+                       total_blocks, W, lse);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+int mil_tm_lmk_attn_bwd_packed(const float* qkv, const float* qL, const float* W, const float* lse, const float* dW, float* dqkv,
+                               float* dqL, float* ws, const int32_t* blk_off, int nb, int total_blocks, void* stream) {
+    if (!qkv || !qL || !W || !lse || !dW || !dqkv || !dqL || !ws || !tm_packed_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    if (!ny_aligned(qkv) || !ny_aligned(qL) || !ny_aligned(W) || !ny_aligned(dW) || !ny_aligned(dqkv)) return MIL_EINVAL;
+    constexpr int per = TM_PACKED_BLK / LA_BC;          // backward chunks per block
+    float* wsdq = ws + (size_t)nb * NY_H * NY_M;
+    hipLaunchKernelGGL(k_lmk_delta, dim3(nb * (NY_H * NY_M / 256)), dim3(256), 0, (hipStream_t)stream, W, dW, ws);
+    hipLaunchKernelGGL(k_lmk_bwd_packed, dim3(total_blocks * per, NY_H), dim3(256), 0, (hipStream_t)stream, qkv, qL, lse, dW, ws,
+                       dqkv, wsdq, blk_off, nb, total_blocks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ny_reduce<1, true>), dim3(NY_M / 32, NY_H, nb), dim3(256), 0, (hipStream_t)stream, wsdq,
+                       per, dqL, (float*)nullptr, TmPackedArg<true>{blk_off, nb, total_blocks});
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mil_common.h"
+#include "tm_packed.h"
 
 namespace {
 
@@ -129,13 +130,29 @@ __device__ __forceinline__ void store_row64(float* __restrict__ p, const f32x16&
 // Sums the partials [nc][8 heads][8 tiles][64 d][32] chunk 0, 1, 2 .. in that order into [8, 256, 64]: block = (tile, head,
 // which of the NZ = gridDim.z partial sets, out0 | out1), element e = d * 32 + row of the tile, thread tid owns e = tid + 256 j.
 // NZ is a template parameter because with one set the index of the set, read from blockIdx.z, cost its launch 0.2 of 20.7 us
-template <int NZ>
+// PACKED (csrc/tm_packed.h): blockIdx.z = set * nb + bag, the partials of a set lie over all bags' chunks, nc = the chunks per
+// 256-row block; bag b's are summed alone, in ascending order, into slice b of the stacked [nb, 8, 256, 64] output - the terms
+// and the order of the single-bag sum on that bag.  The kernel is templated as a whole, not built on a shared body: moved
+// into a function its loop comes out with another addressing and two more registers.
+template <int NZ, bool PACKED = false>
 __global__ __launch_bounds__(256) void k_ny_reduce(const float* __restrict__ ws, int nc, float* __restrict__ out0,
-                                                   float* __restrict__ out1) {
+                                                   float* __restrict__ out1, TmPackedArg<PACKED> pk = {}) {
     const int lt = blockIdx.x, hd = blockIdx.y, tid = threadIdx.x;
-    const size_t set = NZ > 1 ? (size_t)blockIdx.z * nc * NY_H * NY_M * NY_DH : 0;
-    const float* p = ws + set + ((size_t)hd * (NY_M / 32) + lt) * (NY_DH * 32);
-    float* dst = NZ > 1 && blockIdx.z ? out1 : out0;
+    const float* p;
+    float* dst;
+    if constexpr (PACKED) {
+        const int z = blockIdx.z, which = NZ > 1 ? z / pk.nb : 0, bag = z - which * pk.nb;
+        int c0, c1;
+        if (which >= NZ || !tm_packed_range(pk.tab, pk.total_blocks, bag, c0, c1)) return;
+        const size_t part = (size_t)NY_H * NY_M * NY_DH;
+        p = ws + ((size_t)which * pk.total_blocks + c0) * nc * part + ((size_t)hd * (NY_M / 32) + lt) * (NY_DH * 32);
+        dst = (which ? out1 : out0) + (size_t)bag * part;
+        nc *= c1 - c0;
+    } else {
+        const size_t set = NZ > 1 ? (size_t)blockIdx.z * nc * NY_H * NY_M * NY_DH : 0;
+        p = ws + set + ((size_t)hd * (NY_M / 32) + lt) * (NY_DH * 32);
+        dst = NZ > 1 && blockIdx.z ? out1 : out0;
+    }
     float acc[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = 0.f;

@@ -31,10 +31,20 @@ constexpr int TA_FR = 128;                          // rows per forward workgrou
 constexpr int TA_BC = 256;                          // rows per backward workgroup (8 waves x 32)
 constexpr int TA_PART = NY_M * NY_DH;               // floats of one backward partial: [8 landmark tiles][64 d][32 landmarks]
 
-__global__ __launch_bounds__(256) void k_tok_fwd(const float* __restrict__ qkv, const float* __restrict__ kL,
-                                                 const float* __restrict__ U, int n_pad, float* __restrict__ O,
-                                                 float* __restrict__ lse) {
+// The two bodies serve two kernels each: the single-bag one (PACKED false: tab, nb, total_blocks are constants that fold away,
+// and the kernel compiles to what it was before the bodies were shared) and the packed one (csrc/tm_packed.h), where the row
+// tile runs over all bags' rows, n_pad is their count R, and kL / U are taken at the tile's bag.  The bodies' pointers carry no
+// __restrict__: inlined, they ARE the kernel's restrict arguments, which is what keeps the single-bag code as it was.
+template <bool PACKED>
+__device__ __forceinline__ void tok_fwd_body(const float* qkv, const float* kL, const float* U, int n_pad, float* O, float* lse,
+                                             const int32_t* tab, int nb, int total_blocks) {
     const int hd = blockIdx.y;
+    if constexpr (PACKED) {                     // two 128-row tiles per block
+        const int bag = tm_packed_bag(tab, nb, total_blocks, blockIdx.x / (TM_PACKED_BLK / TA_FR));
+        if (bag < 0) return;
+        kL += (size_t)bag * NY_H * NY_M * NY_DH;
+        U += (size_t)bag * NY_H * NY_M * NY_DH;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
     const size_t row = (size_t)blockIdx.x * TA_FR + wave * 32 + r;
     float qr[32];
@@ -59,6 +69,19 @@ __global__ __launch_bounds__(256) void k_tok_fwd(const float* __restrict__ qkv, 
     store_row64(O + row * NY_D + hd * NY_DH + 4 * hh, o0, o1, inv);
 }
 
+__global__ __launch_bounds__(256) void k_tok_fwd(const float* __restrict__ qkv, const float* __restrict__ kL,
+                                                 const float* __restrict__ U, int n_pad, float* __restrict__ O,
+                                                 float* __restrict__ lse) {
+    tok_fwd_body<false>(qkv, kL, U, n_pad, O, lse, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void k_tok_fwd_packed(const float* __restrict__ qkv, const float* __restrict__ kL,
+                                                        const float* __restrict__ U, int n_pad, float* __restrict__ O,
+                                                        float* __restrict__ lse, const int32_t* __restrict__ tab, int nb,
+                                                        int total_blocks) {
+    tok_fwd_body<true>(qkv, kL, U, n_pad, O, lse, tab, nb, total_blocks);
+}
+
 // P = exp(S - lse) and dP = dO U^T of one 32-landmark x 32-row tile, landmark 32 t + mfma32_row(i, hh) down the registers and
 // the row on the lane.  kt / ut: this lane's landmark row of kL / U, qrow / dorow: its row of q / dO, all at d = 32 hh.
 __device__ __forceinline__ void tok_tile(const float* __restrict__ kt, const float* __restrict__ ut,
@@ -75,13 +98,19 @@ __device__ __forceinline__ void tok_tile(const float* __restrict__ kt, const flo
     for (int i = 0; i < 16; ++i) p[i] = expf(p[i] * NY_QSCALE - lse_r);
 }
 
-__global__ __launch_bounds__(512) void k_tok_bwd(const float* __restrict__ qkv, const float* __restrict__ kL,
-                                                 const float* __restrict__ U, const float* __restrict__ lse,
-                                                 const float* __restrict__ dO, int n_pad, float* __restrict__ dqkv,
-                                                 float* __restrict__ wsU, float* __restrict__ wsK) {
+template <bool PACKED>
+__device__ __forceinline__ void tok_bwd_body(const float* qkv, const float* kL, const float* U, const float* lse, const float* dO,
+                                             int n_pad, float* dqkv, float* wsU, float* wsK, const int32_t* tab, int nbags,
+                                             int total_blocks) {
     __shared__ float T[8][2][32 * NY_TLD];        // per wave: P and dS [landmark][row] of the current tile
     __shared__ float R[4][NY_DH * 32];            // per pair of waves (w, w + 4): a [d][landmark] tile, dU^T then dkL^T
     const int c = blockIdx.x, hd = blockIdx.y;
+    if constexpr (PACKED) {                       // TA_BC = 256: a chunk is a block; uniform per workgroup, ahead of every barrier
+        const int bag = tm_packed_bag(tab, nbags, total_blocks, c);
+        if (bag < 0) return;
+        kL += (size_t)bag * NY_H * NY_M * NY_DH;
+        U += (size_t)bag * NY_H * NY_M * NY_DH;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
     const size_t nb = (size_t)c * TA_BC + wave * 32, n = nb + r;      // this wave's 32 rows, this lane's row
     const float* qh = qkv + hd * NY_DH;           // q[row][0] of this head is qh + row * NY_QKV
@@ -137,6 +166,21 @@ __global__ __launch_bounds__(512) void k_tok_bwd(const float* __restrict__ qkv, 
     store_row64(dqkv + n * NY_QKV + hd * NY_DH + 4 * hh, dq0, dq1, 1.f);
 }
 
+__global__ __launch_bounds__(512) void k_tok_bwd(const float* __restrict__ qkv, const float* __restrict__ kL,
+                                                 const float* __restrict__ U, const float* __restrict__ lse,
+                                                 const float* __restrict__ dO, int n_pad, float* __restrict__ dqkv,
+                                                 float* __restrict__ wsU, float* __restrict__ wsK) {
+    tok_bwd_body<false>(qkv, kL, U, lse, dO, n_pad, dqkv, wsU, wsK, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(512) void k_tok_bwd_packed(const float* __restrict__ qkv, const float* __restrict__ kL,
+                                                        const float* __restrict__ U, const float* __restrict__ lse,
+                                                        const float* __restrict__ dO, int n_pad, float* __restrict__ dqkv,
+                                                        float* __restrict__ wsU, float* __restrict__ wsK,
+                                                        const int32_t* __restrict__ tab, int nbags, int total_blocks) {
+    tok_bwd_body<true>(qkv, kL, U, lse, dO, n_pad, dqkv, wsU, wsK, tab, nbags, total_blocks);
+}
+
 }  // namespace
 
 extern "C" {
@@ -165,7 +209,41 @@ int mil_tm_tok_attn_bwd(const float* qkv, const float* kL, const float* U, const
     const int nc = n_pad / TA_BC;
     hipLaunchKernelGGL(k_tok_bwd, dim3(nc, NY_H), dim3(512), 0, (hipStream_t)stream, qkv, kL, U, lse, dO, n_pad, dqkv, ws,
                        ws + (size_t)nc * NY_H * TA_PART);
-    hipLaunchKernelGGL(k_ny_reduce<2>, dim3(NY_M / 32, NY_H, 2), dim3(256), 0, (hipStream_t)stream, ws, nc, dU, dkL);
+    hipLaunchKernelGGL(k_ny_reduce<2>, dim3(NY_M / 32, NY_H, 2), dim3(256), 0, (hipStream_t)stream, ws, nc, dU, dkL,
+                       TmPackedArg<false>{});
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+size_t mil_tm_tok_attn_packed_ws_floats(int total_blocks, int nb, int backward) {
+    if (!tm_packed_ok(&nb, nb, total_blocks) || !backward) return 0;
+    return (size_t)2 * total_blocks * NY_H * TA_PART;
+}
+
+int mil_tm_tok_attn_fwd_packed(const float* qkv, const float* kL, const float* U, float* O, float* lse, float* ws,
+                               const int32_t* blk_off, int nb, int total_blocks, void* stream) {
+    (void)ws;                                   // as the single-bag forward: no workspace
+    if (!qkv || !kL || !U || !O || !lse || !tm_packed_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    if (!ny_aligned(qkv) || !ny_aligned(kL) || !ny_aligned(U) || !ny_aligned(O) || !ny_aligned(lse)) return MIL_EINVAL;
+    const int rows = total_blocks * TM_PACKED_BLK;
+    hipLaunchKernelGGL(k_tok_fwd_packed, dim3(rows / TA_FR, NY_H), dim3(256), 0, (hipStream_t)stream, qkv, kL, U, rows, O, lse,
+                       blk_off, nb, total_blocks);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+int mil_tm_tok_attn_bwd_packed(const float* qkv, const float* kL, const float* U, const float* lse, const float* dO, float* dqkv,
+                               float* dU, float* dkL, float* ws, const int32_t* blk_off, int nb, int total_blocks, void* stream) {
+    if (!qkv || !kL || !U || !lse || !dO || !dqkv || !dU || !dkL || !ws || !tm_packed_ok(blk_off, nb, total_blocks))
+        return MIL_EINVAL;
+    if (!ny_aligned(qkv) || !ny_aligned(kL) || !ny_aligned(U) || !ny_aligned(lse) || !ny_aligned(dO) || !ny_aligned(dqkv) ||
+        !ny_aligned(dU) || !ny_aligned(dkL) || !ny_aligned(ws))
+        return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tok_bwd_packed, dim3(total_blocks, NY_H), dim3(512), 0, (hipStream_t)stream, qkv, kL, U, lse, dO,
+                       total_blocks * TM_PACKED_BLK, dqkv, ws, ws + (size_t)total_blocks * NY_H * TA_PART, blk_off, nb,
+                       total_blocks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ny_reduce<2, true>), dim3(NY_M / 32, NY_H, 2 * nb), dim3(256), 0, (hipStream_t)stream, ws,
+                       TM_PACKED_BLK / TA_BC, dU, dkL, TmPackedArg<true>{blk_off, nb, total_blocks});
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

@@ -18,6 +18,7 @@
 
 #include "mil_common.h"
 #include "tm_bgemm.h"
+#include "tm_packed.h"
 #include "../../include/mil_hip.h"
 
 namespace {
@@ -429,7 +430,7 @@ __global__ __launch_bounds__(256) void k_tm_seq_index_bucket(const int32_t* __re
 }
 
 // qL [8, 256, 64] = qscale * mean of l consecutive q rows, kL the same of k (no scale); thread per (landmark, q|k column)
-__global__ __launch_bounds__(256) void k_tm_landmarks(const float* __restrict__ qkv, int l, float qscale, float* qL, float* kL) {
+__device__ __forceinline__ void tm_landmarks_body(const float* qkv, int l, float qscale, float* qL, float* kL) {
     const int j = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;        // c < 1024
     float s = 0.f;
     for (int t = 0; t < l; ++t) s += qkv[(long)(j * l + t) * TM_QKV + c];
@@ -438,13 +439,46 @@ __global__ __launch_bounds__(256) void k_tm_landmarks(const float* __restrict__ 
     else kL[(hh * TM_M + j) * TM_DH + d] = s / l;
 }
 
-// dqkv[i][q | k column] += coef * d(qL | kL)[head][i / l][d]
-__global__ __launch_bounds__(256) void k_tm_landmarks_bwd(const float* __restrict__ dqL, const float* __restrict__ dkL, int l,
-                                                          float qscale, float* dqkv) {
-    const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+__global__ __launch_bounds__(256) void k_tm_landmarks(const float* __restrict__ qkv, int l, float qscale, float* qL, float* kL) {
+    tm_landmarks_body(qkv, l, qscale, qL, kL);
+}
+
+// The packed forms below (csrc/tm_packed.h) run the single-bag bodies with the bag's own rows, group l_b and slices: the terms
+// and the order of every sum of a bag are those of the single-bag kernel on that bag.
+// blockIdx.z = the bag: the means of ITS l_b = blk_off[b + 1] - blk_off[b] rows, from its first row on, into slice b of qL / kL
+__global__ __launch_bounds__(256) void k_tm_landmarks_packed(const float* __restrict__ qkv, const int32_t* __restrict__ tab, int nb,
+                                                             int total_blocks, float qscale, float* qL, float* kL) {
+    const int bag = blockIdx.z;
+    int c0, c1;
+    if (bag >= nb || !tm_packed_range(tab, total_blocks, bag, c0, c1)) return;
+    const long small = (long)bag * TM_H * TM_M * TM_DH;
+    tm_landmarks_body(qkv + (long)c0 * TM_PACKED_BLK * TM_QKV, c1 - c0, qscale, qL + small, kL + small);
+}
+
+// dqkv[i][q | k column] += coef * d(qL | kL)[head][i / l][d]; i counts from the bag's first row
+__device__ __forceinline__ void tm_landmarks_bwd_body(const float* dqL, const float* dkL, int l, float qscale, float* dqkv, int i) {
+    const int c = blockIdx.y * 256 + threadIdx.x;
     const int cc = c & (TM_D - 1), hh = cc >> 6, d = cc & 63, j = i / l;
     const float g = c < TM_D ? dqL[(hh * TM_M + j) * TM_DH + d] * (qscale / l) : dkL[(hh * TM_M + j) * TM_DH + d] / l;
     dqkv[(long)i * TM_QKV + c] += g;
+}
+
+__global__ __launch_bounds__(256) void k_tm_landmarks_bwd(const float* __restrict__ dqL, const float* __restrict__ dkL, int l,
+                                                          float qscale, float* dqkv) {
+    tm_landmarks_bwd_body(dqL, dkL, l, qscale, dqkv, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_tm_landmarks_bwd_packed(const float* __restrict__ dqL, const float* __restrict__ dkL,
+                                                                 const int32_t* __restrict__ tab, int nb, int total_blocks,
+                                                                 float qscale, float* dqkv) {
+    const int row = blockIdx.x;                                         // < 256 total_blocks: the grid
+    const int bag = tm_packed_bag(tab, nb, total_blocks, row / TM_PACKED_BLK);
+    int c0, c1;
+    if (bag < 0 || !tm_packed_range(tab, total_blocks, bag, c0, c1)) return;
+    const int i = row - c0 * TM_PACKED_BLK;                             // the row inside its bag
+    if (i < 0 || i >= (c1 - c0) * TM_PACKED_BLK) return;                // a table whose two halves disagree
+    const long small = (long)bag * TM_H * TM_M * TM_DH;
+    tm_landmarks_bwd_body(dqL + small, dkL + small, c1 - c0, qscale, dqkv + (long)c0 * TM_PACKED_BLK * TM_QKV, i);
 }
 
 // The start of the pseudo-inverse and its backward, over nb bags at once: A2, Z0, dZ0, dA2 [nb, 8, 256, 256], scale
@@ -571,44 +605,87 @@ __global__ __launch_bounds__(256) void k_tm_pinv_init_bwd_s(const float* __restr
 }
 
 // out[i][c] += sum_t w[head][t] v[i + t - 16][c] (v = columns 1024.. of qkv, zero outside [0, n_pad))
-__global__ __launch_bounds__(256) void k_tm_resconv(const float* __restrict__ qkv, const float* __restrict__ w, int n, float* out) {
+// The conv kernels clip the window at [lo, hi): the single-bag ones at [0, n), compiled to what they were; the packed ones
+// (csrc/tm_packed.h) at the first and one-past-last row of the row's OWN bag, so that no tap reaches a neighbour's rows - the
+// sums of a row are then those of the single-bag kernel on its bag.  The bodies' pointers carry no __restrict__: inlined, they
+// ARE the kernel's arguments.
+__device__ __forceinline__ void tm_resconv_body(const float* qkv, const float* w, int lo, int hi, float* out) {
     const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x, hh = c >> 6;
     float s = 0.f;
 #pragma unroll
     for (int t = 0; t < TM_CONV; ++t) {
         const int ii = i + t - TM_CONV / 2;
-        if (ii >= 0 && ii < n) s += w[hh * TM_CONV + t] * qkv[(long)ii * TM_QKV + 2 * TM_D + c];
+        if (ii >= lo && ii < hi) s += w[hh * TM_CONV + t] * qkv[(long)ii * TM_QKV + 2 * TM_D + c];
     }
     out[(long)i * TM_D + c] += s;
 }
 
-// dv[i][c] += sum_t w[head][t] dout[i - t + 16][c], into the v columns of dqkv
+__global__ __launch_bounds__(256) void k_tm_resconv(const float* __restrict__ qkv, const float* __restrict__ w, int n, float* out) {
+    tm_resconv_body(qkv, w, 0, n, out);
+}
+
+// the rows [lo, hi) of the bag that owns 256-row block `blk`, clamped into [0, 256 total_blocks); false: the workgroup returns
+__device__ __forceinline__ bool tm_packed_rows(const int32_t* __restrict__ tab, int nb, int total_blocks, int blk, int& lo, int& hi) {
+    const int bag = tm_packed_bag(tab, nb, total_blocks, blk);
+    int c0, c1;
+    if (bag < 0 || !tm_packed_range(tab, total_blocks, bag, c0, c1)) return false;
+    lo = c0 * TM_PACKED_BLK;
+    hi = c1 * TM_PACKED_BLK;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_tm_resconv_packed(const float* __restrict__ qkv, const float* __restrict__ w,
+                                                           const int32_t* __restrict__ tab, int nb, int total_blocks, float* out) {
+    int lo, hi;
+    if (!tm_packed_rows(tab, nb, total_blocks, blockIdx.x / TM_PACKED_BLK, lo, hi)) return;
+    tm_resconv_body(qkv, w, lo, hi, out);
+}
+
+// dv[i][c] += sum_t w[head][t] dout[i - t + 16][c], into the v columns of dqkv.  Templated as a whole (TmPackedArg), not
+// built on a shared body: with its clip passed as arguments the single-bag kernel comes out three registers wider.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_tm_resconv_bwd_dv(const float* __restrict__ dout, const float* __restrict__ w, int n,
-                                                           float* dqkv) {
+                                                           float* dqkv, TmPackedArg<PACKED> pk) {
     const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x, hh = c >> 6;
     float s = 0.f;
+    if constexpr (PACKED) {
+        int lo, hi;
+        if (!tm_packed_rows(pk.tab, pk.nb, pk.total_blocks, i / TM_PACKED_BLK, lo, hi)) return;
 #pragma unroll
-    for (int t = 0; t < TM_CONV; ++t) {
-        const int ii = i - t + TM_CONV / 2;
-        if (ii >= 0 && ii < n) s += w[hh * TM_CONV + t] * dout[(long)ii * TM_D + c];
+        for (int t = 0; t < TM_CONV; ++t) {
+            const int ii = i - t + TM_CONV / 2;
+            if (ii >= lo && ii < hi) s += w[hh * TM_CONV + t] * dout[(long)ii * TM_D + c];
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < TM_CONV; ++t) {
+            const int ii = i - t + TM_CONV / 2;
+            if (ii >= 0 && ii < n) s += w[hh * TM_CONV + t] * dout[(long)ii * TM_D + c];
+        }
     }
     dqkv[(long)i * TM_QKV + 2 * TM_D + c] += s;
 }
 
 // dw[head][t] += sum over a chunk of rows i and d of dout[i][head, d] v[i + t - 16][head, d]; block (head * 33 + t, chunk)
 // FIXED: dw is the workspace [chunks][8 x 33] and the chunk's sum a plain store into its row (k_tm_fold adds the rows)
+// PACKED: n = 256 total_blocks, a chunk is a block of one bag and the window is clipped at that bag's rows; a chunk whose bag
+// the table does not give adds nothing (FIXED: stores 0, so that the fold reads no stale float)
 constexpr int RC_CHUNK = 256;
-template <bool FIXED>
-__global__ __launch_bounds__(256) void k_tm_resconv_bwd_dw(const float* __restrict__ dout, const float* __restrict__ qkv, int n,
-                                                           float* dw) {
+static_assert(RC_CHUNK == TM_PACKED_BLK, "a conv chunk of the packed form is one block");
+template <bool FIXED, bool PACKED>
+__device__ __forceinline__ void tm_resconv_bwd_dw_body(const float* dout, const float* qkv, int n, float* dw, const int32_t* tab,
+                                                       int nb, int total_blocks) {
     __shared__ float red[4];
     const int hh = blockIdx.x / TM_CONV, t = blockIdx.x % TM_CONV;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = hh * TM_DH + lane;
-    const int r0 = blockIdx.y * RC_CHUNK, r1 = min(n, r0 + RC_CHUNK);
+    int r0 = blockIdx.y * RC_CHUNK, r1 = min(n, r0 + RC_CHUNK), lo = 0, hi = n;
+    if constexpr (PACKED) {
+        if (!tm_packed_rows(tab, nb, total_blocks, blockIdx.y, lo, hi)) r1 = r0;      // uniform per workgroup
+    }
     float s = 0.f;
     for (int i = r0 + wv; i < r1; i += 4) {
         const int ii = i + t - TM_CONV / 2;
-        if (ii >= 0 && ii < n) s += dout[(long)i * TM_D + c] * qkv[(long)ii * TM_QKV + 2 * TM_D + c];
+        if (ii >= lo && ii < hi) s += dout[(long)i * TM_D + c] * qkv[(long)ii * TM_QKV + 2 * TM_D + c];
     }
     s = wave_sum(s);
     if (lane == 0) red[wv] = s;
@@ -618,6 +695,19 @@ __global__ __launch_bounds__(256) void k_tm_resconv_bwd_dw(const float* __restri
         if constexpr (FIXED) dw[blockIdx.y * (TM_H * TM_CONV) + blockIdx.x] = v;
         else atomicAdd(dw + blockIdx.x, v);
     }
+}
+
+template <bool FIXED>
+__global__ __launch_bounds__(256) void k_tm_resconv_bwd_dw(const float* __restrict__ dout, const float* __restrict__ qkv, int n,
+                                                           float* dw) {
+    tm_resconv_bwd_dw_body<FIXED, false>(dout, qkv, n, dw, nullptr, 0, 0);
+}
+
+template <bool FIXED>
+__global__ __launch_bounds__(256) void k_tm_resconv_bwd_dw_packed(const float* __restrict__ dout, const float* __restrict__ qkv,
+                                                                  float* dw, const int32_t* __restrict__ tab, int nb,
+                                                                  int total_blocks) {
+    tm_resconv_bwd_dw_body<FIXED, true>(dout, qkv, total_blocks * TM_PACKED_BLK, dw, tab, nb, total_blocks);
 }
 
 // PPEG: y[1 + i s + j][c] = bias[c] + sum_{a,b < 7} Wf[c][a][b] x[1 + (i + a - 3) s + (j + b - 3)][c], y[0] = x[0];
@@ -935,7 +1025,8 @@ int mil_tm_resconv(const float* qkv, const float* w, int n_pad, float* out, void
 
 int mil_tm_resconv_bwd(const float* dout, const float* qkv, const float* w, int n_pad, float* dqkv, float* dw, void* stream) {
     if (!dout || !qkv || !w || !dqkv || !dw || n_pad <= 0) return MIL_EINVAL;
-    hipLaunchKernelGGL(k_tm_resconv_bwd_dv, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, dout, w, n_pad, dqkv);
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dv<false>, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, dout, w, n_pad, dqkv,
+                       TmPackedArg<false>{});
     hipLaunchKernelGGL(k_tm_resconv_bwd_dw<false>, dim3(TM_H * TM_CONV, (n_pad + RC_CHUNK - 1) / RC_CHUNK), dim3(256), 0,
                        (hipStream_t)stream, dout, qkv, n_pad, dw);
     return launch_rc();
@@ -1033,9 +1124,66 @@ int mil_tm_resconv_bwd_fixed(const float* dout, const float* qkv, const float* w
                              void* stream) {
     if (!dout || !qkv || !w || !dqkv || !dw || !ws || n_pad <= 0) return MIL_EINVAL;
     const int chunks = (n_pad + RC_CHUNK - 1) / RC_CHUNK;
-    hipLaunchKernelGGL(k_tm_resconv_bwd_dv, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, dout, w, n_pad, dqkv);
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dv<false>, dim3(n_pad, 2), dim3(256), 0, (hipStream_t)stream, dout, w, n_pad, dqkv,
+                       TmPackedArg<false>{});
     hipLaunchKernelGGL(k_tm_resconv_bwd_dw<true>, dim3(TM_H * TM_CONV, chunks), dim3(256), 0, (hipStream_t)stream, dout, qkv, n_pad, ws);
     tm_fold(ws, TM_H * TM_CONV, chunks, TM_H * TM_CONV, dw, (hipStream_t)stream);
+    return launch_rc();
+}
+
+// ---- a step's bags as one packed sequence (csrc/tm_packed.h): the landmarks and the residual conv over all bags' rows
+int mil_tm_landmarks_packed(const float* qkv, float qscale, float* qL, float* kL, const int32_t* blk_off, int nb, int total_blocks,
+                            void* stream) {
+    if (!qkv || !qL || !kL || !tm_packed_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_landmarks_packed, dim3(TM_M, 4, nb), dim3(256), 0, (hipStream_t)stream, qkv, blk_off, nb, total_blocks,
+                       qscale, qL, kL);
+    return launch_rc();
+}
+
+int mil_tm_landmarks_bwd_packed(const float* dqL, const float* dkL, float qscale, float* dqkv, const int32_t* blk_off, int nb,
+                                int total_blocks, void* stream) {
+    if (!dqL || !dkL || !dqkv || !tm_packed_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_landmarks_bwd_packed, dim3(total_blocks * TM_PACKED_BLK, 4), dim3(256), 0, (hipStream_t)stream, dqL, dkL,
+                       blk_off, nb, total_blocks, qscale, dqkv);
+    return launch_rc();
+}
+
+int mil_tm_resconv_packed(const float* qkv, const float* w, float* out, const int32_t* blk_off, int nb, int total_blocks,
+                          void* stream) {
+    if (!qkv || !w || !out || !tm_packed_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_resconv_packed, dim3(total_blocks * TM_PACKED_BLK, 2), dim3(256), 0, (hipStream_t)stream, qkv, w, blk_off,
+                       nb, total_blocks, out);
+    return launch_rc();
+}
+
+// the dw kernels count the chunks in gridDim.y
+inline bool tm_packed_conv_ok(const void* tab, int nb, int total_blocks) {
+    return tm_packed_ok(tab, nb, total_blocks) && total_blocks <= 65535;
+}
+
+int mil_tm_resconv_bwd_packed(const float* dout, const float* qkv, const float* w, float* dqkv, float* dw, const int32_t* blk_off,
+                              int nb, int total_blocks, void* stream) {
+    if (!dout || !qkv || !w || !dqkv || !dw || !tm_packed_conv_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dv<true>, dim3(total_blocks * TM_PACKED_BLK, 2), dim3(256), 0, (hipStream_t)stream, dout, w,
+                       total_blocks * TM_PACKED_BLK, dqkv, TmPackedArg<true>{blk_off, nb, total_blocks});
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dw_packed<false>, dim3(TM_H * TM_CONV, total_blocks), dim3(256), 0, (hipStream_t)stream, dout,
+                       qkv, dw, blk_off, nb, total_blocks);
+    return launch_rc();
+}
+
+size_t mil_tm_resconv_packed_ws_floats(int total_blocks, int nb, int backward) {
+    if (!tm_packed_conv_ok(&nb, nb, total_blocks) || !backward) return 0;
+    return (size_t)total_blocks * (TM_H * TM_CONV);
+}
+
+int mil_tm_resconv_bwd_packed_fixed(const float* dout, const float* qkv, const float* w, float* dqkv, float* dw, float* ws,
+                                    const int32_t* blk_off, int nb, int total_blocks, void* stream) {
+    if (!dout || !qkv || !w || !dqkv || !dw || !ws || !tm_packed_conv_ok(blk_off, nb, total_blocks)) return MIL_EINVAL;
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dv<true>, dim3(total_blocks * TM_PACKED_BLK, 2), dim3(256), 0, (hipStream_t)stream, dout, w,
+                       total_blocks * TM_PACKED_BLK, dqkv, TmPackedArg<true>{blk_off, nb, total_blocks});
+    hipLaunchKernelGGL(k_tm_resconv_bwd_dw_packed<true>, dim3(TM_H * TM_CONV, total_blocks), dim3(256), 0, (hipStream_t)stream, dout,
+                       qkv, ws, blk_off, nb, total_blocks);
+    tm_fold(ws, TM_H * TM_CONV, total_blocks, TM_H * TM_CONV, dw, (hipStream_t)stream);
     return launch_rc();
 }
 

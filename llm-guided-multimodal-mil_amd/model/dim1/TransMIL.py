@@ -145,6 +145,34 @@ def pad_index(g: dict) -> List[int]:
     return [-1] * g["pad"] + list(range(g["seq"]))
 
 
+def packed_index(sides: Sequence[int]) -> Tuple[List[int], List[int], List[int]]:
+    """The static indices of the packed route for bags of these grid sides, one bag after another:
+    (pad [sum n_pad]: every bag's pad_index with its rows shifted by the sequence rows in front of the bag - -1 stays a zero row;
+     unpad [sum seq]: where sequence row j of bag b lies among the padded rows, pad_b + j behind the padded rows in front;
+     blocks [B]: n_pad_b / 256, what ops.tm_packed_table takes)."""
+    pad, unpad, blocks, row, prow = [], [], [], 0, 0
+    for s in sides:
+        g = side_geometry(int(s))
+        pad += [i if i < 0 else row + i for i in pad_index(g)]
+        unpad += range(prow + g["pad"], prow + g["n_pad"])
+        blocks.append(g["l"])
+        row += g["seq"]
+        prow += g["n_pad"]
+    return pad, unpad, blocks
+
+
+class PackedGeometry:
+    """packed_index on the device plus the block table: what TransMIL._run_bags_packed reads.  It depends on the tuple of sides
+    alone; a replayed step builds it once, with its geometry, outside the capture."""
+
+    def __init__(self, sides: Sequence[int], device):
+        pad, unpad, blocks = packed_index(sides)
+        self.sides = tuple(int(s) for s in sides)
+        self.pad_idx = torch.tensor(pad, dtype=torch.int32).to(device, non_blocking=True)
+        self.unpad_idx = torch.tensor(unpad, dtype=torch.int32).to(device, non_blocking=True)
+        self.table = ops.tm_packed_table(blocks, device)
+
+
 class DeviceGeometry:
     """The part of a forward's geometry that a replayed step cannot build on the host: the grid side of every bag (host
     ints, fixed per captured graph), the gather index and the true row count on the device (ops.tm_seq_index writes both
@@ -162,6 +190,7 @@ class DeviceGeometry:
         for s in self.sides:
             if s not in self.pad_idx:
                 self.pad_idx[s] = torch.tensor(pad_index(side_geometry(s)), dtype=torch.int32).to(device)
+        self.packed = PackedGeometry(self.sides, device) if len(self.sides) > 1 else None     # the packed route's static tables
 
     def update(self, x_tail: Optional[torch.Tensor] = None):
         """Index and row count from the lengths now in len_dev; x_tail: the slot's input buffer, its rows behind the bags zeroed."""
@@ -196,6 +225,7 @@ class BucketGeometry:
         for s in self.sides:
             if s not in self.pad_idx:
                 self.pad_idx[s] = torch.tensor(pad_index(side_geometry(s)), dtype=torch.int32).to(device)
+        self.packed = PackedGeometry(self.sides, device) if len(self.sides) > 1 else None     # the packed route's static tables
 
     def update(self, patch_len_dev: torch.Tensor):
         """Index and sequence lengths from the patch counts now on the device (the bucket's len_dev)."""
@@ -267,6 +297,23 @@ class TransLayer(nn.Module):
         return ys
 
 
+    def run_packed(self, x: torch.Tensor, pk: PackedGeometry, bits: Optional[torch.Tensor], deterministic: Optional[bool] = None,
+                   gemm_pieces: Optional[int] = None) -> torch.Tensor:
+        """run() (need_attn False) over all bags of a step as ONE packed sequence: x [sum seq, 512], the bags' sequences one
+        after another -> the same rows.  One LayerNorm, one pad gather into [sum n_pad, 512], one to_qkv, ops.nystrom_core_packed,
+        one gather back, one to_out, one dropout (bits [sum seq, 16], each bag's words in its row slice) / residual."""
+        a = self.attn
+        ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
+        xp = ops.tm_row_gather(ln, None, pk.pad_idx, deterministic)
+        qkv = ops.linear_act(xp, a.to_qkv.weight, None)
+        o = ops.nystrom_core_packed(qkv, pk.table, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces)
+        o = ops.tm_row_gather(o, None, pk.unpad_idx, deterministic)
+        lin = a.to_out[0]
+        if bits is None:
+            return ops.linear_act(o, lin.weight, lin.bias, residual=x)
+        return x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
+
+
 class PPEG(nn.Module):
     def __init__(self, dim: int = 512):
         super().__init__()
@@ -287,7 +334,9 @@ class TransMIL(nn.Module):
     that holds more than one bag and asks for no attention output runs stage by stage across the bags, with the landmark-side
     chain of each layer - A2, the pseudo-inverse, U and their gradients - as one set of launches for all bags
     (ops.nystrom_core_bags) instead of one set per bag.  Every bag keeps its own pseudo-inverse scale and its values are those
-    of the bag-by-bag route (bit-equal under deterministic); the token-side passes, the dense layers and PPEG stay per bag."""
+    of the bag-by-bag route (bit-equal under deterministic); the token-side passes, the dense layers and PPEG stay per bag.
+    packed (MIL_TM_PACKED, default off; it wins over batch_bags): the same call runs every layer over ONE packed sequence of
+    all bags' rows (_run_bags_packed, ops.nystrom_core_packed) - every stage but PPEG one launch set whatever the bag count."""
 
     def __init__(self, n_classes: int, L: int = 768, D: int = 512, K: int = 1):
         super().__init__()
@@ -310,6 +359,7 @@ class TransMIL(nn.Module):
         self.deterministic: Optional[bool] = None    # every cross-workgroup sum in a fixed order (ops.tm_deterministic); None = MIL_TM_DETERMINISTIC
         self.gemm_pieces: Optional[int] = None       # 3: the Nystrom core's products on split-bf16 MFMA (ops.tm_pieces); None = MIL_TM_PIECES
         self.batch_bags: Optional[bool] = None       # a step's bags through one landmark-side chain (ops.tm_batch_bags); None = MIL_TM_BATCH_BAGS
+        self.packed: Optional[bool] = None           # a step's bags as one packed sequence (ops.tm_packed); None = MIL_TM_PACKED; wins over batch_bags
 
     def _drop_state(self, device):
         if self._drop_seed is None:
@@ -317,12 +367,13 @@ class TransMIL(nn.Module):
         if self._drop_ctr is None or self._drop_ctr.device != device:
             self._drop_ctr = torch.zeros(1, device=device, dtype=torch.int32)
 
-    def _bits(self, b: int, seq: int, device):
-        """Keep bits of the two Dropout(0.1) of bag b: key seed ^ layer, stream offset 2 b (+1) + the device pass counter."""
+    def _bits(self, b: int, seq: int, device, out=(None, None)):
+        """Keep bits of the two Dropout(0.1) of bag b: key seed ^ layer, stream offset 2 b (+1) + the device pass counter.
+        out: per layer where the words go (the packed route: the bag's rows of the step's buffer); default fresh tensors."""
         if self.force_bits is not None:
             return self.force_bits[b]
         return tuple(ops.dropout_keep_bits(seq, self.D, TM_DROP_P, self._drop_seed ^ (0x5472616E734D494C + j), 2 * b + j, device,
-                                           offset_dev=self._drop_ctr) for j in range(2))
+                                           out=out[j], offset_dev=self._drop_ctr) for j in range(2))
 
     def forward(self, x: torch.Tensor, lengths: Optional[Sequence[int]] = None, need_attn=False,
                 geom: Optional[DeviceGeometry] = None):
@@ -419,6 +470,8 @@ class TransMIL(nn.Module):
         train = self.training
         if train:
             self._drop_state(dev)
+        if need_attn is False and len(geo) > 1 and ops.tm_packed(self.packed):
+            return self._run_bags_packed(seqs, geo, geom)
         if need_attn is False and len(geo) > 1 and ops.tm_batch_bags(self.batch_bags):
             return self._run_bags_batched(seqs, geo, geom)
         cls_rows, attn0, attn1, bits_used = [], [], [], []
@@ -479,4 +532,35 @@ class TransMIL(nn.Module):
             ops.counter_add(self._drop_ctr, 1)
         self.last_bits = bits_used if train else None
         hc = torch.cat([x[:1] for x in xs], 0)
+        return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), [None, None]
+
+    def _run_bags_packed(self, seqs: torch.Tensor, geo: List[dict], geom):
+        """_run_bags (need_attn False, several bags) over ONE packed sequence (packed, ops.tm_packed: the attribute, else
+        MIL_TM_PACKED; default off; it wins over batch_bags): per layer every stage but PPEG is one launch set over all bags'
+        rows (TransLayer.run_packed).  PPEG runs per bag on row slices, its grid follows the side.  The keep bits of
+        (bag, layer) are those of the bag-by-bag route, drawn into that bag's rows of one [sum seq, 16] buffer per layer;
+        last_bits stays the per-bag list (views), and the pass counter advances once."""
+        dev = seqs.device
+        train = self.training
+        pk = getattr(geom, "packed", None) if geom is not None else None
+        if pk is None:                                  # host lengths: built per call, as pad_index is on the other routes
+            pk = PackedGeometry([g["s"] for g in geo], dev)
+        rows = [0]
+        for g in geo:
+            rows.append(rows[-1] + g["seq"])
+        keep, bits_used = (None, None), [(None, None)] * len(geo)
+        if train and self.force_bits is not None:
+            bits_used = [self.force_bits[b] for b in range(len(geo))]
+            keep = tuple(torch.cat([k[j] for k in bits_used], 0) for j in range(2))
+        elif train:
+            keep = tuple(torch.empty((rows[-1], self.D // 32), device=dev, dtype=torch.int32) for _ in range(2))
+            bits_used = [self._bits(b, g["seq"], dev, tuple(keep[j][rows[b]:rows[b + 1]] for j in range(2)))
+                         for b, g in enumerate(geo)]
+        x = self.layer1.run_packed(seqs, pk, keep[0], self.deterministic, self.gemm_pieces)
+        x = torch.cat([self.pos_layer.run(x[rows[b]:rows[b + 1]], g["s"], self.deterministic) for b, g in enumerate(geo)], 0)
+        x = self.layer2.run_packed(x, pk, keep[1], self.deterministic, self.gemm_pieces)
+        if train and self.force_bits is None:
+            ops.counter_add(self._drop_ctr, 1)
+        self.last_bits = bits_used if train else None
+        hc = torch.cat([x[r:r + 1] for r in rows[:-1]], 0)
         return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), [None, None]

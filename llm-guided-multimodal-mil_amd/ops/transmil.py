@@ -58,6 +58,14 @@ def tm_batch_bags(value=None) -> bool:
     return bool(value)
 
 
+def tm_packed(value=None) -> bool:
+    """The switch of the packed sequence (nystrom_core_packed): the keyword (a module passes its `packed` attribute here), else
+    the environment variable MIL_TM_PACKED (default 0), read per call."""
+    if value is None:
+        value = os.environ.get("MIL_TM_PACKED", "0") not in ("", "0")
+    return bool(value)
+
+
 def _tm_pieces_route(M: int, N: int, K: int) -> bool:
     """Which products take mil_tm_bgemm_pieces when pieces == 3: those with K >= 256 - the pseudo-inverse chain and its
     backward (256^3), W, U, O, dU, dW, dq, dk, dv, dqL, dkL, and the whole-map products of need_attn True.  The K = 64
@@ -834,3 +842,133 @@ def nystrom_core_bags(qkvs, w, *, fused_a3=None, fused_a1=None, deterministic=No
                                        tm_deterministic(deterministic), tm_pieces(pieces), *qkvs))
 
 
+
+# ---- a step's bags as one packed sequence (csrc/tm_packed.h): every token-side stage one launch set over all bags' rows
+class TmPackedTable:
+    """The segment table of the mil_tm_*_packed entries for bags of `blocks` 256-row blocks each (host ints: the launch shapes):
+    `dev`, int32 [nb + 1 + total_blocks] on the device = the cumulative block counts blk_off [nb + 1], then the bag of every
+    block.  Build it with tm_packed_table, outside any capture; it depends on the bags' sides alone."""
+
+    def __init__(self, blocks, dev):
+        self.blocks = tuple(int(k) for k in blocks)
+        self.nb, self.total_blocks, self.dev = len(self.blocks), sum(self.blocks), dev
+        self.rows = TM_M * self.total_blocks
+
+    def args(self):
+        return _p(self.dev), self.nb, self.total_blocks
+
+
+def tm_packed_table_host(blocks):
+    """The table's int32 values as a list: blk_off [nb + 1], then bag_of_blk [total_blocks]."""
+    blocks = [int(k) for k in blocks]
+    if not 1 <= len(blocks) <= TM_MAX_BATCH_BAGS or min(blocks) < 1 or sum(blocks) > (2 ** 31 - 1) // TM_M:
+        raise ValueError(f"tm_packed_table: 1 .. {TM_MAX_BATCH_BAGS} bags of at least one 256-row block each, got {blocks}")
+    off = [0]
+    for k in blocks:
+        off.append(off[-1] + k)
+    return off + [b for b, k in enumerate(blocks) for _ in range(k)]
+
+
+def tm_packed_table(blocks, device=None) -> TmPackedTable:
+    """blocks: per bag n_pad / 256 -> the TmPackedTable on `device` (default: the current GPU).  One small host-to-device
+    copy, so a replayed step builds it once per graph key, not per step."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    return TmPackedTable(blocks, torch.tensor(tm_packed_table_host(blocks), dtype=torch.int32).to(device, non_blocking=True))
+
+
+def _tm_fwd_packed(qkv, tab, w, det=False, pieces=0):
+    """_tm_fwd_bags with both passes fused, on the packed rows: the phases in the same order, each token-side one a single
+    packed launch set; the landmark-side chain (A2, its softmax, the pseudo-inverse, U) exactly as _tm_fwd_bags runs it."""
+    bg = _tm_bg(det, pieces)
+    nb, tb, R = tab.nb, tab.total_blocks, tab.rows
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    H, M, DH = TM_H, TM_M, TM_DH
+    lib, ck = _lib.lib(), _lib.checked()
+    qL, kL, W = (torch.empty((nb, H, M, DH), **f32) for _ in range(3))
+    ck.mil_tm_landmarks_packed(_p(qkv), TM_QSCALE, _p(qL), _p(kL), *tab.args(), _stream())
+    lse3 = torch.empty((nb, H, M), **f32)
+    ws = _ws(lib.mil_tm_lmk_attn_packed_ws_floats(tb, nb, 0), qkv)
+    ck.mil_tm_lmk_attn_fwd_packed(_p(qkv), _p(qL), _p(W), _p(lse3), _p(ws), *tab.args(), _stream())
+    A2 = tm_softmax_rows(_tm_fwd_a2(qL, kL, torch.empty((nb, H, M, M), **f32), bg, nb * H))
+    Z, pinv = _tm_pinv_fwd(A2, det, pieces, nb=nb)
+    U = _tm_fwd_u(Z, W, torch.empty((nb, H, M, DH), **f32), bg, nb * H)
+    O = torch.empty((R, TM_D), **f32)
+    lse1 = torch.empty((H, R), **f32)
+    ck.mil_tm_tok_attn_fwd_packed(_p(qkv), _p(kL), _p(U), _p(O), _p(lse1), None, *tab.args(), _stream())
+    ck.mil_tm_resconv_packed(_p(qkv), _p(w), _p(O), *tab.args(), _stream())
+    saved = SimpleNamespace(qL=qL, kL=kL, A2=A2, W=W, U=U, Z=Z, pinv=pinv, lse1=lse1, lse3=lse3, det=det, pieces=pieces)
+    return O, saved
+
+
+def _tm_bwd_packed(dO, qkv, tab, w, saved):
+    """_tm_bwd_bags with both passes fused, on the packed rows; every column of every dqkv row is written in the order the
+    bag-by-bag route writes it (dq, dk | dv, the conv's += on v, the landmarks' += on q and k).  dw is ONE sum over all bags."""
+    s = saved
+    qL, kL, A2, W, U, Z = s.qL, s.kL, s.A2, s.W, s.U, s.Z
+    det, pieces = s.det, s.pieces
+    bg = _tm_bg(det, pieces)
+    nb, tb, R = tab.nb, tab.total_blocks, tab.rows
+    f32 = dict(device=qkv.device, dtype=torch.float32)
+    H, M, DH = TM_H, TM_M, TM_DH
+    lib, ck = _lib.lib(), _lib.checked()
+    dqkv = torch.empty((R, 3 * TM_D), **f32)
+    dU, dkL, dqL, dW = (torch.empty((nb, H, M, DH), **f32) for _ in range(4))
+    ws = _ws(lib.mil_tm_tok_attn_packed_ws_floats(tb, nb, 1), qkv)
+    ck.mil_tm_tok_attn_bwd_packed(_p(qkv), _p(kL), _p(U), _p(s.lse1), _p(dO), _p(dqkv), _p(dU), _p(dkL), _p(ws), *tab.args(),
+                                  _stream())
+    dZ = torch.empty((nb, H, M, M), **f32)
+    _tm_bwd_zw(dU, W, Z, dZ, dW, bg, nb * H)
+    ws = _ws(lib.mil_tm_lmk_attn_packed_ws_floats(tb, nb, 1), qkv)
+    ck.mil_tm_lmk_attn_bwd_packed(_p(qkv), _p(qL), _p(W), _p(s.lse3), _p(dW), _p(dqkv), _p(dqL), _p(ws), *tab.args(), _stream())
+    if det:                                                             # the fold overwrites dw
+        dw = torch.empty(H * TM_CONV, **f32)
+        ws = _ws(lib.mil_tm_resconv_packed_ws_floats(tb, nb, 1), qkv)
+        ck.mil_tm_resconv_bwd_packed_fixed(_p(dO), _p(qkv), _p(w), _p(dqkv), _p(dw), _p(ws), *tab.args(), _stream())
+    else:
+        dw = torch.zeros(H * TM_CONV, **f32)
+        ck.mil_tm_resconv_bwd_packed(_p(dO), _p(qkv), _p(w), _p(dqkv), _p(dw), *tab.args(), _stream())
+    dS2 = tm_softmax_rows_bwd(A2, _tm_pinv_bwd(dZ, A2, *s.pinv, det=det, pieces=pieces, nb=nb))
+    _tm_bwd_s2(dS2, qL, kL, dkL, dqL, True, bg, nb * H)
+    ck.mil_tm_landmarks_bwd_packed(_p(dqL), _p(dkL), TM_QSCALE, _p(dqkv), *tab.args(), _stream())
+    return dqkv, dw
+
+
+class _NystromCorePacked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, w, tab, det, pieces):
+        if (qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] != tab.rows or w.numel() != TM_H * TM_CONV
+                or qkv.device != w.device or tab.dev.device != qkv.device):
+            raise _lib.MilHipError(f"nystrom_core_packed: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape "
+                                   f"for blocks {tab.blocks}, or on two devices")
+        qkv = _f32c(qkv, "qkv")
+        w = _f32c(w, "res_conv.weight")
+        O, saved = _tm_fwd_packed(qkv, tab, w, det, pieces)
+        ctx.saved, ctx.tab = saved, tab
+        ctx.save_for_backward(qkv, w)
+        ctx.w_shape = w.shape
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        qkv, w = ctx.saved_tensors
+        dqkv, dw = _tm_bwd_packed(_f32c(dO, "dO"), qkv, ctx.tab, w, ctx.saved)
+        ctx.saved = None
+        return dqkv, dw.reshape(ctx.w_shape), None, None, None
+
+
+def nystrom_core_packed(qkv, blocks_or_table, w, *, deterministic=None, pieces=None):
+    """nystrom_core (need_attn False) for all bags of a step over ONE packed sequence: qkv [256 sum(blocks), 1536] = the bags'
+    to_qkv rows of their front-zero-padded LayerNorm output one after another, bag b 256 blocks[b] rows; blocks_or_table = the
+    per-bag block counts (the table is then built here: a host-to-device copy, not for a capture) or a TmPackedTable
+    (tm_packed_table); w = res_conv.weight -> out [256 sum(blocks), 512], bag b's rows where its input rows are.
+    The landmarks, the landmark-query pass, the token-query pass, the residual conv and their backwards are one packed launch
+    set each (mil_tm_*_packed), whatever the number of bags; the landmark-side chain runs as in nystrom_core_bags on buffers
+    stacked [nb, 8, 256, .].  Both passes always run fused: no A1 or A3 map exists on this route, and no attention output.
+    Every bag's rows of out and (deterministic) of dqkv are bit-equal to nystrom_core_bags with both fused switches on; dw is
+    one sum over all bags' 256-row chunks - atomic, or with deterministic in ascending packed order.
+    deterministic, pieces: as in nystrom_core (None reads the environment); they apply to the chain unchanged.  No host read;
+    every workspace is a torch.empty, so with a TmPackedTable the call can be captured into a graph.  The switch that sends a
+    module's step here is tm_packed (MIL_TM_PACKED, default 0)."""
+    tab = blocks_or_table if isinstance(blocks_or_table, TmPackedTable) else tm_packed_table(blocks_or_table, qkv.device)
+    return _NystromCorePacked.apply(qkv, w, tab, tm_deterministic(deterministic), tm_pieces(pieces))

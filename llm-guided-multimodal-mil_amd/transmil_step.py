@@ -112,6 +112,24 @@ class RaggedTransMILStepper:
             out += list(m.last_patch_attn[0]) + list(m.last_patch_attn[1])
         return tuple(out)
 
+    def key(self, sides: Sequence[int]) -> tuple:
+        """The graph key of a slot of these sides under the model's switches as they stand now."""
+        m = self.model
+        attn = bool(getattr(m, "patch_attn", False))
+        # a graph captured without the attention outputs is never replayed for a request with them, and the other way round
+        # ... nor is one captured on the atomic sums replayed for a model that asks for the fixed-order ones
+        det = ops.tm_deterministic(m.extractor_pathology.deterministic)
+        # ... nor one captured on the fp32 products for a model that asks for the split-bf16 ones
+        pieces = ops.tm_pieces(m.extractor_pathology.gemm_pieces)
+        # ... nor one captured bag by bag for a model that asks for the batched landmark-side chain (several bags, no attention
+        # outputs: what TransMIL._run_bags takes that route for)
+        batched = ops.tm_batch_bags(m.extractor_pathology.batch_bags) and len(sides) > 1 and not attn
+        # ... nor one of either of those for a model that asks for the packed sequence, which wins over the batched chain
+        packed = ops.tm_packed(m.extractor_pathology.packed) and len(sides) > 1 and not attn
+        return (("transmil-sides", tuple(sides), bool(m.training), self.backward) + (("patch_attn",) if attn else ())
+                + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
+                + (("packed",) if packed else ("batch_bags",) if batched else ()))
+
     def step(self, slot, lengths: Sequence[int], on_device: bool = False):
         """One step on the bags packed at the front of slot.x.  on_device: the lengths already sit in slot.len_dev (the
         cohort's feed launch wrote them); otherwise they are copied there.  Returns (loss, prob); slot.last holds h, logits,
@@ -125,17 +143,7 @@ class RaggedTransMILStepper:
         m = self.model
         training = bool(m.training)
         attn = bool(getattr(m, "patch_attn", False))
-        # a graph captured without the attention outputs is never replayed for a request with them, and the other way round
-        # ... nor is one captured on the atomic sums replayed for a model that asks for the fixed-order ones
-        det = ops.tm_deterministic(m.extractor_pathology.deterministic)
-        # ... nor one captured on the fp32 products for a model that asks for the split-bf16 ones
-        pieces = ops.tm_pieces(m.extractor_pathology.gemm_pieces)
-        # ... nor one captured bag by bag for a model that asks for the batched landmark-side chain (several bags, no attention
-        # outputs: what TransMIL._run_bags takes that route for)
-        batched = ops.tm_batch_bags(m.extractor_pathology.batch_bags) and len(slot.sides) > 1 and not attn
-        key = (("transmil-sides", slot.sides, training, self.backward) + (("patch_attn",) if attn else ())
-               + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
-               + (("batch_bags",) if batched else ()))
+        key = self.key(slot.sides)
         body = lambda: self._body(slot)      # noqa: E731
         ctr = m.extractor_pathology._drop_ctr
         # the warm-up passes in front of a capture draw masks too: the pass counter goes back, so the stream of a replayed

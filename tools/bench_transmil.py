@@ -29,7 +29,8 @@ rows carry the value and the min - max of the regions next to the median: run 0 
 replayed (RaggedTransMILStepper, B bags per slot) - with the landmark-side chain bag by bag (TransMIL.batch_bags = False: the
 route of MIL_TM_BATCH_BAGS=0), batched over the bags (= True: ops.nystrom_core_bags), and bag by bag again, in one process, same
 model, same bags; median (min - max) of --reps regions each and the peak allocated bytes of one eager step per route.  The
-first and third columns are the yardstick.  B = 1 (the default) leaves every other row as it is."""
+first and third columns are the yardstick.  B = 1 (the default) leaves every other row as it is.  --packed adds the column of
+TransMIL.packed (ops.nystrom_core_packed: every token-side stage one launch set over all bags' rows), --mix makes the bags ragged."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -326,10 +327,10 @@ def bags_rows(a, dev, args):
         o_e = FlatAdam(list(m_e.parameters()), lr=1e-5, counted=True)
         o_r = FlatAdam(list(m_r.parameters()), lr=1e-5, counted=True)
         st = RaggedTransMILStepper(m_r, o_r, B=B, drop_seed=1)
-        lengths = [N] * B
-        x = torch.cat([syn.make_bags(N + b, 1, N, 768)[0] for b in range(B)], 0).to(dev)
+        lengths = [max(1, N * (4 - b % 4) // 4) for b in range(B)] if a.mix else [N] * B       # --mix: N, 3N/4, N/2, N/4, N, ..
+        x = torch.cat([syn.make_bags(N + b, 1, n, 768)[0] for b, n in enumerate(lengths)], 0).to(dev)
         slot = st.slot(lengths)
-        slot.x[:B * N].copy_(x)
+        slot.x[:sum(lengths)].copy_(x)
         slot.y.copy_(y)
 
         def eager():
@@ -341,27 +342,35 @@ def bags_rows(a, dev, args):
         def replay():
             st.step(slot, lengths)
 
-        res = dict(N=N, bags=B, n_pad=geometry(N)["n_pad"], regions=a.reps)
-        for on, tag in ((False, "off"), (True, "on"), (False, "off_again")):
-            m_e.extractor_pathology.batch_bags = m_r.extractor_pathology.batch_bags = on
+        res = dict(N=N, bags=B, lengths=lengths, n_pad=geometry(N)["n_pad"], regions=a.reps,
+                   fused_env=[os.environ.get(k, "0") for k in ("MIL_TM_FUSED_A1", "MIL_TM_FUSED_A3")])
+        routes = ((False, False, "off"), (True, False, "on")) + (((False, True, "packed"),) if a.packed else ()) + ((False, False, "off_again"),)
+        for on, pk, tag in routes:
+            for m in (m_e, m_r):
+                m.extractor_pathology.batch_bags, m.extractor_pathology.packed = on, pk
             for _ in range(3):                        # the stepper: eager visit, capture, first replay of this route's key
                 replay()
             for name, fn in (("eager", eager), ("replay", replay)):
                 ts = region_times(fn, a.reps, a.warmup)
                 res.update({f"{name}_{tag}_ms": round(med(ts), 3), f"{name}_{tag}_min_ms": round(min(ts), 3),
                             f"{name}_{tag}_max_ms": round(max(ts), 3)})
-        for on, tag in ((False, "off"), (True, "on")):
-            m_e.extractor_pathology.batch_bags = on
+        for on, pk, tag in routes[:-1]:
+            m_e.extractor_pathology.batch_bags, m_e.extractor_pathology.packed = on, pk
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
             eager()
             torch.cuda.synchronize()
             res[f"eager_{tag}_peak_mib"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
-        assert st.n_graphs == 2, st.n_graphs          # one graph per route: the switch is part of the key
+        assert st.n_graphs == len(routes) - 1, st.n_graphs          # one graph per route: the switches are part of the key
         for name in ("eager", "replay"):
-            res[f"{name}_on_over_off"] = round(res[f"{name}_on_ms"] / min(res[f"{name}_off_ms"], res[f"{name}_off_again_ms"]), 4)
-        res["graph_mib"] = {("on" if "batch_bags" in k else "off"): round(v / 2 ** 20, 1) for k, v in st.graph_bytes.items()}
+            off = min(res[f"{name}_off_ms"], res[f"{name}_off_again_ms"])
+            res[f"{name}_on_over_off"] = round(res[f"{name}_on_ms"] / off, 4)
+            if a.packed:
+                res[f"{name}_packed_over_off"] = round(res[f"{name}_packed_ms"] / off, 4)
+                res[f"{name}_packed_over_on"] = round(res[f"{name}_packed_ms"] / res[f"{name}_on_ms"], 4)
+        res["graph_mib"] = {("packed" if "packed" in k else "on" if "batch_bags" in k else "off"): round(v / 2 ** 20, 1)
+                            for k, v in st.graph_bytes.items()}
         print(json.dumps(res), flush=True)
         del st, slot, m_e, m_r, o_e, o_r, x
         torch.cuda.empty_cache()
@@ -403,6 +412,10 @@ def main():
                     "split-bf16 products in the Nystrom core, 0 = fp32 products; unset: MIL_TM_PIECES decides")
     ap.add_argument("--bags", type=int, default=1, help="B > 1: the training step over B bags of N patches, eager and "
                     "replayed, with TransMIL.batch_bags off, on, off again: ms and peak allocated bytes")
+    ap.add_argument("--packed", action="store_true", help="--bags B: one more column, the step with TransMIL.packed set (a step's "
+                    "bags as one packed sequence), between `on` and `off_again`.  It always runs both attention passes fused: "
+                    "set MIL_TM_FUSED_A1=1 MIL_TM_FUSED_A3=1 so that the other two columns do too")
+    ap.add_argument("--mix", action="store_true", help="--bags B: a ragged mix, bag b of N (4 - b mod 4) / 4 patches")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
