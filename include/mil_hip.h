@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 20 */
+int mil_abi_version(void);   /* 21 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1300,6 +1300,37 @@ int mil_tm_resconv_bwd_packed(const float* dout, const float* qkv, const float* 
                               int nb, int total_blocks, void* stream);
 int mil_tm_resconv_bwd_packed_fixed(const float* dout, const float* qkv, const float* w, float* dqkv, float* dw, float* ws,
                                     const int32_t* blk_off, int nb, int total_blocks, void* stream);
+/* ---- TransMIL, PPEG of a step's bags in one launch set (ABI 21; csrc/tm_ppeg_packed.h; ops: tm_ppeg_packed /
+ * MIL_TM_PACKED_PPEG=1 on the packed route).  x, y, dy, dx hold the bags' UNPADDED sequences [1 + s_b^2, 512] (cls row first)
+ * one after another, total_rows = R = sum (1 + s_b^2) rows, so a bag starts at a row that is no multiple of 256 and the block
+ * table above does not describe it.  Each entry takes its single-bag twin's arguments without s, and three more:
+ *   tab         device int32 [4 nb + 3 + gmax + cmax], gmax = floor(sqrt(nb (R - nb))), cmax = min(gmax, (gmax + 7 nb) / 8):
+ *               row_off [nb + 1] (bag b's first row, row_off[nb] = R) | side [nb] | grow_off [nb + 1] (grid rows in front of
+ *               bag b) | chunk_off [nb + 1] (8-grid-row chunks in front of bag b) | bag_of_gridrow [gmax] | bag_of_chunk [cmax],
+ *               the last two -1 behind sum s_b and sum ceil(s_b / 8).  ops.tm_ppeg_table builds it from the sides alone.
+ *   nb          the bags, 1 .. 1024
+ *   total_rows  2 nb <= R <= INT_MAX / 512
+ * The launches are shaped by (nb, R) alone: the single-bag grid (grid row x 2 channel halves x 8-column chunks) flattened over
+ * gmax grid rows, the weight gradient over cmax chunks; a workgroup the table does not place returns.  The kernels are the
+ * single-bag ones with the bag read off the grid row or chunk, taps, border skips and bias-first accumulate unchanged: every
+ * bag's rows of y and dx are BIT-EQUAL to mil_tm_ppeg_fwd / mil_tm_ppeg_bwd on that bag's slice, every bag's cls row passes
+ * through.  The sums that cross bags are dWf [512, 49] and db [512]: += over all chunks of all bags, atomic and
+ * caller-initialised (mil_tm_ppeg_bwd_packed), or (_fixed) every chunk's partial into ws with plain stores and ONE fold that
+ * adds them in ascending packed chunk order - bag 0's chunks first - and overwrites both: no float atomic, no counter, and with
+ * a one-bag table the bits of mil_tm_ppeg_bwd_fixed.  ws: mil_tm_ppeg_packed_ws_floats(sum ceil(s_b / 8)) = that count x 50 x
+ * 512 floats, a chunk's row laid out [dWf | db]; 0 for a count outside [1, INT_MAX / (50 x 512)]; for one bag it is
+ * mil_tm_ppeg_ws_floats(s).
+ * A null pointer (ws included), nb outside [1, 1024], total_rows < 2 nb or above INT_MAX / 512: MIL_EINVAL before any launch.
+ * The kernels trust nothing the table holds: a workgroup whose bag lies outside [0, nb), whose side is < 1, whose rows
+ * [row_off, row_off + 1 + s^2) leave [0, R) or whose grid row or chunk lies outside its bag returns without touching memory, and
+ * the fold adds at most cmax chunks.  Launches: forward 1, backward 2, _fixed 3 - whatever nb. */
+int mil_tm_ppeg_fwd_packed(const float* x, const float* W7, const float* b7, const float* W5, const float* b5, const float* W3,
+                           const float* b3, float* y, const int32_t* tab, int nb, int total_rows, void* stream);
+int mil_tm_ppeg_bwd_packed(const float* dy, const float* x, const float* W7, const float* W5, const float* W3, float* dx,
+                           float* dWf, float* db, const int32_t* tab, int nb, int total_rows, void* stream);
+size_t mil_tm_ppeg_packed_ws_floats(int total_chunks);
+int mil_tm_ppeg_bwd_packed_fixed(const float* dy, const float* x, const float* W7, const float* W5, const float* W3, float* dx,
+                                 float* dWf, float* db, float* ws, const int32_t* tab, int nb, int total_rows, void* stream);
 
 #ifdef __cplusplus
 }

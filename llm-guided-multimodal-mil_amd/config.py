@@ -144,10 +144,17 @@ def create_arg_parser(argv=None):
                    help="train_ddp.py and test_ddp.py: 1 = a TransMIL step of several bags runs every layer over ONE packed "
                         "sequence of all bags' rows - LayerNorm, the pad gather, to_qkv, the landmarks, both fused attention "
                         "passes, the residual conv, to_out, the dropout and the residual one launch set each, whatever the "
-                        "number of bags; PPEG stays per bag.  It wins over --tm_batch_bags.  Set on every TransMIL module of "
+                        "number of bags; PPEG stays per bag (--tm_packed_ppeg).  It wins over --tm_batch_bags.  Set on every TransMIL module of "
                         "the model; a step of one bag and a request for attention outputs keep the bag-by-bag route.  Models "
                         "without a TransMIL module accept the flag and ignore it.  0: the environment variable MIL_TM_PACKED "
                         "decides (default 0)")
+    p.add_argument("--tm_packed_ppeg", type=int, default=0, choices=[0, 1],
+                   help="train_ddp.py and test_ddp.py: 1 = where --tm_packed 1 runs a TransMIL step over one packed sequence, "
+                        "PPEG too is one launch set over all bags' sequence rows (a table of per-bag row offsets and sides), "
+                        "with no per-bag slice or concatenation between the two layers; per bag the same values, the PPEG "
+                        "weight and bias gradients one sum over all bags.  Without the packed route it changes nothing.  Set "
+                        "on every TransMIL module of the model, as --tm_packed is.  0: the environment variable "
+                        "MIL_TM_PACKED_PPEG decides (default 0)")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,

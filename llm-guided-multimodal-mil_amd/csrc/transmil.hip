@@ -19,6 +19,7 @@
 #include "mil_common.h"
 #include "tm_bgemm.h"
 #include "tm_packed.h"
+#include "tm_ppeg_packed.h"
 #include "../../include/mil_hip.h"
 
 namespace {
@@ -726,16 +727,19 @@ __device__ __forceinline__ void tm_ppeg_fold(const float* W7, const float* W5, c
         }
 }
 
-__global__ __launch_bounds__(256) void k_tm_ppeg(const float* __restrict__ x, int s, const float* __restrict__ W7,
-                                                 const float* __restrict__ b7, const float* __restrict__ W5,
-                                                 const float* __restrict__ b5, const float* __restrict__ W3,
-                                                 const float* __restrict__ b3, int flip, float* __restrict__ y) {
-    const int i = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+// The body of one workgroup: grid row i, channel half blockIdx.y, the columns of chunk jz of ONE bag whose rows start at x / y.
+// The single-bag kernel passes blockIdx.x / blockIdx.z; the packed one the bag's grid row, with x and y moved to the bag's rows.
+__device__ __forceinline__ void tm_ppeg_body(const float* __restrict__ x, int s, const float* __restrict__ W7,
+                                             const float* __restrict__ b7, const float* __restrict__ W5,
+                                             const float* __restrict__ b5, const float* __restrict__ W3,
+                                             const float* __restrict__ b3, int flip, float* __restrict__ y, const int i,
+                                             const int jz) {
+    const int c = blockIdx.y * 256 + threadIdx.x;
     float wf[49];
     tm_ppeg_fold(W7, W5, W3, c, wf);
     const float bias = flip ? 0.f : b7[c] + b5[c] + b3[c];
-    if (i == 0 && blockIdx.z == 0) y[c] = x[c];
-    const int j0 = blockIdx.z * PPEG_COLS, j1 = min(s, j0 + PPEG_COLS);
+    if (i == 0 && jz == 0) y[c] = x[c];
+    const int j0 = jz * PPEG_COLS, j1 = min(s, j0 + PPEG_COLS);
     for (int j = j0; j < j1; ++j) {
         float acc = bias;
 #pragma unroll
@@ -753,16 +757,40 @@ __global__ __launch_bounds__(256) void k_tm_ppeg(const float* __restrict__ x, in
     }
 }
 
+__global__ __launch_bounds__(256) void k_tm_ppeg(const float* __restrict__ x, int s, const float* __restrict__ W7,
+                                                 const float* __restrict__ b7, const float* __restrict__ W5,
+                                                 const float* __restrict__ b5, const float* __restrict__ W3,
+                                                 const float* __restrict__ b3, int flip, float* __restrict__ y) {
+    tm_ppeg_body(x, s, W7, b7, W5, b5, W3, b3, flip, y, blockIdx.x, blockIdx.z);
+}
+
+// All bags of a step (csrc/tm_ppeg_packed.h): the single-bag grid flattened over the bags - blockIdx.x the packed grid row, the
+// table gives its bag, that bag's side and first row and the grid row inside the bag; a workgroup past a smaller bag's column
+// chunks returns.  Every bag's cls row passes through (its grid row 0, column chunk 0).
+__global__ __launch_bounds__(256) void k_tm_ppeg_packed(const float* __restrict__ x, const float* __restrict__ W7,
+                                                        const float* __restrict__ b7, const float* __restrict__ W5,
+                                                        const float* __restrict__ b5, const float* __restrict__ W3,
+                                                        const float* __restrict__ b3, int flip, float* __restrict__ y,
+                                                        const int32_t* __restrict__ tab, int nb, int total_rows, int gmax) {
+    int s, row, i;
+    if (!tm_ppeg_gridrow(tab, nb, total_rows, gmax, blockIdx.x, s, row, i)) return;
+    if ((int)blockIdx.z * PPEG_COLS >= s) return;
+    const long off = (long)row * TM_D;
+    tm_ppeg_body(x + off, s, W7, b7, W5, b5, W3, b3, flip, y + off, i, blockIdx.z);
+}
+
 // dWf[c][tap] (tap < 49) and db[c] (tap 49) += sums over a chunk of 8 grid rows; thread per (tap, channel)
 // FIXED: dWf is the workspace [chunks][50 x 512], a chunk's row laid out [dWf 512 x 49 | db 512], plain stores (db unused)
+// The body of one workgroup: the chunk of grid rows [r0, r0 + 8) of ONE bag whose rows start at dy / x; FIXED: into row `chunk`.
 constexpr int PPEG_ROWS = 8;
+static_assert(PPEG_ROWS == TM_PPEG_CHUNK && TM_D == TM_PPEG_D, "the PPEG table's chunks are those of k_tm_ppeg_dw");
 template <bool FIXED>
-__global__ __launch_bounds__(256) void k_tm_ppeg_dw(const float* __restrict__ dy, const float* __restrict__ x, int s, float* dWf,
-                                                    float* db) {
+__device__ __forceinline__ void tm_ppeg_dw_body(const float* __restrict__ dy, const float* __restrict__ x, int s, float* dWf,
+                                                float* db, const int r0, const int chunk) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= 50 * TM_D) return;
     const int tap = e / TM_D, c = e % TM_D, a = tap / 7 - 3, b = tap % 7 - 3;
-    const int r0 = blockIdx.y * PPEG_ROWS, r1 = min(s, r0 + PPEG_ROWS);
+    const int r1 = min(s, r0 + PPEG_ROWS);
     float acc = 0.f;
     for (int i = r0; i < r1; ++i) {
         if (tap == 49) {
@@ -775,11 +803,51 @@ __global__ __launch_bounds__(256) void k_tm_ppeg_dw(const float* __restrict__ dy
             acc += dy[(long)(1 + i * s + j) * TM_D + c] * x[(long)(1 + ii * s + j + b) * TM_D + c];
     }
     if constexpr (FIXED) {
-        dWf[(long)blockIdx.y * (50 * TM_D) + (tap == 49 ? 49 * TM_D + c : c * 49 + tap)] = acc;
+        dWf[(long)chunk * (50 * TM_D) + (tap == 49 ? 49 * TM_D + c : c * 49 + tap)] = acc;
     } else {
         if (tap == 49) atomicAdd(db + c, acc);
         else atomicAdd(dWf + c * 49 + tap, acc);
     }
+}
+
+template <bool FIXED>
+__global__ __launch_bounds__(256) void k_tm_ppeg_dw(const float* __restrict__ dy, const float* __restrict__ x, int s, float* dWf,
+                                                    float* db) {
+    tm_ppeg_dw_body<FIXED>(dy, x, s, dWf, db, blockIdx.y * PPEG_ROWS, blockIdx.y);
+}
+
+// All bags of a step: blockIdx.y the packed chunk (bag 0's chunks first, ascending), the table gives its bag and first grid row.
+// A chunk the table does not place adds nothing; FIXED: it stores 0 into its row when the fold will read that row (k below the
+// table's chunk count), so that the fold reads no stale float, and touches nothing otherwise.
+template <bool FIXED>
+__global__ __launch_bounds__(256) void k_tm_ppeg_dw_packed(const float* __restrict__ dy, const float* __restrict__ x, float* dWf,
+                                                           float* db, const int32_t* __restrict__ tab, int nb, int total_rows,
+                                                           int gmax, int cmax) {
+    const int k = blockIdx.y;
+    int s, row, r0;
+    if (!tm_ppeg_chunk(tab, nb, total_rows, gmax, cmax, k, s, row, r0)) {
+        if constexpr (FIXED) {
+            const int e = blockIdx.x * 256 + threadIdx.x;
+            if (k < tm_ppeg_chunks(tab, nb, cmax) && e < 50 * TM_D) dWf[(long)k * (50 * TM_D) + e] = 0.f;
+        }
+        return;
+    }
+    if constexpr (FIXED)
+        if (k >= tm_ppeg_chunks(tab, nb, cmax)) return;             // behind the rows the workspace holds
+    const long off = (long)row * TM_D;
+    tm_ppeg_dw_body<FIXED>(dy + off, x + off, s, dWf, db, r0, k);
+}
+
+// dWf [512 x 49] | db [512] <- the sum of the workspace rows [dWf | db] of the table's chunks, chunk 0, 1, 2 .. in that order
+__global__ __launch_bounds__(256) void k_tm_ppeg_fold_packed(const float* __restrict__ ws, const int32_t* __restrict__ tab, int nb,
+                                                             int cmax, float* __restrict__ dWf, float* __restrict__ db) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= 50 * TM_D) return;
+    const int chunks = tm_ppeg_chunks(tab, nb, cmax);
+    float v = chunks > 0 ? ws[e] : 0.f;
+    for (int c = 1; c < chunks; ++c) v += ws[(long)c * (50 * TM_D) + e];
+    if (e < 49 * TM_D) dWf[e] = v;
+    else db[e - 49 * TM_D] = v;
 }
 
 // Per-patch cls-token attention: the cls row (padded row `pad`) of A1 Z A3 without the [n_pad, n_pad] map, in two launches.
@@ -1198,6 +1266,44 @@ int mil_tm_ppeg_bwd_fixed(const float* dy, const float* x, int s, const float* W
                        (float*)nullptr);
     tm_fold(ws, 50 * TM_D, chunks, 49 * TM_D, dWf, (hipStream_t)stream);
     tm_fold(ws + 49 * TM_D, 50 * TM_D, chunks, TM_D, db, (hipStream_t)stream);
+    return launch_rc();
+}
+
+// ---- PPEG of a step's bags in one launch set (csrc/tm_ppeg_packed.h): the launch shapes come from (nb, total_rows) alone
+int mil_tm_ppeg_fwd_packed(const float* x, const float* W7, const float* b7, const float* W5, const float* b5, const float* W3,
+                           const float* b3, float* y, const int32_t* tab, int nb, int total_rows, void* stream) {
+    if (!x || !W7 || !b7 || !W5 || !b5 || !W3 || !b3 || !y || !tm_ppeg_ok(tab, nb, total_rows)) return MIL_EINVAL;
+    const TmPpegDims d = tm_ppeg_dims(nb, total_rows);
+    hipLaunchKernelGGL(k_tm_ppeg_packed, dim3(d.gmax, 2, d.zmax), dim3(256), 0, (hipStream_t)stream, x, W7, b7, W5, b5, W3, b3, 0, y,
+                       tab, nb, total_rows, d.gmax);
+    return launch_rc();
+}
+
+int mil_tm_ppeg_bwd_packed(const float* dy, const float* x, const float* W7, const float* W5, const float* W3, float* dx,
+                           float* dWf, float* db, const int32_t* tab, int nb, int total_rows, void* stream) {
+    if (!dy || !x || !W7 || !W5 || !W3 || !dx || !dWf || !db || !tm_ppeg_ok(tab, nb, total_rows)) return MIL_EINVAL;
+    const TmPpegDims d = tm_ppeg_dims(nb, total_rows);
+    hipLaunchKernelGGL(k_tm_ppeg_packed, dim3(d.gmax, 2, d.zmax), dim3(256), 0, (hipStream_t)stream, dy, W7, W7, W5, W5, W3, W3, 1,
+                       dx, tab, nb, total_rows, d.gmax);
+    hipLaunchKernelGGL(k_tm_ppeg_dw_packed<false>, dim3((50 * TM_D + 255) / 256, d.cmax), dim3(256), 0, (hipStream_t)stream, dy, x,
+                       dWf, db, tab, nb, total_rows, d.gmax, d.cmax);
+    return launch_rc();
+}
+
+size_t mil_tm_ppeg_packed_ws_floats(int total_chunks) {
+    return total_chunks >= 1 && total_chunks <= INT_MAX / (50 * TM_D) ? (size_t)total_chunks * (50 * TM_D) : 0;
+}
+
+int mil_tm_ppeg_bwd_packed_fixed(const float* dy, const float* x, const float* W7, const float* W5, const float* W3, float* dx,
+                                 float* dWf, float* db, float* ws, const int32_t* tab, int nb, int total_rows, void* stream) {
+    if (!dy || !x || !W7 || !W5 || !W3 || !dx || !dWf || !db || !ws || !tm_ppeg_ok(tab, nb, total_rows)) return MIL_EINVAL;
+    const TmPpegDims d = tm_ppeg_dims(nb, total_rows);
+    hipLaunchKernelGGL(k_tm_ppeg_packed, dim3(d.gmax, 2, d.zmax), dim3(256), 0, (hipStream_t)stream, dy, W7, W7, W5, W5, W3, W3, 1,
+                       dx, tab, nb, total_rows, d.gmax);
+    hipLaunchKernelGGL(k_tm_ppeg_dw_packed<true>, dim3((50 * TM_D + 255) / 256, d.cmax), dim3(256), 0, (hipStream_t)stream, dy, x, ws,
+                       (float*)nullptr, tab, nb, total_rows, d.gmax, d.cmax);
+    hipLaunchKernelGGL(k_tm_ppeg_fold_packed, dim3((50 * TM_D + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, tab, nb, d.cmax,
+                       dWf, db);
     return launch_rc();
 }
 

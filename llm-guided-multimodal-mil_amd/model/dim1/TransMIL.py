@@ -162,8 +162,9 @@ def packed_index(sides: Sequence[int]) -> Tuple[List[int], List[int], List[int]]
 
 
 class PackedGeometry:
-    """packed_index on the device plus the block table: what TransMIL._run_bags_packed reads.  It depends on the tuple of sides
-    alone; a replayed step builds it once, with its geometry, outside the capture."""
+    """packed_index on the device plus the block table and the PPEG table (ops.tm_ppeg_table: the unpadded sequence rows, per-bag
+    row offsets and sides): what TransMIL._run_bags_packed reads.  It depends on the tuple of sides alone; a replayed step builds
+    it once, with its geometry, outside the capture."""
 
     def __init__(self, sides: Sequence[int], device):
         pad, unpad, blocks = packed_index(sides)
@@ -171,6 +172,7 @@ class PackedGeometry:
         self.pad_idx = torch.tensor(pad, dtype=torch.int32).to(device, non_blocking=True)
         self.unpad_idx = torch.tensor(unpad, dtype=torch.int32).to(device, non_blocking=True)
         self.table = ops.tm_packed_table(blocks, device)
+        self.ppeg_table = ops.tm_ppeg_table(self.sides, device)
 
 
 class DeviceGeometry:
@@ -325,6 +327,12 @@ class PPEG(nn.Module):
         return ops.tm_ppeg(x, s, self.proj.weight, self.proj.bias, self.proj1.weight, self.proj1.bias, self.proj2.weight,
                            self.proj2.bias, deterministic)
 
+    def run_packed(self, x: torch.Tensor, table, deterministic: Optional[bool] = None) -> torch.Tensor:
+        """run() over all bags of a step in one launch set: x [sum (1 + s_b^2), 512], the bags' sequences one after another,
+        table = PackedGeometry.ppeg_table -> the same rows (ops.tm_ppeg_packed)."""
+        return ops.tm_ppeg_packed(x, table, self.proj.weight, self.proj.bias, self.proj1.weight, self.proj1.bias, self.proj2.weight,
+                                  self.proj2.bias, deterministic)
+
 
 class TransMIL(nn.Module):
     """The reference's TransMIL extractor on the HIP kernels of csrc/transmil.hip: _fc1, the cls token, two Nystrom layers with
@@ -336,7 +344,9 @@ class TransMIL(nn.Module):
     (ops.nystrom_core_bags) instead of one set per bag.  Every bag keeps its own pseudo-inverse scale and its values are those
     of the bag-by-bag route (bit-equal under deterministic); the token-side passes, the dense layers and PPEG stay per bag.
     packed (MIL_TM_PACKED, default off; it wins over batch_bags): the same call runs every layer over ONE packed sequence of
-    all bags' rows (_run_bags_packed, ops.nystrom_core_packed) - every stage but PPEG one launch set whatever the bag count."""
+    all bags' rows (_run_bags_packed, ops.nystrom_core_packed) - every stage but PPEG one launch set whatever the bag count.
+    packed_ppeg (MIL_TM_PACKED_PPEG, default off; it has an effect only where the packed route runs): PPEG too is one launch set
+    over the packed sequence rows (ops.tm_ppeg_packed), with no per-bag slice or concatenation between the layers."""
 
     def __init__(self, n_classes: int, L: int = 768, D: int = 512, K: int = 1):
         super().__init__()
@@ -360,6 +370,7 @@ class TransMIL(nn.Module):
         self.gemm_pieces: Optional[int] = None       # 3: the Nystrom core's products on split-bf16 MFMA (ops.tm_pieces); None = MIL_TM_PIECES
         self.batch_bags: Optional[bool] = None       # a step's bags through one landmark-side chain (ops.tm_batch_bags); None = MIL_TM_BATCH_BAGS
         self.packed: Optional[bool] = None           # a step's bags as one packed sequence (ops.tm_packed); None = MIL_TM_PACKED; wins over batch_bags
+        self.packed_ppeg: Optional[bool] = None      # on the packed route, PPEG as one launch set too (ops.tm_packed_ppeg); None = MIL_TM_PACKED_PPEG
 
     def _drop_state(self, device):
         if self._drop_seed is None:
@@ -537,7 +548,9 @@ class TransMIL(nn.Module):
     def _run_bags_packed(self, seqs: torch.Tensor, geo: List[dict], geom):
         """_run_bags (need_attn False, several bags) over ONE packed sequence (packed, ops.tm_packed: the attribute, else
         MIL_TM_PACKED; default off; it wins over batch_bags): per layer every stage but PPEG is one launch set over all bags'
-        rows (TransLayer.run_packed).  PPEG runs per bag on row slices, its grid follows the side.  The keep bits of
+        rows (TransLayer.run_packed).  PPEG runs per bag on row slices, its grid follows the side - or, with packed_ppeg
+        (ops.tm_packed_ppeg: the attribute, else MIL_TM_PACKED_PPEG; default off), as one launch set on the rows as they stand
+        (PPEG.run_packed: per bag the same values, the weight and bias gradients one sum over all bags).  The keep bits of
         (bag, layer) are those of the bag-by-bag route, drawn into that bag's rows of one [sum seq, 16] buffer per layer;
         last_bits stays the per-bag list (views), and the pass counter advances once."""
         dev = seqs.device
@@ -557,7 +570,10 @@ class TransMIL(nn.Module):
             bits_used = [self._bits(b, g["seq"], dev, tuple(keep[j][rows[b]:rows[b + 1]] for j in range(2)))
                          for b, g in enumerate(geo)]
         x = self.layer1.run_packed(seqs, pk, keep[0], self.deterministic, self.gemm_pieces)
-        x = torch.cat([self.pos_layer.run(x[rows[b]:rows[b + 1]], g["s"], self.deterministic) for b, g in enumerate(geo)], 0)
+        if ops.tm_packed_ppeg(self.packed_ppeg):
+            x = self.pos_layer.run_packed(x, pk.ppeg_table, self.deterministic)
+        else:
+            x = torch.cat([self.pos_layer.run(x[rows[b]:rows[b + 1]], g["s"], self.deterministic) for b, g in enumerate(geo)], 0)
         x = self.layer2.run_packed(x, pk, keep[1], self.deterministic, self.gemm_pieces)
         if train and self.force_bits is None:
             ops.counter_add(self._drop_ctr, 1)

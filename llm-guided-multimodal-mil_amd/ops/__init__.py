@@ -41,4 +41,5 @@ from .transmil import (TM_H, TM_DH, TM_D, TM_M, TM_CONV, TM_PINV_ITERS, TM_QSCAL
                        tm_cls_attention, tm_cls_attention_fused, tm_lmk_attn, tm_lmk_attn_bwd, tm_tok_attn, tm_tok_attn_bwd, _tm_fused_a3,
                        _tm_fused_a1, _tm_fused_cls, _tm_pinv_fwd, _tm_fwd, _tm_fwd_bags, _tm_pinv_bwd, _tm_bwd, _tm_bwd_bags, _NystromCore, nystrom_core,
                        _NystromCoreBags, nystrom_core_bags, tm_packed, TmPackedTable, tm_packed_table_host, tm_packed_table,
-                       _tm_fwd_packed, _tm_bwd_packed, _NystromCorePacked, nystrom_core_packed)
+                       _tm_fwd_packed, _tm_bwd_packed, _NystromCorePacked, nystrom_core_packed, tm_packed_ppeg, TmPpegTable,
+                       tm_ppeg_table_host, tm_ppeg_table, _TmPPEGPacked, tm_ppeg_packed)

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import os
 from types import SimpleNamespace
 
@@ -63,6 +64,15 @@ def tm_packed(value=None) -> bool:
     the environment variable MIL_TM_PACKED (default 0), read per call."""
     if value is None:
         value = os.environ.get("MIL_TM_PACKED", "0") not in ("", "0")
+    return bool(value)
+
+
+def tm_packed_ppeg(value=None) -> bool:
+    """The switch of the packed PPEG (tm_ppeg_packed) on the packed route: the keyword (a module passes its `packed_ppeg`
+    attribute here), else the environment variable MIL_TM_PACKED_PPEG (default 0), read per call.  It has an effect only where
+    the packed route runs (tm_packed)."""
+    if value is None:
+        value = os.environ.get("MIL_TM_PACKED_PPEG", "0") not in ("", "0")
     return bool(value)
 
 
@@ -972,3 +982,97 @@ def nystrom_core_packed(qkv, blocks_or_table, w, *, deterministic=None, pieces=N
     module's step here is tm_packed (MIL_TM_PACKED, default 0)."""
     tab = blocks_or_table if isinstance(blocks_or_table, TmPackedTable) else tm_packed_table(blocks_or_table, qkv.device)
     return _NystromCorePacked.apply(qkv, w, tab, tm_deterministic(deterministic), tm_pieces(pieces))
+
+
+# ---- PPEG of a step's bags in one launch set (csrc/tm_ppeg_packed.h): the unpadded sequences, one bag after another
+class TmPpegTable:
+    """The table of the mil_tm_ppeg_*_packed entries for bags of grid sides `sides` (host ints): `dev`, int32
+    [4 nb + 3 + gmax + cmax] on the device (tm_ppeg_table_host has the layout); `rows` = sum (1 + s^2), the packed sequence rows;
+    `chunks` = sum ceil(s / 8), what sizes the fixed-order workspace.  Build it with tm_ppeg_table, outside any capture; it
+    depends on the bags' sides alone."""
+
+    def __init__(self, sides, dev):
+        self.sides = tuple(int(s) for s in sides)
+        self.nb, self.dev = len(self.sides), dev
+        self.rows = sum(1 + s * s for s in self.sides)
+        self.chunks = sum(-(-s // 8) for s in self.sides)
+
+    def args(self):
+        return _p(self.dev), self.nb, self.rows
+
+
+def tm_ppeg_table_host(sides):
+    """The table's int32 values as a list, for R = sum (1 + s^2) rows, gmax = isqrt(nb (R - nb)) >= sum s and
+    cmax = min(gmax, (gmax + 7 nb) // 8) >= sum ceil(s / 8) (both follow from (nb, R) alone, as the launch shapes do):
+    row_off [nb + 1] | side [nb] | grow_off [nb + 1] | chunk_off [nb + 1] | bag_of_gridrow [gmax] | bag_of_chunk [cmax], the
+    last two -1 behind the bags' grid rows and chunks."""
+    sides = [int(s) for s in sides]
+    if not 1 <= len(sides) <= TM_MAX_BATCH_BAGS or min(sides) < 1 or sum(1 + s * s for s in sides) > (2 ** 31 - 1) // TM_D:
+        raise ValueError(f"tm_ppeg_table: 1 .. {TM_MAX_BATCH_BAGS} bags of side >= 1, at most {(2 ** 31 - 1) // TM_D} rows, got {sides}")
+    nb = len(sides)
+    row, grow, chunk = [0], [0], [0]
+    for s in sides:
+        row.append(row[-1] + 1 + s * s)
+        grow.append(grow[-1] + s)
+        chunk.append(chunk[-1] + -(-s // 8))
+    gmax = math.isqrt(nb * (row[-1] - nb))
+    cmax = min(gmax, (gmax + 7 * nb) // 8)
+    bag_g = [b for b, s in enumerate(sides) for _ in range(s)]
+    bag_c = [b for b, s in enumerate(sides) for _ in range(-(-s // 8))]
+    return row + sides + grow + chunk + bag_g + [-1] * (gmax - len(bag_g)) + bag_c + [-1] * (cmax - len(bag_c))
+
+
+def tm_ppeg_table(sides, device=None) -> TmPpegTable:
+    """sides: per bag the grid side -> the TmPpegTable on `device` (default: the current GPU).  One small host-to-device copy,
+    so a replayed step builds it once per graph key, not per step."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    return TmPpegTable(sides, torch.tensor(tm_ppeg_table_host(sides), dtype=torch.int32).to(device, non_blocking=True))
+
+
+class _TmPPEGPacked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, tab, W7, b7, W5, b5, W3, b3, deterministic=False):
+        if x.dim() != 2 or x.shape[1] != TM_D or x.shape[0] != tab.rows or tab.dev.device != x.device:
+            raise _lib.MilHipError(f"tm_ppeg_packed: x {tuple(x.shape)} outside the built shape [{tab.rows}, {TM_D}] for sides "
+                                   f"{tab.sides}, or on two devices")
+        x = _f32c(x, "x")
+        W7, W5, W3 = _f32c(W7, "W7"), _f32c(W5, "W5"), _f32c(W3, "W3")
+        y = torch.empty_like(x)
+        _lib.checked().mil_tm_ppeg_fwd_packed(_p(x), _p(W7), _p(_f32c(b7, "b7")), _p(W5), _p(_f32c(b5, "b5")), _p(W3),
+                                              _p(_f32c(b3, "b3")), _p(y), *tab.args(), _stream())
+        ctx.save_for_backward(x, W7, W5, W3)
+        ctx.tab, ctx.deterministic = tab, deterministic
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W7, W5, W3 = ctx.saved_tensors
+        tab = ctx.tab
+        dy = _f32c(dy, "dy")
+        dx = torch.empty_like(x)
+        if ctx.deterministic:       # the fold overwrites dWf and db
+            dWf = torch.empty((TM_D, 1, 7, 7), device=x.device, dtype=torch.float32)
+            db = torch.empty(TM_D, device=x.device, dtype=torch.float32)
+            ws = _ws(_lib.lib().mil_tm_ppeg_packed_ws_floats(tab.chunks), x)
+            _lib.checked().mil_tm_ppeg_bwd_packed_fixed(_p(dy), _p(x), _p(W7), _p(W5), _p(W3), _p(dx), _p(dWf), _p(db), _p(ws),
+                                                        *tab.args(), _stream())
+        else:
+            dWf = torch.zeros((TM_D, 1, 7, 7), device=x.device, dtype=torch.float32)
+            db = torch.zeros(TM_D, device=x.device, dtype=torch.float32)
+            _lib.checked().mil_tm_ppeg_bwd_packed(_p(dy), _p(x), _p(W7), _p(W5), _p(W3), _p(dx), _p(dWf), _p(db), *tab.args(),
+                                                  _stream())
+        # as _TmPPEG: dW7 is the whole map, dW5 / dW3 its central 5 x 5 / 3 x 3; the three biases share db
+        return (dx, None, dWf, db, dWf[:, :, 1:6, 1:6].contiguous(), db.clone(), dWf[:, :, 2:5, 2:5].contiguous(), db.clone(), None)
+
+
+def tm_ppeg_packed(x, table, W7, b7, W5, b5, W3, b3, deterministic=None):
+    """tm_ppeg for all bags of a step in ONE launch set: x [sum (1 + s_b^2), 512] = the bags' sequences one after another,
+    table = a TmPpegTable (tm_ppeg_table) or the tuple of sides (the table is then built here: a host-to-device copy, not for a
+    capture).  Every bag's rows of the result and of dx are bit-equal to tm_ppeg on that bag's slice; the weight and bias
+    gradients are ONE sum over all bags' 8-grid-row chunks - atomic, or with deterministic in ascending packed order
+    (mil_tm_ppeg_bwd_packed_fixed) -, where the per-bag route lets autograd add per-bag totals.  No host read; the workspace is a
+    torch.empty, so with a TmPpegTable the call can be captured into a graph.  The switch that sends a module's packed step
+    here is tm_packed_ppeg (MIL_TM_PACKED_PPEG, default 0)."""
+    tab = table if isinstance(table, TmPpegTable) else tm_ppeg_table(table, x.device)
+    return _TmPPEGPacked.apply(x, tab, W7, b7, W5, b5, W3, b3, tm_deterministic(deterministic))

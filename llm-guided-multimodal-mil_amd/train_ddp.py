@@ -57,6 +57,10 @@ def build_model(args):
         for m in model.modules():           # and once more
             if type(m).__name__ == "TransMIL":
                 m.packed = True
+    if getattr(args, "tm_packed_ppeg", 0):
+        for m in model.modules():           # on the packed route, PPEG as one launch set too
+            if type(m).__name__ == "TransMIL":
+                m.packed_ppeg = True
     if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
             and getattr(args, "transmil_graph", 0)):
         model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward

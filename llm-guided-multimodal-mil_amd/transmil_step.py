@@ -126,9 +126,11 @@ class RaggedTransMILStepper:
         batched = ops.tm_batch_bags(m.extractor_pathology.batch_bags) and len(sides) > 1 and not attn
         # ... nor one of either of those for a model that asks for the packed sequence, which wins over the batched chain
         packed = ops.tm_packed(m.extractor_pathology.packed) and len(sides) > 1 and not attn
+        # ... nor one with PPEG per bag for a model that asks for the packed PPEG on that route
+        ppeg = packed and ops.tm_packed_ppeg(getattr(m.extractor_pathology, "packed_ppeg", None))
         return (("transmil-sides", tuple(sides), bool(m.training), self.backward) + (("patch_attn",) if attn else ())
                 + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
-                + (("packed",) if packed else ("batch_bags",) if batched else ()))
+                + (("packed", "ppeg") if ppeg else ("packed",) if packed else ("batch_bags",) if batched else ()))
 
     def step(self, slot, lengths: Sequence[int], on_device: bool = False):
         """One step on the bags packed at the front of slot.x.  on_device: the lengths already sit in slot.len_dev (the

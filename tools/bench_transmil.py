@@ -30,7 +30,9 @@ replayed (RaggedTransMILStepper, B bags per slot) - with the landmark-side chain
 route of MIL_TM_BATCH_BAGS=0), batched over the bags (= True: ops.nystrom_core_bags), and bag by bag again, in one process, same
 model, same bags; median (min - max) of --reps regions each and the peak allocated bytes of one eager step per route.  The
 first and third columns are the yardstick.  B = 1 (the default) leaves every other row as it is.  --packed adds the column of
-TransMIL.packed (ops.nystrom_core_packed: every token-side stage one launch set over all bags' rows), --mix makes the bags ragged."""
+TransMIL.packed (ops.nystrom_core_packed: every token-side stage one launch set over all bags' rows) and, behind it, the column
+of TransMIL.packed + TransMIL.packed_ppeg (ops.tm_ppeg_packed: PPEG too one launch set), read against the packed column
+(`*_packed_ppeg_over_packed`); --mix makes the bags ragged."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -344,18 +346,22 @@ def bags_rows(a, dev, args):
 
         res = dict(N=N, bags=B, lengths=lengths, n_pad=geometry(N)["n_pad"], regions=a.reps,
                    fused_env=[os.environ.get(k, "0") for k in ("MIL_TM_FUSED_A1", "MIL_TM_FUSED_A3")])
-        routes = ((False, False, "off"), (True, False, "on")) + (((False, True, "packed"),) if a.packed else ()) + ((False, False, "off_again"),)
-        for on, pk, tag in routes:
+        routes = (((False, False, False, "off"), (True, False, False, "on"))
+                  + (((False, True, False, "packed"), (False, True, True, "packed_ppeg")) if a.packed else ())
+                  + ((False, False, False, "off_again"),))
+        for on, pk, pp, tag in routes:
             for m in (m_e, m_r):
-                m.extractor_pathology.batch_bags, m.extractor_pathology.packed = on, pk
+                ex = m.extractor_pathology
+                ex.batch_bags, ex.packed, ex.packed_ppeg = on, pk, pp
             for _ in range(3):                        # the stepper: eager visit, capture, first replay of this route's key
                 replay()
             for name, fn in (("eager", eager), ("replay", replay)):
                 ts = region_times(fn, a.reps, a.warmup)
                 res.update({f"{name}_{tag}_ms": round(med(ts), 3), f"{name}_{tag}_min_ms": round(min(ts), 3),
                             f"{name}_{tag}_max_ms": round(max(ts), 3)})
-        for on, pk, tag in routes[:-1]:
-            m_e.extractor_pathology.batch_bags, m_e.extractor_pathology.packed = on, pk
+        for on, pk, pp, tag in routes[:-1]:
+            ex = m_e.extractor_pathology
+            ex.batch_bags, ex.packed, ex.packed_ppeg = on, pk, pp
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
@@ -369,7 +375,8 @@ def bags_rows(a, dev, args):
             if a.packed:
                 res[f"{name}_packed_over_off"] = round(res[f"{name}_packed_ms"] / off, 4)
                 res[f"{name}_packed_over_on"] = round(res[f"{name}_packed_ms"] / res[f"{name}_on_ms"], 4)
-        res["graph_mib"] = {("packed" if "packed" in k else "on" if "batch_bags" in k else "off"): round(v / 2 ** 20, 1)
+                res[f"{name}_packed_ppeg_over_packed"] = round(res[f"{name}_packed_ppeg_ms"] / res[f"{name}_packed_ms"], 4)
+        res["graph_mib"] = {("packed_ppeg" if "ppeg" in k else "packed" if "packed" in k else "on" if "batch_bags" in k else "off"): round(v / 2 ** 20, 1)
                             for k, v in st.graph_bytes.items()}
         print(json.dumps(res), flush=True)
         del st, slot, m_e, m_r, o_e, o_r, x
@@ -413,7 +420,7 @@ def main():
     ap.add_argument("--bags", type=int, default=1, help="B > 1: the training step over B bags of N patches, eager and "
                     "replayed, with TransMIL.batch_bags off, on, off again: ms and peak allocated bytes")
     ap.add_argument("--packed", action="store_true", help="--bags B: one more column, the step with TransMIL.packed set (a step's "
-                    "bags as one packed sequence), between `on` and `off_again`.  It always runs both attention passes fused: "
+                    "bags as one packed sequence) and the one with TransMIL.packed_ppeg on top (PPEG as one launch set), between `on` and `off_again`.  It always runs both attention passes fused: "
                     "set MIL_TM_FUSED_A1=1 MIL_TM_FUSED_A3=1 so that the other two columns do too")
     ap.add_argument("--mix", action="store_true", help="--bags B: a ragged mix, bag b of N (4 - b mod 4) / 4 patches")
     ap.add_argument("--seed", type=int, default=7)
