@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 21 */
+int mil_abi_version(void);   /* 22 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1331,6 +1331,30 @@ int mil_tm_ppeg_bwd_packed(const float* dy, const float* x, const float* W7, con
 size_t mil_tm_ppeg_packed_ws_floats(int total_chunks);
 int mil_tm_ppeg_bwd_packed_fixed(const float* dy, const float* x, const float* W7, const float* W5, const float* W3, float* dx,
                                  float* dWf, float* db, float* ws, const int32_t* tab, int nb, int total_rows, void* stream);
+/* ---- TransMIL, the per-patch cls attention of a packed step's bags in one launch set (ABI 22; csrc/cls_attn_fused.hip; ops:
+ * tm_cls_attention_packed / MIL_TM_PACKED_CLS=1 on the packed route).  mil_tm_cls_attn_fused for every bag of the packed
+ * sequence above: qkv [256 total_blocks, 1536] the packed rows, qL, kL [nb, 8, 256, 64], Z [nb, 8, 256, 256], lse3 [nb, 8, 256]
+ * stacked as the packed core holds them, (blk_off, nb, total_blocks) the block table, and
+ *   cls_tab        device int32 [2 nb + 1]: side [nb] (s_b, the grid side of bag b) | off [nb + 1] (off_b = the sum of s^2 over
+ *                  the bags in front of b, off[nb] = total_patches).  ops.tm_cls_table builds it from the sides alone.
+ *   total_patches  the sum of s_b^2, nb <= total_patches < 256 total_blocks: the patches of `out`
+ *   len_dev        device int32 [nb]: the bags' lengths, each read on the device and clamped into ((s_b - 1)^2, s_b^2]
+ * out: total_patches x 8 floats, bag b's [8, s_b^2] - laid out as the single-bag entry's output, zeros from N_b on - at float
+ * 8 off_b; every element is written.  Per bag on the device: l_b = blk_off[b + 1] - blk_off[b], pad_b = 256 l_b - s_b^2 - 1.
+ * ws: mil_tm_cls_attn_packed_ws_floats(total_blocks, nb) = nb x 8 x 256 (t) + 8 x 256 x total_blocks (r) floats; 0 for
+ * refused arguments.  The launches are shaped by (nb, total_blocks) alone - t (4, 8, nb), key (2 total_blocks, 8): a 128-key
+ * chunk lies in one block and so in one bag, and what lies wholly in front of its bag's column pad_b + 1 returns at once; fold
+ * (total_blocks, 8) - and the kernels are the single-bag ones with the bag read off the tables: a bag's t and a key's sum keep
+ * their terms and order, so every bag's [8, s_b^2] is BIT-EQUAL to mil_tm_cls_attn_fused on that bag's rows and slices.
+ * A null pointer, nb / total_blocks the packed entries refuse, total_patches outside the range above, or a qkv, qL or kL that
+ * is not 16-byte aligned: MIL_EINVAL before any launch.  The kernels trust nothing the tables hold: a workgroup whose bag lies
+ * outside [0, nb), whose block range leaves [0, total_blocks], whose side is < 1, whose pad_b lies outside [0, 256) or whose
+ * [off_b, off_b + s_b^2) leaves [0, total_patches) returns without touching memory.  No atomics, no host read, nothing
+ * allocated; three launches whatever nb. */
+size_t mil_tm_cls_attn_packed_ws_floats(int total_blocks, int nb);
+int mil_tm_cls_attn_packed(const float* qkv, const float* qL, const float* kL, const float* Z, const float* lse3,
+                           const int32_t* cls_tab, int total_patches, const int32_t* len_dev, float* ws, float* out,
+                           const int32_t* blk_off, int nb, int total_blocks, void* stream);
 
 #ifdef __cplusplus
 }

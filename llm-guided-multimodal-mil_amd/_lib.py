@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -240,6 +240,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_tm_ppeg_bwd_packed": (c_int, [_P, _P] + [_P] * 6 + [_P, c_int, c_int, _P]),
     "mil_tm_ppeg_packed_ws_floats": (c_size_t, [c_int]),
     "mil_tm_ppeg_bwd_packed_fixed": (c_int, [_P, _P] + [_P] * 6 + [_P, _P, c_int, c_int, _P]),
+    # the packed cls attention: the five operands, (cls_tab, total_patches), len_dev, ws, out, then the block table's three
+    "mil_tm_cls_attn_packed_ws_floats": (c_size_t, [c_int, c_int]),
+    "mil_tm_cls_attn_packed": (c_int, [_P] * 5 + [_P, c_int, _P, _P, _P, _P, c_int, c_int, _P]),
 }
 # entries that return a value, not a status: checked() leaves them without an errcheck
 VALUE_RETURNING = frozenset(n for n, (res, _) in SIGNATURES.items() if res is c_size_t) | frozenset((

@@ -155,6 +155,13 @@ def create_arg_parser(argv=None):
                         "weight and bias gradients one sum over all bags.  Without the packed route it changes nothing.  Set "
                         "on every TransMIL module of the model, as --tm_packed is.  0: the environment variable "
                         "MIL_TM_PACKED_PPEG decides (default 0)")
+    p.add_argument("--tm_packed_cls", type=int, default=0, choices=[0, 1],
+                   help="train_ddp.py and test_ddp.py: 1 = with --tm_packed 1, a TransMIL step of several bags that asks for the "
+                        "per-patch cls attention (--save_patch_attn, the fusion model's note attention over a TransMIL "
+                        "aggregator) stays on the packed route: each layer's cls attention of all bags is one launch set, "
+                        "bit-equal per bag to the fused single-bag kernels.  Without the packed route, and for a step of one "
+                        "bag, it changes nothing.  Set on every TransMIL module of the model, as --tm_packed is.  0: the "
+                        "environment variable MIL_TM_PACKED_CLS decides (default 0)")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,

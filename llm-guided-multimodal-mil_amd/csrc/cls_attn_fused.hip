@@ -23,10 +23,17 @@
 //               workgroups.  The launch reads 8 n_pad floats that are still in L2.
 // N is the host `n`, or len_dev[bag] read on the device and clamped into the side's bucket exactly as k_tm_cls_row does; only
 // the fold needs it.  Nothing is read on the host and nothing is allocated: the entry is capture-safe.
+//
+// mil_tm_cls_attn_packed: the same three kernels over ALL bags of a packed step (csrc/tm_packed.h) in one launch set.  The
+// bag of a workgroup comes from the block table, its side and output offset from a second small table, its length from
+// len_dev; t is [nb, 8, 256], r [8, 256 total_blocks] over the packed rows, out the bags' [8, s_b^2] one after another.  The
+// grids follow from (nb, total_blocks) alone: t (4, 8, nb), key (2 total_blocks, 8), fold (total_blocks, 8).  A key's sum and
+// a bag's t do not depend on the grid, so every bag's output has the bits of mil_tm_cls_attn_fused on its rows and slices.
 #include <hip/hip_runtime.h>
 
 #include "mil_common.h"
 #include "nystrom_tile.h"
+#include "tm_packed.h"
 #include "../../include/mil_hip.h"
 
 namespace {
@@ -46,11 +53,56 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// What a packed workgroup knows of its bag (csrc/tm_packed.h): the first block c0 and the block count l from the block table,
+// the side s and the output offset off (in patches) from the cls table (ops.tm_cls_table: side [nb] | off [nb + 1]), and from
+// these pad = 256 l - s^2 - 1.  false - the workgroup returns - for a block range outside [0, total_blocks], s < 1, pad outside
+// [0, 256) or [off, off + s^2) outside the total_patches patches of out: whatever the tables hold, no address leaves the rows,
+// the nb slices, the workspace or out.  Everything here is wave-uniform.
+struct ClsfBag {
+    int c0, l, s, S2, pad, off;
+};
+__device__ __forceinline__ bool clsf_bag(const int32_t* __restrict__ tab, const int32_t* __restrict__ ctab, int nb,
+                                         int total_blocks, int total_patches, int bag, ClsfBag& g) {
+    int c1;
+    if (bag < 0 || bag >= nb || !tm_packed_range(tab, total_blocks, bag, g.c0, c1)) return false;
+    g.l = c1 - g.c0;
+    g.s = __builtin_amdgcn_readfirstlane(ctab[bag]);
+    g.off = __builtin_amdgcn_readfirstlane(ctab[nb + bag]);
+    if (g.s < 1 || g.s > 46340) return false;           // s^2 in an int
+    g.S2 = g.s * g.s;
+    const long pad = (long)TM_PACKED_BLK * g.l - g.S2 - 1;
+    if (pad < 0 || pad >= TM_PACKED_BLK) return false;
+    g.pad = (int)pad;
+    return g.off >= 0 && g.off <= total_patches - g.S2;
+}
+
+// The table and the packed sizes as ONE trailing argument, empty in the single-bag kernels (as TmPackedArg)
+template <bool PACKED>
+struct ClsfArg {
+    const int32_t *tab, *ctab;
+    int nb, total_blocks, total_patches;
+};
+template <>
+struct ClsfArg<false> {};
+
+// The three kernels below are each one body with a single-bag and a packed instantiation: the packed one reads its bag's
+// geometry off the tables and moves the pointers to the bag's rows and slices; every sum keeps its terms and their order.
+// packed: blockIdx.z = the bag; t is [nb, 8, 256]
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_clsf_t(const float* __restrict__ qkv, const float* __restrict__ kL,
-                                                const float* __restrict__ Z, int pad, float* __restrict__ t) {
+                                                const float* __restrict__ Z, int pad, float* __restrict__ t, ClsfArg<PACKED> pk) {
     __shared__ float q[NY_DH];
     __shared__ float a[NY_M];
     __shared__ float red[4][64];
+    if constexpr (PACKED) {                         // uniform per workgroup, ahead of every barrier
+        ClsfBag g;
+        if (!clsf_bag(pk.tab, pk.ctab, pk.nb, pk.total_blocks, pk.total_patches, blockIdx.z, g)) return;
+        pad = g.pad;
+        qkv += (size_t)g.c0 * TM_PACKED_BLK * NY_QKV;
+        kL += (size_t)blockIdx.z * NY_H * NY_M * NY_DH;
+        Z += (size_t)blockIdx.z * NY_H * NY_M * NY_M;
+        t += (size_t)blockIdx.z * NY_H * NY_M;
+    }
     const int hd = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid < NY_DH) q[tid] = qkv[(size_t)pad * NY_QKV + hd * NY_DH + tid] * NY_QSCALE;    // row pad holds the unscaled q
     __syncthreads();
@@ -83,18 +135,39 @@ __global__ __launch_bounds__(256) void k_clsf_t(const float* __restrict__ qkv, c
     if (wv == 0) t[hd * NY_M + j] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
 }
 
-// tile0: the first 32-key tile that holds a column from pad + 1 on; r [8, n_pad] gets the keys from 32 tile0 on
+// tile0: the first 32-key tile that holds a column from pad + 1 on; r [8, n_pad] gets the keys from 32 tile0 on.
+// packed: blockIdx.x = a 128-key chunk of the packed rows - half a block, so inside one bag -, n_pad = all 256 total_blocks rows
+// and r [8, n_pad] is indexed by the packed row.  A chunk that lies wholly in front of its bag's column pad + 1 returns ahead of
+// the barrier; a wave whose tile does returns behind it, where the single-bag kernel drops its spare waves.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_clsf_key(const float* __restrict__ qkv, const float* __restrict__ qL,
                                                   const float* __restrict__ t, const float* __restrict__ lse3, int n_pad,
-                                                  int tile0, float* __restrict__ r_ws) {
+                                                  int tile0, float* __restrict__ r_ws, ClsfArg<PACKED> pk) {
     __shared__ float ts[NY_M], ls[NY_M];
     const int hd = blockIdx.y, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+    int tile = tile0 + (CF_KC / 32) * blockIdx.x + wave;
+    if constexpr (PACKED) {
+        const int blk = blockIdx.x / (TM_PACKED_BLK / CF_KC);
+        const int bag = tm_packed_bag(pk.tab, pk.nb, pk.total_blocks, blk);
+        ClsfBag g;
+        if (bag < 0 || !clsf_bag(pk.tab, pk.ctab, pk.nb, pk.total_blocks, pk.total_patches, bag, g)) return;
+        if (blk < g.c0 || blk >= g.c0 + g.l) return;               // a table whose two halves disagree
+        const int first = g.c0 * (TM_PACKED_BLK / 32) + (g.pad + 1) / 32;      // the bag's first tile with a column from pad + 1 on
+        if ((CF_KC / 32) * (int)blockIdx.x + CF_KC / 32 <= first) return;
+        tile = (CF_KC / 32) * blockIdx.x + wave;
+        tile0 = first;
+        qL += (size_t)bag * NY_H * NY_M * NY_DH;
+        t += (size_t)bag * NY_H * NY_M;
+        lse3 += (size_t)bag * NY_H * NY_M;
+    }
     ts[tid] = t[hd * NY_M + tid];
     ls[tid] = lse3[hd * NY_M + tid];
     __syncthreads();
-    const int tile = tile0 + (CF_KC / 32) * blockIdx.x + wave;
     if (tile >= n_pad / 32) return;                 // the last workgroup's spare waves; no barrier follows
+    if constexpr (PACKED) {
+        if (tile < tile0) return;
+    }
     const size_t key0 = (size_t)tile * 32;
     float kr[32];
     load32(qkv + (key0 + r) * NY_QKV + NY_D + hd * NY_DH + 32 * hh, kr);
@@ -114,12 +187,28 @@ __global__ __launch_bounds__(256) void k_clsf_key(const float* __restrict__ qkv,
     if (hh == 0) r_ws[(size_t)hd * n_pad + key0 + r] = acc;
 }
 
+// packed: blockIdx.x = a 256-row block; block k of bag b folds the patches 256 (k - c0) + tid < s^2 of that bag, the length is
+// len_dev[b], and the bag's [8, s^2] lies at float 8 off of out.  n_pad = all 256 total_blocks rows, as in k_clsf_key.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_clsf_fold(const float* __restrict__ r_ws, int n_pad, int pad, int s, int n_host,
-                                                   const int32_t* __restrict__ len_dev, int bag, float* __restrict__ out) {
+                                                   const int32_t* __restrict__ len_dev, int bag, float* __restrict__ out,
+                                                   ClsfArg<PACKED> pk) {
+    int blk = blockIdx.x;
+    if constexpr (PACKED) {
+        bag = tm_packed_bag(pk.tab, pk.nb, pk.total_blocks, blk);
+        ClsfBag g;
+        if (bag < 0 || !clsf_bag(pk.tab, pk.ctab, pk.nb, pk.total_blocks, pk.total_patches, bag, g)) return;
+        if (blk < g.c0 || blk >= g.c0 + g.l) return;               // a table whose two halves disagree
+        blk -= g.c0;
+        s = g.s;
+        pad = g.pad;
+        r_ws += (size_t)g.c0 * TM_PACKED_BLK;
+        out += (size_t)NY_H * g.off;
+    }
     const int S2 = s * s;
     const int N = len_dev != nullptr ? min(max(len_dev[bag], (s - 1) * (s - 1) + 1), S2) : n_host;
     const int add = S2 - N;
-    const int hd = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int hd = blockIdx.y, i = blk * 256 + threadIdx.x;
     if (i >= S2) return;
     const float* row = r_ws + (size_t)hd * n_pad + pad + 1;     // the S2 sequence keys: i < N and N + i < S2 stay inside
     float v = 0.f;
@@ -149,11 +238,38 @@ int mil_tm_cls_attn_fused(const float* qkv, const float* qL, const float* kL, co
     float* t = ws;
     float* r_ws = ws + NY_H * NY_M;
     const int tile0 = (pad + 1) / 32, tiles = n_pad / 32 - tile0;                     // pad + 1 < n_pad: tiles >= 1
-    hipLaunchKernelGGL(k_clsf_t, dim3(NY_M / 64, NY_H), dim3(256), 0, (hipStream_t)stream, qkv, kL, Z, pad, t);
-    hipLaunchKernelGGL(k_clsf_key, dim3((tiles + CF_KC / 32 - 1) / (CF_KC / 32), NY_H), dim3(256), 0, (hipStream_t)stream, qkv, qL, t, lse3, n_pad,
-                       tile0, r_ws);
-    hipLaunchKernelGGL(k_clsf_fold, dim3((unsigned)((S2 + 255) / 256), NY_H), dim3(256), 0, (hipStream_t)stream, r_ws, n_pad,
-                       pad, s, n, len_dev, bag, out);
+    hipLaunchKernelGGL(k_clsf_t<false>, dim3(NY_M / 64, NY_H), dim3(256), 0, (hipStream_t)stream, qkv, kL, Z, pad, t,
+                       ClsfArg<false>{});
+    hipLaunchKernelGGL(k_clsf_key<false>, dim3((tiles + CF_KC / 32 - 1) / (CF_KC / 32), NY_H), dim3(256), 0, (hipStream_t)stream,
+                       qkv, qL, t, lse3, n_pad, tile0, r_ws, ClsfArg<false>{});
+    hipLaunchKernelGGL(k_clsf_fold<false>, dim3((unsigned)((S2 + 255) / 256), NY_H), dim3(256), 0, (hipStream_t)stream, r_ws, n_pad,
+                       pad, s, n, len_dev, bag, out, ClsfArg<false>{});
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}
+
+size_t mil_tm_cls_attn_packed_ws_floats(int total_blocks, int nb) {
+    if (!tm_packed_ok(&nb, nb, total_blocks)) return 0;
+    return (size_t)nb * NY_H * NY_M + (size_t)NY_H * TM_PACKED_BLK * total_blocks;      // t [nb, 8, 256] | r [8, 256 total_blocks]
+}
+
+int mil_tm_cls_attn_packed(const float* qkv, const float* qL, const float* kL, const float* Z, const float* lse3,
+                           const int32_t* cls_tab, int total_patches, const int32_t* len_dev, float* ws, float* out,
+                           const int32_t* blk_off, int nb, int total_blocks, void* stream) {
+    if (!qkv || !qL || !kL || !Z || !lse3 || !cls_tab || !len_dev || !ws || !out || !tm_packed_ok(blk_off, nb, total_blocks))
+        return MIL_EINVAL;
+    if (!ny_aligned(qkv) || !ny_aligned(qL) || !ny_aligned(kL)) return MIL_EINVAL;     // read as float4
+    // every bag has 1 <= s^2 < 256 l: nb <= sum s^2 < 256 total_blocks
+    if (total_patches < nb || total_patches >= (long)TM_PACKED_BLK * total_blocks) return MIL_EINVAL;
+    float* t = ws;
+    float* r_ws = ws + (size_t)nb * NY_H * NY_M;
+    const int R = TM_PACKED_BLK * total_blocks;
+    const ClsfArg<true> pk{blk_off, cls_tab, nb, total_blocks, total_patches};
+    hipLaunchKernelGGL(k_clsf_t<true>, dim3(NY_M / 64, NY_H, nb), dim3(256), 0, (hipStream_t)stream, qkv, kL, Z, 0, t, pk);
+    hipLaunchKernelGGL(k_clsf_key<true>, dim3(total_blocks * (TM_PACKED_BLK / CF_KC), NY_H), dim3(256), 0, (hipStream_t)stream,
+                       qkv, qL, t, lse3, R, 0, r_ws, pk);
+    hipLaunchKernelGGL(k_clsf_fold<true>, dim3(total_blocks, NY_H), dim3(256), 0, (hipStream_t)stream, r_ws, R, 0, 0, 0, len_dev,
+                       0, out, pk);
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }

@@ -250,9 +250,11 @@ class RaggedFusionTransMILStepper:
         batched = ops.tm_batch_bags(agg.batch_bags) and len(lengths) > 1      # the aggregator's batched landmark-side chain
         packed = ops.tm_packed(agg.packed) and len(lengths) > 1               # its packed sequence, which wins over that
         ppeg = packed and ops.tm_packed_ppeg(getattr(agg, "packed_ppeg", None))  # ... with PPEG as one launch set too
+        cls = packed and ops.tm_packed_cls(getattr(agg, "packed_cls", None))     # ... and the cls attention on that route
+        route = (("packed",) + (("ppeg",) if ppeg else ()) + (("cls",) if cls else ())) if packed else ("batch_bags",) if batched else ()
         return (("fusion-transmil", int(cap), self.sides(lengths), bool(self.model.training), bool(agg.training), self.backward)
                 + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
-                + (("packed", "ppeg") if ppeg else ("packed",) if packed else ("batch_bags",) if batched else ()))
+                + route)
 
     def encode_notes(self, slot, ids):
         """Frozen text tower on this step's notes (token ids [B, P, ctx]) -> slot.text; outside the graph."""

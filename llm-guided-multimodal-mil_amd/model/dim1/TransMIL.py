@@ -162,8 +162,9 @@ def packed_index(sides: Sequence[int]) -> Tuple[List[int], List[int], List[int]]
 
 
 class PackedGeometry:
-    """packed_index on the device plus the block table and the PPEG table (ops.tm_ppeg_table: the unpadded sequence rows, per-bag
-    row offsets and sides): what TransMIL._run_bags_packed reads.  It depends on the tuple of sides alone; a replayed step builds
+    """packed_index on the device plus the block table, the PPEG table (ops.tm_ppeg_table: the unpadded sequence rows, per-bag
+    row offsets and sides) and the cls attention's table (ops.tm_cls_table: per-bag sides and output offsets): what
+    TransMIL._run_bags_packed reads.  It depends on the tuple of sides alone; a replayed step builds
     it once, with its geometry, outside the capture."""
 
     def __init__(self, sides: Sequence[int], device):
@@ -173,6 +174,7 @@ class PackedGeometry:
         self.unpad_idx = torch.tensor(unpad, dtype=torch.int32).to(device, non_blocking=True)
         self.table = ops.tm_packed_table(blocks, device)
         self.ppeg_table = ops.tm_ppeg_table(self.sides, device)
+        self.cls_table = ops.tm_cls_table(self.sides, device)
 
 
 class DeviceGeometry:
@@ -300,20 +302,29 @@ class TransLayer(nn.Module):
 
 
     def run_packed(self, x: torch.Tensor, pk: PackedGeometry, bits: Optional[torch.Tensor], deterministic: Optional[bool] = None,
-                   gemm_pieces: Optional[int] = None) -> torch.Tensor:
-        """run() (need_attn False) over all bags of a step as ONE packed sequence: x [sum seq, 512], the bags' sequences one
-        after another -> the same rows.  One LayerNorm, one pad gather into [sum n_pad, 512], one to_qkv, ops.nystrom_core_packed,
-        one gather back, one to_out, one dropout (bits [sum seq, 16], each bag's words in its row slice) / residual."""
+                   gemm_pieces: Optional[int] = None, need_attn=False, cls: Optional[dict] = None):
+        """run() (need_attn False or "cls") over all bags of a step as ONE packed sequence: x [sum seq, 512], the bags' sequences
+        one after another -> the same rows.  One LayerNorm, one pad gather into [sum n_pad, 512], one to_qkv,
+        ops.nystrom_core_packed, one gather back, one to_out, one dropout (bits [sum seq, 16], each bag's words in its row slice)
+        / residual.  need_attn="cls": -> (the rows, [one [8, s_b^2] cls attention per bag]), formed by the core in one launch set;
+        cls = the bag lengths, dict(n=[..]) or dict(len_dev=..)."""
         a = self.attn
         ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         xp = ops.tm_row_gather(ln, None, pk.pad_idx, deterministic)
         qkv = ops.linear_act(xp, a.to_qkv.weight, None)
-        o = ops.nystrom_core_packed(qkv, pk.table, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces)
+        attn = None
+        if need_attn is False:
+            o = ops.nystrom_core_packed(qkv, pk.table, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces)
+        else:
+            o, attn = ops.nystrom_core_packed(qkv, pk.table, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces,
+                                              need_attn=need_attn, cls=dict(sides=pk.cls_table, **cls))
         o = ops.tm_row_gather(o, None, pk.unpad_idx, deterministic)
         lin = a.to_out[0]
         if bits is None:
-            return ops.linear_act(o, lin.weight, lin.bias, residual=x)
-        return x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
+            y = ops.linear_act(o, lin.weight, lin.bias, residual=x)
+        else:
+            y = x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
+        return y if need_attn is False else (y, attn)
 
 
 class PPEG(nn.Module):
@@ -346,7 +357,10 @@ class TransMIL(nn.Module):
     packed (MIL_TM_PACKED, default off; it wins over batch_bags): the same call runs every layer over ONE packed sequence of
     all bags' rows (_run_bags_packed, ops.nystrom_core_packed) - every stage but PPEG one launch set whatever the bag count.
     packed_ppeg (MIL_TM_PACKED_PPEG, default off; it has an effect only where the packed route runs): PPEG too is one launch set
-    over the packed sequence rows (ops.tm_ppeg_packed), with no per-bag slice or concatenation between the layers."""
+    over the packed sequence rows (ops.tm_ppeg_packed), with no per-bag slice or concatenation between the layers.
+    packed_cls (MIL_TM_PACKED_CLS, default off; it too has an effect only where the packed route can run - several bags, packed
+    on): need_attn="cls" takes the packed route as well, the bags' per-patch cls attention of each layer formed in one launch set
+    (ops.tm_cls_attention_packed); off, such a call keeps the bag-by-bag launches.  need_attn=True always does."""
 
     def __init__(self, n_classes: int, L: int = 768, D: int = 512, K: int = 1):
         super().__init__()
@@ -371,6 +385,7 @@ class TransMIL(nn.Module):
         self.batch_bags: Optional[bool] = None       # a step's bags through one landmark-side chain (ops.tm_batch_bags); None = MIL_TM_BATCH_BAGS
         self.packed: Optional[bool] = None           # a step's bags as one packed sequence (ops.tm_packed); None = MIL_TM_PACKED; wins over batch_bags
         self.packed_ppeg: Optional[bool] = None      # on the packed route, PPEG as one launch set too (ops.tm_packed_ppeg); None = MIL_TM_PACKED_PPEG
+        self.packed_cls: Optional[bool] = None       # need_attn="cls" on the packed route too (ops.tm_packed_cls); None = MIL_TM_PACKED_CLS
 
     def _drop_state(self, device):
         if self._drop_seed is None:
@@ -475,7 +490,8 @@ class TransMIL(nn.Module):
         False the bags run stage by stage instead (_run_bags_batched): the same values per bag, the landmark-side chain of each
         layer - A2, the pseudo-inverse, U and their gradients, whose shapes do not depend on the bag - once for all bags.  The
         token-side passes, the dense layers and PPEG stay per bag.  With one bag, the switch off or need_attn set, the launches
-        are the bag-by-bag ones."""
+        are the bag-by-bag ones - but for need_attn "cls" with packed and packed_cls (ops.tm_packed_cls: the attribute, else
+        MIL_TM_PACKED_CLS; default off) both on, which takes the packed route with the attention formed there."""
         want_cls = not isinstance(need_attn, bool)
         dev = seqs.device
         train = self.training
@@ -483,6 +499,8 @@ class TransMIL(nn.Module):
             self._drop_state(dev)
         if need_attn is False and len(geo) > 1 and ops.tm_packed(self.packed):
             return self._run_bags_packed(seqs, geo, geom)
+        if want_cls and len(geo) > 1 and ops.tm_packed(self.packed) and ops.tm_packed_cls(self.packed_cls):
+            return self._run_bags_packed(seqs, geo, geom, "cls")
         if need_attn is False and len(geo) > 1 and ops.tm_batch_bags(self.batch_bags):
             return self._run_bags_batched(seqs, geo, geom)
         cls_rows, attn0, attn1, bits_used = [], [], [], []
@@ -545,14 +563,18 @@ class TransMIL(nn.Module):
         hc = torch.cat([x[:1] for x in xs], 0)
         return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), [None, None]
 
-    def _run_bags_packed(self, seqs: torch.Tensor, geo: List[dict], geom):
-        """_run_bags (need_attn False, several bags) over ONE packed sequence (packed, ops.tm_packed: the attribute, else
+    def _run_bags_packed(self, seqs: torch.Tensor, geo: List[dict], geom, need_attn=False):
+        """_run_bags (need_attn False or "cls", several bags) over ONE packed sequence (packed, ops.tm_packed: the attribute, else
         MIL_TM_PACKED; default off; it wins over batch_bags): per layer every stage but PPEG is one launch set over all bags'
         rows (TransLayer.run_packed).  PPEG runs per bag on row slices, its grid follows the side - or, with packed_ppeg
         (ops.tm_packed_ppeg: the attribute, else MIL_TM_PACKED_PPEG; default off), as one launch set on the rows as they stand
         (PPEG.run_packed: per bag the same values, the weight and bias gradients one sum over all bags).  The keep bits of
         (bag, layer) are those of the bag-by-bag route, drawn into that bag's rows of one [sum seq, 16] buffer per layer;
-        last_bits stays the per-bag list (views), and the pass counter advances once."""
+        last_bits stays the per-bag list (views), and the pass counter advances once.
+        need_attn="cls" (packed_cls): each layer's core also forms every bag's cls attention, one launch set for all bags
+        (TransLayer.run_packed); returned in the bag-by-bag route's form - [attn0, attn1], each a list with one tensor per bag,
+        [8, N_b] with host lengths (uploaded once here, outside any capture) and the static [8, s_b^2] with zeros from the device
+        length on with geom."""
         dev = seqs.device
         train = self.training
         pk = getattr(geom, "packed", None) if geom is not None else None
@@ -569,14 +591,24 @@ class TransMIL(nn.Module):
             keep = tuple(torch.empty((rows[-1], self.D // 32), device=dev, dtype=torch.int32) for _ in range(2))
             bits_used = [self._bits(b, g["seq"], dev, tuple(keep[j][rows[b]:rows[b + 1]] for j in range(2)))
                          for b, g in enumerate(geo)]
-        x = self.layer1.run_packed(seqs, pk, keep[0], self.deterministic, self.gemm_pieces)
+        cls = None
+        if need_attn is not False:
+            cls = dict(len_dev=geom.len_dev if geom is not None else
+                       torch.tensor([g["N"] for g in geo], dtype=torch.int32).to(dev, non_blocking=True))
+        x = self.layer1.run_packed(seqs, pk, keep[0], self.deterministic, self.gemm_pieces, need_attn, cls)
+        if cls is not None:
+            x, attn0 = x
         if ops.tm_packed_ppeg(self.packed_ppeg):
             x = self.pos_layer.run_packed(x, pk.ppeg_table, self.deterministic)
         else:
             x = torch.cat([self.pos_layer.run(x[rows[b]:rows[b + 1]], g["s"], self.deterministic) for b, g in enumerate(geo)], 0)
-        x = self.layer2.run_packed(x, pk, keep[1], self.deterministic, self.gemm_pieces)
+        x = self.layer2.run_packed(x, pk, keep[1], self.deterministic, self.gemm_pieces, need_attn, cls)
+        if cls is not None:
+            x, attn1 = x
+            if geom is None:
+                attn0, attn1 = ([a[:, :g["N"]] for a, g in zip(attn, geo)] for attn in (attn0, attn1))
         if train and self.force_bits is None:
             ops.counter_add(self._drop_ctr, 1)
         self.last_bits = bits_used if train else None
         hc = torch.cat([x[r:r + 1] for r in rows[:-1]], 0)
-        return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), [None, None]
+        return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), ([None, None] if cls is None else [attn0, attn1])

@@ -76,6 +76,16 @@ def tm_packed_ppeg(value=None) -> bool:
     return bool(value)
 
 
+def tm_packed_cls(value=None) -> bool:
+    """The switch of the per-patch cls attention on the packed route (nystrom_core_packed(need_attn="cls"),
+    tm_cls_attention_packed): the keyword (a module passes its `packed_cls` attribute here), else the environment variable
+    MIL_TM_PACKED_CLS (default 0), read per call.  It has an effect only where the packed route can run (tm_packed, several
+    bags) and only for need_attn="cls"; off, such a request keeps the bag-by-bag launches."""
+    if value is None:
+        value = os.environ.get("MIL_TM_PACKED_CLS", "0") not in ("", "0")
+    return bool(value)
+
+
 def _tm_pieces_route(M: int, N: int, K: int) -> bool:
     """Which products take mil_tm_bgemm_pieces when pieces == 3: those with K >= 256 - the pseudo-inverse chain and its
     backward (256^3), W, U, O, dU, dW, dq, dk, dv, dqL, dkL, and the whole-map products of need_attn True.  The K = 64
@@ -887,9 +897,85 @@ def tm_packed_table(blocks, device=None) -> TmPackedTable:
     return TmPackedTable(blocks, torch.tensor(tm_packed_table_host(blocks), dtype=torch.int32).to(device, non_blocking=True))
 
 
-def _tm_fwd_packed(qkv, tab, w, det=False, pieces=0):
+class TmClsTable:
+    """The geometry table of mil_tm_cls_attn_packed for bags of grid sides `sides` (host ints): `dev`, int32 [2 nb + 1] on the
+    device (tm_cls_table_host has the layout); `patches` = sum s^2, the patches of the output; `off` the host offsets.  Build it
+    with tm_cls_table, outside any capture; it depends on the bags' sides alone."""
+
+    def __init__(self, sides, dev):
+        self.sides = tuple(int(s) for s in sides)
+        self.nb, self.dev = len(self.sides), dev
+        self.off = [0]
+        for s in self.sides:
+            self.off.append(self.off[-1] + s * s)
+        self.patches = self.off[-1]
+
+
+def tm_cls_table_host(sides):
+    """The table's int32 values as a list: side [nb] | off [nb + 1], off[b] = the sum of s^2 over the bags in front of bag b -
+    where bag b's [8, s_b^2] starts in the output, in patches - and off[nb] = the patches of all bags.  A table of its own and
+    not the PPEG table's row_off | side: that one counts the cls rows in (row_off[b] = off[b] + b) and carries four more arrays
+    sized by its own launches, and the attention should not depend on whether PPEG runs packed."""
+    sides = [int(s) for s in sides]
+    if not 1 <= len(sides) <= TM_MAX_BATCH_BAGS or min(sides) < 1 or sum(s * s for s in sides) > 2 ** 31 - 1:
+        raise ValueError(f"tm_cls_table: 1 .. {TM_MAX_BATCH_BAGS} bags of side >= 1, at most 2^31 - 1 patches, got {sides}")
+    off = [0]
+    for s in sides:
+        off.append(off[-1] + s * s)
+    return sides + off
+
+
+def tm_cls_table(sides, device=None) -> TmClsTable:
+    """sides: per bag the grid side -> the TmClsTable on `device` (default: the current GPU).  One small host-to-device copy, so
+    a replayed step builds it once per graph key, not per step."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    return TmClsTable(sides, torch.tensor(tm_cls_table_host(sides), dtype=torch.int32).to(device, non_blocking=True))
+
+
+def tm_cls_attention_packed(qkv, table, qL, kL, Z, lse3, sides, n=None, len_dev=None):
+    """tm_cls_attention_fused for all bags of a packed step in ONE launch set (mil_tm_cls_attn_packed, csrc/cls_attn_fused.hip):
+    qkv [256 total_blocks, 1536] the packed rows, table the TmPackedTable (tm_packed_table), qL (scaled), kL [nb, 8, 256, 64],
+    Z [nb, 8, 256, 256], lse3 [nb, 8, 256] as _tm_fwd_packed holds them, sides = the bags' grid sides or a TmClsTable
+    (tm_cls_table; from sides it is built here - a host-to-device copy, not for a capture).  The lengths: `n`, a host list - each
+    must lie in its side's bucket ((s - 1)^2, s^2], else MilHipError as from the single-bag entry; they are then uploaded, a copy
+    and so not for a capture - or `len_dev`, int32 [nb] on the device, each read there and clamped into its bucket.  Exactly one
+    of the two.  Returns a list of per-bag [8, s_b^2] fp32 views of ONE buffer, bag b at float 8 off_b, zeros from N_b on, each
+    bit-equal to tm_cls_attention_fused on that bag's rows and slices.  One torch.empty of workspace (nb x 2048 + 2048 x
+    total_blocks floats); three launches whatever the bag count, no atomics, no host read."""
+    if (n is None) == (len_dev is None):
+        raise ValueError("tm_cls_attention_packed: give the bag lengths either as n (host list) or as len_dev")
+    qkv, qL, kL, Z, lse3 = (_f32c(t, nm) for t, nm in ((qkv, "qkv"), (qL, "qL"), (kL, "kL"), (Z, "Z"), (lse3, "lse3")))
+    nb, H, M, DH = table.nb, TM_H, TM_M, TM_DH
+    if (qkv.dim() != 2 or tuple(qkv.shape) != (table.rows, 3 * TM_D) or tuple(qL.shape) != (nb, H, M, DH)
+            or tuple(kL.shape) != (nb, H, M, DH) or tuple(Z.shape) != (nb, H, M, M) or lse3.numel() != nb * H * M):
+        raise _lib.MilHipError(f"tm_cls_attention_packed: qkv {tuple(qkv.shape)} / qL {tuple(qL.shape)} / kL {tuple(kL.shape)} / "
+                               f"Z {tuple(Z.shape)} / lse3 {tuple(lse3.shape)} outside the built shape for blocks {table.blocks}")
+    if any(t.device != qkv.device for t in (qL, kL, Z, lse3, table.dev)):
+        raise _lib.MilHipError("tm_cls_attention_packed: qkv, qL, kL, Z, lse3 and the table must be on one device")
+    ctab = sides if isinstance(sides, TmClsTable) else tm_cls_table(sides, qkv.device)
+    if ctab.dev.device != qkv.device or ctab.nb != nb or any(k != -(-(s * s + 1) // M) for k, s in zip(table.blocks, ctab.sides)):
+        raise _lib.MilHipError(f"tm_cls_attention_packed: sides {ctab.sides} do not go with blocks {table.blocks} (256 x blocks = "
+                               "ceil((s^2 + 1) / 256) x 256), or their table is on another device")
+    if n is not None:
+        n = [int(v) for v in n]
+        if len(n) != nb or any(not (s - 1) * (s - 1) < v <= s * s for v, s in zip(n, ctab.sides)):
+            raise _lib.MilHipError(f"tm_cls_attention_packed: lengths {n} outside the buckets of sides {ctab.sides}")
+        len_dev = torch.tensor(n, dtype=torch.int32).to(qkv.device, non_blocking=True)
+    elif len_dev.dtype != torch.int32 or len_dev.device != qkv.device or len_dev.numel() < nb or not len_dev.is_contiguous():
+        raise _lib.MilHipError(f"tm_cls_attention_packed: len_dev must be contiguous int32 on qkv's device and hold {nb} entries")
+    out = torch.empty(H * ctab.patches, device=qkv.device, dtype=torch.float32)
+    ws = _ws(_lib.lib().mil_tm_cls_attn_packed_ws_floats(table.total_blocks, nb), qkv)
+    _lib.checked().mil_tm_cls_attn_packed(_p(qkv), _p(qL), _p(kL), _p(Z), _p(lse3), _p(ctab.dev), ctab.patches, _p(len_dev), _p(ws),
+                                          _p(out), *table.args(), _stream())
+    return [out[H * o:H * (o + s * s)].view(H, s * s) for o, s in zip(ctab.off, ctab.sides)]
+
+
+def _tm_fwd_packed(qkv, tab, w, det=False, pieces=0, cls=None):
     """_tm_fwd_bags with both passes fused, on the packed rows: the phases in the same order, each token-side one a single
-    packed launch set; the landmark-side chain (A2, its softmax, the pseudo-inverse, U) exactly as _tm_fwd_bags runs it."""
+    packed launch set; the landmark-side chain (A2, its softmax, the pseudo-inverse, U) exactly as _tm_fwd_bags runs it.
+    cls: None, or the keywords of tm_cls_attention_packed (sides and n or len_dev) - the bags' cls attention is then formed from
+    qL, kL, Z and lse3 behind U, where _tm_fwd forms it, and returned as the third value (else None)."""
     bg = _tm_bg(det, pieces)
     nb, tb, R = tab.nb, tab.total_blocks, tab.rows
     f32 = dict(device=qkv.device, dtype=torch.float32)
@@ -903,12 +989,13 @@ def _tm_fwd_packed(qkv, tab, w, det=False, pieces=0):
     A2 = tm_softmax_rows(_tm_fwd_a2(qL, kL, torch.empty((nb, H, M, M), **f32), bg, nb * H))
     Z, pinv = _tm_pinv_fwd(A2, det, pieces, nb=nb)
     U = _tm_fwd_u(Z, W, torch.empty((nb, H, M, DH), **f32), bg, nb * H)
+    attn = tm_cls_attention_packed(qkv, tab, qL, kL, Z, lse3, **cls) if cls is not None else None
     O = torch.empty((R, TM_D), **f32)
     lse1 = torch.empty((H, R), **f32)
     ck.mil_tm_tok_attn_fwd_packed(_p(qkv), _p(kL), _p(U), _p(O), _p(lse1), None, *tab.args(), _stream())
     ck.mil_tm_resconv_packed(_p(qkv), _p(w), _p(O), *tab.args(), _stream())
     saved = SimpleNamespace(qL=qL, kL=kL, A2=A2, W=W, U=U, Z=Z, pinv=pinv, lse1=lse1, lse3=lse3, det=det, pieces=pieces)
-    return O, saved
+    return O, saved, attn
 
 
 def _tm_bwd_packed(dO, qkv, tab, w, saved):
@@ -946,29 +1033,32 @@ def _tm_bwd_packed(dO, qkv, tab, w, saved):
 
 class _NystromCorePacked(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, w, tab, det, pieces):
+    def forward(ctx, qkv, w, tab, det, pieces, cls=None):
         if (qkv.dim() != 2 or qkv.shape[1] != 3 * TM_D or qkv.shape[0] != tab.rows or w.numel() != TM_H * TM_CONV
                 or qkv.device != w.device or tab.dev.device != qkv.device):
             raise _lib.MilHipError(f"nystrom_core_packed: qkv {tuple(qkv.shape)} / res_conv {tuple(w.shape)} outside the built shape "
                                    f"for blocks {tab.blocks}, or on two devices")
         qkv = _f32c(qkv, "qkv")
         w = _f32c(w, "res_conv.weight")
-        O, saved = _tm_fwd_packed(qkv, tab, w, det, pieces)
+        O, saved, attn = _tm_fwd_packed(qkv, tab, w, det, pieces, cls)
         ctx.saved, ctx.tab = saved, tab
         ctx.save_for_backward(qkv, w)
         ctx.w_shape = w.shape
-        return O
+        if attn is None:
+            return O
+        ctx.mark_non_differentiable(*attn)                  # the bags' views of one buffer, formed from the saved operands
+        return (O, *attn)
 
     @staticmethod
-    def backward(ctx, dO):
+    def backward(ctx, dO, *_dattn):
         qkv, w = ctx.saved_tensors
         dqkv, dw = _tm_bwd_packed(_f32c(dO, "dO"), qkv, ctx.tab, w, ctx.saved)
         ctx.saved = None
-        return dqkv, dw.reshape(ctx.w_shape), None, None, None
+        return dqkv, dw.reshape(ctx.w_shape), None, None, None, None
 
 
-def nystrom_core_packed(qkv, blocks_or_table, w, *, deterministic=None, pieces=None):
-    """nystrom_core (need_attn False) for all bags of a step over ONE packed sequence: qkv [256 sum(blocks), 1536] = the bags'
+def nystrom_core_packed(qkv, blocks_or_table, w, *, deterministic=None, pieces=None, need_attn=False, cls=None):
+    """nystrom_core (need_attn False or "cls") for all bags of a step over ONE packed sequence: qkv [256 sum(blocks), 1536] = the bags'
     to_qkv rows of their front-zero-padded LayerNorm output one after another, bag b 256 blocks[b] rows; blocks_or_table = the
     per-bag block counts (the table is then built here: a host-to-device copy, not for a capture) or a TmPackedTable
     (tm_packed_table); w = res_conv.weight -> out [256 sum(blocks), 512], bag b's rows where its input rows are.
@@ -979,9 +1069,24 @@ def nystrom_core_packed(qkv, blocks_or_table, w, *, deterministic=None, pieces=N
     one sum over all bags' 256-row chunks - atomic, or with deterministic in ascending packed order.
     deterministic, pieces: as in nystrom_core (None reads the environment); they apply to the chain unchanged.  No host read;
     every workspace is a torch.empty, so with a TmPackedTable the call can be captured into a graph.  The switch that sends a
-    module's step here is tm_packed (MIL_TM_PACKED, default 0)."""
+    module's step here is tm_packed (MIL_TM_PACKED, default 0).
+    need_attn: False -> out alone, as above.  "cls" -> (out, [attn_b]): the cls token's per-patch attention of every bag, [8, s_b^2]
+    each with zeros from the bag's length on, all views of one buffer (tm_cls_attention_packed: one launch set for all bags);
+    cls = dict(sides=.., n=[..]) with host lengths (validated and uploaded: not for a capture) or dict(sides=.., len_dev=..)
+    with the lengths on the device, sides the grid sides or a TmClsTable.  The attention is formed in the forward from qL, kL, Z
+    and lse3, behind U; it carries no gradient and the backward is the one of need_attn False, so out and dqkv keep their bits.
+    True raises ValueError: the whole [8, n_pad, n_pad] map has no packed form.  The switch that sends a module's "cls" request
+    here is tm_packed_cls (MIL_TM_PACKED_CLS, default 0)."""
+    if not (need_attn is False or (isinstance(need_attn, str) and need_attn == "cls")):
+        raise ValueError(f"nystrom_core_packed: need_attn must be False or 'cls' (the whole map has no packed form), got {need_attn!r}")
     tab = blocks_or_table if isinstance(blocks_or_table, TmPackedTable) else tm_packed_table(blocks_or_table, qkv.device)
-    return _NystromCorePacked.apply(qkv, w, tab, tm_deterministic(deterministic), tm_pieces(pieces))
+    if need_attn is False:
+        return _NystromCorePacked.apply(qkv, w, tab, tm_deterministic(deterministic), tm_pieces(pieces))
+    if not isinstance(cls, dict) or "sides" not in cls or (cls.get("n") is None) == (cls.get("len_dev") is None):
+        raise ValueError("nystrom_core_packed: need_attn='cls' needs cls=dict(sides=.., n=[..]) or dict(sides=.., len_dev=..)")
+    cls = dict(sides=cls["sides"], n=cls.get("n"), len_dev=cls.get("len_dev"))
+    O, *attn = _NystromCorePacked.apply(qkv, w, tab, tm_deterministic(deterministic), tm_pieces(pieces), cls)
+    return O, attn
 
 
 # ---- PPEG of a step's bags in one launch set (csrc/tm_ppeg_packed.h): the unpadded sequences, one bag after another

@@ -61,6 +61,10 @@ def build_model(args):
         for m in model.modules():           # on the packed route, PPEG as one launch set too
             if type(m).__name__ == "TransMIL":
                 m.packed_ppeg = True
+    if getattr(args, "tm_packed_cls", 0):
+        for m in model.modules():           # on the packed route, the per-patch cls attention too (need_attn="cls")
+            if type(m).__name__ == "TransMIL":
+                m.packed_cls = True
     if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
             and getattr(args, "transmil_graph", 0)):
         model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward

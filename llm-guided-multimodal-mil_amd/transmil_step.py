@@ -125,12 +125,15 @@ class RaggedTransMILStepper:
         # outputs: what TransMIL._run_bags takes that route for)
         batched = ops.tm_batch_bags(m.extractor_pathology.batch_bags) and len(sides) > 1 and not attn
         # ... nor one of either of those for a model that asks for the packed sequence, which wins over the batched chain
-        packed = ops.tm_packed(m.extractor_pathology.packed) and len(sides) > 1 and not attn
+        # (with the attention outputs only for a model that asks for the packed cls attention too: TransMIL.packed_cls)
+        cls = attn and ops.tm_packed_cls(getattr(m.extractor_pathology, "packed_cls", None))
+        packed = ops.tm_packed(m.extractor_pathology.packed) and len(sides) > 1 and (not attn or cls)
         # ... nor one with PPEG per bag for a model that asks for the packed PPEG on that route
         ppeg = packed and ops.tm_packed_ppeg(getattr(m.extractor_pathology, "packed_ppeg", None))
+        route = (("packed",) + (("ppeg",) if ppeg else ()) + (("cls",) if cls else ())) if packed else ("batch_bags",) if batched else ()
         return (("transmil-sides", tuple(sides), bool(m.training), self.backward) + (("patch_attn",) if attn else ())
                 + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
-                + (("packed", "ppeg") if ppeg else ("packed",) if packed else ("batch_bags",) if batched else ()))
+                + route)
 
     def step(self, slot, lengths: Sequence[int], on_device: bool = False):
         """One step on the bags packed at the front of slot.x.  on_device: the lengths already sit in slot.len_dev (the

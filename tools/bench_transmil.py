@@ -32,7 +32,10 @@ model, same bags; median (min - max) of --reps regions each and the peak allocat
 first and third columns are the yardstick.  B = 1 (the default) leaves every other row as it is.  --packed adds the column of
 TransMIL.packed (ops.nystrom_core_packed: every token-side stage one launch set over all bags' rows) and, behind it, the column
 of TransMIL.packed + TransMIL.packed_ppeg (ops.tm_ppeg_packed: PPEG too one launch set), read against the packed column
-(`*_packed_ppeg_over_packed`); --mix makes the bags ragged."""
+(`*_packed_ppeg_over_packed`); --mix makes the bags ragged.
+--packed-cls: the eval forward WITH the per-patch cls attention (patch_attn; need_attn="cls") for 2, 4 and 8 ragged bags of up to
+N patches, eager and replayed - the best route without the packed cls attention (bag by bag with MIL_TM_FUSED_CLS=1: no A1 / A3
+map) next to packed + packed_cls and packed + packed_ppeg + packed_cls, the routes alternating region by region."""
 import argparse, json, os, sys
 from types import SimpleNamespace
 import torch
@@ -383,6 +386,64 @@ def bags_rows(a, dev, args):
         torch.cuda.empty_cache()
 
 
+def cls_packed_rows(a, dev, args):
+    """Per bag count one JSON line: medians (and min / max) over a.reps regions of a.calls eval forwards each, in ms per forward.
+    The routes take turns inside every repetition, so a drift of the machine lands on all of them alike."""
+    from mil_amd.transmil_step import RaggedTransMILStepper
+    routes = (("bag_fused_cls", dict(packed=False, packed_ppeg=False, packed_cls=False)),
+              ("packed_cls", dict(packed=True, packed_ppeg=False, packed_cls=True)),
+              ("packed_ppeg_cls", dict(packed=True, packed_ppeg=True, packed_cls=True)))
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    for N in a.N:
+        for B in (2, 4, 8):
+            torch.manual_seed(1234)
+            model = get_model(args).to(dev).eval()
+            model.patch_attn = True
+            ex = model.extractor_pathology
+            ex.fused_cls = True                         # the bag-by-bag route at its best; the packed route is fused anyway
+            st = RaggedTransMILStepper(model, None, B=B, backward=False)
+            lengths = [max(1, N * (4 - b % 4) // 4) for b in range(B)]                  # N, 3N/4, N/2, N/4, N, ..
+            x = torch.cat([syn.make_bags(N + b, 1, n, 768)[0] for b, n in enumerate(lengths)], 0).to(dev)
+            slot = st.slot(lengths)
+            slot.x[:sum(lengths)].copy_(x)
+
+            def eager():
+                with torch.no_grad():
+                    for _ in range(a.calls):
+                        ex(x, lengths, need_attn="cls")
+
+            def replay():
+                for _ in range(a.calls):
+                    st.step(slot, lengths)
+
+            def route(kw):
+                for k, v in kw.items():
+                    setattr(ex, k, v)
+
+            for _, kw in routes:                        # every route: eager visit, capture, first replays; and a warm eager pass
+                route(kw)
+                for _ in range(3):
+                    st.step(slot, lengths)
+                eager()
+            ts = {(name, tag): [] for name in ("eager", "replay") for tag, _ in routes}
+            for _ in range(a.reps):
+                for name, fn in (("eager", eager), ("replay", replay)):
+                    for tag, kw in routes:
+                        route(kw)
+                        ts[name, tag] += [t / a.calls for t in region_times(fn, 1, 0)]
+            res = dict(N=N, bags=B, lengths=lengths, regions=a.reps, calls_per_region=a.calls)
+            for (name, tag), v in ts.items():
+                res.update({f"{name}_{tag}_ms": round(med(v), 3), f"{name}_{tag}_min_ms": round(min(v), 3),
+                            f"{name}_{tag}_max_ms": round(max(v), 3)})
+            for name in ("eager", "replay"):
+                for tag, _ in routes[1:]:
+                    res[f"{name}_{tag}_over_bag_fused_cls"] = round(res[f"{name}_{tag}_ms"] / res[f"{name}_bag_fused_cls_ms"], 4)
+            assert st.n_graphs == len(routes), st.n_graphs                  # one graph per route: the switches are part of the key
+            print(json.dumps(res), flush=True)
+            del st, slot, model, x
+            torch.cuda.empty_cache()
+
+
 def region_times(fn, reps, warm):
     for _ in range(warm):
         fn()
@@ -423,10 +484,17 @@ def main():
                     "bags as one packed sequence) and the one with TransMIL.packed_ppeg on top (PPEG as one launch set), between `on` and `off_again`.  It always runs both attention passes fused: "
                     "set MIL_TM_FUSED_A1=1 MIL_TM_FUSED_A3=1 so that the other two columns do too")
     ap.add_argument("--mix", action="store_true", help="--bags B: a ragged mix, bag b of N (4 - b mod 4) / 4 patches")
+    ap.add_argument("--packed-cls", dest="packed_cls", action="store_true", help="the eval forward with patch_attn for 2 / 4 / 8 "
+                    "ragged bags of up to N patches (give --N 2000): bag by bag with MIL_TM_FUSED_CLS next to the packed route with "
+                    "TransMIL.packed_cls, eager and replayed, alternating regions of --calls forwards")
+    ap.add_argument("--calls", type=int, default=10, help="--packed-cls: forwards per timed region")
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     dev = torch.device("cuda")
     args = SimpleNamespace(modality=["pathology"], model_pathology="TransMIL", num_classes=2, patch_dim=768, variant="image_only")
+    if a.packed_cls:
+        cls_packed_rows(a, dev, args)
+        return
     if a.bags > 1:
         bags_rows(a, dev, args)
         return
