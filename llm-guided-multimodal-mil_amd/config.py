@@ -137,30 +137,30 @@ def create_arg_parser(argv=None):
                    help="train_ddp.py and test_ddp.py: 1 = a TransMIL step of several bags (--batch_size > 1, several bags per "
                         "slot, the fusion model's TransMIL aggregator) runs the landmark-side chain of its bags - A2, the "
                         "pseudo-inverse, U and their gradients - as one set of launches at batch 8 x bags instead of once per "
-                        "bag; each bag keeps its own pseudo-inverse scale.  Set on every TransMIL module of the model; a step "
-                        "of one bag and a request for attention outputs keep the bag-by-bag route.  Models without a TransMIL "
+                        "bag; each bag keeps its own pseudo-inverse scale.  Which steps take this route: ops.tm_route (DESIGN 4.6, "
+                        "Route of a step).  Set on every TransMIL module of the model.  Models without a TransMIL "
                         "module accept the flag and ignore it.  0: the environment variable MIL_TM_BATCH_BAGS decides (default 0)")
     p.add_argument("--tm_packed", type=int, default=0, choices=[0, 1],
                    help="train_ddp.py and test_ddp.py: 1 = a TransMIL step of several bags runs every layer over ONE packed "
                         "sequence of all bags' rows - LayerNorm, the pad gather, to_qkv, the landmarks, both fused attention "
                         "passes, the residual conv, to_out, the dropout and the residual one launch set each, whatever the "
-                        "number of bags; PPEG stays per bag (--tm_packed_ppeg).  It wins over --tm_batch_bags.  Set on every TransMIL module of "
-                        "the model; a step of one bag and a request for attention outputs keep the bag-by-bag route.  Models "
+                        "number of bags; PPEG stays per bag (--tm_packed_ppeg).  Which steps take this route: ops.tm_route (DESIGN 4.6, Route of a "
+                        "step).  Set on every TransMIL module of the model.  Models "
                         "without a TransMIL module accept the flag and ignore it.  0: the environment variable MIL_TM_PACKED "
                         "decides (default 0)")
     p.add_argument("--tm_packed_ppeg", type=int, default=0, choices=[0, 1],
                    help="train_ddp.py and test_ddp.py: 1 = where --tm_packed 1 runs a TransMIL step over one packed sequence, "
                         "PPEG too is one launch set over all bags' sequence rows (a table of per-bag row offsets and sides), "
                         "with no per-bag slice or concatenation between the two layers; per bag the same values, the PPEG "
-                        "weight and bias gradients one sum over all bags.  Without the packed route it changes nothing.  Set "
+                        "weight and bias gradients one sum over all bags.  When it applies: ops.tm_route (DESIGN 4.6).  Set "
                         "on every TransMIL module of the model, as --tm_packed is.  0: the environment variable "
                         "MIL_TM_PACKED_PPEG decides (default 0)")
     p.add_argument("--tm_packed_cls", type=int, default=0, choices=[0, 1],
                    help="train_ddp.py and test_ddp.py: 1 = with --tm_packed 1, a TransMIL step of several bags that asks for the "
                         "per-patch cls attention (--save_patch_attn, the fusion model's note attention over a TransMIL "
                         "aggregator) stays on the packed route: each layer's cls attention of all bags is one launch set, "
-                        "bit-equal per bag to the fused single-bag kernels.  Without the packed route, and for a step of one "
-                        "bag, it changes nothing.  Set on every TransMIL module of the model, as --tm_packed is.  0: the "
+                        "bit-equal per bag to the fused single-bag kernels.  When it applies: ops.tm_route (DESIGN 4.6).  "
+                        "Set on every TransMIL module of the model, as --tm_packed is.  0: the "
                         "environment variable MIL_TM_PACKED_CLS decides (default 0)")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:

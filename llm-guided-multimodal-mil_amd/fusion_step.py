@@ -246,15 +246,12 @@ class RaggedFusionTransMILStepper:
     def key(self, cap: int, lengths: Sequence[int]) -> tuple:
         agg = self.model.aggregator
         from . import ops
-        det, pieces = ops.tm_deterministic(agg.deterministic), ops.tm_pieces(agg.gemm_pieces)
-        batched = ops.tm_batch_bags(agg.batch_bags) and len(lengths) > 1      # the aggregator's batched landmark-side chain
-        packed = ops.tm_packed(agg.packed) and len(lengths) > 1               # its packed sequence, which wins over that
-        ppeg = packed and ops.tm_packed_ppeg(getattr(agg, "packed_ppeg", None))  # ... with PPEG as one launch set too
-        cls = packed and ops.tm_packed_cls(getattr(agg, "packed_cls", None))     # ... and the cls attention on that route
-        route = (("packed",) + (("ppeg",) if ppeg else ()) + (("cls",) if cls else ())) if packed else ("batch_bags",) if batched else ()
+        route = ops.tm_route(agg, len(lengths), False)      # the route the aggregator's flat_bucket resolves for this step
+        # this key has carried "cls" wherever it carries "packed" and packed_cls is on, although the graph step never asks for
+        # attention; that is not what the route says, so it is added here and existing keys stay what they were
+        cls = ("cls",) if route.bags == "packed" and ops.tm_packed_cls(agg.packed_cls) else ()
         return (("fusion-transmil", int(cap), self.sides(lengths), bool(self.model.training), bool(agg.training), self.backward)
-                + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
-                + route)
+                + route.key() + cls)
 
     def encode_notes(self, slot, ids):
         """Frozen text tower on this step's notes (token ids [B, P, ctx]) -> slot.text; outside the graph."""

@@ -161,10 +161,15 @@ def packed_index(sides: Sequence[int]) -> Tuple[List[int], List[int], List[int]]
     return pad, unpad, blocks
 
 
+def _check_need_attn(need_attn):
+    if not (isinstance(need_attn, bool) or (isinstance(need_attn, str) and need_attn == "cls")):
+        raise ValueError(f"TransMIL: need_attn must be False, True or 'cls', got {need_attn!r}")
+
+
 class PackedGeometry:
     """packed_index on the device plus the block table, the PPEG table (ops.tm_ppeg_table: the unpadded sequence rows, per-bag
     row offsets and sides) and the cls attention's table (ops.tm_cls_table: per-bag sides and output offsets): what
-    TransMIL._run_bags_packed reads.  It depends on the tuple of sides alone; a replayed step builds
+    TransMIL._run_bags reads on the packed route.  It depends on the tuple of sides alone; a replayed step builds
     it once, with its geometry, outside the capture."""
 
     def __init__(self, sides: Sequence[int], device):
@@ -175,6 +180,16 @@ class PackedGeometry:
         self.table = ops.tm_packed_table(blocks, device)
         self.ppeg_table = ops.tm_ppeg_table(self.sides, device)
         self.cls_table = ops.tm_cls_table(self.sides, device)
+
+
+def _static_geometry(sides: Sequence[int], device, pad_cache: Optional[dict]):
+    """What a captured step's geometry holds that depends on the sides alone: (the pad index per side - filled into pad_cache,
+    which a stepper shares among its slots -, the packed route's static tables, None for a single bag)."""
+    pad_idx = pad_cache if pad_cache is not None else {}
+    for s in sides:
+        if s not in pad_idx:
+            pad_idx[s] = torch.tensor(pad_index(side_geometry(s)), dtype=torch.int32).to(device)
+    return pad_idx, PackedGeometry(sides, device) if len(sides) > 1 else None
 
 
 class DeviceGeometry:
@@ -190,11 +205,7 @@ class DeviceGeometry:
         self.idx = torch.zeros(sum(1 + s * s for s in self.sides), **i32)
         self.rows_dev = torch.zeros(1, **i32)
         self.flag = flag if flag is not None else torch.zeros(1, **i32)
-        self.pad_idx = pad_cache if pad_cache is not None else {}
-        for s in self.sides:
-            if s not in self.pad_idx:
-                self.pad_idx[s] = torch.tensor(pad_index(side_geometry(s)), dtype=torch.int32).to(device)
-        self.packed = PackedGeometry(self.sides, device) if len(self.sides) > 1 else None     # the packed route's static tables
+        self.pad_idx, self.packed = _static_geometry(self.sides, device, pad_cache)
 
     def update(self, x_tail: Optional[torch.Tensor] = None):
         """Index and row count from the lengths now in len_dev; x_tail: the slot's input buffer, its rows behind the bags zeroed."""
@@ -225,11 +236,7 @@ class BucketGeometry:
             cls_idx += [-2] + list(range(row + 1, row + 1 + s * s))
             row += 1 + s * s
         self.cls_idx = torch.tensor(cls_idx, dtype=torch.int32).to(device)
-        self.pad_idx = pad_cache if pad_cache is not None else {}
-        for s in self.sides:
-            if s not in self.pad_idx:
-                self.pad_idx[s] = torch.tensor(pad_index(side_geometry(s)), dtype=torch.int32).to(device)
-        self.packed = PackedGeometry(self.sides, device) if len(self.sides) > 1 else None     # the packed route's static tables
+        self.pad_idx, self.packed = _static_geometry(self.sides, device, pad_cache)
 
     def update(self, patch_len_dev: torch.Tensor):
         """Index and sequence lengths from the patch counts now on the device (the bucket's len_dev)."""
@@ -250,81 +257,58 @@ class NystromAttention(nn.Module):
 
 
 class TransLayer(nn.Module):
+    """x + to_out(Nystrom(LN(x))).  One front and one back around the core; `route` (ops.TmRoute) names the core's entries."""
+
     def __init__(self, norm_layer=nn.LayerNorm, dim: int = 512):
         super().__init__()
         self.norm = norm_layer(dim)
         self.attn = NystromAttention(dim=dim)
 
-    def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn, cls: Optional[dict] = None,
-            fused_cls: Optional[bool] = None, deterministic: Optional[bool] = None, gemm_pieces: Optional[int] = None):
-        """x [seq, 512] of one bag -> (x + to_out(Nystrom(LN(x)))[last seq rows], attn map / cls attention [8, s^2] / None).
-        cls: the bag length for need_attn="cls", dict(n=N) or dict(len_dev=.., bag=b); fused_cls: ops.nystrom_core's switch of
-        that output (None = the environment); deterministic: the fixed-order sums of ops.nystrom_core and ops.tm_row_gather
-        (None = MIL_TM_DETERMINISTIC); gemm_pieces: ops.nystrom_core's `pieces` (None = MIL_TM_PIECES)."""
-        a = self.attn
+    def front(self, x: torch.Tensor, pad_idx: torch.Tensor, route) -> torch.Tensor:
+        """LayerNorm, the zero rows in front (one gather through pad_idx) and to_qkv: x [rows, 512] -> [padded rows, 1536]."""
         ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
-        xp = ops.tm_row_gather(ln, None, pad_idx, deterministic)                    # zero rows in front: [n_pad, 512]
-        qkv = ops.linear_act(xp, a.to_qkv.weight, None)
-        if cls is not None:
-            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, pad=g["pad"], s=g["s"], fused_cls=fused_cls,
-                                       deterministic=deterministic, pieces=gemm_pieces, **cls)
-        else:
-            o, attn = ops.nystrom_core(qkv, a.res_conv.weight, need_attn, deterministic=deterministic, pieces=gemm_pieces)
-        o = o[g["pad"]:]
-        lin = a.to_out[0]
+        return ops.linear_act(ops.tm_row_gather(ln, None, pad_idx, route.det), self.attn.to_qkv.weight, None)
+
+    def back(self, x: torch.Tensor, o: torch.Tensor, bits: Optional[torch.Tensor]) -> torch.Tensor:
+        """to_out on the core's rows o (those of x) and the residual: fused into the product, or behind the dropout of `bits`."""
+        lin = self.attn.to_out[0]
         if bits is None:
-            y = ops.linear_act(o, lin.weight, lin.bias, residual=x)
-        else:
-            y = x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
-        return y, attn
+            return ops.linear_act(o, lin.weight, lin.bias, residual=x)
+        return x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
 
-    def run_bags(self, xs: Sequence[torch.Tensor], geo: Sequence[dict], pad_idxs: Sequence[torch.Tensor], bits: Sequence[Optional[torch.Tensor]],
-                 deterministic: Optional[bool] = None, gemm_pieces: Optional[int] = None) -> List[torch.Tensor]:
-        """run() (need_attn False) over all bags of a step, stage by stage: per bag LayerNorm, pad gather and to_qkv; the Nystrom
-        cores of all bags as one ops.nystrom_core_bags, whose landmark-side chain is one set of launches at batch 8 x bags; per bag
-        the slice, to_out and the dropout / residual.  Bag b's values are those of run() on bag b."""
-        a = self.attn
-        qkvs = []
-        for x, pad_idx in zip(xs, pad_idxs):
-            ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
-            xp = ops.tm_row_gather(ln, None, pad_idx, deterministic)
-            qkvs.append(ops.linear_act(xp, a.to_qkv.weight, None))
-        outs = ops.nystrom_core_bags(qkvs, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces)
-        lin = a.to_out[0]
-        ys = []
-        for x, g, o, keep in zip(xs, geo, outs, bits):
-            o = o[g["pad"]:]
-            if keep is None:
-                ys.append(ops.linear_act(o, lin.weight, lin.bias, residual=x))
-            else:
-                ys.append(x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), keep, 1.0 / (1.0 - TM_DROP_P)))
-        return ys
+    def run(self, x: torch.Tensor, g: dict, pad_idx: torch.Tensor, bits: Optional[torch.Tensor], need_attn, route,
+            cls: Optional[dict] = None):
+        """x [seq, 512] of one bag -> (the layer's rows, attn map / cls attention [8, s^2] / None).
+        cls: the bag length for need_attn="cls", dict(n=N) or dict(len_dev=.., bag=b)."""
+        geo = dict(pad=g["pad"], s=g["s"], **cls) if cls is not None else {}
+        o, attn = ops.nystrom_core(self.front(x, pad_idx, route), self.attn.res_conv.weight, need_attn, fused_a3=route.fused_a3,
+                                   fused_a1=route.fused_a1, fused_cls=route.cls == "fused", deterministic=route.det,
+                                   pieces=route.pieces, **geo)
+        return self.back(x, o[g["pad"]:], bits), attn
 
+    def run_bags(self, xs: Sequence[torch.Tensor], geo: Sequence[dict], pad_idxs: Sequence[torch.Tensor],
+                 bits: Sequence[Optional[torch.Tensor]], route) -> List[torch.Tensor]:
+        """run() (need_attn False) over all bags of a step, stage by stage: the front per bag; the Nystrom cores of all bags as
+        one ops.nystrom_core_bags, whose landmark-side chain is one set of launches at batch 8 x bags; the back per bag.  Bag
+        b's values are those of run() on bag b."""
+        qkvs = [self.front(x, pad_idx, route) for x, pad_idx in zip(xs, pad_idxs)]
+        outs = ops.nystrom_core_bags(qkvs, self.attn.res_conv.weight, fused_a3=route.fused_a3, fused_a1=route.fused_a1,
+                                     deterministic=route.det, pieces=route.pieces)
+        return [self.back(x, o[g["pad"]:], keep) for x, g, o, keep in zip(xs, geo, outs, bits)]
 
-    def run_packed(self, x: torch.Tensor, pk: PackedGeometry, bits: Optional[torch.Tensor], deterministic: Optional[bool] = None,
-                   gemm_pieces: Optional[int] = None, need_attn=False, cls: Optional[dict] = None):
-        """run() (need_attn False or "cls") over all bags of a step as ONE packed sequence: x [sum seq, 512], the bags' sequences
-        one after another -> the same rows.  One LayerNorm, one pad gather into [sum n_pad, 512], one to_qkv,
-        ops.nystrom_core_packed, one gather back, one to_out, one dropout (bits [sum seq, 16], each bag's words in its row slice)
-        / residual.  need_attn="cls": -> (the rows, [one [8, s_b^2] cls attention per bag]), formed by the core in one launch set;
-        cls = the bag lengths, dict(n=[..]) or dict(len_dev=..)."""
-        a = self.attn
-        ln = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
-        xp = ops.tm_row_gather(ln, None, pk.pad_idx, deterministic)
-        qkv = ops.linear_act(xp, a.to_qkv.weight, None)
+    def run_packed(self, x: torch.Tensor, pk: PackedGeometry, bits: Optional[torch.Tensor], route, cls: Optional[dict] = None):
+        """run() over all bags of a step as ONE packed sequence: x [sum seq, 512], the bags' sequences one after another ->
+        (the same rows, None).  One front into [sum n_pad, 1536], ops.nystrom_core_packed, one gather back, one back (bits
+        [sum seq, 16], each bag's words in its row slice).  cls (need_attn="cls"): the bag lengths, dict(n=[..]) or
+        dict(len_dev=..) -> (the rows, [one [8, s_b^2] cls attention per bag]), formed by the core in one launch set."""
         attn = None
-        if need_attn is False:
-            o = ops.nystrom_core_packed(qkv, pk.table, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces)
+        kw = dict(deterministic=route.det, pieces=route.pieces)
+        if cls is None:
+            o = ops.nystrom_core_packed(self.front(x, pk.pad_idx, route), pk.table, self.attn.res_conv.weight, **kw)
         else:
-            o, attn = ops.nystrom_core_packed(qkv, pk.table, a.res_conv.weight, deterministic=deterministic, pieces=gemm_pieces,
-                                              need_attn=need_attn, cls=dict(sides=pk.cls_table, **cls))
-        o = ops.tm_row_gather(o, None, pk.unpad_idx, deterministic)
-        lin = a.to_out[0]
-        if bits is None:
-            y = ops.linear_act(o, lin.weight, lin.bias, residual=x)
-        else:
-            y = x + ops.dropout_bits(ops.linear_act(o, lin.weight, lin.bias), bits, 1.0 / (1.0 - TM_DROP_P))
-        return y if need_attn is False else (y, attn)
+            o, attn = ops.nystrom_core_packed(self.front(x, pk.pad_idx, route), pk.table, self.attn.res_conv.weight,
+                                              need_attn="cls", cls=dict(sides=pk.cls_table, **cls), **kw)
+        return self.back(x, ops.tm_row_gather(o, None, pk.unpad_idx, route.det), bits), attn
 
 
 class PPEG(nn.Module):
@@ -334,11 +318,11 @@ class PPEG(nn.Module):
         self.proj1 = nn.Conv2d(dim, dim, 5, 1, 5 // 2, groups=dim)
         self.proj2 = nn.Conv2d(dim, dim, 3, 1, 3 // 2, groups=dim)
 
-    def run(self, x: torch.Tensor, s: int, deterministic: Optional[bool] = None) -> torch.Tensor:
+    def run(self, x: torch.Tensor, s: int, deterministic: bool) -> torch.Tensor:
         return ops.tm_ppeg(x, s, self.proj.weight, self.proj.bias, self.proj1.weight, self.proj1.bias, self.proj2.weight,
                            self.proj2.bias, deterministic)
 
-    def run_packed(self, x: torch.Tensor, table, deterministic: Optional[bool] = None) -> torch.Tensor:
+    def run_packed(self, x: torch.Tensor, table, deterministic: bool) -> torch.Tensor:
         """run() over all bags of a step in one launch set: x [sum (1 + s_b^2), 512], the bags' sequences one after another,
         table = PackedGeometry.ppeg_table -> the same rows (ops.tm_ppeg_packed)."""
         return ops.tm_ppeg_packed(x, table, self.proj.weight, self.proj.bias, self.proj1.weight, self.proj1.bias, self.proj2.weight,
@@ -348,19 +332,17 @@ class PPEG(nn.Module):
 class TransMIL(nn.Module):
     """The reference's TransMIL extractor on the HIP kernels of csrc/transmil.hip: _fc1, the cls token, two Nystrom layers with
     PPEG between them, LayerNorm of the cls rows; one bag or a ragged batch of bags per call.
-    Switches, each an attribute that overrides its environment variable when not None: fused_cls (MIL_TM_FUSED_CLS),
-    deterministic (MIL_TM_DETERMINISTIC), gemm_pieces (MIL_TM_PIECES), and batch_bags (MIL_TM_BATCH_BAGS, default off): a call
-    that holds more than one bag and asks for no attention output runs stage by stage across the bags, with the landmark-side
-    chain of each layer - A2, the pseudo-inverse, U and their gradients - as one set of launches for all bags
-    (ops.nystrom_core_bags) instead of one set per bag.  Every bag keeps its own pseudo-inverse scale and its values are those
-    of the bag-by-bag route (bit-equal under deterministic); the token-side passes, the dense layers and PPEG stay per bag.
-    packed (MIL_TM_PACKED, default off; it wins over batch_bags): the same call runs every layer over ONE packed sequence of
-    all bags' rows (_run_bags_packed, ops.nystrom_core_packed) - every stage but PPEG one launch set whatever the bag count.
-    packed_ppeg (MIL_TM_PACKED_PPEG, default off; it has an effect only where the packed route runs): PPEG too is one launch set
-    over the packed sequence rows (ops.tm_ppeg_packed), with no per-bag slice or concatenation between the layers.
-    packed_cls (MIL_TM_PACKED_CLS, default off; it too has an effect only where the packed route can run - several bags, packed
-    on): need_attn="cls" takes the packed route as well, the bags' per-patch cls attention of each layer formed in one launch set
-    (ops.tm_cls_attention_packed); off, such a call keeps the bag-by-bag launches.  need_attn=True always does."""
+    Switches, each an attribute that overrides its environment variable when not None (all default off): fused_cls
+    (MIL_TM_FUSED_CLS), deterministic (MIL_TM_DETERMINISTIC), gemm_pieces (MIL_TM_PIECES), batch_bags (MIL_TM_BATCH_BAGS), packed
+    (MIL_TM_PACKED), packed_ppeg (MIL_TM_PACKED_PPEG), packed_cls (MIL_TM_PACKED_CLS).  Which of them take effect in a step, and
+    which wins, is decided once per step by ops.tm_route and stated there, nowhere else.  The routes:
+    each - bag by bag;
+    batched - stage by stage across the bags, the landmark-side chain of each layer (A2, the pseudo-inverse, U and their
+    gradients) as one set of launches for all bags (ops.nystrom_core_bags); every bag keeps its own pseudo-inverse scale and the
+    values of the bag-by-bag route (bit-equal under deterministic); the token-side passes, the dense layers and PPEG stay per bag;
+    packed - every layer over ONE packed sequence of all bags' rows (ops.nystrom_core_packed), every stage but PPEG one launch
+    set whatever the bag count; with packed_ppeg PPEG too (ops.tm_ppeg_packed), with no per-bag slice or concatenation between
+    the layers; with packed_cls the bags' per-patch cls attention of each layer as well (ops.tm_cls_attention_packed)."""
 
     def __init__(self, n_classes: int, L: int = 768, D: int = 512, K: int = 1):
         super().__init__()
@@ -383,7 +365,7 @@ class TransMIL(nn.Module):
         self.deterministic: Optional[bool] = None    # every cross-workgroup sum in a fixed order (ops.tm_deterministic); None = MIL_TM_DETERMINISTIC
         self.gemm_pieces: Optional[int] = None       # 3: the Nystrom core's products on split-bf16 MFMA (ops.tm_pieces); None = MIL_TM_PIECES
         self.batch_bags: Optional[bool] = None       # a step's bags through one landmark-side chain (ops.tm_batch_bags); None = MIL_TM_BATCH_BAGS
-        self.packed: Optional[bool] = None           # a step's bags as one packed sequence (ops.tm_packed); None = MIL_TM_PACKED; wins over batch_bags
+        self.packed: Optional[bool] = None           # a step's bags as one packed sequence (ops.tm_packed); None = MIL_TM_PACKED
         self.packed_ppeg: Optional[bool] = None      # on the packed route, PPEG as one launch set too (ops.tm_packed_ppeg); None = MIL_TM_PACKED_PPEG
         self.packed_cls: Optional[bool] = None       # need_attn="cls" on the packed route too (ops.tm_packed_cls); None = MIL_TM_PACKED_CLS
 
@@ -409,8 +391,7 @@ class TransMIL(nn.Module):
         only); "cls" -> (h, [a0, a1]), a_l a list with one [8, N_b] tensor per bag: what the cls token gives each patch in
         layer l, a repeated patch's two keys summed (ops.tm_cls_attention; any bag size, train or eval).  With geom each entry is
         the static [8, s_b^2] tensor, zeros behind the bag's length on the device."""
-        if not (isinstance(need_attn, bool) or (isinstance(need_attn, str) and need_attn == "cls")):
-            raise ValueError(f"TransMIL: need_attn must be False, True or 'cls', got {need_attn!r}")
+        _check_need_attn(need_attn)
         dev = x.device
         if geom is not None:
             if x.dim() != 2 or x.shape[0] != geom.cap:
@@ -438,8 +419,7 @@ class TransMIL(nn.Module):
             geo = [geometry(n) for n in lengths]
             # [cls | tokens | first `add` tokens again] per bag, one gather for all bags; index -2 = the cls row
             idx_dev = torch.tensor(seq_index(lengths), dtype=torch.int32).to(dev, non_blocking=True)
-        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev, self.deterministic)
-        return self._run_bags(seqs, geo, need_attn, geom)
+        return self._run_bags(h, idx_dev, geo, need_attn, geom)
 
     def flat_segments(self, x0: torch.Tensor, segs: Sequence[Sequence[Tuple[int, int]]], need_attn=False):
         """forward() over rows that are not contiguous per bag: x0 [R, L], segs[b] = the bag's (first row, length) pieces in
@@ -448,8 +428,7 @@ class TransMIL(nn.Module):
         [B, 9] table of the pieces (ops.tm_seq_index_segs: no list of 1 + s^2 ints per bag is built or uploaded), then the
         bags run as in forward().  Same returns; with need_attn="cls" bag b's entries are [8, L_b] in sequence order.  Rows of
         x0 that no bag names get a zero gradient."""
-        if not (isinstance(need_attn, bool) or (isinstance(need_attn, str) and need_attn == "cls")):
-            raise ValueError(f"TransMIL: need_attn must be False, True or 'cls', got {need_attn!r}")
+        _check_need_attn(need_attn)
         if x0.dim() != 2 or x0.shape[1] != self.L:
             raise ValueError(f"TransMIL: flat_segments wants rows [R, {self.L}], got {tuple(x0.shape)}")
         R = x0.shape[0]
@@ -461,8 +440,7 @@ class TransMIL(nn.Module):
         table = torch.tensor(rows, dtype=torch.int32).to(x0.device, non_blocking=True)
         h = ops.linear_act(x0, self._fc1[0].weight, self._fc1[0].bias, "relu")        # [R, 512]
         idx_dev = ops.tm_seq_index_segs(table, total, R)
-        seqs = ops.tm_row_gather(h, self.cls_token, idx_dev, self.deterministic)
-        return self._run_bags(seqs, [geometry(sum(n for _, n in bag)) for bag in segs], need_attn, None)
+        return self._run_bags(h, idx_dev, [geometry(sum(n for _, n in bag)) for bag in segs], need_attn, None)
 
     def flat_bucket(self, x0: torch.Tensor, geom: BucketGeometry, patch_len_dev: torch.Tensor):
         """flat_segments() in its capture-safe form, for a step replayed from a hipGraph: x0 [cap + B sum(tail), L] is the
@@ -479,136 +457,95 @@ class TransMIL(nn.Module):
         if self.training and (self._drop_seed is None or self._drop_ctr is None or self._drop_ctr.device != x0.device):
             raise ValueError("TransMIL: fix the dropout stream (_drop_state) before a forward with geom")
         geom.update(patch_len_dev)
-        rows = ops.tm_row_gather(x0, None, geom.idx, self.deterministic)               # [sum(1 + s^2), L]
+        route = ops.tm_route(self, len(geom.sides), False)
+        rows = ops.tm_row_gather(x0, None, geom.idx, route.det)                         # [sum(1 + s^2), L]
         h = ops.linear_act(rows, self._fc1[0].weight, self._fc1[0].bias, "relu")
-        seqs = ops.tm_row_gather(h, self.cls_token, geom.cls_idx, self.deterministic)
-        return self._run_bags(seqs, [side_geometry(s) for s in geom.sides], False, geom)
+        return self._run_bags(h, geom.cls_idx, [side_geometry(s) for s in geom.sides], False, geom, route)
 
-    def _run_bags(self, seqs: torch.Tensor, geo: List[dict], need_attn, geom: Optional[DeviceGeometry]):
-        """The assembled sequences [sum(1 + s_b^2), 512], one bag after another: layer1 -> PPEG -> layer2 -> norm of the cls rows.
-        With batch_bags (ops.tm_batch_bags: the attribute, else MIL_TM_BATCH_BAGS; default off), more than one bag and need_attn
-        False the bags run stage by stage instead (_run_bags_batched): the same values per bag, the landmark-side chain of each
-        layer - A2, the pseudo-inverse, U and their gradients, whose shapes do not depend on the bag - once for all bags.  The
-        token-side passes, the dense layers and PPEG stay per bag.  With one bag, the switch off or need_attn set, the launches
-        are the bag-by-bag ones - but for need_attn "cls" with packed and packed_cls (ops.tm_packed_cls: the attribute, else
-        MIL_TM_PACKED_CLS; default off) both on, which takes the packed route with the attention formed there."""
-        want_cls = not isinstance(need_attn, bool)
-        dev = seqs.device
-        train = self.training
-        if train:
-            self._drop_state(dev)
-        if need_attn is False and len(geo) > 1 and ops.tm_packed(self.packed):
-            return self._run_bags_packed(seqs, geo, geom)
-        if want_cls and len(geo) > 1 and ops.tm_packed(self.packed) and ops.tm_packed_cls(self.packed_cls):
-            return self._run_bags_packed(seqs, geo, geom, "cls")
-        if need_attn is False and len(geo) > 1 and ops.tm_batch_bags(self.batch_bags):
-            return self._run_bags_batched(seqs, geo, geom)
-        cls_rows, attn0, attn1, bits_used = [], [], [], []
-        row = 0
-        for b, g in enumerate(geo):
-            xb = seqs[row:row + g["seq"]]
-            row += g["seq"]
-            if geom is not None:
-                pad_idx = geom.pad_idx[g["s"]]
-            else:
-                pad_idx = torch.tensor(pad_index(g), dtype=torch.int32).to(dev, non_blocking=True)
-            bits = self._bits(b, g["seq"], dev) if train else (None, None)
-            bits_used.append(bits)
-            cls = None
-            if want_cls:
-                cls = dict(len_dev=geom.len_dev, bag=b) if geom is not None else dict(n=g["N"])
-            xb, a0 = self.layer1.run(xb, g, pad_idx, bits[0], need_attn, cls, self.fused_cls, self.deterministic, self.gemm_pieces)
-            xb = self.pos_layer.run(xb, g["s"], self.deterministic)
-            xb, a1 = self.layer2.run(xb, g, pad_idx, bits[1], need_attn, cls, self.fused_cls, self.deterministic, self.gemm_pieces)
-            if want_cls and geom is None:
-                a0, a1 = a0[:, :g["N"]], a1[:, :g["N"]]
-            cls_rows.append(xb[:1])
-            attn0.append(a0)
-            attn1.append(a1)
-        if train and self.force_bits is None:
-            ops.counter_add(self._drop_ctr, 1)
-        self.last_bits = bits_used if train else None
-        hc = cls_rows[0] if len(cls_rows) == 1 else torch.cat(cls_rows, 0)
-        out = ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps)     # norm of the cls rows only
-        if not need_attn:
-            return out, [None, None]
-        if want_cls:
-            return out, [attn0, attn1]
-        if len(geo) == 1:
-            return out, [attn0[0].unsqueeze(0), attn1[0].unsqueeze(0)]
-        return out, [attn0, attn1]                   # ragged bags: one [8, n_pad, n_pad] map per bag
+    def _keep_bits(self, rows: List[int], dev, packed: bool):
+        """All bags' keep bits in front of the layers, for the batched and the packed route -> (bits: per bag those of (layer1,
+        layer2), the bag-by-bag route's; keep: per layer the words of all bags as one [sum seq, 16] tensor for the packed
+        route, else (None, None)).  The packed route draws each bag's words into its row slice of the step's buffer, so `bits`
+        are views of `keep`."""
+        bags = range(len(rows) - 1)
+        if not packed:
+            return [self._bits(b, rows[b + 1] - rows[b], dev) for b in bags], (None, None)
+        if self.force_bits is not None:
+            bits = [self._bits(b, 0, dev) for b in bags]
+            return bits, tuple(torch.cat([k[j] for k in bits], 0) for j in range(2))
+        keep = tuple(torch.empty((rows[-1], self.D // 32), device=dev, dtype=torch.int32) for _ in range(2))
+        return [self._bits(b, rows[b + 1] - rows[b], dev, tuple(k[rows[b]:rows[b + 1]] for k in keep)) for b in bags], keep
 
-    def _run_bags_batched(self, seqs: torch.Tensor, geo: List[dict], geom: Optional[DeviceGeometry]):
-        """_run_bags (need_attn False, several bags) stage by stage across the bags.  The keep bits of (bag, layer) are those of
-        the bag-by-bag route and the pass counter advances once.  All bags' layer tensors are alive at once: in eval mode,
-        where the bag-by-bag route frees a bag's before the next, the peak grows with the number of bags."""
-        dev = seqs.device
-        train = self.training
-        xs, pad_idxs, bits_used = [], [], []
-        row = 0
-        for b, g in enumerate(geo):
-            xs.append(seqs[row:row + g["seq"]])
-            row += g["seq"]
-            if geom is not None:
-                pad_idxs.append(geom.pad_idx[g["s"]])
-            else:
-                pad_idxs.append(torch.tensor(pad_index(g), dtype=torch.int32).to(dev, non_blocking=True))
-            bits_used.append(self._bits(b, g["seq"], dev) if train else (None, None))
-        xs = self.layer1.run_bags(xs, geo, pad_idxs, [k[0] for k in bits_used], self.deterministic, self.gemm_pieces)
-        xs = [self.pos_layer.run(x, g["s"], self.deterministic) for x, g in zip(xs, geo)]
-        xs = self.layer2.run_bags(xs, geo, pad_idxs, [k[1] for k in bits_used], self.deterministic, self.gemm_pieces)
-        if train and self.force_bits is None:
-            ops.counter_add(self._drop_ctr, 1)
-        self.last_bits = bits_used if train else None
-        hc = torch.cat([x[:1] for x in xs], 0)
-        return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), [None, None]
-
-    def _run_bags_packed(self, seqs: torch.Tensor, geo: List[dict], geom, need_attn=False):
-        """_run_bags (need_attn False or "cls", several bags) over ONE packed sequence (packed, ops.tm_packed: the attribute, else
-        MIL_TM_PACKED; default off; it wins over batch_bags): per layer every stage but PPEG is one launch set over all bags'
-        rows (TransLayer.run_packed).  PPEG runs per bag on row slices, its grid follows the side - or, with packed_ppeg
-        (ops.tm_packed_ppeg: the attribute, else MIL_TM_PACKED_PPEG; default off), as one launch set on the rows as they stand
-        (PPEG.run_packed: per bag the same values, the weight and bias gradients one sum over all bags).  The keep bits of
-        (bag, layer) are those of the bag-by-bag route, drawn into that bag's rows of one [sum seq, 16] buffer per layer;
-        last_bits stays the per-bag list (views), and the pass counter advances once.
-        need_attn="cls" (packed_cls): each layer's core also forms every bag's cls attention, one launch set for all bags
-        (TransLayer.run_packed); returned in the bag-by-bag route's form - [attn0, attn1], each a list with one tensor per bag,
-        [8, N_b] with host lengths (uploaded once here, outside any capture) and the static [8, s_b^2] with zeros from the device
-        length on with geom."""
-        dev = seqs.device
-        train = self.training
-        pk = getattr(geom, "packed", None) if geom is not None else None
-        if pk is None:                                  # host lengths: built per call, as pad_index is on the other routes
-            pk = PackedGeometry([g["s"] for g in geo], dev)
+    def _run_bags(self, h: torch.Tensor, idx: torch.Tensor, geo: List[dict], need_attn, geom, route=None):
+        """h [rows, 512] behind _fc1 and the index that assembles the sequences [sum(1 + s_b^2), 512], one bag after another:
+        layer1 -> PPEG -> layer2 -> norm of the cls rows, on the route ops.tm_route resolves here, once, from the module's
+        switches, the number of bags and need_attn (flat_bucket hands in the one it resolved).  The routes share the prologue (the
+        dropout stream, the keep bits of every (bag, layer) - the bag-by-bag route draws a bag's, and uploads its pad index, just
+        in front of that bag's layers, so that this host work runs under the launches of the bag before) and the epilogue (the pass counter advances once, last_bits is the per-bag list, the norm of the cls rows,
+        the attention in its three forms); only the layers between differ.  On the batched and the packed route all bags' layer
+        tensors are alive at once: in eval mode, where the bag-by-bag route frees a bag's before the next, the peak grows with
+        the number of bags.  need_attn="cls" returns [attn0, attn1], each a list with one tensor per bag: [8, N_b] with host
+        lengths, the static [8, s_b^2] with zeros from the device length on with geom."""
+        route = route or ops.tm_route(self, len(geo), need_attn)
+        seqs = ops.tm_row_gather(h, self.cls_token, idx, route.det)
+        dev, train, packed = seqs.device, self.training, route.bags == "packed"
         rows = [0]
         for g in geo:
             rows.append(rows[-1] + g["seq"])
-        keep, bits_used = (None, None), [(None, None)] * len(geo)
-        if train and self.force_bits is not None:
-            bits_used = [self.force_bits[b] for b in range(len(geo))]
-            keep = tuple(torch.cat([k[j] for k in bits_used], 0) for j in range(2))
-        elif train:
-            keep = tuple(torch.empty((rows[-1], self.D // 32), device=dev, dtype=torch.int32) for _ in range(2))
-            bits_used = [self._bits(b, g["seq"], dev, tuple(keep[j][rows[b]:rows[b + 1]] for j in range(2)))
-                         for b, g in enumerate(geo)]
-        cls = None
-        if need_attn is not False:
-            cls = dict(len_dev=geom.len_dev if geom is not None else
-                       torch.tensor([g["N"] for g in geo], dtype=torch.int32).to(dev, non_blocking=True))
-        x = self.layer1.run_packed(seqs, pk, keep[0], self.deterministic, self.gemm_pieces, need_attn, cls)
-        if cls is not None:
-            x, attn0 = x
-        if ops.tm_packed_ppeg(self.packed_ppeg):
-            x = self.pos_layer.run_packed(x, pk.ppeg_table, self.deterministic)
+        bits, keep = [(None, None)] * len(geo), (None, None)
+        if train:
+            self._drop_state(dev)
+            if route.bags != "each":
+                bits, keep = self._keep_bits(rows, dev, packed)
+        if packed:
+            pk = geom.packed if geom is not None else PackedGeometry([g["s"] for g in geo], dev)   # host lengths: built per call
+            cls = None
+            if route.cls:               # host lengths are uploaded once here, outside any capture
+                cls = dict(len_dev=geom.len_dev if geom is not None else
+                           torch.tensor([g["N"] for g in geo], dtype=torch.int32).to(dev, non_blocking=True))
+            x, attn0 = self.layer1.run_packed(seqs, pk, keep[0], route, cls)
+            if route.ppeg_packed:       # one launch set on the rows as they stand; else per bag on row slices: its grid follows the side
+                x = self.pos_layer.run_packed(x, pk.ppeg_table, route.det)
+            else:
+                x = torch.cat([self.pos_layer.run(x[rows[b]:rows[b + 1]], g["s"], route.det) for b, g in enumerate(geo)], 0)
+            x, attn1 = self.layer2.run_packed(x, pk, keep[1], route, cls)
+            cls_rows = [x[r:r + 1] for r in rows[:-1]]
         else:
-            x = torch.cat([self.pos_layer.run(x[rows[b]:rows[b + 1]], g["s"], self.deterministic) for b, g in enumerate(geo)], 0)
-        x = self.layer2.run_packed(x, pk, keep[1], self.deterministic, self.gemm_pieces, need_attn, cls)
-        if cls is not None:
-            x, attn1 = x
-            if geom is None:
-                attn0, attn1 = ([a[:, :g["N"]] for a, g in zip(attn, geo)] for attn in (attn0, attn1))
+            xs = [seqs[rows[b]:rows[b + 1]] for b in range(len(geo))]
+            attn0, attn1 = [], []
+
+            def pad_of(g):
+                if geom is not None:
+                    return geom.pad_idx[g["s"]]
+                return torch.tensor(pad_index(g), dtype=torch.int32).to(dev, non_blocking=True)
+            if route.bags == "batched":
+                pads = [pad_of(g) for g in geo]
+                xs = self.layer1.run_bags(xs, geo, pads, [k[0] for k in bits], route)
+                xs = [self.pos_layer.run(x, g["s"], route.det) for x, g in zip(xs, geo)]
+                xs = self.layer2.run_bags(xs, geo, pads, [k[1] for k in bits], route)
+            else:
+                for b, g in enumerate(geo):
+                    pad = pad_of(g)
+                    if train:
+                        bits[b] = self._bits(b, g["seq"], dev)
+                    cls = None
+                    if route.cls:
+                        cls = dict(len_dev=geom.len_dev, bag=b) if geom is not None else dict(n=g["N"])
+                    x, a0 = self.layer1.run(xs[b], g, pad, bits[b][0], need_attn, route, cls)
+                    x = self.pos_layer.run(x, g["s"], route.det)
+                    xs[b], a1 = self.layer2.run(x, g, pad, bits[b][1], need_attn, route, cls)
+                    attn0.append(a0)
+                    attn1.append(a1)
+            cls_rows = [x[:1] for x in xs]
         if train and self.force_bits is None:
             ops.counter_add(self._drop_ctr, 1)
-        self.last_bits = bits_used if train else None
-        hc = torch.cat([x[r:r + 1] for r in rows[:-1]], 0)
-        return ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps), ([None, None] if cls is None else [attn0, attn1])
+        self.last_bits = bits if train else None
+        hc = cls_rows[0] if len(cls_rows) == 1 else torch.cat(cls_rows, 0)
+        out = ops.layer_norm(hc, self.norm.weight, self.norm.bias, self.norm.eps)     # norm of the cls rows only
+        if need_attn is False:
+            return out, [None, None]
+        if route.cls and geom is None:
+            attn0, attn1 = ([a[:, :g["N"]] for a, g in zip(attn, geo)] for attn in (attn0, attn1))
+        if need_attn is True and len(geo) == 1:
+            return out, [attn0[0].unsqueeze(0), attn1[0].unsqueeze(0)]
+        return out, [attn0, attn1]      # several bags: one [8, n_pad, n_pad] map, or one cls attention, per bag

@@ -43,4 +43,4 @@ from .transmil import (TM_H, TM_DH, TM_D, TM_M, TM_CONV, TM_PINV_ITERS, TM_QSCAL
                        _NystromCoreBags, nystrom_core_bags, tm_packed, TmPackedTable, tm_packed_table_host, tm_packed_table,
                        _tm_fwd_packed, _tm_bwd_packed, _NystromCorePacked, nystrom_core_packed, tm_packed_ppeg, TmPpegTable,
                        tm_ppeg_table_host, tm_ppeg_table, _TmPPEGPacked, tm_ppeg_packed, tm_packed_cls, TmClsTable,
-                       tm_cls_table_host, tm_cls_table, tm_cls_attention_packed)
+                       tm_cls_table_host, tm_cls_table, tm_cls_attention_packed, TmRoute, tm_route)

@@ -2,10 +2,13 @@
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import functools
+import itertools
 import math
 import os
 from types import SimpleNamespace
+from typing import Optional
 
 import torch
 
@@ -28,18 +31,49 @@ def _tm_splits(M: int, N: int, batch: int, K: int) -> int:
     return max(1, min(K // 256, 512 // tiles))
 
 
-def tm_deterministic(value=None) -> bool:
-    """The switch of the fixed-order sums: the keyword (a module passes its `deterministic` attribute here), else the
-    environment variable MIL_TM_DETERMINISTIC (default 0), read per call."""
+def _tm_env(value, name: str) -> bool:
+    """A switch of this file: the value where it is not None (a keyword, or the module attribute a caller passes), else the
+    environment variable `name`, read per call; unset, "" and "0" are off."""
     if value is None:
-        value = os.environ.get("MIL_TM_DETERMINISTIC", "0") not in ("", "0")
+        value = os.environ.get(name, "0") not in ("", "0")
     return bool(value)
 
 
+def tm_deterministic(value=None) -> bool:       # TransMIL.deterministic: the fixed-order sums (the mil_tm_*_fixed entries)
+    return _tm_env(value, "MIL_TM_DETERMINISTIC")
+
+
+def tm_batch_bags(value=None) -> bool:          # TransMIL.batch_bags: the batched landmark-side chain (nystrom_core_bags)
+    return _tm_env(value, "MIL_TM_BATCH_BAGS")
+
+
+def tm_packed(value=None) -> bool:              # TransMIL.packed: the packed sequence (nystrom_core_packed)
+    return _tm_env(value, "MIL_TM_PACKED")
+
+
+def tm_packed_ppeg(value=None) -> bool:         # TransMIL.packed_ppeg: on the packed route, PPEG as one launch set (tm_ppeg_packed)
+    return _tm_env(value, "MIL_TM_PACKED_PPEG")
+
+
+def tm_packed_cls(value=None) -> bool:          # TransMIL.packed_cls: need_attn="cls" on the packed route (tm_cls_attention_packed)
+    return _tm_env(value, "MIL_TM_PACKED_CLS")
+
+
+def _tm_fused_a3(value, need_attn) -> bool:     # the landmark-query pass on its fused entries (tm_lmk_attn); the attention
+    return _tm_env(value, "MIL_TM_FUSED_A3") and need_attn is False     # outputs are formed from the maps: need_attn False only
+
+
+def _tm_fused_a1(value, need_attn) -> bool:     # the token-query pass on its fused entries (tm_tok_attn): the same
+    return _tm_env(value, "MIL_TM_FUSED_A1") and need_attn is False
+
+
+def _tm_fused_cls(value, need_attn) -> bool:    # TransMIL.fused_cls: need_attn "cls" from the fused passes' operands, both then fused
+    return _tm_env(value, "MIL_TM_FUSED_CLS") and isinstance(need_attn, str) and need_attn == "cls"
+
+
 def tm_pieces(value=None) -> int:
-    """The switch of the split-bf16 products: the keyword (a module passes its `gemm_pieces` attribute here), else the
-    environment variable MIL_TM_PIECES (default 0), read per call.  0: every product on fp32 MFMA; 3: the products that
-    _tm_pieces_route names on three-piece split-bf16 MFMA (mil_tm_bgemm_pieces).  Anything else raises ValueError."""
+    """The split-bf16 products: TransMIL.gemm_pieces, else MIL_TM_PIECES (default 0), read per call.  0: every product on fp32
+    MFMA; 3: those that _tm_pieces_route names on three-piece split-bf16 MFMA (mil_tm_bgemm_pieces); else ValueError."""
     if value is None:
         value = os.environ.get("MIL_TM_PIECES", "") or "0"
     try:
@@ -51,39 +85,52 @@ def tm_pieces(value=None) -> int:
     return pieces
 
 
-def tm_batch_bags(value=None) -> bool:
-    """The switch of the batched landmark-side chain (nystrom_core_bags): the keyword (a module passes its `batch_bags`
-    attribute here), else the environment variable MIL_TM_BATCH_BAGS (default 0), read per call."""
-    if value is None:
-        value = os.environ.get("MIL_TM_BATCH_BAGS", "0") not in ("", "0")
-    return bool(value)
+@dataclasses.dataclass(frozen=True)
+class TmRoute:
+    """What one TransMIL step launches, as tm_route resolves it: how the bags run ("each", "batched", "packed"), PPEG as one
+    launch set, either attention pass on its fused entries, where the per-patch cls attention comes from (None, "maps" =
+    tm_cls_attention on A1 / A3, "fused", "packed"), the fixed-order sums and the split-bf16 products (0 or 3)."""
+    bags: str
+    ppeg_packed: bool
+    fused_a1: bool
+    fused_a3: bool
+    cls: Optional[str]
+    det: bool
+    pieces: int
+
+    def key(self) -> tuple:
+        """The route's part of a graph key.  A fused switch is named only where it changes the route's launches: none on the
+        packed route, which runs both passes fused whatever they say, nor a1 / a3 under the fused cls attention."""
+        alone = self.bags != "packed" and self.cls != "fused"
+        return ((("deterministic",) if self.det else ()) + ((("gemm_pieces", self.pieces),) if self.pieces else ())
+                + (("fused_a1",) if alone and self.fused_a1 else ()) + (("fused_a3",) if alone and self.fused_a3 else ())
+                + (("fused_cls",) if self.cls == "fused" else ())
+                + ((("packed",) + (("ppeg",) if self.ppeg_packed else ()) + (("cls",) if self.cls == "packed" else ()))
+                   if self.bags == "packed" else ("batch_bags",) if self.bags == "batched" else ()))
 
 
-def tm_packed(value=None) -> bool:
-    """The switch of the packed sequence (nystrom_core_packed): the keyword (a module passes its `packed` attribute here), else
-    the environment variable MIL_TM_PACKED (default 0), read per call."""
-    if value is None:
-        value = os.environ.get("MIL_TM_PACKED", "0") not in ("", "0")
-    return bool(value)
-
-
-def tm_packed_ppeg(value=None) -> bool:
-    """The switch of the packed PPEG (tm_ppeg_packed) on the packed route: the keyword (a module passes its `packed_ppeg`
-    attribute here), else the environment variable MIL_TM_PACKED_PPEG (default 0), read per call.  It has an effect only where
-    the packed route runs (tm_packed)."""
-    if value is None:
-        value = os.environ.get("MIL_TM_PACKED_PPEG", "0") not in ("", "0")
-    return bool(value)
-
-
-def tm_packed_cls(value=None) -> bool:
-    """The switch of the per-patch cls attention on the packed route (nystrom_core_packed(need_attn="cls"),
-    tm_cls_attention_packed): the keyword (a module passes its `packed_cls` attribute here), else the environment variable
-    MIL_TM_PACKED_CLS (default 0), read per call.  It has an effect only where the packed route can run (tm_packed, several
-    bags) and only for need_attn="cls"; off, such a request keeps the bag-by-bag launches."""
-    if value is None:
-        value = os.environ.get("MIL_TM_PACKED_CLS", "0") not in ("", "0")
-    return bool(value)
+def tm_route(switches, n_bags: int, need_attn) -> TmRoute:
+    """The route of a step of `n_bags` bags that asks for need_attn (False, True or "cls").  switches: a TransMIL module, or
+    anything with its seven attributes deterministic, gemm_pieces, batch_bags, packed, packed_ppeg, packed_cls, fused_cls; each
+    overrides its environment variable when it is not None.  The two fused passes have environment switches only
+    (MIL_TM_FUSED_A1, MIL_TM_FUSED_A3).  This is the one statement of the precedence:
+      packed   more than one bag, packed on, and need_attn False - or "cls" with packed_cls on.  Both passes run fused whatever
+               their switches say; PPEG is one launch set too with packed_ppeg on (it has no effect on another route); the cls
+               attention is formed on the packed rows.
+      batched  otherwise, with more than one bag, need_attn False and batch_bags on.
+      each     otherwise: bag by bag.  need_attn True always lands here, with both maps materialised.  "cls" with fused_cls on
+               takes the cls attention from the fused passes' operands and runs both passes fused; off, from the maps.
+      On each and batched fused_a1 / fused_a3 apply with need_attn False only; deterministic and gemm_pieces go with every route."""
+    want_cls = isinstance(need_attn, str) and need_attn == "cls"
+    if n_bags > 1 and tm_packed(switches.packed) and (need_attn is False or (want_cls and tm_packed_cls(switches.packed_cls))):
+        bags, fused_a1, fused_a3, cls = "packed", True, True, "packed" if want_cls else None
+    else:
+        bags = "batched" if n_bags > 1 and need_attn is False and tm_batch_bags(switches.batch_bags) else "each"
+        fused_cls = _tm_fused_cls(switches.fused_cls, need_attn)
+        fused_a1, fused_a3 = fused_cls or _tm_fused_a1(None, need_attn), fused_cls or _tm_fused_a3(None, need_attn)
+        cls = ("fused" if fused_cls else "maps") if want_cls else None
+    return TmRoute(bags, bags == "packed" and tm_packed_ppeg(switches.packed_ppeg), fused_a1, fused_a3, cls,
+                   tm_deterministic(switches.deterministic), tm_pieces(switches.gemm_pieces))
 
 
 def _tm_pieces_route(M: int, N: int, K: int) -> bool:
@@ -417,38 +464,9 @@ def tm_tok_attn_bwd(qkv, kL, U, lse, dO, dqkv=None, dU=None, dkL=None):
     return dqkv, dU, dkL
 
 
-def _tm_switch(value, env_name, need_attn) -> bool:
-    """The switch of a fused pass: the keyword, else the environment variable (default 0), read per call.  The attention outputs
-    (need_attn True / "cls") are formed from the maps (tm_cls_attention takes A1 and A3), so they keep the materialised route."""
-    if value is None:
-        value = os.environ.get(env_name, "0") not in ("", "0")
-    return bool(value) and need_attn is False
-
-
-def _tm_fused_a3(fused_a3, need_attn) -> bool:      # the landmark-query pass
-    return _tm_switch(fused_a3, "MIL_TM_FUSED_A3", need_attn)
-
-
-def _tm_fused_a1(fused_a1, need_attn) -> bool:      # the token-query pass
-    return _tm_switch(fused_a1, "MIL_TM_FUSED_A1", need_attn)
-
-
-def _tm_fused_cls(value, need_attn) -> bool:
-    """The switch of the cls attention on the fused passes (tm_cls_attention_fused): the keyword, else MIL_TM_FUSED_CLS
-    (default 0), read per call.  It applies with need_attn "cls" only, and then puts both passes on their fused entries."""
-    if value is None:
-        value = os.environ.get("MIL_TM_FUSED_CLS", "0") not in ("", "0")
-    return bool(value) and isinstance(need_attn, str) and need_attn == "cls"
-
-
 def _tm_bg(det: bool, pieces: int):
     """tm_bgemm with the arithmetic of one core call bound: the fixed-order split-K form and / or the split-bf16 route."""
-    kw = {}
-    if det:
-        kw["deterministic"] = True
-    if pieces:
-        kw["pieces"] = pieces
-    return functools.partial(tm_bgemm, **kw) if kw else tm_bgemm
+    return functools.partial(tm_bgemm, deterministic=det, pieces=pieces) if det or pieces else tm_bgemm
 
 
 # ---- the Nystrom core in phases.  _tm_fwd / _tm_bwd (one bag) and _tm_fwd_bags / _tm_bwd_bags (all bags of a step) issue the
@@ -788,21 +806,17 @@ def nystrom_core(qkv, w, need_attn=False, *, pad=None, s=None, n=None, len_dev=N
     (out [n_pad, 512] merged heads before to_out, attn).  need_attn: False -> attn None; True -> the whole map
     [8, n_pad, n_pad]; "cls" -> the cls token's per-patch attention [8, s^2] (tm_cls_attention), which needs the bag's geometry
     as keywords: pad, s and the length as n or as len_dev (+ bag).  attn carries no gradient in any mode.
+    The switches are keywords: a module passes what tm_route resolved, None reads the switch's environment variable at the call.
     fused_a3: the landmark-query pass (softmax(qL k^T) v and its backward) as one kernel family that never forms the
-    [8, 256, n_pad] map (tm_lmk_attn); None reads the environment switch MIL_TM_FUSED_A3 (default 0) at every call.  It applies
-    with need_attn False only: True and "cls" read the map and keep the materialised route whatever the switch says.
-    fused_a1: the same for the token-query pass (softmax(q kL^T) U and its backward, tm_tok_attn), which never forms the
-    [8, n_pad, 256] map; None reads MIL_TM_FUSED_A1 (default 0).  The two switches are independent of each other.
-    fused_cls: with need_attn "cls", the cls attention from the fused passes' operands (tm_cls_attention_fused); None reads
-    MIL_TM_FUSED_CLS (default 0).  When it applies BOTH passes run fused, forward and backward, whatever fused_a1 / fused_a3
-    say, and no map is formed; with need_attn False or True it changes nothing.
+    [8, 256, n_pad] map (tm_lmk_attn).  fused_a1: the same for the token-query pass (softmax(q kL^T) U, tm_tok_attn) and the
+    [8, n_pad, 256] map.  The two are independent and apply with need_attn False only: True and "cls" read the maps.
+    fused_cls: with need_attn "cls", the cls attention from the fused passes' operands (tm_cls_attention_fused); BOTH passes then
+    run fused, forward and backward, whatever the other two say, and no map is formed.
     deterministic: every sum that crosses workgroups in a fixed order (the mil_tm_*_fixed entries: split-K products, the
-    pseudo-inverse scale's gradient, the res_conv weight gradient), forward and backward, so that two runs give the same bits;
-    None reads MIL_TM_DETERMINISTIC (default 0).  It goes with every need_attn and every fused switch.
+    pseudo-inverse scale's gradient, the res_conv weight gradient), forward and backward: two runs give the same bits.
     pieces: 0 or 3.  3 runs the core's products with K >= 256 (_tm_pieces_route) as three-piece split-bf16 products on
-    v_mfma_f32_32x32x16_bf16 (mil_tm_bgemm_pieces; fp32-level error), forward and backward; None reads MIL_TM_PIECES (default 0;
-    any value but 0 / 3 raises ValueError).  It goes with every need_attn, every fused switch and deterministic; the fused
-    passes have kernels of their own and are untouched."""
+    v_mfma_f32_32x32x16_bf16 (mil_tm_bgemm_pieces; fp32-level error), forward and backward; the fused passes have kernels of
+    their own and are untouched.  deterministic and pieces go with every need_attn and every fused switch."""
     det = tm_deterministic(deterministic)
     pieces = tm_pieces(pieces)
     if isinstance(need_attn, bool):
@@ -855,12 +869,10 @@ def nystrom_core_bags(qkvs, w, *, fused_a3=None, fused_a1=None, deterministic=No
     one launch of batch 8 nb.  These products have K <= 256 and so one split at any batch: a bag's tiles see the arithmetic
     of the bag-by-bag launch, and with deterministic=True every out_b and dqkv_b is bit-equal to nystrom_core on that bag.
     dw is the bags' dw_b added in bag order 0, 1, 2, ...
-    fused_a3, fused_a1, deterministic, pieces: as in nystrom_core (None reads the environment).  need_attn is not offered:
-    callers keep the bag-by-bag route for True and "cls".  No host read; every workspace is a torch.empty, so the call can be
-    captured into a graph.  The switch that sends a module's step here is tm_batch_bags (MIL_TM_BATCH_BAGS, default 0)."""
+    fused_a3, fused_a1, deterministic, pieces: as in nystrom_core.  need_attn is not offered: True and "cls" keep the bag-by-bag
+    route (tm_route).  No host read; every workspace is a torch.empty, so the call can be captured into a graph."""
     return list(_NystromCoreBags.apply(w, _tm_fused_a3(fused_a3, False), _tm_fused_a1(fused_a1, False),
                                        tm_deterministic(deterministic), tm_pieces(pieces), *qkvs))
-
 
 
 # ---- a step's bags as one packed sequence (csrc/tm_packed.h): every token-side stage one launch set over all bags' rows
@@ -883,18 +895,20 @@ def tm_packed_table_host(blocks):
     blocks = [int(k) for k in blocks]
     if not 1 <= len(blocks) <= TM_MAX_BATCH_BAGS or min(blocks) < 1 or sum(blocks) > (2 ** 31 - 1) // TM_M:
         raise ValueError(f"tm_packed_table: 1 .. {TM_MAX_BATCH_BAGS} bags of at least one 256-row block each, got {blocks}")
-    off = [0]
-    for k in blocks:
-        off.append(off[-1] + k)
-    return off + [b for b, k in enumerate(blocks) for _ in range(k)]
+    return list(itertools.accumulate(blocks, initial=0)) + [b for b, k in enumerate(blocks) for _ in range(k)]
+
+
+def _tm_table_dev(values, device):
+    """A table's int32 values on `device` (default: the current GPU).  One small host-to-device copy, so a replayed step builds
+    its tables once per graph key, not per step."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    return torch.tensor(values, dtype=torch.int32).to(device, non_blocking=True)
 
 
 def tm_packed_table(blocks, device=None) -> TmPackedTable:
-    """blocks: per bag n_pad / 256 -> the TmPackedTable on `device` (default: the current GPU).  One small host-to-device
-    copy, so a replayed step builds it once per graph key, not per step."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    return TmPackedTable(blocks, torch.tensor(tm_packed_table_host(blocks), dtype=torch.int32).to(device, non_blocking=True))
+    """blocks: per bag n_pad / 256 -> the TmPackedTable on `device` (_tm_table_dev)."""
+    return TmPackedTable(blocks, _tm_table_dev(tm_packed_table_host(blocks), device))
 
 
 class TmClsTable:
@@ -905,9 +919,7 @@ class TmClsTable:
     def __init__(self, sides, dev):
         self.sides = tuple(int(s) for s in sides)
         self.nb, self.dev = len(self.sides), dev
-        self.off = [0]
-        for s in self.sides:
-            self.off.append(self.off[-1] + s * s)
+        self.off = list(itertools.accumulate((s * s for s in self.sides), initial=0))
         self.patches = self.off[-1]
 
 
@@ -919,18 +931,12 @@ def tm_cls_table_host(sides):
     sides = [int(s) for s in sides]
     if not 1 <= len(sides) <= TM_MAX_BATCH_BAGS or min(sides) < 1 or sum(s * s for s in sides) > 2 ** 31 - 1:
         raise ValueError(f"tm_cls_table: 1 .. {TM_MAX_BATCH_BAGS} bags of side >= 1, at most 2^31 - 1 patches, got {sides}")
-    off = [0]
-    for s in sides:
-        off.append(off[-1] + s * s)
-    return sides + off
+    return sides + list(itertools.accumulate((s * s for s in sides), initial=0))
 
 
 def tm_cls_table(sides, device=None) -> TmClsTable:
-    """sides: per bag the grid side -> the TmClsTable on `device` (default: the current GPU).  One small host-to-device copy, so
-    a replayed step builds it once per graph key, not per step."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    return TmClsTable(sides, torch.tensor(tm_cls_table_host(sides), dtype=torch.int32).to(device, non_blocking=True))
+    """sides: per bag the grid side -> the TmClsTable on `device` (_tm_table_dev)."""
+    return TmClsTable(sides, _tm_table_dev(tm_cls_table_host(sides), device))
 
 
 def tm_cls_attention_packed(qkv, table, qL, kL, Z, lse3, sides, n=None, len_dev=None):
@@ -1067,16 +1073,14 @@ def nystrom_core_packed(qkv, blocks_or_table, w, *, deterministic=None, pieces=N
     stacked [nb, 8, 256, .].  Both passes always run fused: no A1 or A3 map exists on this route, and no attention output.
     Every bag's rows of out and (deterministic) of dqkv are bit-equal to nystrom_core_bags with both fused switches on; dw is
     one sum over all bags' 256-row chunks - atomic, or with deterministic in ascending packed order.
-    deterministic, pieces: as in nystrom_core (None reads the environment); they apply to the chain unchanged.  No host read;
-    every workspace is a torch.empty, so with a TmPackedTable the call can be captured into a graph.  The switch that sends a
-    module's step here is tm_packed (MIL_TM_PACKED, default 0).
+    deterministic, pieces: as in nystrom_core; they apply to the chain unchanged.  No host read; every workspace is a
+    torch.empty, so with a TmPackedTable the call can be captured into a graph.  tm_route says which steps come here.
     need_attn: False -> out alone, as above.  "cls" -> (out, [attn_b]): the cls token's per-patch attention of every bag, [8, s_b^2]
     each with zeros from the bag's length on, all views of one buffer (tm_cls_attention_packed: one launch set for all bags);
     cls = dict(sides=.., n=[..]) with host lengths (validated and uploaded: not for a capture) or dict(sides=.., len_dev=..)
     with the lengths on the device, sides the grid sides or a TmClsTable.  The attention is formed in the forward from qL, kL, Z
     and lse3, behind U; it carries no gradient and the backward is the one of need_attn False, so out and dqkv keep their bits.
-    True raises ValueError: the whole [8, n_pad, n_pad] map has no packed form.  The switch that sends a module's "cls" request
-    here is tm_packed_cls (MIL_TM_PACKED_CLS, default 0)."""
+    True raises ValueError: the whole [8, n_pad, n_pad] map has no packed form."""
     if not (need_attn is False or (isinstance(need_attn, str) and need_attn == "cls")):
         raise ValueError(f"nystrom_core_packed: need_attn must be False or 'cls' (the whole map has no packed form), got {need_attn!r}")
     tab = blocks_or_table if isinstance(blocks_or_table, TmPackedTable) else tm_packed_table(blocks_or_table, qkv.device)
@@ -1128,11 +1132,8 @@ def tm_ppeg_table_host(sides):
 
 
 def tm_ppeg_table(sides, device=None) -> TmPpegTable:
-    """sides: per bag the grid side -> the TmPpegTable on `device` (default: the current GPU).  One small host-to-device copy,
-    so a replayed step builds it once per graph key, not per step."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    return TmPpegTable(sides, torch.tensor(tm_ppeg_table_host(sides), dtype=torch.int32).to(device, non_blocking=True))
+    """sides: per bag the grid side -> the TmPpegTable on `device` (_tm_table_dev)."""
+    return TmPpegTable(sides, _tm_table_dev(tm_ppeg_table_host(sides), device))
 
 
 class _TmPPEGPacked(torch.autograd.Function):
@@ -1177,7 +1178,6 @@ def tm_ppeg_packed(x, table, W7, b7, W5, b5, W3, b3, deterministic=None):
     capture).  Every bag's rows of the result and of dx are bit-equal to tm_ppeg on that bag's slice; the weight and bias
     gradients are ONE sum over all bags' 8-grid-row chunks - atomic, or with deterministic in ascending packed order
     (mil_tm_ppeg_bwd_packed_fixed) -, where the per-bag route lets autograd add per-bag totals.  No host read; the workspace is a
-    torch.empty, so with a TmPpegTable the call can be captured into a graph.  The switch that sends a module's packed step
-    here is tm_packed_ppeg (MIL_TM_PACKED_PPEG, default 0)."""
+    torch.empty, so with a TmPpegTable the call can be captured into a graph."""
     tab = table if isinstance(table, TmPpegTable) else tm_ppeg_table(table, x.device)
     return _TmPPEGPacked.apply(x, tab, W7, b7, W5, b5, W3, b3, tm_deterministic(deterministic))

@@ -39,32 +39,17 @@ def build_model(args):
     else:
         from .model.utils import get_model
     model = get_model(args)
-    if getattr(args, "deterministic", 0):
-        # every TransMIL module of the model (the image-only extractor; the fusion model's aggregator and its unused
-        # extractor); a model without one has no float atomic in its step and nothing to set
-        for m in model.modules():
-            if type(m).__name__ == "TransMIL":
-                m.deterministic = True
-    if getattr(args, "tm_gemm_pieces", 0):
-        for m in model.modules():           # the same modules; a model without one ignores the flag
-            if type(m).__name__ == "TransMIL":
-                m.gemm_pieces = int(args.tm_gemm_pieces)
-    if getattr(args, "tm_batch_bags", 0):
-        for m in model.modules():           # the same modules again
-            if type(m).__name__ == "TransMIL":
-                m.batch_bags = True
-    if getattr(args, "tm_packed", 0):
-        for m in model.modules():           # and once more
-            if type(m).__name__ == "TransMIL":
-                m.packed = True
-    if getattr(args, "tm_packed_ppeg", 0):
-        for m in model.modules():           # on the packed route, PPEG as one launch set too
-            if type(m).__name__ == "TransMIL":
-                m.packed_ppeg = True
-    if getattr(args, "tm_packed_cls", 0):
-        for m in model.modules():           # on the packed route, the per-patch cls attention too (need_attn="cls")
-            if type(m).__name__ == "TransMIL":
-                m.packed_cls = True
+    # the TransMIL switches (flag, module attribute, value); a flag at 0 leaves the attribute None, so that the environment
+    # decides.  They go to every TransMIL module of the model (the image-only extractor; the fusion model's aggregator and its
+    # unused extractor); a model without one has nothing to set
+    switches = [(attr, value) for flag, attr, value in (
+        ("deterministic", "deterministic", True), ("tm_gemm_pieces", "gemm_pieces", int(getattr(args, "tm_gemm_pieces", 0) or 0)),
+        ("tm_batch_bags", "batch_bags", True), ("tm_packed", "packed", True), ("tm_packed_ppeg", "packed_ppeg", True),
+        ("tm_packed_cls", "packed_cls", True)) if getattr(args, flag, 0)]
+    for m in model.modules():
+        if type(m).__name__ == "TransMIL":
+            for attr, value in switches:
+                setattr(m, attr, value)
     if (args.variant == "image_only" and getattr(args, "model_pathology", "ABMIL") == "TransMIL"
             and getattr(args, "transmil_graph", 0)):
         model.graph_eval = True          # evaluation (test_ddp.py, batch 1, eval mode, no grad): the replayed forward

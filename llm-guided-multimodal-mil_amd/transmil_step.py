@@ -116,24 +116,12 @@ class RaggedTransMILStepper:
         """The graph key of a slot of these sides under the model's switches as they stand now."""
         m = self.model
         attn = bool(getattr(m, "patch_attn", False))
-        # a graph captured without the attention outputs is never replayed for a request with them, and the other way round
-        # ... nor is one captured on the atomic sums replayed for a model that asks for the fixed-order ones
-        det = ops.tm_deterministic(m.extractor_pathology.deterministic)
-        # ... nor one captured on the fp32 products for a model that asks for the split-bf16 ones
-        pieces = ops.tm_pieces(m.extractor_pathology.gemm_pieces)
-        # ... nor one captured bag by bag for a model that asks for the batched landmark-side chain (several bags, no attention
-        # outputs: what TransMIL._run_bags takes that route for)
-        batched = ops.tm_batch_bags(m.extractor_pathology.batch_bags) and len(sides) > 1 and not attn
-        # ... nor one of either of those for a model that asks for the packed sequence, which wins over the batched chain
-        # (with the attention outputs only for a model that asks for the packed cls attention too: TransMIL.packed_cls)
-        cls = attn and ops.tm_packed_cls(getattr(m.extractor_pathology, "packed_cls", None))
-        packed = ops.tm_packed(m.extractor_pathology.packed) and len(sides) > 1 and (not attn or cls)
-        # ... nor one with PPEG per bag for a model that asks for the packed PPEG on that route
-        ppeg = packed and ops.tm_packed_ppeg(getattr(m.extractor_pathology, "packed_ppeg", None))
-        route = (("packed",) + (("ppeg",) if ppeg else ()) + (("cls",) if cls else ())) if packed else ("batch_bags",) if batched else ()
+        # a graph captured without the attention outputs is never replayed for a request with them, and the other way round;
+        # nor one captured on one route for a model whose switches now name another: the route the extractor's forward will
+        # resolve for this step (ops.tm_route) is part of the key
+        route = ops.tm_route(m.extractor_pathology, len(sides), "cls" if attn else False)
         return (("transmil-sides", tuple(sides), bool(m.training), self.backward) + (("patch_attn",) if attn else ())
-                + (("deterministic",) if det else ()) + ((("gemm_pieces", pieces),) if pieces else ())
-                + route)
+                + route.key())
 
     def step(self, slot, lengths: Sequence[int], on_device: bool = False):
         """One step on the bags packed at the front of slot.x.  on_device: the lengths already sit in slot.len_dev (the

@@ -110,9 +110,9 @@ def test_the_switch_keyword_then_attribute_then_environment(monkeypatch):
         else:
             monkeypatch.setenv("MIL_TM_DETERMINISTIC", env)
         assert ops.tm_deterministic(kw) is bool(kw if kw is not None else env == "1"), (kw, env)
-    # the attribute is what the module hands to every op as the keyword (None: the op reads the environment, above).  The ops
-    # are replaced by shape-only stand-ins that note it: one eval forward on the CPU reaches the sequence gather, both
-    # layers' pad gather and core, and PPEG.
+    # the module resolves the switch once per forward - the attribute, else the environment as it stands at that call - and
+    # hands every op that one bool as the keyword.  The ops are replaced by shape-only stand-ins that note it: one eval forward
+    # on the CPU reaches the sequence gather, both layers' pad gather and core, and PPEG.
     net = TransMIL(n_classes=2, L=768).eval()
     assert net.deterministic is None
     seen = []
@@ -134,11 +134,14 @@ def test_the_switch_keyword_then_attribute_then_environment(monkeypatch):
     monkeypatch.setattr(ops, "tm_ppeg", ppeg)
     monkeypatch.setattr(ops, "layer_norm", lambda x, w, b, eps: x)
     monkeypatch.setattr(ops, "linear_act", lambda x, W, b, act=None, residual=None, rows_dev=None: torch.zeros((x.shape[0], W.shape[0])))
-    for attr in (None, True, False):
+    for attr, env in itertools.product((None, True, False), ("0", "1")):
         net.deterministic = attr
+        monkeypatch.setenv("MIL_TM_DETERMINISTIC", env)
+        want = attr if attr is not None else env == "1"
         seen.clear()
         net(torch.zeros((7, 768)), [7])
-        assert seen == [(k, attr) for k in ("gather", "gather", "core", "ppeg", "gather", "core")], (attr, seen)
+        assert seen == [(k, want) for k in ("gather", "gather", "core", "ppeg", "gather", "core")], (attr, env, seen)
+        assert all(v is want for _, v in seen)                          # a bool, never None: no op reads the environment again
 
 
 def test_ops_take_the_keyword():

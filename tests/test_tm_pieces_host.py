@@ -49,9 +49,19 @@ def test_keyword_attribute_and_environment(monkeypatch):
     assert inspect.signature(ops.nystrom_core).parameters["pieces"].default is None
     assert inspect.signature(ops._tm_fwd).parameters["pieces"].default == 0
     assert inspect.signature(ops._tm_pinv_bwd).parameters["pieces"].default == 0
-    assert "gemm_pieces" in inspect.signature(TransLayer.run).parameters
-    assert TransMIL(2).gemm_pieces is None
+    assert "route" in inspect.signature(TransLayer.run).parameters      # the layer takes the step's resolved route ...
+    net = TransMIL(2)
+    assert net.gemm_pieces is None
     monkeypatch.delenv("MIL_TM_PIECES", raising=False)
+    assert ops.tm_route(net, 1, False).pieces == 0                      # ... which carries the attribute, else the environment
+    net.gemm_pieces = 3
+    assert ops.tm_route(net, 1, False).pieces == 3 and ops.tm_route(net, 2, "cls").pieces == 3
+    monkeypatch.setenv("MIL_TM_PIECES", "3")
+    net.gemm_pieces = None
+    assert ops.tm_route(net, 1, True).pieces == 3
+    net.gemm_pieces = 0
+    assert ops.tm_route(net, 1, True).pieces == 0
+    monkeypatch.delenv("MIL_TM_PIECES")
     assert ops.tm_pieces() == 0 and ops.tm_pieces(3) == 3 and ops.tm_pieces(0) == 0
     monkeypatch.setenv("MIL_TM_PIECES", "3")
     assert ops.tm_pieces() == 3 and ops.tm_pieces(0) == 0               # the keyword wins over the environment
