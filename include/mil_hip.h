@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 22 */
+int mil_abi_version(void);   /* 23 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -268,6 +268,13 @@ int mil_attn_pool_bwd(const float* x, const float* scores, const float* lse, con
  * row_off [B + 1]; scores and w cover row_off[B] rows.  len_dev [B] (nullable): the true length of bag b on the device - the
  * rows behind it inside the bag's slot get 0.  One workgroup per bag, sums in a fixed order. */
 int mil_bag_softmax(const float* scores, const int32_t* row_off, const int32_t* len_dev, int B, float* w, void* stream);
+
+/* The same weights over a capacity bucket (ABI 23; mil_build_fusion_segs_tail): scores and w cover the R = cap + B sum(tail)
+ * rows of the bucket's multi-modal bag buffer, bag b's rows are those of its tiles [bag_tile_off[b], bag_tile_off[b + 1]) of
+ * tile_map [T][4] = {bag, row0, nrows, 0}, and row_bag [R] is -1 on the padding rows, which get 0.  w[r] = exp(s_r - lse[bag(r)]).
+ * Everything is read on the device; one workgroup per bag, max and sum in an order the map fixes (no atomics).  B <= 1024. */
+int mil_bag_softmax_rows(const float* scores, const int32_t* tile_map, const int32_t* bag_tile_off, int T,
+                         const int32_t* row_bag, int B, int R, float* w, void* stream);
 
 /* Gate parameter gradients from the saved gates and ds:
  * dWv = dPreV^T x, dWu = dPreU^T x, dbv, dbu, dw = sum_i ds_i V_i U_i, db = sum_i ds_i,

@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -28,6 +28,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "mil_gate_scores_fwd_draw": (c_int, [_P] * 9 + [c_int, c_int, c_int, _P, c_float, _P, c_int, c_uint64, c_uint64, c_uint64, _P, _P]),
     "mil_attn_pool_fwd": (c_int, [_P] * 4 + [c_int, c_int, c_int, _P, _P, _P, _P, c_float, _P]),
     "mil_bag_softmax": (c_int, [_P] * 3 + [c_int, _P, _P]),
+    "mil_bag_softmax_rows": (c_int, [_P] * 3 + [c_int, _P, c_int, c_int, _P, _P]),
     "mil_attn_pool_partial": (c_int, [_P] * 3 + [c_int, c_int, _P, _P, c_float, _P]),
     "mil_attn_pool_partial_h": (c_int, [_P] * 3 + [c_int, c_int, _P, _P, c_int, _P, _P, c_float, _P, c_float, _P]),
     "mil_attn_pool_bwd_from_h": (c_int, [_P] * 6 + [c_int, c_int, _P, _P]),

@@ -107,7 +107,17 @@ def create_arg_parser(argv=None):
                    "--fusion_transmil 1: bag [2, 8, N + P] = layers x heads x rows, the cls token's attention to each row of the "
                    "multi-modal bag, a repeated row's two keys summed, patches first).  The flag switches --hip_graph off: "
                    "with --hip_graph 1 the evaluation runs the eager forward, not the replayed one.  The files are written when "
-                   "the run ends")
+                   "the run ends.  With --note_attn_scope all also --modality \"['CT']\" and \"['CT','pathology']\", and "
+                   "--hip_graph 1 (stays on) or --fusion_transmil_graph 1: the weights come out of the replayed forward.  With CT "
+                   "the file gains note_ct [3, P, 8, D], the note's weights over the D CT tokens at the three sites of the "
+                   "transformer's CT pass; note is there only with pathology; bag covers the whole multi-modal bag in memory "
+                   "order: [D + P] (CT tokens, text tokens) or [N + P + D + P] (patches, CT-side text tokens, CT tokens, "
+                   "pathology-side text tokens), [2, 8, that] with the TransMIL aggregator")
+    p.add_argument("--note_attn_scope", type=str, default="pathology", choices=["pathology", "all"],
+                   help="what --save_note_attn covers.  pathology: --modality \"['pathology']\" on the eager forward (model.note_attn "
+                        "= True).  all: wherever the token->image sites run on the absorbed pools - CT in the modality, the "
+                        "capacity-bucket forwards and the replayed evaluation (model.note_attn = 'all'); --modality \"['CI']\" and "
+                        "--variant image_only stay refused")
     p.add_argument("--flat_adam", type=int, default=1, help="autograd path: parameters in one flat buffer, one gradient "
                    "all-reduce and one Adam launch per step (optim.FlatAdam); 0 = torch DDP + torch.optim.Adam")
     p.add_argument("--fusion_transmil", type=int, default=0, help="--variant fusion: 1 = build --aggregator TransMIL (and "
@@ -177,16 +187,18 @@ def create_arg_parser(argv=None):
         if args.learnablePrompt:
             raise ValueError("--fusion_transmil_graph 1: learnable prompts (their SGD inside the graph) are not built, "
                              "drop --learnablePrompt 1")
-        if args.save_note_attn:
-            raise ValueError("--fusion_transmil_graph 1 keeps no attention weights: drop --save_note_attn")
+        if args.save_note_attn and args.note_attn_scope != "all":
+            raise ValueError("--fusion_transmil_graph 1 keeps no attention weights: drop --save_note_attn "
+                             "(or ask for them from the replayed forward: --note_attn_scope all)")
     if args.save_patch_attn and (args.variant != "image_only" or args.model_pathology != "TransMIL"):
         # refused here, before an entry point touches the GPU
         raise ValueError("--save_patch_attn writes TransMIL's cls-token attention: it needs --variant image_only "
                          "--model_pathology TransMIL (ABMIL keeps its scores in extractor_pathology.last_scores)")
-    if args.save_note_attn and (args.variant != "fusion" or list(args.modality) != ["pathology"]):
+    wide = args.note_attn_scope == "all" and list(args.modality) in (["CT"], ["CT", "pathology"])
+    if args.save_note_attn and (args.variant != "fusion" or (list(args.modality) != ["pathology"] and not wide)):
         raise ValueError("--save_note_attn writes the note's attention over the patches: it needs --variant fusion "
                          "--modality \"['pathology']\"")
-    if args.save_note_attn and args.hip_graph:
+    if args.save_note_attn and args.hip_graph and args.note_attn_scope != "all":
         # the weights come out of the eager forward (model.note_attn), not the replayed one: test_ddp.py then takes its
         # op-by-op evaluation loop
         args.hip_graph = 0

@@ -427,3 +427,62 @@ extern "C" int mil_bag_softmax(const float* scores, const int32_t* row_off, cons
     MIL_CHECK_LAUNCH();
     return MIL_OK;
 }
+
+// The same weights over a CAPACITY BUCKET (segments.FusionBucket): a bag's rows are scattered - its patch rows inside the
+// `cap` block, one piece per tail segment behind it - and its length lives on the device, so the rows of bag b are named by
+// its tiles [bag_tile_off[b], bag_tile_off[b + 1]) of the bucket's 32-row map {bag, row0, nrows, 0}.  Workgroup b < B walks
+// those tiles twice (eight tiles per sweep, one row per thread): per-thread online (max, sum), merged over the wave and then
+// over the four waves in wave order - the order is fixed by the map alone, the same bits every run -, then the weights.
+// Workgroups >= B write the 0 of the rows no bag owns (row_bag < 0): no tile names them, so no row has two writers.
+__global__ __launch_bounds__(256) void k_bag_softmax_rows(const float* __restrict__ scores, const int32_t* __restrict__ tile_map,
+                                                          const int32_t* __restrict__ bag_tile_off, int T,
+                                                          const int32_t* __restrict__ row_bag, int B, int R,
+                                                          float* __restrict__ w) {
+    __shared__ float m_lds[4], l_lds[4];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= B) {
+        const int nz = gridDim.x - B;
+        for (int r = ((int)blockIdx.x - B) * 256 + tid; r < R; r += nz * 256)
+            if (row_bag[r] < 0) w[r] = 0.f;
+        return;
+    }
+    const int b = blockIdx.x;
+    const int t0 = max(bag_tile_off[b], 0), t1 = min(bag_tile_off[b + 1], T);
+    const int sub = tid / MIL_POOL_TILE, lane = tid % MIL_POOL_TILE;
+    constexpr int SWEEP = 256 / MIL_POOL_TILE;
+    float m = -INFINITY, l = 0.f;
+    for (int t = t0 + sub; t < t1; t += SWEEP) {
+        const int4 tm = reinterpret_cast<const int4*>(tile_map)[t];
+        const int row = tm.y + lane;
+        if (lane < tm.z && row >= 0 && row < R) {
+            const float s = scores[row];
+            if (s > m) { l = l * expf(m - s) + 1.0f; m = s; }
+            else l += expf(s - m);
+        }
+    }
+    const float mw = wave_allmax(m);
+    l = wave_allsum(m == -INFINITY ? 0.f : l * expf(m - mw));
+    if ((tid & 63) == 0) { m_lds[tid >> 6] = mw; l_lds[tid >> 6] = l; }
+    __syncthreads();
+    const float mt = fmaxf(fmaxf(m_lds[0], m_lds[1]), fmaxf(m_lds[2], m_lds[3]));
+    float lt = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) lt += m_lds[k] == -INFINITY ? 0.f : l_lds[k] * expf(m_lds[k] - mt);
+    const float inv = 1.0f / lt;
+    for (int t = t0 + sub; t < t1; t += SWEEP) {
+        const int4 tm = reinterpret_cast<const int4*>(tile_map)[t];
+        const int row = tm.y + lane;
+        if (lane < tm.z && row >= 0 && row < R) w[row] = expf(scores[row] - mt) * inv;
+    }
+}
+
+extern "C" int mil_bag_softmax_rows(const float* scores, const int32_t* tile_map, const int32_t* bag_tile_off, int T,
+                                    const int32_t* row_bag, int B, int R, float* w, void* stream) {
+    if (!scores || !tile_map || !bag_tile_off || !row_bag || !w || B < 0 || B > 1024 || T < 0 || R < 0) return MIL_EINVAL;
+    if (B == 0 || R == 0) return MIL_OK;
+    const int nz = min((R + 255) / 256, 64);
+    hipLaunchKernelGGL(k_bag_softmax_rows, dim3(B + nz), dim3(256), 0, (hipStream_t)stream, scores, tile_map, bag_tile_off, T,
+                       row_bag, B, R, w);
+    MIL_CHECK_LAUNCH();
+    return MIL_OK;
+}

@@ -138,6 +138,13 @@ class RaggedFusionStepper:
         return self.gs.run(key, (), body, after_backward=self.opt.step)
 
 
+def _exports_note_attn(model, backward: bool) -> bool:
+    """The evaluation forward of a model whose note_attn scope is "all": the stepper's body also runs the export's launches
+    (aggregator._note_device) and returns their capacity-shaped results, so they are static outputs of the key's graph; step()
+    slices them by the call's host lengths afterwards (aggregator.note_attn_finish).  Never with backward."""
+    return (not backward) and (not model.training) and getattr(model, "note_attn", False) == "all"
+
+
 class RaggedFusionTransMILStepper:
     """The same regime for the fusion model with the TransMIL aggregator (`--aggregator TransMIL --fusion_transmil 1`, the
     authors' own run), training step or evaluation forward.  The branch in front of the aggregator follows the capacity bucket
@@ -217,6 +224,7 @@ class RaggedFusionTransMILStepper:
         cap = DEFAULT_MAX_GRAPHS if max_graphs is None else int(max_graphs)
         self.gs = GraphedStep(params, max_graphs=cap if self.use_graph else 0, share_pool=True, backward=self.backward)
         self.last = None
+        self._note_metas: dict = {}                         # per key: how the export's tensors of that graph are laid out
 
     @property
     def replays(self):
@@ -246,12 +254,18 @@ class RaggedFusionTransMILStepper:
     def key(self, cap: int, lengths: Sequence[int]) -> tuple:
         agg = self.model.aggregator
         from . import ops
-        route = ops.tm_route(agg, len(lengths), False)      # the route the aggregator's flat_bucket resolves for this step
+        note = _exports_note_attn(self.model, self.backward)
+        # the route the aggregator's flat_bucket resolves for this step; a forward that exports the attention (scope "all")
+        # runs the cls route and more launches behind it: it never shares a key with one that does not
+        route = ops.tm_route(agg, len(lengths), "cls" if note else False)
         # this key has carried "cls" wherever it carries "packed" and packed_cls is on, although the graph step never asks for
         # attention; that is not what the route says, so it is added here and existing keys stay what they were
         cls = ("cls",) if route.bags == "packed" and ops.tm_packed_cls(agg.packed_cls) else ()
         return (("fusion-transmil", int(cap), self.sides(lengths), bool(self.model.training), bool(agg.training), self.backward)
-                + route.key() + cls)
+                + route.key() + cls + (("note_attn", "all") if note else ()))
+
+    def _note_scope(self) -> bool:
+        return _exports_note_attn(self.model, self.backward)
 
     def encode_notes(self, slot, ids):
         """Frozen text tower on this step's notes (token ids [B, P, ctx]) -> slot.text; outside the graph."""
@@ -281,6 +295,8 @@ class RaggedFusionTransMILStepper:
                 res += list(pair)
         if m.last_head_bits is not None:
             res.append(m.last_head_bits)
+        if m._note_meta is not None:                       # scope "all": the export's tensors, last
+            res += list(m._note_tensors)
         return tuple(res)
 
     def step(self, slot, lengths: Sequence[int], on_device: bool = False):
@@ -297,6 +313,7 @@ class RaggedFusionTransMILStepper:
             geom = self.geoms[key[1:3]] = BucketGeometry(slot.cap, self.tail, key[2], self.device, self._pad_cache, self.flag)
         m = self.model
         body = lambda: self._body(slot, geom)      # noqa: E731
+        m._note_meta = None                        # set by a pass of the body that exports; a replay runs none
         ctr = m.aggregator._drop_ctr
         from . import ops
         # the warm-up passes in front of a capture draw masks too: the pass counter goes back, so the stream of a replayed
@@ -313,6 +330,11 @@ class RaggedFusionTransMILStepper:
         nt = self.ntok
         self.last = dict(h=out[2], logits=out[3], tokens=list(out[4:4 + nt]),
                          bits=list(out[4 + nt:]) if m.aggregator.training else None)
+        if self._note_scope():
+            if m._note_meta is not None:
+                self._note_metas[key] = m._note_meta
+            meta = m._note_meta = self._note_metas[key]
+            m.note_attn_finish(lengths, out[len(out) - meta["count"]:])
         return out[0], out[1]
 
     def pool_bytes(self) -> int:
@@ -384,17 +406,32 @@ class RaggedFusionInference:
         else:
             out = self.model(xs, None, text_features=slot.text, bucket=slot.bucket)
         prob = out[0][0] if isinstance(out[0], list) else out[0]
-        return prob
+        m = self.model
+        if m._note_meta is None:
+            return prob
+        return (prob, m._note_meta, *m._note_tensors)      # scope "all": the export's tensors are outputs of the forward
+
+    def _finish(self, out, lengths):
+        """prob of a pass of the body; with the export (model.note_attn = "all") the per-bag slicing by this call's lengths."""
+        if not isinstance(out, tuple):
+            return out
+        self.model._note_meta = out[1]
+        self.model.note_attn_finish(lengths, out[2:])
+        return out[0]
 
     @torch.no_grad()
     def forward(self, slot, lengths: Sequence[int], on_device: bool = False):
         slot.bucket.set_lengths(lengths, on_device=on_device)
-        ent = self._graphs.get(slot.cap)
+        m = self.model
+        m._note_meta = None
+        # a forward that exports the attention runs more launches: it has graphs of its own
+        key = (slot.cap, "note_attn", "all") if (m.note_attn == "all" and not m.training) else slot.cap
+        ent = self._graphs.get(key)
         if ent is None:
-            n = self._seen[slot.cap] = self._seen.get(slot.cap, 0) + 1
+            n = self._seen[key] = self._seen.get(key, 0) + 1
             if not self.use_graph or n < 2:
                 self.eager += 1
-                return self._body(slot)
+                return self._finish(self._body(slot), lengths)
             from . import lifetime
             cur = torch.cuda.current_stream()
             with lifetime.recording() as keep:
@@ -405,7 +442,7 @@ class RaggedFusionInference:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=self.stream):
                     prob = self._body(slot)
-            ent = self._graphs[slot.cap] = (g, prob, keep)
+            ent = self._graphs[key] = (g, prob, keep)
         ent[0].replay()
         self.replays += 1
-        return ent[1]
+        return self._finish(ent[1], lengths)

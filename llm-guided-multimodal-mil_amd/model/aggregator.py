@@ -111,10 +111,24 @@ class aggregator(nn.Module):
         #       x heads x rows: the cls token's attention to each row of the bag (a repeated row's two keys summed, not
         #       renormalised; ops.tm_cls_attention), in the same patches-first order.
         # Off: the forward issues exactly the launches it always did and both stay None.  The returned tuple never changes.
+        # note_attn = "all" (True keeps the scope above, and its refusals): the same export wherever the three token->image
+        # sites run on the absorbed one-token / multi-token pools - CT in the modality, the capacity-bucket forwards, the
+        # replayed evaluation.  It adds
+        #   last_note_attn_ct[site][bag]  [8, D] ([P, 8, D]): the note's weights over the D CT tokens at the three sites of the
+        #       transformer that ran the CT side (TwoWayTransformer_CT; the first pass through TwoWayTransformer_Both with
+        #       pathology beside it - last_note_attn then comes from the second pass; None for ['CT'] alone);
+        #   last_bag_attn[bag] over the bag's rows in memory order: [D + P] for ['CT'] (CT tokens, text tokens),
+        #       [N_b + P + D + P] for CT + pathology (patches, CT-side text tokens, CT tokens, pathology-side text tokens).
+        # The work is split in two: the launches run inside the forward, read nothing from the host and leave their results in
+        # capacity shape (_note_device: capture-safe, a graph's static outputs); note_attn_finish(lengths) slices them per bag
+        # by the step's host lengths afterwards.  A forward without bucket= calls both; with bucket= the caller calls the second
+        # (fusion_step.RaggedFusionInference / RaggedFusionTransMILStepper do, after the replay).
         self.note_attn = False
         self.last_note_attn = None
+        self.last_note_attn_ct = None
         self.last_bag_attn = None
         self._tm_bag_attn = None
+        self._note_ctx, self._note_meta, self._note_tensors = None, None, None
         self._tm_geom, self._tm_len_dev = None, None       # set per forward from bucket.tm_geom (the replayed TransMIL step)
         self.last_head_bits = None
         # graph_eval (train_ddp.build_model sets it for --fusion_transmil_graph 1): an eval-mode, no-grad forward of ONE bag
@@ -131,7 +145,8 @@ class aggregator(nn.Module):
         THE DEVICE (note [3, P, 8, N] and bag [N + P] - [2, 8, N + P] with a TransMIL aggregator - per bag), and flush_note_attn() - registered to run when the process
         ends - copies them to the host and writes DIR/<names[i] or i>.npz, float32, bags numbered in the order they ran: an
         entry point that times each forward has no host copy and no file inside its bracket.  Beyond NOTE_KEEP_BYTES kept, a
-        forward flushes first."""
+        forward flushes first.  Under note_attn = "all" with CT in the modality the file gains note_ct [3, P, 8, D], note is
+        there only with pathology, and bag covers the whole multi-modal bag in memory order."""
         import atexit
         import os
         os.makedirs(directory, exist_ok=True)
@@ -142,24 +157,113 @@ class aggregator(nn.Module):
     def flush_note_attn(self):
         import os
         import numpy as np
-        for note, bag in self._note_kept:
+        for kept in self._note_kept:
             i = self._note_done
             name = str(self._note_names[i]) if self._note_names is not None and i < len(self._note_names) else str(i)
-            np.savez(os.path.join(self._note_dir, name + ".npz"), note=note.float().cpu().numpy(), bag=bag.float().cpu().numpy())
+            np.savez(os.path.join(self._note_dir, name + ".npz"),
+                     **{k: v.float().cpu().numpy() for k, v in zip(("note", "bag", "note_ct"), kept) if v is not None})
             self._note_done += 1
         self._note_kept = []
 
     def _keep_note_attn(self):
-        if self._note_dir is None or self.last_note_attn is None or self.last_bag_attn is None:
+        if self._note_dir is None or self.last_bag_attn is None or (self.last_note_attn is None
+                                                                    and self.last_note_attn_ct is None):
             return
-        if sum(n.numel() + b.numel() for n, b in self._note_kept) * 4 > self.NOTE_KEEP_BYTES:
+        if sum(t.numel() for kept in self._note_kept for t in kept if t is not None) * 4 > self.NOTE_KEEP_BYTES:
             self.flush_note_attn()
+        stack = lambda sites, b: torch.stack([site[b].reshape(-1, 8, site[b].shape[-1]) for site in sites])   # noqa: E731
         for b, bag in enumerate(self.last_bag_attn):
-            note = torch.stack([site[b].reshape(-1, 8, site[b].shape[-1]) for site in self.last_note_attn])
-            self._note_kept.append((note, bag.clone()))
+            note = stack(self.last_note_attn, b) if self.last_note_attn is not None else None
+            if self.last_note_attn_ct is None:
+                self._note_kept.append((note, bag.clone()))
+            else:                                          # note_ct [3, P, 8, D]; stack() copies, like note
+                self._note_kept.append((note, bag.clone(), stack(self.last_note_attn_ct, b)))
 
     def _wants_note_attn(self) -> bool:
         return bool(self.note_attn) and not self.training and not torch.is_grad_enabled()
+
+    def _note_all(self) -> bool:
+        return isinstance(self.note_attn, str) and self.note_attn == "all"
+
+    def _note_device(self, sites):
+        """note_attn = "all", inside the forward: the weights of the token->image sites from what their kernels held (three
+        records per branch, in the order the branches ran) - one mil_absorbed_pool_attn launch per one-token site, the
+        softmaxed score matrix the multi-token pool holds anyway - and the aggregator's weights (ABMIL: ops.bag_softmax of its
+        scores; TransMIL: the cls attention _pool_head asked for).  Nothing here reads the host; every tensor keeps the shape
+        of its buffer (a capacity bucket: zeros behind the bags).  Leaves (_note_meta, _note_tensors) for note_attn_finish."""
+        ctx = self._note_ctx
+        if len(sites) != 3 * len(ctx["branches"]):
+            raise NotImplementedError(f"note_attn: {len(sites)} of the {3 * len(ctx['branches'])} token->image attention sites "
+                                      "(three per branch) ran on the absorbed one-token / multi-token pool; the general "
+                                      "attention_pool route keeps no weights")
+        tensors, TH = [], []
+        for rec in sites:
+            if "A" in rec:          # P = 2 .. 12: the softmaxed score matrix [rows, P 8 (+ padding)], column t 8 + h
+                tensors.append(rec["A"])
+                TH.append(int(rec["TH"]))
+            else:
+                tensors.append(ops.absorbed_pool_attention(rec["keys"], rec["pe"], rec["Qp"], rec["lse"], rec["segs"], rec["C"]))
+                TH.append(8)
+        meta = dict(ctx, TH=TH, bag=None)
+        agg = getattr(self, "aggregator", None)
+        if self._is_transmil():
+            if ctx["cap"] is None:                         # host lengths: _pool_head has sliced and reordered already
+                meta["bag"] = "final"
+                tensors += list(self._tm_bag_attn)
+            else:                                          # [attn0, attn1], each one static [8, s_b^2] per bag
+                meta["bag"] = "transmil"
+                tensors += list(self._tm_bag_attn[0]) + list(self._tm_bag_attn[1])
+        elif agg is not None and getattr(agg, "last_scores", None) is not None:
+            meta["bag"] = "rows" if ctx["cap"] is not None else "bags"
+            tensors.append(ops.bag_softmax(agg.last_scores, ctx["layout"]))
+        meta["count"] = len(tensors)
+        self._note_meta, self._note_tensors = meta, tensors
+
+    def note_attn_finish(self, lengths=None, tensors=None):
+        """note_attn = "all", after the forward: slice what _note_device left per bag.  lengths: the step's patch counts on the
+        host (the capacity-bucket forwards; a forward without bucket= has called this itself).  tensors: the static outputs
+        of a replayed graph standing in for the tensors of the pass that was captured.  Views only - _keep_note_attn clones."""
+        meta = self._note_meta
+        if meta is None:
+            return
+        ts = list(tensors) if tensors is not None else self._note_tensors
+        B, P, D, cap, tail = meta["B"], meta["P"], meta["D"], meta["cap"], meta["tail"]
+        n_len = [int(n) for n in (lengths if lengths is not None else meta["n_len"] or [])]
+        if "pth" in meta["branches"] and len(n_len) != B:
+            raise ValueError(f"note_attn_finish: {B} bags, lengths {n_len}")
+        offs = dict(ct=_offsets([D] * B), pth=_offsets(n_len))
+        out = {}
+        for i, br in enumerate(meta["branches"]):
+            off, sites = offs[br], []
+            for X, TH in zip(ts[3 * i:3 * i + 3], meta["TH"][3 * i:3 * i + 3]):
+                per = [X[off[b]:off[b + 1], :TH].t() for b in range(B)]
+                sites.append([a.reshape(P, TH // P, -1) for a in per] if P > 1 else per)
+            out[br] = sites
+        self.last_note_attn, self.last_note_attn_ct = out.get("pth"), out.get("ct")
+        bag = ts[3 * len(meta["branches"]):]
+        T = sum(tail)                                      # the static rows behind a bag's patches
+        off = offs["pth"] if n_len else [0] * (B + 1)
+        if meta["bag"] == "final":
+            self.last_bag_attn = bag
+        elif meta["bag"] == "bags":
+            self.last_bag_attn = list(torch.split(bag[0], list(meta["layout"].lengths)))
+        elif meta["bag"] == "rows":
+            # the bucket's rows: [cap patch rows | segment 0 of every bag | segment 1 of every bag | ..]
+            w, base = bag[0], cap
+            pieces = [[w[off[b]:off[b + 1]]] for b in range(B)]
+            for rows in tail:
+                for b in range(B):
+                    pieces[b].append(w[base + b * rows:base + (b + 1) * rows])
+                base += B * rows
+            self.last_bag_attn = [torch.cat(p) for p in pieces]
+        elif meta["bag"] == "transmil":
+            # sequence order of the bucket form: [tail segments | patches]; exported: patches first
+            self.last_bag_attn = []
+            for b in range(B):
+                a = torch.stack([bag[b], bag[B + b]])      # [2, 8, s_b^2]: layers x heads x sequence rows
+                n = off[b + 1] - off[b]
+                self.last_bag_attn.append(torch.cat([a[..., T:T + n], a[..., :T]], -1))
+        self._keep_note_attn()
 
     def _note_attention(self, sites, n_len, P, layout):
         """After the forward: the weights of the three token->image sites from what their kernels held (`sites`,
@@ -243,8 +347,9 @@ class aggregator(nn.Module):
         geom = self._tm_geom
         if self._is_transmil() and geom is not None:
             # the capacity-bucket form (fusion_step.RaggedFusionTransMILStepper): lengths on the device, sides from the key
-            M, _ = self.aggregator.flat_bucket(x0, geom, self._tm_len_dev)
-            self._tm_bag_attn = None
+            want = self._wants_note_attn()                 # scope "all": any other has raised in _forward
+            M, attn = self.aggregator.flat_bucket(x0, geom, self._tm_len_dev, need_attn="cls" if want else False)
+            self._tm_bag_attn = attn if want else None
         elif self._is_transmil():
             # TransMIL returns (h, attn); element 0 feeds fc.  need_attn="cls" only under note_attn (eval, no grad)
             want = self._wants_note_attn()
@@ -289,6 +394,7 @@ class aggregator(nn.Module):
                                                   keys_tail_rows=B * P)                       # :179
             x0 = ops.append_rows(k, q, tail_reserved=True)                                    # :184
             layout = BagLayout.two_segment([D] * B, [P] * B, dev)
+            self._note_ctx = dict(branches=["ct"], B=B, P=P, D=D, cap=None, tail=[], n_len=None, layout=layout)
             segs = [[(B * D + b * P, P), (b * D, D)] for b in range(B)] if self._is_transmil() else None   # :184
             return self._pool_head(x0, layout, segs), q.view(B, P, EMBED)                     # :204-205
         x = x_list[1]
@@ -312,6 +418,7 @@ class aggregator(nn.Module):
         # the last LayerNorm wrote it, the small blocks are appended, the tile map says which rows form a bag.
         x0 = ops.append_rows(k_p, torch.cat([q_ct, k_ct, q_p], 0), tail_reserved=True)
         layout = BagLayout.multi_segment([n_len, [P] * B, [D] * B, [P] * B], dev)
+        self._note_ctx = dict(branches=["ct", "pth"], B=B, P=P, D=D, cap=None, tail=[P, D, P], n_len=n_len, layout=layout)
         segs = None
         if self._is_transmil():
             R, off = sum(n_len), _offsets(n_len)
@@ -335,6 +442,8 @@ class aggregator(nn.Module):
         q, k = self.TwoWayTransformer_Pth.flat(xi, point, self.pe_rows(bucket.cap, xi.device), None, None,
                                                keys_tail_rows=B * P, segs=(bucket.s_tt, bucket.s_ti, bucket.s_it))
         x0 = ops.append_rows(k, q, tail_reserved=True)                                     # :192 (no concat copy)
+        self._note_ctx = dict(branches=["pth"], B=B, P=P, D=0, cap=bucket.cap, tail=list(bucket.tail), n_len=None,
+                              layout=bucket.layout)
         return self._pool_head(x0, bucket.layout, None), q.view(B, P, EMBED)               # :198-200,207
 
     def _forward_ct_bucket(self, x_list, t, bucket):
@@ -362,6 +471,8 @@ class aggregator(nn.Module):
         q_p, k_p = tw.flat(xi, self._lin_tanh(self.fc_CI2Pth, tflat), self.pe_rows(bucket.cap, dev), None, None,
                            keys_tail_rows=bucket.tail_rows, segs=(bucket.s_tt, bucket.s_ti, bucket.s_it))
         x0 = ops.append_rows(k_p, torch.cat([q_ct, k_ct, q_p], 0), tail_reserved=True)        # :173 (no concat of the patches)
+        self._note_ctx = dict(branches=["ct", "pth"], B=B, P=P, D=D, cap=bucket.cap, tail=list(bucket.tail), n_len=None,
+                              layout=bucket.layout)
         return self._pool_head(x0, bucket.layout, None), q_ct.view(B, P, EMBED), q_p.view(B, P, EMBED)
 
     def _graph_eval_forward(self, x_list, x_CI):
@@ -419,6 +530,15 @@ class aggregator(nn.Module):
             return [out[0], out[0], out[0]], [out[1], out[2]], None
         return out[0], out[1], None
 
+    def _forward_branch(self, x_list, t, lengths, bucket):
+        """The CT branches and the capacity-bucket forms."""
+        modality = self.args.modality
+        if "CT" in modality and "pathology" in modality and bucket is not None:
+            return self._forward_ct_bucket(x_list, t, bucket)
+        if "CT" in modality:
+            return self._forward_ct(x_list, t, lengths)
+        return self._forward_bucket(x_list[0], t, bucket)
+
     def _forward(self, x_list: List[torch.Tensor], x_CI: torch.Tensor, lengths: Optional[List[int]] = None,
                  text_features: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
                  loss_scale: Optional[float] = None, bucket=None):
@@ -429,7 +549,7 @@ class aggregator(nn.Module):
         # train_ddp.py:323-324 evaluated inside, result in `self.last_loss` (mean loss unless loss_scale is given);
         # the return tuple is unchanged
         if (self.graph_eval and bucket is None and not self.training and not torch.is_grad_enabled() and lengths is None
-                and text_features is None and labels is None and not self._wants_note_attn()):
+                and text_features is None and labels is None and (not self._wants_note_attn() or self._note_all())):
             out = self._graph_eval_forward(x_list, x_CI)
             if out is not None:
                 return out
@@ -448,20 +568,31 @@ class aggregator(nn.Module):
                              f"{self._tm_geom.B} bags x {self._tm_geom.cap} rows, tail {list(self._tm_geom.tail)}")
         want = self._wants_note_attn()
         if want:
-            self.last_note_attn = self.last_bag_attn = None
-            if "CT" in modality or bucket is not None:
+            self.last_note_attn = self.last_note_attn_ct = self.last_bag_attn = None
+            self._note_meta = self._note_tensors = None
+            if self.note_attn is not True and not self._note_all():
+                raise ValueError(f"note_attn must be False, True or 'all', got {self.note_attn!r}")
+            if self._note_all() and _arg(self.args, "alignment_base", "CI") == "CT":
+                raise NotImplementedError("note_attn: with alignment_base='CT' the token->image sites run on the general "
+                                          "attention_pool route, which keeps no weights")
+            if not self._note_all() and ("CT" in modality or bucket is not None):
                 raise NotImplementedError("note_attn is built for modality ['pathology'] (or ['CI']) on host-side bag lengths: "
                                           "the CT branches and the capacity-bucket forward keep no attention weights")
         # text_features [B, P, 512] (optional): embeddings of the frozen text tower computed earlier by
         # `self.clinic_extractor(x_CI)`; lets a captured hipGraph replay the trainable part only
         t = text_features if text_features is not None else self.clinic_extractor(x_CI)   # :151  [B, P, 512]
         B, P, _ = t.shape
-        if "CT" in modality and "pathology" in modality and bucket is not None:
-            return self._forward_ct_bucket(x_list, t, bucket)
-        if "CT" in modality:
-            return self._forward_ct(x_list, t, lengths)
-        if "pathology" in modality and bucket is not None:
-            return self._forward_bucket(x_list[0], t, bucket)
+        if want and ("CT" in modality or ("pathology" in modality and bucket is not None)):
+            # scope "all": the branch under the site tap, then the device part; the slicing by host lengths follows at once
+            # on host-side lengths and is the caller's with a bucket (note_attn_finish)
+            with ops.note_sites() as sites:
+                out = self._forward_branch(x_list, t, lengths, bucket)
+            self._note_device(sites)
+            if bucket is None:
+                self.note_attn_finish()
+            return out
+        if "CT" in modality or ("pathology" in modality and bucket is not None):
+            return self._forward_branch(x_list, t, lengths, bucket)
         if "pathology" in modality:
             x = x_list[0]
             if x.dim() == 2:

@@ -442,7 +442,7 @@ class TransMIL(nn.Module):
         idx_dev = ops.tm_seq_index_segs(table, total, R)
         return self._run_bags(h, idx_dev, [geometry(sum(n for _, n in bag)) for bag in segs], need_attn, None)
 
-    def flat_bucket(self, x0: torch.Tensor, geom: BucketGeometry, patch_len_dev: torch.Tensor):
+    def flat_bucket(self, x0: torch.Tensor, geom: BucketGeometry, patch_len_dev: torch.Tensor, need_attn=False):
         """flat_segments() in its capture-safe form, for a step replayed from a hipGraph: x0 [cap + B sum(tail), L] is the
         bucket's multi-modal bag buffer, the patch counts are on the device, the sides come from geom - nothing below touches
         the host.  Rows [sum of the lengths, cap) of x0 hold whatever an earlier step left there; x0 is an autograd intermediate
@@ -451,16 +451,20 @@ class TransMIL(nn.Module):
         entries read as zero rows), _fc1 + ReLU runs over the gathered [sum(1 + s_b^2), L] rows - it is row-wise, so the values
         are those of flat_segments, and a repeated row adds twice in dW as it does through the gather's backward there -, and a
         second gather through the static cls_idx puts the cls token in front of every bag.  No product ever reads a row of x0
-        that no bag names.  Returns (h [B, D], [None, None])."""
+        that no bag names.  Returns (h [B, D], [None, None]); with need_attn="cls" (no other form is offered here) the second is
+        [attn0, attn1], per layer one static [8, s_b^2] tensor per bag in SEQUENCE order - the tail segments, then the patches -
+        with zeros from the bag's length on the device on.  The route is the one ops.tm_route gives for that need_attn."""
+        if not (need_attn is False or (isinstance(need_attn, str) and need_attn == "cls")):
+            raise ValueError(f"TransMIL: flat_bucket offers need_attn False or 'cls', got {need_attn!r}")
         if x0.dim() != 2 or x0.shape[1] != self.L or x0.shape[0] != geom.x_rows:
             raise ValueError(f"TransMIL: flat_bucket wants rows [{geom.x_rows}, {self.L}], got {tuple(x0.shape)}")
         if self.training and (self._drop_seed is None or self._drop_ctr is None or self._drop_ctr.device != x0.device):
             raise ValueError("TransMIL: fix the dropout stream (_drop_state) before a forward with geom")
         geom.update(patch_len_dev)
-        route = ops.tm_route(self, len(geom.sides), False)
+        route = ops.tm_route(self, len(geom.sides), need_attn)
         rows = ops.tm_row_gather(x0, None, geom.idx, route.det)                         # [sum(1 + s^2), L]
         h = ops.linear_act(rows, self._fc1[0].weight, self._fc1[0].bias, "relu")
-        return self._run_bags(h, geom.cls_idx, [side_geometry(s) for s in geom.sides], False, geom, route)
+        return self._run_bags(h, geom.cls_idx, [side_geometry(s) for s in geom.sides], need_attn, geom, route)
 
     def _keep_bits(self, rows: List[int], dev, packed: bool):
         """All bags' keep bits in front of the layers, for the batched and the packed route -> (bits: per bag those of (layer1,

@@ -359,12 +359,29 @@ def _bag_order(layout):
     return hit
 
 
+def _bag_softmax_bucket(scores, layout):
+    """bag_softmax over the multi-modal bag face of a capacity bucket (segments.FusionBucket.layout): the bags' rows are
+    scattered over [cap patch rows | B tail rows per segment] and their lengths live on the device, so the weights come back
+    in the ROW order of the buffer, w [R], 0 on the padding rows (mil_bag_softmax_rows: the bucket's tile map names each bag's
+    rows; nothing is read on the host - capture-safe)."""
+    if scores.numel() != layout.R:
+        raise ValueError(f"bag_softmax: {scores.numel()} scores for a bucket of {layout.R} rows")
+    w = torch.empty_like(scores)
+    _lib.checked().mil_bag_softmax_rows(_p(scores), _p(layout.tile_map), _p(layout.bag_tile_off), layout.T,
+                                        _p(layout.row_bag()), layout.B, layout.R, _p(w), _stream())
+    return w
+
+
 def bag_softmax(scores, layout_or_segs, len_dev=None):
     """The gated-attention pool's weights: w = softmax of `scores` [R] over the rows of each bag (mil_bag_softmax), returned bag
     by bag - bag b at [off[b], off[b] + lengths[b]), off = cumsum of the layout's lengths, its rows in the order they have
     in memory (a two-segment multi-modal bag: its patch rows, then its token rows).  len_dev (int32 [B], on the device): the
-    layout's lengths are slot capacities and bag b has len_dev[b] rows; the rows behind them get 0.  No gradient."""
+    layout's lengths are slot capacities and bag b has len_dev[b] rows; the rows behind them get 0.  A capacity bucket's
+    multi-modal bag face (device lengths, scattered rows): see _bag_softmax_bucket - w in row order.  No gradient."""
     scores = _f32c(scores.detach(), "scores").reshape(-1)
+    if getattr(layout_or_segs, "device_lengths", False) and getattr(layout_or_segs, "lengths", None) is None \
+            and hasattr(layout_or_segs, "bag_tile_off") and hasattr(layout_or_segs, "row_bag"):
+        return _bag_softmax_bucket(scores, layout_or_segs)
     lengths, perm = _bag_order(layout_or_segs)
     if scores.numel() != sum(lengths):
         raise ValueError(f"bag_softmax: {scores.numel()} scores for bags of {sum(lengths)} rows")

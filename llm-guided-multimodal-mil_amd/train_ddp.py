@@ -67,13 +67,17 @@ def build_model(args):
         model.save_patch_attn_to(save, names)
     save = getattr(args, "save_note_attn", "") or ""
     if save:
-        if args.variant != "fusion" or list(args.modality) != ["pathology"]:
+        scope_all = getattr(args, "note_attn_scope", "pathology") == "all"
+        if args.variant != "fusion" or (list(args.modality) != ["pathology"]
+                                        and not (scope_all and list(args.modality) in (["CT"], ["CT", "pathology"]))):
             raise ValueError("--save_note_attn needs --variant fusion --modality \"['pathology']\"")
         names = None
         if getattr(args, "path_data_pathology", ""):
             from .dataset import load_cohort
             names = list(load_cohort(args, "test", 1)[0].keys)
         model.save_note_attn_to(save, names)
+        if scope_all:
+            model.note_attn = "all"                # config.py --note_attn_scope: CT, the bucket forwards, the replayed evaluation
     return model
 
 

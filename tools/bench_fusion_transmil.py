@@ -9,7 +9,11 @@ wall-clock of the host thread, the device idle at the start of every region, plu
 
 --graph: per N, the same eager TransMIL-aggregator step next to the step replayed from its hipGraph
 (fusion_step.RaggedFusionTransMILStepper, counted FlatAdam inside the graph; --fusion_transmil_graph 1), one region = one
-step, and the bytes the graph keeps resident in the stepper's memory pool."""
+step, and the bytes the graph keeps resident in the stepper's memory pool.
+
+--graph_eval: per N, the replayed EVALUATION forward (RaggedFusionTransMILStepper, backward=False; test_ddp.py
+--fusion_transmil_graph 1) with the note-attention export off and with model.note_attn = "all" (the export's launches inside the
+graph, the per-bag slicing behind the replay); one region = --inner forwards, reported per forward."""
 import argparse, json, os, sys, time
 from types import SimpleNamespace
 import torch
@@ -115,6 +119,36 @@ def graph_rows(a, dev):
         print(json.dumps(res), flush=True)
 
 
+def graph_eval_rows(a, dev):
+    from mil_amd.fusion_step import RaggedFusionTransMILStepper
+    ct = torch.randn((1, D_CT, 512), generator=torch.Generator().manual_seed(5)).to(dev)
+    t = torch.randn((1, P, 512), generator=torch.Generator().manual_seed(6)).to(dev)
+    for N in a.N:
+        x = syn.make_bags(N, 1, N, 768).to(dev)
+        res = dict(N=N, rows=N + 2 * P + D_CT, inner=a.inner)
+        for tag, scope in (("off", False), ("all", "all")):
+            torch.manual_seed(1234)
+            model = get_model(make_args("TransMIL", a.clip_layers)).to(dev).eval()
+            model.note_attn = scope
+            st = RaggedFusionTransMILStepper(model, None, B=1, P=P, ct_shape=(D_CT, 512), backward=False)
+            slot = st.slot(N)
+            slot.x[:N].copy_(x[0])
+            slot.ct.copy_(ct)
+            slot.text.copy_(t)
+
+            def region():
+                for _ in range(a.inner):
+                    st.step(slot, [N])
+            st.step(slot, [N])                               # eager visit; the capture and the first replays are the warm-up
+            ts = [v / a.inner for v in region_times(region, a.reps, max(a.warmup, 2))]
+            assert st.n_graphs == 1 and st.replays >= a.reps * a.inner and int(st.flag.item()) == 0
+            assert (model.last_bag_attn is not None) == (scope == "all")
+            res.update({tag + "_ms": round(med(ts), 4), tag + "_min_ms": round(min(ts), 4), tag + "_max_ms": round(max(ts), 4)})
+            del st, slot, model
+            torch.cuda.empty_cache()
+        print(json.dumps(res), flush=True)
+
+
 def index_rows(a, dev):
     for N in a.N:
         R = N + 2 * P + D_CT
@@ -155,10 +189,12 @@ def main():
     ap.add_argument("--clip_layers", type=int, default=1, help="the frozen text tower runs outside the timed region")
     ap.add_argument("--index", action="store_true")
     ap.add_argument("--graph", action="store_true", help="the eager step next to the step replayed from its hipGraph")
+    ap.add_argument("--graph_eval", action="store_true", help="the replayed evaluation forward, note-attention export off / all")
+    ap.add_argument("--inner", type=int, default=20, help="--graph_eval: forwards per timed region")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    (graph_rows if a.graph else index_rows if a.index else step_rows)(a, dev)
+    (graph_eval_rows if a.graph_eval else graph_rows if a.graph else index_rows if a.index else step_rows)(a, dev)
 
 
 if __name__ == "__main__":
