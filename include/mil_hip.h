@@ -63,7 +63,7 @@ extern "C" {
 #define MIL_SMALL_ROWS 64  /* most rows the token-side mil_linear_small_* entry points accept */
 
 /* Library/ABI version, for the host mirror's load-time check. */
-int mil_abi_version(void);   /* 23 */
+int mil_abi_version(void);   /* 24 */
 
 /* ---- dropout keep bits (train mode) -------------------------------------------------------
  * model.train() upstream drops the bag rows with p = 0.5 BEFORE the gate and pools the dropped rows
@@ -1362,6 +1362,67 @@ size_t mil_tm_cls_attn_packed_ws_floats(int total_blocks, int nb);
 int mil_tm_cls_attn_packed(const float* qkv, const float* qL, const float* kL, const float* Z, const float* lse3,
                            const int32_t* cls_tab, int total_patches, const int32_t* len_dev, float* ws, float* out,
                            const int32_t* blk_off, int nb, int total_blocks, void* stream);
+
+/* ---- evaluation log and ROC metrics (ABI 24; csrc/metrics.hip; ops: eval_push / eval_rank / eval_reduce, metrics.EvalLog).
+ * What the reference's valid() (train_ddp.py:382-513) and test_ddp.py:141-162,286-309 compute from per-bag host reads, kept on
+ * the device until the epoch ends.  The log, all caller-allocated, for a capacity of `capacity` bags:
+ *   log_prob   float  [capacity, C]   the Last head's probabilities per bag
+ *   log_cls    int32  [capacity, 2]   {label class, predicted class}: argmax, the first maximal index wins (torch.argmax)
+ *   step_b     int32  [capacity]      bags of each pushed step
+ *   step_loss  double [capacity, 4]   per step: the criterion of the Last, CT and Pth terms (0 beyond nterm), then `extra`
+ *   ctr        int32  [4]             {rows, steps, flag, 0}; zero it to reset the log
+ *   rank       int32  [capacity, 3]   mil_eval_rank's {ge_pos, ge_neg, eq_neg}
+ * All counting is integer and every floating sum runs in a fixed order: the results are the same bits every run.  No float
+ * atomics, no host read, nothing allocated. */
+#define MIL_EVAL_MAX_TERMS 3
+#define MIL_EVAL_LOSS_SLOTS 4          /* MIL_EVAL_MAX_TERMS + the extra (textCosSim) term */
+#define MIL_EVAL_TILE 64               /* tile edge of mil_eval_rank: samples per workgroup and per LDS stage */
+#define MIL_EVAL_MAX_ROWS 65536
+#define MIL_EVAL_CTR_ROWS 0
+#define MIL_EVAL_CTR_STEPS 1
+#define MIL_EVAL_CTR_FLAG 2
+#define MIL_EVAL_FLAG_OVERFLOW 1       /* a push beyond the capacity was dropped */
+#define MIL_EVAL_FLAG_NAN 2            /* a pushed probability was NaN */
+/* Append one step, one launch of one wave: p_last / p_ct / p_pth [B, C] the probabilities of the first `nterm` (1..3) terms,
+ * y [B, C] the one-hot fp32 labels, extra a nullable device scalar (the textCosSim term), B C <= 64.  Per term the criterion in
+ * double: ce == 0 BCELoss, the mean over B C with each log clamped at -100 as torch does; ce != 0 CrossEntropyLoss on the
+ * probabilities with the float targets, the mean over B (train_ddp.py:95-98).  The row and step indices are read from ctr on
+ * the device and advanced by the kernel, so the launch is capture-safe: replayed, it appends a new step each time.  A push that
+ * does not fit `capacity` is dropped and raises MIL_EVAL_FLAG_OVERFLOW in ctr; a NaN probability raises MIL_EVAL_FLAG_NAN. */
+int mil_eval_push(const float* p_last, const float* p_ct, const float* p_pth, const float* y, const float* extra, int B, int C,
+                  int nterm, int ce, int capacity, float* log_prob, int32_t* log_cls, int32_t* step_b, double* step_loss,
+                  int32_t* ctr, void* stream);
+/* Binary models (C == 2): over the n = ctr[rows] logged samples with scores s_i = log_prob[i][1] and positives = label class 1,
+ * rank[i] = {#positives j with s_j >= s_i, #negatives j with s_j >= s_i, #negatives j with s_j == s_i}.  All pairs, one
+ * workgroup per MIL_EVAL_TILE samples i (one per lane), the j side staged in LDS a tile at a time; the grid covers `capacity`
+ * (<= MIL_EVAL_MAX_ROWS) and workgroups beyond n leave at once. */
+int mil_eval_rank(const float* log_prob, const int32_t* log_cls, const int32_t* ctr, int capacity, int32_t* rank, void* stream);
+/* One workgroup, fixed order.  out: mil_eval_out_bytes(C) bytes, 8-byte aligned: MIL_EVAL_OUT_WORDS 8-byte words, int64 unless
+ * marked double, then the confusion matrix int32 [C, C], conf[label][pred].  rank may be NULL (C != 2): the binary words are 0.
+ *   P, NEG            positives and negatives among the labels
+ *   S2                sum over positives i of 2 (NEG - ge_neg_i) + eq_neg_i: AUC = S2 / (2 P NEG)
+ *   TP_AT, FP_AT      positives / negatives with s >= thres, compared in double
+ *   ISTAR, JSTAR      i* = argmax_i (ge_pos_i NEG - ge_neg_i P), compared in int64; ties go to the larger score, then the
+ *                     lower index; J* is that maximum; GE_POS, GE_NEG, SSTAR (double) are i*'s counts and score
+ *   LOSS .. LOSS + 3  (double) sum over steps of loss_step B_step per slot of step_loss; LOSS + 4 (double) sum of B_step */
+#define MIL_EVAL_OUT_N 0
+#define MIL_EVAL_OUT_STEPS 1
+#define MIL_EVAL_OUT_FLAG 2
+#define MIL_EVAL_OUT_P 3
+#define MIL_EVAL_OUT_NEG 4
+#define MIL_EVAL_OUT_S2 5
+#define MIL_EVAL_OUT_TP_AT 6
+#define MIL_EVAL_OUT_FP_AT 7
+#define MIL_EVAL_OUT_JSTAR 8
+#define MIL_EVAL_OUT_ISTAR 9
+#define MIL_EVAL_OUT_GE_POS 10
+#define MIL_EVAL_OUT_GE_NEG 11
+#define MIL_EVAL_OUT_SSTAR 12
+#define MIL_EVAL_OUT_LOSS 13
+#define MIL_EVAL_OUT_WORDS 18
+size_t mil_eval_out_bytes(int C);      /* 0 for C outside 1..64 */
+int mil_eval_reduce(const float* log_prob, const int32_t* log_cls, const int32_t* step_b, const double* step_loss,
+                    const int32_t* ctr, const int32_t* rank, int capacity, int C, double thres, void* out, void* stream);
 
 #ifdef __cplusplus
 }

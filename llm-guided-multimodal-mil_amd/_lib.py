@@ -8,13 +8,13 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from ctypes import c_long, c_float, c_int, c_int32, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import c_long, c_double, c_float, c_int, c_int32, c_size_t, c_uint32, c_uint64, c_void_p
 from typing import Dict, List, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmil_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mil_hip.h")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _P = c_void_p
 # name -> (restype, argtypes); mirrors include/mil_hip.h one to one
@@ -244,6 +244,11 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     # the packed cls attention: the five operands, (cls_tab, total_patches), len_dev, ws, out, then the block table's three
     "mil_tm_cls_attn_packed_ws_floats": (c_size_t, [c_int, c_int]),
     "mil_tm_cls_attn_packed": (c_int, [_P] * 5 + [_P, c_int, _P, _P, _P, _P, c_int, c_int, _P]),
+    # the evaluation log (csrc/metrics.hip): push = probabilities x3, y, extra, (B, C, nterm, ce, capacity), the five log buffers
+    "mil_eval_push": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 5 + [_P]),
+    "mil_eval_rank": (c_int, [_P, _P, _P, c_int, _P, _P]),
+    "mil_eval_out_bytes": (c_size_t, [c_int]),
+    "mil_eval_reduce": (c_int, [_P] * 6 + [c_int, c_int, c_double, _P, _P]),
 }
 # entries that return a value, not a status: checked() leaves them without an errcheck
 VALUE_RETURNING = frozenset(n for n, (res, _) in SIGNATURES.items() if res is c_size_t) | frozenset((

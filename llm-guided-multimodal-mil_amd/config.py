@@ -172,6 +172,16 @@ def create_arg_parser(argv=None):
                         "bit-equal per bag to the fused single-bag kernels.  When it applies: ops.tm_route (DESIGN 4.6).  "
                         "Set on every TransMIL module of the model, as --tm_packed is.  0: the "
                         "environment variable MIL_TM_PACKED_CLS decides (default 0)")
+    # ---- validation and metrics (metrics.EvalLog: a device-side log, one small launch per forward, one host read per pass)
+    p.add_argument("--validate", type=int, default=0, choices=[0, 1],
+                   help="train_ddp.py: 1 = after every epoch run the validation bags one per forward (eval mode, true lengths, "
+                        "no zero padding) and print one 'Valid Epoch' line - loss, accuracy and the AUC / recall / precision of "
+                        "the argmax predictions as the reference's valid(), for two classes also the score AUC and the Youden "
+                        "threshold; writes checkpoint_last.pth.tar every epoch.  0: no validation, checkpoints as before")
+    p.add_argument("--index_json_valid", type=str, default="", help="--validate 1 with an on-disk cohort: the validation "
+                   "cohort's index (bags under --path_data_pathology); synthetic cohorts draw their own validation bags")
+    p.add_argument("--save_best", action="store_true", help="--validate 1: write checkpoint_{epoch:04d} and checkpoint_best only "
+                   "when the validation AUC is >= the best so far (the reference's flag); off: every epoch")
     args = p.parse_args(argv)
     if args.fusion_transmil and args.hip_graph:
         # refused here, before an entry point touches the GPU: the bucketed steppers key their graphs by row capacity,

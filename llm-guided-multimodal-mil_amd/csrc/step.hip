@@ -35,7 +35,7 @@ static bool fuse_pool16_enabled(bool train) {
     return e != nullptr && e[0] != '0';
 }
 
-extern "C" int mil_abi_version(void) { return 23; }
+extern "C" int mil_abi_version(void) { return 24; }
 
 extern "C" int mil_image_only_step_run(const mil_image_only_step* a, void* stream) {
     int rc = step_check(a);

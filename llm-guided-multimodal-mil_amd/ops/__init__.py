@@ -44,3 +44,5 @@ from .transmil import (TM_H, TM_DH, TM_D, TM_M, TM_CONV, TM_PINV_ITERS, TM_QSCAL
                        _tm_fwd_packed, _tm_bwd_packed, _NystromCorePacked, nystrom_core_packed, tm_packed_ppeg, TmPpegTable,
                        tm_ppeg_table_host, tm_ppeg_table, _TmPPEGPacked, tm_ppeg_packed, tm_packed_cls, TmClsTable,
                        tm_cls_table_host, tm_cls_table, tm_cls_attention_packed, TmRoute, tm_route)
+from .metrics import (EVAL_TILE, EVAL_MAX_ROWS, EVAL_MAX_TERMS, EVAL_LOSS_SLOTS, EVAL_FLAG_OVERFLOW, EVAL_FLAG_NAN, EVAL_OUT_WORDS,
+                      eval_out_bytes, eval_push, eval_rank, eval_reduce)

@@ -9,7 +9,19 @@ train_ddp.py:587-624) or under torchrun (RANK/LOCAL_RANK/WORLD_SIZE in the env).
 Two step implementations:
   * default: `generator = DDP(get_model(args))`, autograd through the HIP operators - the reference's loop
     (train_ddp.py:295-348) with `loss_point='Last'` semantics (:323-324);
-  * `--variant image_only --fused_step`: `trainer.ImageOnlyTrainer`, no autograd graph, one flat all-reduce."""
+  * `--variant image_only --fused_step`: `trainer.ImageOnlyTrainer`, no autograd graph, one flat all-reduce.
+
+`--validate 1` adds the reference's validation pass after every epoch (train_ddp.py:382-513): eval mode, no grad, the
+validation bags ONE PER FORWARD with their true lengths through the forward test_ddp.py uses (evaluate.BagEvaluator), each
+forward followed by one push into a device-side log (metrics.EvalLog) and nothing read on the host until the pass ends.  The
+reference pads a validation batch with zero rows, which changes the result; this pass does not.  Every rank validates the whole
+set, rank 0 saves: checkpoint_last every epoch and, with `--save_best`, checkpoint_{epoch:04d} + checkpoint_best only when the
+validation AUC is >= the best so far (metrics.select_best; `write_checkpoints` below).  The best AUC so far is not stored
+in a checkpoint: after `--resume` it starts at 0 again, as the reference's does.  Where `--hip_graph 1` selects the replayed
+fusion forward, building the evaluator puts the text tower of the model into its fixed-shape form
+(`clinic_extractor.model.static_rows`, fusion_step.RaggedFusionInference), the form the replayed training step runs as well unless `--cache_text 1` keeps the tower outside it.
+Without `--validate` nothing changes."""
+import copy
 import os
 import sys
 import time
@@ -79,6 +91,27 @@ def build_model(args):
         if scope_all:
             model.note_attn = "all"                # config.py --note_attn_scope: CT, the bucket forwards, the replayed evaluation
     return model
+
+
+def dropout_passes(model, tr=None):
+    """Every dropout pass counter of the training stream: the modules' device counters and the fused trainer's host one."""
+    vals = [int(m._drop_ctr) for m in model.modules() if torch.is_tensor(getattr(m, "_drop_ctr", None))]
+    return vals + ([int(tr.drop_pass)] if tr is not None else [])
+
+
+def write_checkpoints(state, save_dir: str, epoch: int, validate: bool, auc_hard, best_auc: float, save_best: bool) -> float:
+    """Rank 0's files of one epoch; returns the best validation AUC afterwards.  Without --validate: checkpoint_{epoch:04d} +
+    checkpoint_best every epoch, as before.  With it: the pair only when metrics.select_best keeps the epoch (always without
+    --save_best), and checkpoint_last.pth.tar every epoch (train_ddp.py:214-244)."""
+    if not validate:
+        save_checkpoint(state, True, save_dir, f"checkpoint_{epoch:04d}.pth.tar")
+        return best_auc
+    from .metrics import select_best
+    keep, best_auc = select_best(auc_hard, best_auc, save_best)
+    if keep:
+        save_checkpoint(state, True, save_dir, f"checkpoint_{epoch:04d}.pth.tar")
+    torch.save(state, os.path.join(save_dir, "checkpoint_last.pth.tar"))
+    return best_auc
 
 
 def main_worker(local_rank: int, nprocs: int, args):
@@ -273,6 +306,38 @@ def main_worker(local_rank: int, nprocs: int, args):
         g_ct = torch.Generator(device=dev).manual_seed(args.seed + 7919)
         ct_pool = torch.randn((16,) + CT_SHAPE, device=dev, generator=g_ct)
 
+    # ---- validation (--validate 1): the evaluator (its inference graphs, its resident cohort) and the log are built at the
+    # first pass, in eval mode, and kept
+    validate = bool(getattr(args, "validate", 0))
+    validator = vlog = None
+    best_auc = 0.0                                                                       # train_ddp.py:198
+
+    def run_validation(epoch_):
+        nonlocal validator, vlog
+        from .metrics import EvalLog, format_valid
+        if fused:
+            model.load_state_dict(tr.model_state_dict())                                 # the fused step owns the weights
+        before = dropout_passes(model, tr if fused else None)
+        model.eval()
+        try:
+            if validator is None:
+                from .evaluate import BagEvaluator
+                vargs = copy.copy(args)
+                if getattr(args, "index_json_valid", ""):
+                    vargs.index_json = args.index_json_valid
+                vdata, _ = load_cohort(vargs, "valid", prompts)
+                validator = BagEvaluator(args, model, vdata, dev, prompts)
+                vlog = EvalLog(len(vdata), args.num_classes, validator.nterm, dev)
+            vlog.reset()
+            validator.run(vlog, timed=False, read=False)                                 # no host read inside the loop
+            m_ = vlog.finish()
+        finally:
+            model.train()
+        # eval mode draws no bits: the training stream's dropout passes stand where they stood
+        assert dropout_passes(model, tr if fused else None) == before, "validation moved a dropout pass counter"
+        print(format_valid(epoch_, m_), flush=True)
+        return m_
+
     for epoch in range(args.start_epoch, args.n_epochs):
         idx = shard_indices(len(data), world, rank, epoch)                               # sampler.set_epoch(epoch)
         if cohort is not None:
@@ -416,6 +481,7 @@ def main_worker(local_rank: int, nprocs: int, args):
                 bt.update(time.time() - end)
                 progress.display(it)
             end = time.time()
+        vm = run_validation(epoch) if validate else None                                 # every rank, the whole set
         if rank == 0 and args.save_dir:
             os.makedirs(args.save_dir, exist_ok=True)
             # same key schema either way (the model's own names), optimizer state included: a fused-step checkpoint
@@ -423,7 +489,8 @@ def main_worker(local_rank: int, nprocs: int, args):
             sd = tr.model_state_dict() if fused else model.state_dict()
             state = {"epoch": epoch + 1, "state_dict": sd,
                      "optimizer": tr.optimizer_state_dict() if fused else optimizer.state_dict()}
-            save_checkpoint(state, True, args.save_dir, f"checkpoint_{epoch:04d}.pth.tar")
+            best_auc = write_checkpoints(state, args.save_dir, epoch, validate, vm["auc_hard"] if validate else None, best_auc,
+                                         bool(args.save_best))
     if not fused and ftm_graph:
         print(f"fusion TransMIL graphs {fstepper.n_graphs}  replays {fstepper.replays}  eager {fstepper.eager_steps}")
     if world > 1:
